@@ -57,8 +57,8 @@ class FramePipeline:
         # static outputs that the caller copies from.  Results are those of the eager launches, kernel for kernel.
         # Replays of different buckets are independent and each fills a small part of the chip (a bucket holds 1..10 crops): they go out on
         # side streams side by side (APE_BUCKET_STREAMS, default 32: one per bucket) and the caller's stream joins them before it scatters
-        # the results.  HIP multiplexes its streams onto GPU_MAX_HW_QUEUES hardware queues (default 4: two chains then run side by side,
-        # not four); the process has to set that variable before its first HIP call (bench.py does: 40) for the streams to be concurrent.
+        # the results.  HIP multiplexes its streams onto the process's hardware queues: how many chains run side by side is bounded by
+        # the queue count the environment gives the process (GPU_MAX_HW_QUEUES), not by the number of streams.
         self.pose_graphs = bool(pose_graphs)
         self._bucket_streams = [torch.cuda.Stream() for _ in range(int(os.environ.get("APE_BUCKET_STREAMS", "32")))] if pose_graphs else []
         self._graphs = {}

@@ -18,12 +18,6 @@ import os
 import sys
 import time
 
-# HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  The `sweep` leg replays one captured graph per
-# crop-size bucket on its own stream (FramePipeline(pose_graphs=True)): with four queues two chains run side by side, with one queue
-# per stream all of them do (pose stage of the ragged batch 32 -> 17 ms).  Must be set before the first HIP call; no effect on `value`
-# (same-box A/B of 2 / 4 / 8 / 16 queues: 31.85 ms per step each).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "40")
-
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -75,6 +69,27 @@ def ranks_seen(rank, device, dist):
     parts = [None] * dist.get_world_size()
     dist.all_gather_object(parts, mine)
     return parts
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: write `arrays` (name -> tensor / array: what the timed path returned in its last step) as <directory>/<name>.npy so
+    that two builds can be compared output for output.  float64 stays float64; every other type becomes float32 (float64 for integers
+    beyond 2^24, which float32 would round).  Each array may take an equal share of DUMP_LIMIT_BYTES (npy headers included); a larger one
+    is replaced by a sample of its flattened elements at positions drawn with a fixed seed, the same positions in every run."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1) - 4096
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        if a.dtype != np.float64:
+            wide = a.dtype.kind in "iu" and a.size and np.abs(a.astype(np.float64)).max() >= 2 ** 24
+            a = a.astype(np.float64 if wide else np.float32)
+        if a.nbytes > share:
+            pick = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def make_frame(rank, i):
@@ -549,6 +564,14 @@ def label_main(args, rank, world, device, dist, embedded=False):
         dist.all_reduce(counts)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt, icp_ms_max = float(tmax[0]), float(tmax[1])
+    if args.dump_outputs and rank == 0 and not embedded:
+        # rank 0's chains: the fused cloud and the per-view transforms of each (NaN for a view without surface points)
+        arrays = {}
+        for c, (cloud, transforms) in sorted(res.items()):
+            arrays["chain%d_points" % c] = np.zeros((0, 3)) if cloud is None else cloud.points
+            arrays["chain%d_transforms" % c] = np.stack([np.full((4, 4), np.nan) if T is None else
+                                                         torch.as_tensor(T).double().cpu().numpy() for T in transforms])
+        dump_outputs(args.dump_outputs, arrays)
     if rank == 0:
         regs, evals, pairs, p0, p1, fused_pts = [float(x) for x in counts]
         icp_bytes = p0 * ICP_BYTES_PER_PAIR[0] + p1 * ICP_BYTES_PER_PAIR[1]
@@ -674,6 +697,8 @@ def pose_main(args, rank, world, device, dist, embedded=False):
     if dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax[0])
+    if args.dump_outputs and rank == 0 and not embedded:
+        dump_outputs(args.dump_outputs, {"results": gathered, "pose": pose, "choose": choose, "adds": dis})
     if rank == 0:
         m = model.shape[1]
         pairs = n * m * m
@@ -836,6 +861,10 @@ def main():
     ap.add_argument("--no-overlap", dest="overlap", action="store_false", help="one stream, segmentation and pose stage back to back")
     ap.add_argument("--dump-launches", default="", help="write [[kernel label, layer shape], ...] of ONE step's profiled launches in launch order "
                     "(for tools/pmc_summary.py --shapes: per-shape HBM traffic from the rocprofv3 PMC passes; use with --no-overlap)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all; a larger output as a fixed seeded sample): the same arguments give the same inputs in every "
+                         "run, so two builds can be compared output for output")
     ap.add_argument("--no-staged", action="store_true", help="skip the secondary `staged` leg (the same loop fed from pinned host memory through a copy stream)")
     ap.add_argument("--no-modes", action="store_true", help="skip the secondary `modes` leg (two steps of the exact-fp32 operand mode after the timed region)")
     ap.add_argument("--no-sweep", action="store_true", help="skip the compact secondary `sweep` leg (4 steps of the --mixed frames, no parity block)")
@@ -1019,6 +1048,10 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t[0])
+    if args.dump_outputs and rank == 0:
+        # the last timed step: its gathered (class, q, t) block of every frame, and what FramePipeline returned for its last sub-batch
+        dump_outputs(args.dump_outputs, {"poses": out["gathered"], "pose": out["pose"], "objects": out["objects"], "n_cand": out["n_cand"],
+                                         "choose": out["choose"], "objmap": out["objmap"]})
 
     # Every TIMED step's result block against the same step (same frames, same sampling seed) run again on ONE stream after the timed
     # region: the overlapped loop must give the single-stream bits (round 5 found a co-stream fault in this arrangement; the parity block

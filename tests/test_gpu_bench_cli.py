@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -31,9 +32,17 @@ def _common(d, steps, warmup):
     assert r["bound"] in ("hbm", "mfma") and r["unit"] in ("GB/s", "TFLOP/s") and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
 
 
-def test_default_line_has_roofline_cpu_baseline_and_parity():
-    d = _run("--steps", "2", "--warmup", "1")
+def test_default_line_has_roofline_cpu_baseline_and_parity(tmp_path):
+    d = _run("--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path))
     _common(d, 2, 1)
+    # --dump-outputs: what the last timed step returned, float32 / float64, 64 MB at most
+    dumped = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(dumped) == {"poses", "pose", "objects", "n_cand", "choose", "objmap"}
+    assert all(a.dtype in (np.float32, np.float64) for a in dumped.values())
+    assert sum(os.path.getsize(tmp_path / (k + ".npy")) for k in dumped) <= 64 << 20
+    assert dumped["poses"].shape == (64, 1, 8) and set(np.unique(dumped["poses"][:, 0, 0])) <= {1.0, 2.0, 3.0}
+    n = d["config"]["objects_found_last_step"]
+    assert dumped["objects"].shape == (n, 6) and dumped["pose"].shape == (n, 7) and dumped["choose"].shape == (n, 1000)
     assert d["unit"] == "frames/s" and d["scaling"] == "weak" and d["dtype"] == "bf16x3"
     assert abs(d["value"] - 64 * 2 / (d["ms_per_step"] * 2e-3)) < 0.02 * d["value"]
     # the line says what it measures (inputs resident in HBM) and carries the same loop fed from pinned host memory beside it

@@ -222,6 +222,21 @@ def gen_knn():
     save("knn", **cases)
 
 
+def gen_knn_object():
+    """tests/test_oracle_knn.py::test_oracle_knn_matches_reference_object's seeded cases through the reference's compiled knn_cpu"""
+    rng = np.random.default_rng(123)
+    cases = {}
+    for i, (b, d, nr, nq, k, qz) in enumerate([(1, 3, 300, 400, 1, 0), (1, 3, 128, 256, 1, 0.5), (2, 5, 40, 33, 3, 0.5)]):
+        ref = rng.standard_normal((b, d, nr)).astype(np.float32)
+        qry = rng.standard_normal((b, d, nq)).astype(np.float32)
+        if qz:
+            ref, qry = (np.round(ref / qz) * qz).astype(np.float32), (np.round(qry / qz) * qz).astype(np.float32)
+        idx = ref_shim.ref_knn(torch.from_numpy(ref), torch.from_numpy(qry), k).numpy()
+        cases["ref_%d" % i], cases["query_%d" % i], cases["idx_%d" % i] = ref, qry, idx
+    cases["n_cases"] = 3
+    save("knn_ref_object", **cases)
+
+
 def gen_loss():
     rng = np.random.default_rng(9)
     out = {}
@@ -303,6 +318,7 @@ if __name__ == "__main__":
         gen_posenet()
         sys.exit(0)
     gen_knn()
+    gen_knn_object()
     gen_bbox()
     gen_pose_utils()
     gen_loss()

@@ -2,7 +2,7 @@
 the cost of producing S32 in the epilogue.  Result (round 2): gemm_s32 is 8-10 % faster, writing S32 costs the producer 4-10 % -- a wash, so
 the pose side keeps fp32 activations.  python tools/mb_pose_gemm.py"""
 import os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from autoposeestimation_amd import engine as E
 shapes = [("feat 512->1024 (x3/step)", 64, 1000, 1, 512, 1024), ("384->1920", 64, 1000, 1, 384, 1920), ("crop up_1 mix", 64, 20, 20, 1024, 2304),

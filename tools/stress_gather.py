@@ -2,7 +2,6 @@
 src1) under the conditions that exposed those faults: hundreds of launches beside a second stream that keeps the chip busy, every output compared bit
 for bit with the ROW kernel's (same arithmetic, no packed instructions: ape_upconv3x3_gather_strip_rows(0))."""
 import os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "40")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from autoposeestimation_amd import _lib, engine as E

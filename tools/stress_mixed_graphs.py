@@ -1,7 +1,6 @@
 """Stress: the captured per-bucket pose graphs replayed side by side (FramePipeline(pose_graphs=True), one stream per bucket) against the
 eager single-stream pipeline, bit for bit, over many steps of a 64-frame ragged batch; prints which objects / crop sizes ever differ."""
 import os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "40")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch

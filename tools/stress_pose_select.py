@@ -1,6 +1,5 @@
 """pose_select (one small workgroup per crop) beside ONE other stage of the pose path on a second stream: which neighbour corrupts it?"""
 import os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "40")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from autoposeestimation_amd import engine as E, synthetic as S

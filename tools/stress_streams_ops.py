@@ -1,7 +1,6 @@
 """Which stage of the pose path gives different results when several crop-size buckets run side by side on their own streams?  Every bucket's
 stages are computed alone first (reference), then all buckets concurrently for some rounds; differing stages are listed."""
 import os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "40")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
