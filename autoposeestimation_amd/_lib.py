@@ -81,6 +81,10 @@ SIGNATURES = {
     "ape_seg_components_workspace_bytes": [_I, _I, _I, _I],
     "ape_seg_components": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _c.c_size_t, _P],
     "ape_conv3x3_halo_seghead_bf16": [_P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P],
+    "ape_unet_conv3x3_supported": [_I, _I, _I, _I],
+    "ape_unet_conv3x3_bf16": [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "ape_unet_conv3x3_seghead_bf16": [_P, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ape_nearest_upsample_nhwc_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "ape_seg_components_scored": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _c.c_size_t, _P],
     "ape_bgsub_features_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "ape_conv2d_wgrad_workspace_bytes": [_P],

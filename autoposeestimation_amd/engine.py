@@ -456,6 +456,96 @@ def conv_seg_head(conv, x, head_w, head_b, double_softmax=True, upsample2x=False
     return label, score
 
 
+
+# ---- smp Unet decoder (csrc/unet.hip) -------------------------------------------------------------------------------------------
+def bn_fold(weight, gamma, beta, mean, var, eps=1e-5):
+    """conv (no bias) followed by eval-mode BatchNorm2d  ->  (w', b') of one conv with bias: w' = w * g / sqrt(var + eps),
+    b' = beta - mean * g / sqrt(var + eps), formed in fp64 on the host.  Returns fp64 CPU tensors (the caller casts)."""
+    s = gamma.detach().double().cpu() / torch.sqrt(var.detach().double().cpu() + eps)
+    w = weight.detach().double().cpu() * s.view(-1, *([1] * (weight.dim() - 1)))
+    b = beta.detach().double().cpu() - mean.detach().double().cpu() * s
+    return w, b
+
+
+def unet_conv3x3_supported(c1, c2, cout, ups):
+    return bool(_lib.lib().ape_unet_conv3x3_supported(int(c1), int(c2), int(cout), int(bool(ups))))
+
+
+def _unet_operands(conv, a, b, ups):
+    """(B, H, W, C1, C2, ldb) of a decoder conv over cat([nearest_up2(a) | a, b]); checks the channel split against the layer"""
+    if conv.kh != 3 or conv.kw != 3 or conv.stride != 1 or conv.pad != 1 or conv.dil != 1 or not conv.nsplit:
+        raise ValueError("the Unet decoder kernel takes 3x3 / stride 1 / pad 1 layers in the bf16 precisions")
+    bb, ha, wa, lda = a.shape
+    h, w = (2 * ha, 2 * wa) if ups else (ha, wa)
+    c2 = 0 if b is None else b.shape[3]
+    c1 = conv.cin_real - c2
+    if c1 != lda:          # (a wider `a` would be read in part: the kernel takes channels 0..C1-1 of it)
+        raise ValueError("input channels %d + %d do not match the layer's %d" % (lda, c2, conv.cin_real))
+    if b is not None and tuple(b.shape[:3]) != (bb, h, w):
+        raise ValueError("skip %s does not match the output %s" % (tuple(b.shape[:3]), (bb, h, w)))
+    return bb, h, w, c1, c2, (0 if b is None else b.shape[3])
+
+
+def unet_conv3x3(conv, a, b=None, ups=True, out=None, yoff=0):
+    """relu(conv(cat([nearest_up2(a), b])) + bias) (ups=False: a at full resolution) -> out[B,H,W,ldy] channels yoff..yoff+Cout;
+    conv: an engine.Conv (3x3 p1, the BN folded into weight and bias, precision bf16x3 | bf16) whose input channels are [a's | b's]"""
+    bb, h, w, c1, c2, ldb = _unet_operands(conv, a, b, ups)
+    if not unet_conv3x3_supported(c1, c2, conv.cout, ups):
+        raise ValueError("no Unet decoder kernel for C1 %d, C2 %d, Cout %d" % (c1, c2, conv.cout))
+    if out is None:
+        out = torch.empty(bb, h, w, conv.cout, dtype=torch.float32, device=a.device)
+    if tuple(out.shape[:3]) != (bb, h, w):
+        raise ValueError("output buffer %s does not match %s" % (tuple(out.shape), (bb, h, w)))
+    nc = 4 if conv.cout >= 64 else 2 if conv.cout in (32, 48) else 1
+    label = "unet_conv3x3_kernel<%d,%s,%d,%d,false>" % (conv.nsplit, "true" if ups else "false", nc, 4 if nc == 4 else 8)
+    e0 = _prof_begin(label)
+    rc = _lib.lib().ape_unet_conv3x3_bf16(_lib.dptr(a, torch.float32), a.shape[3], c1, _lib.dptr(b, torch.float32), ldb, c2,
+                                          _lib.dptr(conv.wp), _lib.dptr(conv.bias), _lib.dptr(out, torch.float32), out.shape[3], yoff,
+                                          bb, h, w, conv.cout, int(bool(ups)), conv.nsplit, _st())
+    _lib.check(rc, "ape_unet_conv3x3_bf16")
+    if e0 is not None:
+        m = bb * h * w
+        lo = (bb * a.shape[1] * a.shape[2] * c1 + m * c2)
+        _prof_end(e0, label, "%dx%dx%d %d+%d->%d%s" % (bb, h, w, c1, c2, conv.cout, " ups" if ups else ""),
+                  2.0 * m * conv.cout * 9 * conv.cin_real, 4.0 * (lo + conv.cout * 9 * conv.cin_real + m * conv.cout))
+    return out
+
+
+def unet_conv3x3_seghead(conv, a, b=None, ups=False, double_softmax=True):
+    """the segmentation head: conv(cat([a (up-sampled when ups), b])) + bias (conv.cout = classes <= 16) -> softmax (+ softmax) -> arg-max,
+    -> (label u8[B,H,W], score f32[B,H,W]); the logits are never stored"""
+    bb, h, w, c1, c2, ldb = _unet_operands(conv, a, b, ups)
+    if conv.cout > 16:
+        raise ValueError("the fused head takes at most 16 classes")
+    label = torch.empty(bb, h, w, dtype=torch.uint8, device=a.device)
+    score = torch.empty(bb, h, w, dtype=torch.float32, device=a.device)
+    klabel = "unet_conv3x3_kernel<%d,%s,1,8,true>" % (conv.nsplit, "true" if ups else "false")
+    e0 = _prof_begin(klabel)
+    rc = _lib.lib().ape_unet_conv3x3_seghead_bf16(_lib.dptr(a, torch.float32), a.shape[3], c1, _lib.dptr(b, torch.float32),
+                                                  ldb, c2, _lib.dptr(conv.wp), _lib.dptr(conv.bias), conv.cout, _lib.dptr(label), _lib.dptr(score),
+                                                  bb, h, w, int(bool(ups)), conv.nsplit, int(bool(double_softmax)), _st())
+    _lib.check(rc, "ape_unet_conv3x3_seghead_bf16")
+    if e0 is not None:
+        m = bb * h * w
+        _prof_end(e0, klabel, "%dx%dx%d %d+%d->%d%s +head" % (bb, h, w, c1, c2, conv.cout, " ups" if ups else ""),
+                  2.0 * m * conv.cout * 9 * conv.cin_real,
+                  4.0 * (bb * a.shape[1] * a.shape[2] * c1 + m * c2 + conv.cout * 9 * conv.cin_real) + 5.0 * m)
+    return label, score
+
+
+def nearest_up2(x, out=None, yoff=0, scale=2):
+    """x[B,h,w,C] -> out[B,2h,2w,ldy] channels yoff..yoff+C = F.interpolate(scale_factor=2, mode='nearest') (scale=1: a copy).  The materialised
+    form of the Unet decoder's first step: the up-sample and the skip are written into their channel windows of one concatenation buffer"""
+    b, h, w, c = x.shape
+    if out is None:
+        out = torch.empty(b, scale * h, scale * w, c, dtype=torch.float32, device=x.device)
+    if tuple(out.shape[:3]) != (b, scale * h, scale * w):
+        raise ValueError("nearest_up2 output buffer mismatch")
+    rc = _lib.lib().ape_nearest_upsample_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(out, torch.float32), b, h, w, c, scale, out.shape[3], yoff, _st())
+    _lib.check(rc, "ape_nearest_upsample_nhwc_f32")
+    return out
+
+
 USE_FUSED_STEM = os.environ.get("APE_USE_FUSED_STEM", "1") != "0"
 USE_U8_STEM = os.environ.get("APE_USE_U8_STEM", "1") != "0"      # the stem reads the uint8 frames itself (ToTensor / Normalize fused into its patch load)
 

@@ -1,7 +1,7 @@
 """Drop-in for `get_default_model` of label_generator/create_labels.py (reference :20-37).
 
-The reference hard-codes smp's Unet-resnet34; that third-party model is unavailable (see segmentation/utils.py), so the
-default here is the in-repo PSPNet ('PsPNet', resnet34 encoder) with the same config keys and checkpoint convention:
+The reference hard-codes smp's Unet-resnet34 (served here as name='Unet', segmentation/unet.py); the default stays the in-repo PSPNet
+('PsPNet', resnet34 encoder) with the same config keys and checkpoint convention:
 `<root>/segmentation/trained_models/<ds_name>/<name>_<encoder>.ckpt` holding {'state_dict': ...}."""
 import os
 
@@ -24,9 +24,8 @@ def get_default_model(root, ds_name, n_classes, name="PsPNet", encoder_name="res
             smp_ckpt = os.path.join(ckpt_dir, "Unet_{}.ckpt".format(segmentation_config["encoder_name"]))
             hint = ""
             if os.path.exists(smp_ckpt):
-                hint = (" -- {} is the reference's segmentation_models_pytorch Unet checkpoint (create_labels.py:20-35): its state-dict "
-                        "layout belongs to a third-party model that is not part of the reference tree and cannot be loaded here; train the "
-                        "in-repo 'PsPNet' segmentor and save it as {}".format(smp_ckpt, os.path.basename(path)))
+                hint = (" -- {} is the reference's segmentation_models_pytorch Unet checkpoint (create_labels.py:20-35): load it with "
+                        "name='Unet' (segmentation/unet.py)".format(smp_ckpt))
             raise FileNotFoundError("segmentor checkpoint {} not found{}".format(path, hint))
         cp = torch.load(path, map_location=torch.device("cpu"))
         model.load_state_dict(cp["state_dict"])

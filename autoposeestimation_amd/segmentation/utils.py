@@ -5,7 +5,8 @@ Linknet), which is neither vendored in the reference tree nor installed here, so
 pinned.  DECISION: `get_model('PsPNet', cfg)` returns the reference's OWN in-repo PSPNet
 (DenseFusion/lib/pspnet.py, BasicBlock encoder `cfg['encoder_name']` in {resnet18, resnet34}) executed by the gfx950
 kernels; `predict()` returns the first `classes` channels of its `final` 1x1 conv with the configured activation.
-smp-format Unet / LinkNet checkpoints cannot be honoured and raise NotImplementedError.
+`get_model('Unet', cfg)` returns segmentation/unet.py's UnetSegmentor, a restatement of smp 0.1.3's Unet (resnet18 / resnet34
+encoder) with smp's state-dict keys, so the reference's `Unet_resnet34.ckpt` files load; LinkNet raises NotImplementedError.
 
 Training-only symbols of the reference module (jaccard_loss, IoU, ConfusionMatrix, transforms, animate*) are outside the
 hot path and are not provided.
@@ -81,7 +82,12 @@ def _unavailable(name):
     return ctor
 
 
-nets = {"Unet": _unavailable("smp.Unet"), "PsPNet": PsPNetSegmentor, "LinkNet": _unavailable("smp.Linknet")}
+def _unet(**cfg):
+    from autoposeestimation_amd.segmentation.unet import UnetSegmentor
+    return UnetSegmentor(**cfg)
+
+
+nets = {"Unet": _unet, "PsPNet": PsPNetSegmentor, "LinkNet": _unavailable("smp.Linknet")}
 
 
 def get_model(name, segmentation_config):

@@ -90,6 +90,51 @@ def pspnet_state_dict(backend="resnet18", seed=0, prefix="", n_classes=21, stem_
     return _fill(spec, seed, prefix, over)
 
 
+
+def unet_spec(encoder="resnet34", in_channels=3, classes=1):
+    """[(key, shape)] of smp 0.1.3's Unet (segmentation/unet.py) in state_dict order; BatchNorm layers as (prefix, (C,), 'bn')"""
+    spec = [("encoder.conv1.weight", (64, in_channels, 7, 7)), ("encoder.bn1", (64,), "bn")]
+    cin = 64
+    for li, (planes, n) in enumerate(zip((64, 128, 256, 512), _BLOCKS[encoder]), 1):
+        for b in range(n):
+            p = "encoder.layer%d.%d." % (li, b)
+            spec += [(p + "conv1.weight", (planes, cin, 3, 3)), (p + "bn1", (planes,), "bn"),
+                     (p + "conv2.weight", (planes, planes, 3, 3)), (p + "bn2", (planes,), "bn")]
+            if b == 0 and li > 1:
+                spec += [(p + "downsample.0.weight", (planes, cin, 1, 1)), (p + "downsample.1", (planes,), "bn")]
+            cin = planes
+    for i, (c1, c2, co) in enumerate(zip((512, 256, 128, 64, 32), (256, 128, 64, 64, 0), (256, 128, 64, 32, 16))):
+        p = "decoder.blocks.%d." % i
+        spec += [(p + "conv1.0.weight", (co, c1 + c2, 3, 3)), (p + "conv1.1", (co,), "bn"),
+                 (p + "conv2.0.weight", (co, co, 3, 3)), (p + "conv2.1", (co,), "bn")]
+    spec += [("segmentation_head.0.weight", (classes, 16, 3, 3)), ("segmentation_head.0.bias", (classes,))]
+    return spec
+
+
+def unet_state_dict(encoder="resnet34", seed=0, in_channels=3, classes=1):
+    """Synthetic weights for segmentation/unet.py with every key of smp's Unet: He-normal convolutions, BatchNorm layers with non-trivial
+    running statistics (mean +-0.2, variance 0.5..2, gamma / beta), the residual branches' last BN at half gain so that the 8..16 blocks do
+    not blow the variance up; activations stay O(1) through all ~45 layers"""
+    sd = OrderedDict()
+    for item in unet_spec(encoder, in_channels, classes):
+        key, shape = item[0], item[1]
+        if len(item) == 3:                               # BatchNorm2d(C): weight, bias, running_mean, running_var, num_batches_tracked
+            c = shape[0]
+            g = 0.5 if (key.endswith("bn2") and ".layer" in key) else 1.0
+            sd[key + ".weight"] = (0.8 + 0.4 * _rng(seed, key + "g").random(c)).astype(np.float32) * np.float32(g)
+            sd[key + ".bias"] = _uniform(seed, key + "b", (c,), 0.1)
+            sd[key + ".running_mean"] = _uniform(seed, key + "m", (c,), 0.2)
+            sd[key + ".running_var"] = torch.from_numpy((0.5 + 1.5 * _rng(seed, key + "v").random(c)).astype(np.float32))
+            sd[key + ".num_batches_tracked"] = torch.tensor(1000, dtype=torch.int64)
+            sd[key + ".weight"] = torch.from_numpy(sd[key + ".weight"])
+            continue
+        if key.endswith(".bias"):
+            sd[key] = _uniform(seed, key, shape, 0.05)
+            continue
+        fan_in = int(np.prod(shape[1:]))
+        sd[key] = _normal(seed, key, shape, (2.0 / fan_in) ** 0.5)
+    return sd
+
 def _pointnet_spec(refine):
     c5 = 384 if refine else 256
     return [("feat.conv1.weight", (64, 3, 1)), ("feat.conv1.bias", (64,)),
@@ -211,7 +256,7 @@ def model_cloud(cls, m=1000, seed=1234):
 def fit_final_layer(feats, labels, n_out, margin=8.0, ridge=1e-2):
     """Least-squares "training" of a segmentor's final 1x1 conv on frozen random features, so that synthetic frames
     segment into their painted object with real logit margins (random weights alone give a random label map).
-    feats[P,64] float tensor (any device), labels[P] int64 in [0,n_out) -> (W[n_out,64], b[n_out]) float32 on CPU.
+    feats[P,C] float tensor (any device; C = 64 for the PSPNet), labels[P] int64 in [0,n_out) -> (W[n_out,C], b[n_out]) float32 on CPU.
     Targets: +margin for the pixel's class, -margin for every other class."""
     f = feats.double()
     p = f.shape[0]
@@ -219,8 +264,9 @@ def fit_final_layer(feats, labels, n_out, margin=8.0, ridge=1e-2):
     t = torch.full((p, n_out), -float(margin), dtype=torch.float64, device=f.device)
     t[torch.arange(p, device=f.device), labels.to(f.device)] = float(margin)
     ata = a.t() @ a + ridge * p * torch.eye(a.shape[1], dtype=torch.float64, device=f.device)
-    sol = torch.linalg.solve(ata, a.t() @ t)          # [65, n_out]
-    return sol[:64].t().float().cpu().contiguous(), sol[64].float().cpu().contiguous()
+    sol = torch.linalg.solve(ata, a.t() @ t)          # [C + 1, n_out]
+    c = f.shape[1]
+    return sol[:c].t().float().cpu().contiguous(), sol[c].float().cpu().contiguous()
 
 
 # ---- label path (BASELINE configs[4]): synthetic multi-view depth renders of a known object --------------------------------------

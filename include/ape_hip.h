@@ -460,6 +460,34 @@ int ape_conv3x3_halo_seghead_bf16(const float* x, const void* w_packed, const fl
                                   const float* head_w, const float* head_b, int C, uint8_t* label, float* score, int double_softmax,
                                   void* stream);
 
+/* ---- smp Unet decoder (segmentation_models_pytorch 0.1.3, restated in autoposeestimation_amd/segmentation/unet.py) ---------------
+ * Replaces, in the Unet the reference builds at label_generator/create_labels.py:20-37, background_subtraction/utils.py:648-663 and
+ * segmentation/__init__.py:252-256 (smp.Unet(encoder_name='resnet34')), smp's DecoderBlock.forward
+ *     x = F.interpolate(x, scale_factor=2, mode='nearest'); x = torch.cat([x, skip], dim=1); x = conv1(x); x = conv2(x)
+ * (each conv = Conv2d 3x3 p1 no bias + BatchNorm2d + ReLU, the BN folded into the weights and bias by the caller) and the
+ * SegmentationHead (Conv2d 3x3 p1 + activation), on the bf16 matrix cores (nsplit 3 = split-bf16, 1 = plain bf16; fp32 accumulate).
+ * The conv reads the VIRTUAL input cat([nearest_up2(a), b]): channel c < C1 of output pixel (y, x) is a[(y >> ups, x >> ups), c]
+ * (a: [B][H >> ups][W >> ups][lda]), channel C1 + c is b[(y, x), c] (b: [B][H][W][ldb], C2 = 0: no skip, b may be null);
+ * nothing up-sampled or concatenated is written.  H, W = the OUTPUT size (even when ups = 1).  w_packed = ape_pack_weights_bf16 of
+ * the [Cout][3][3][C1 + C2] weights (K = 9 (C1 + C2), [tap][C1 | C2] order).  C1, C2, Cout multiples of 16 (C1 >= 16).
+ * Offsets are 64-bit: no batch limit.  ape_unet_conv3x3_supported says whether a layer's channel counts are taken. */
+int ape_unet_conv3x3_supported(int C1, int C2, int Cout, int ups);
+/* y[b][y][x][yoff + co] = relu(conv + bias[co]) (fp32 NHWC, ldy % 4 == 0, yoff % 4 == 0). */
+int ape_unet_conv3x3_bf16(const float* a, int lda, int C1, const float* b, int ldb, int C2, const void* w_packed,
+                          const float* bias, float* y, int ldy, int yoff, int B, int H, int W, int Cout, int ups, int nsplit,
+                          void* stream);
+/* The segmentation head with the reference's post-processing fused (pipeline/utils.py:429-435): logits = conv + bias (C <= 16
+ * classes, w_packed [C][3][3][C1 + C2]), then softmax (+ the second softmax when double_softmax) and arg-max by csrc/seg_head.h --
+ * the same tie rule and score formula as ape_seg_head_f32 -- written as label[B][H][W] u8 and score[B][H][W] f32; the logits are
+ * never stored. */
+int ape_unet_conv3x3_seghead_bf16(const float* a, int lda, int C1, const float* b, int ldb, int C2, const void* w_packed,
+                                  const float* bias, int C, uint8_t* label, float* score, int B, int H, int W, int ups, int nsplit,
+                                  int double_softmax, void* stream);
+/* F.interpolate(x, scale_factor=2, mode='nearest') (smp DecoderBlock, the materialised route; scale 1: a plain copy, for the skip half):
+ * x[B][h][w][C] -> y[B][scale h][scale w][ldy] channels yoff .. yoff + C - 1 (C, ldy, yoff multiples of 4), i.e. straight into one
+ * channel window of the concatenation buffer. */
+int ape_nearest_upsample_nhwc_f32(const float* x, float* y, int B, int h, int w, int C, int scale, int ldy, int yoff, void* stream);
+
 
 /* ---- training step: the backward kernels behind DenseFusion/tools/train.py:205-238 -------------------
  * `loss.backward()` / `dis.backward()` there run torch autograd over cuDNN; each entry below is one backward rule of the ops
