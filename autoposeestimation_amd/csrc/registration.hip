@@ -1,0 +1,546 @@
+// Global registration kernels (reference pc_reconstruction/open3d_utils.py:19-49: FPFH features of both down-sampled clouds, then RANSAC
+// on feature matches before ICP), float64 like the rest of the point-cloud path, restating open3d 0.9 Feature.cpp / Registration.cpp:
+//   fpfh_spfh_kernel     hybrid neighbour list of every point (d^2 < r^2, ordered by (d^2, index), first max_nn) + its SPFH histogram;
+//                        the lists are kept for the second pass (see below)
+//   fpfh_kernel          FPFH = per-sub-histogram normalised sum of the neighbours' SPFH weighted by 1 / d^2, plus the point's own SPFH
+//   feature_nn_kernel    nearest target feature of every source feature (squared L2 over 33 dimensions, exact, ties -> lowest index):
+//                        target tiles in LDS, the target range split over blockIdx.y, partial winners merged in slice order
+//   ransac_hyp_kernel    one RANSAC iteration per thread (seeded splitmix64 draws, edge-length checker, Umeyama, distance checker) and
+//                        an ordered in-block compaction of the passing iteration indices; ransac_append_kernel keeps the first
+//                        max_validation of them in iteration order
+//   ransac_validate_*    every kept hypothesis against the whole source cloud (nearest target within max_correspondence_distance through
+//                        the target's grid), fixed-order sums, then the winner by (fitness desc, rmse asc, iteration asc)
+// The neighbour lists of pass 1 are written out (12 B per entry) rather than recomputed in pass 2: the selection -- min(max_nn, candidates)
+// rounds of a 32-lane shuffle reduction over the candidate list -- is most of pass 1's time, and re-reading 1.2 KB per point is not.
+#include "common.h"
+#include "pc_grid.h"
+
+namespace {
+
+constexpr int kT = 256;
+constexpr int kGroups = kT / kG;          // queries per block in the kG-lanes-per-query kernels
+constexpr int kFeatMaxNN = 128;           // largest max_nn of the FPFH search
+constexpr int kFCand = 256;               // in-radius candidates a group keeps in LDS; more: the selection rounds re-walk the cells
+constexpr int kBins = 33;
+constexpr int kMaxRansacN = 16;
+constexpr int kNNT = 128;                 // source features per block of feature_nn_kernel (one per thread)
+constexpr int kNNTile = 64;               // target features per LDS tile
+
+size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+__device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+__device__ __forceinline__ void cross3(const double* a, const double* b, double* c)
+{
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// open3d ComputePairFeatures: f = (f0 angle, f1, f2, |d|); all zero when the points coincide or d is parallel to the chosen normal
+__device__ void pair_features(const double* p1, const double* n1, const double* p2, const double* n2, double f[4])
+{
+    f[0] = f[1] = f[2] = f[3] = 0.0;
+    double dp[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
+    const double len = sqrt(dot3(dp, dp));
+    if (len == 0.0) return;
+    const double a1 = dot3(n1, dp) / len, a2 = dot3(n2, dp) / len;
+    const double* m1 = n1;
+    const double* m2 = n2;
+    double f2;
+    if (acos(fabs(a1)) > acos(fabs(a2))) {
+        m1 = n2; m2 = n1;
+        dp[0] = -dp[0]; dp[1] = -dp[1]; dp[2] = -dp[2];
+        f2 = -a2;
+    } else {
+        f2 = a1;
+    }
+    double v[3], w[3];
+    cross3(dp, m1, v);
+    const double vn = sqrt(dot3(v, v));
+    if (vn == 0.0) return;
+    v[0] /= vn; v[1] /= vn; v[2] /= vn;
+    cross3(m1, v, w);
+    f[3] = len;
+    f[2] = f2;
+    f[1] = dot3(v, m2);
+    f[0] = atan2(dot3(w, m2), dot3(m1, m2));
+}
+
+__device__ __forceinline__ int bin11(double x)
+{
+    const double v = floor(x);
+    if (!(v >= 0.0)) return 0;
+    return v >= 10.0 ? 10 : (int)v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// FPFH pass 1: kG lanes per point (as normals_kernel in pointcloud.hip).  The in-radius candidates of the 27 cells go to the group's LDS
+// list; cnt = min(max_nn, candidates) rounds take the smallest (d^2, original index) after the last one taken.  Entry 0 (the point
+// itself) is skipped like open3d does; every further entry adds 100 / (cnt - 1) to three bins, summed in list order by the bin's lane.
+__global__ __launch_bounds__(kT) void fpfh_spfh_kernel(Grid g, const double* __restrict__ pts, const double* __restrict__ nrm, int n, double r2,
+                                                       int max_nn, int* __restrict__ nbr, double* __restrict__ nbr_d2, int* __restrict__ nbr_cnt,
+                                                       double* __restrict__ spfh)
+{
+    __shared__ double cand_d[kGroups][kFCand];
+    __shared__ int cand_o[kGroups][kFCand];
+    __shared__ int sel[kGroups][kFeatMaxNN];
+    __shared__ unsigned char bins[kGroups][kFeatMaxNN][3];
+    __shared__ int ncand[kGroups];
+    const int lane = threadIdx.x % kG, grp = threadIdx.x / kG;
+    const int i = (blockIdx.x * kT + threadIdx.x) / kG;
+    const bool valid = i < n;
+    if (lane == 0) ncand[grp] = 0;
+    __syncthreads();
+    double q[3] = {0, 0, 0};
+    if (valid) {
+        for (int d = 0; d < 3; ++d) q[d] = pts[(size_t)i * 3 + d];
+        for_my_cell(g, q, lane, [&](int j, double d2) {
+            if (d2 >= r2) return;
+            const int p = atomicAdd(&ncand[grp], 1);
+            if (p < kFCand) { cand_d[grp][p] = d2; cand_o[grp][p] = (int)g.order[j]; }
+        });
+    }
+    __syncthreads();
+    const int nc = ncand[grp];
+    const bool listed = nc <= kFCand;
+    const int cnt = valid ? (nc < max_nn ? nc : max_nn) : 0;
+    double last_d = -1.0;
+    int last_o = -1;
+    for (int r = 0; r < cnt; ++r) {
+        double bd = 1e300;
+        int bo = 0x7fffffff;
+        auto offer = [&](int o, double d) {
+            const bool after = d > last_d || (d == last_d && o > last_o);
+            if (after && (d < bd || (d == bd && o < bo))) { bd = d; bo = o; }
+        };
+        if (listed) for (int p = lane; p < nc; p += kG) offer(cand_o[grp][p], cand_d[grp][p]);
+        else for_my_cell(g, q, lane, [&](int j, double d2) { if (d2 < r2) offer((int)g.order[j], d2); });
+        for (int m = kG / 2; m >= 1; m >>= 1) {
+            const double od = __shfl_xor(bd, m, kG);
+            const int oo = __shfl_xor(bo, m, kG);
+            if (od < bd || (od == bd && oo < bo)) { bd = od; bo = oo; }
+        }
+        last_d = bd; last_o = bo;
+        if (lane == 0) {
+            sel[grp][r] = bo;
+            nbr[(size_t)i * max_nn + r] = bo;
+            nbr_d2[(size_t)i * max_nn + r] = bd;
+        }
+    }
+    if (valid && lane == 0) nbr_cnt[i] = cnt;
+    __syncthreads();
+    if (cnt > 1) {
+        double ni[3];
+        for (int d = 0; d < 3; ++d) ni[d] = nrm[(size_t)i * 3 + d];
+        for (int k = 1 + lane; k < cnt; k += kG) {
+            const int o = sel[grp][k];
+            double f[4];
+            pair_features(q, ni, pts + (size_t)o * 3, nrm + (size_t)o * 3, f);
+            bins[grp][k][0] = (unsigned char)bin11(11.0 * (f[0] + M_PI) / (2.0 * M_PI));
+            bins[grp][k][1] = (unsigned char)(11 + bin11(11.0 * (f[1] + 1.0) * 0.5));
+            bins[grp][k][2] = (unsigned char)(22 + bin11(11.0 * (f[2] + 1.0) * 0.5));
+        }
+    }
+    __syncthreads();
+    if (valid) {
+        const double incr = cnt > 1 ? 100.0 / (double)(cnt - 1) : 0.0;
+        for (int b = lane; b < kBins; b += kG) {
+            double h = 0.0;
+            for (int k = 1; k < cnt; ++k) if (bins[grp][k][b / 11] == b) h += incr;
+            spfh[(size_t)i * kBins + b] = h;
+        }
+    }
+}
+
+// FPFH pass 2: lane b sums SPFH_k[b] / d^2_k over the list in order (d^2 = 0 skipped), each 11-bin block is scaled to 100, then SPFH_i is
+// added.  Points with at most one list entry get zeros.
+__global__ __launch_bounds__(kT) void fpfh_kernel(const int* __restrict__ nbr, const double* __restrict__ nbr_d2, const int* __restrict__ nbr_cnt,
+                                                  const double* __restrict__ spfh, int n, int max_nn, double* __restrict__ out)
+{
+    __shared__ double F[kGroups][kBins];
+    const int lane = threadIdx.x % kG, grp = threadIdx.x / kG;
+    const int i = (blockIdx.x * kT + threadIdx.x) / kG;
+    const bool valid = i < n;
+    const int cnt = valid ? nbr_cnt[i] : 0;
+    for (int b = lane; b < kBins; b += kG) {
+        double acc = 0.0;
+        for (int k = 1; k < cnt; ++k) {
+            const double d = nbr_d2[(size_t)i * max_nn + k];
+            if (d == 0.0) continue;
+            acc += spfh[(size_t)nbr[(size_t)i * max_nn + k] * kBins + b] / d;
+        }
+        F[grp][b] = acc;
+    }
+    __syncthreads();
+    if (!valid) return;
+    for (int b = lane; b < kBins; b += kG) {
+        double v = 0.0;
+        if (cnt > 1) {
+            const int b0 = b / 11 * 11;
+            double s = 0.0;
+            for (int j = 0; j < 11; ++j) s += F[grp][b0 + j];
+            const double sc = s != 0.0 ? 100.0 / s : 0.0;
+            v = F[grp][b] * sc + spfh[(size_t)i * kBins + b];
+        }
+        out[(size_t)i * kBins + b] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// nearest feature: blockIdx.y takes target slice [y * slice, min(nt, (y + 1) * slice)); d = sum_j (a_j - b_j)^2 in j order; strict < in
+// ascending target order keeps the lowest index of a tie, and so does the slice-ordered merge
+__global__ __launch_bounds__(kNNT) void feature_nn_kernel(const double* __restrict__ src, int ns, const double* __restrict__ tgt, int nt, int slice,
+                                                          double* __restrict__ part_d, int* __restrict__ part_i)
+{
+    __shared__ double tile[kNNTile][kBins];
+    const int s = blockIdx.x * kNNT + threadIdx.x;
+    const bool valid = s < ns;
+    double a[kBins];
+#pragma unroll
+    for (int j = 0; j < kBins; ++j) a[j] = valid ? src[(size_t)s * kBins + j] : 0.0;
+    const int t0 = blockIdx.y * slice;
+    const int t1 = min(nt, t0 + slice);
+    double best = INFINITY;
+    int bi = -1;
+    for (int tb = t0; tb < t1; tb += kNNTile) {
+        const int m = min(kNNTile, t1 - tb);
+        __syncthreads();
+        for (int e = threadIdx.x; e < m * kBins; e += kNNT) tile[e / kBins][e % kBins] = tgt[(size_t)tb * kBins + e];
+        __syncthreads();
+        if (!valid) continue;
+        for (int k = 0; k < m; ++k) {
+            double d = 0.0;
+#pragma unroll
+            for (int j = 0; j < kBins; ++j) { const double e = a[j] - tile[k][j]; d += e * e; }
+            if (d < best) { best = d; bi = tb + k; }
+        }
+    }
+    if (valid) { part_d[(size_t)blockIdx.y * ns + s] = best; part_i[(size_t)blockIdx.y * ns + s] = bi; }
+}
+
+__global__ void feature_nn_merge_kernel(const double* __restrict__ part_d, const int* __restrict__ part_i, int ns, int nslice, int* __restrict__ nn)
+{
+    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < ns; s += gridDim.x * blockDim.x) {
+        double best = part_d[s];
+        int bi = part_i[s];
+        for (int y = 1; y < nslice; ++y) {
+            const double d = part_d[(size_t)y * ns + s];
+            if (d < best) { best = d; bi = part_i[(size_t)y * ns + s]; }
+        }
+        nn[s] = bi;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// RANSAC (open3d 0.9 RegistrationRANSACBasedOnFeatureMatching with a seeded sampler instead of rand())
+struct Hyp {
+    const double* src; int ns;
+    const double* tgt; int nt;
+    const int* nn;              // [ns] nearest target feature of every source feature
+    int ransac_n;
+    u64 seed;
+    double edge_sim;            // < 0: no edge-length checker
+    double dist_thr;            // < 0: no distance checker
+};
+
+__device__ __forceinline__ u64 splitmix64(u64 x)
+{
+    u64 z = x + 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+// iteration `it`: draw, check, estimate; T[12] = rows 0..2 of the 4x4.  With checks = false only the draw and the estimate run (the
+// validation recomputes the transformations of the kept iterations this way)
+__device__ bool ransac_hypothesis(const Hyp& h, int it, bool checks, double T[12])
+{
+    int s[kMaxRansacN], t[kMaxRansacN];
+    const int rn = h.ransac_n;
+    for (int j = 0; j < rn; ++j) {
+        s[j] = (int)(splitmix64((h.seed << 32) ^ (u64)((long long)it * rn + j)) % (u64)h.ns);
+        t[j] = h.nn[s[j]];
+        if (t[j] < 0 || t[j] >= h.nt) return false;
+    }
+    if (checks && h.edge_sim >= 0.0)                     // CorrespondenceCheckerBasedOnEdgeLength: every pair of edges
+        for (int a = 0; a < rn; ++a)
+            for (int b = a + 1; b < rn; ++b) {
+                const double* sa = h.src + (size_t)s[a] * 3; const double* sb = h.src + (size_t)s[b] * 3;
+                const double* ta = h.tgt + (size_t)t[a] * 3; const double* tb = h.tgt + (size_t)t[b] * 3;
+                const double es[3] = {sa[0] - sb[0], sa[1] - sb[1], sa[2] - sb[2]}, et[3] = {ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2]};
+                const double ds = sqrt(dot3(es, es)), dt = sqrt(dot3(et, et));
+                if (ds < dt * h.edge_sim || dt < ds * h.edge_sim) return false;
+            }
+    // Eigen::umeyama without scaling: C = (1/n) sum (t - mu_t)(s - mu_s)^T, R from its SVD, t = mu_t - R mu_s
+    double mu_s[3] = {0, 0, 0}, mu_t[3] = {0, 0, 0};
+    for (int j = 0; j < rn; ++j)
+        for (int d = 0; d < 3; ++d) { mu_s[d] += h.src[(size_t)s[j] * 3 + d]; mu_t[d] += h.tgt[(size_t)t[j] * 3 + d]; }
+    for (int d = 0; d < 3; ++d) { mu_s[d] /= (double)rn; mu_t[d] /= (double)rn; }
+    double C[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, R[3][3];
+    for (int j = 0; j < rn; ++j) {
+        double es[3], et[3];
+        for (int d = 0; d < 3; ++d) { es[d] = h.src[(size_t)s[j] * 3 + d] - mu_s[d]; et[d] = h.tgt[(size_t)t[j] * 3 + d] - mu_t[d]; }
+        for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) C[a][b] += et[a] * es[b];
+    }
+    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) C[a][b] /= (double)rn;
+    svd3_rotation(C, R);
+    for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b) T[a * 4 + b] = R[a][b];
+        T[a * 4 + 3] = mu_t[a] - ((R[a][0] * mu_s[0] + R[a][1] * mu_s[1]) + R[a][2] * mu_s[2]);
+    }
+    if (checks && h.dist_thr >= 0.0)                     // CorrespondenceCheckerBasedOnDistance: |t - T s| <= thr for every pair
+        for (int j = 0; j < rn; ++j) {
+            const double* p = h.src + (size_t)s[j] * 3;
+            const double* q = h.tgt + (size_t)t[j] * 3;
+            double e[3];
+            for (int a = 0; a < 3; ++a) e[a] = q[a] - (((T[a * 4] * p[0] + T[a * 4 + 1] * p[1]) + T[a * 4 + 2] * p[2]) + T[a * 4 + 3]);
+            if (sqrt(dot3(e, e)) > h.dist_thr) return false;
+        }
+    return true;
+}
+
+// iterations [it0, it0 + n_it): block b writes its passing iterations in order to blist[b][0..bcount[b]); a no-op once n_kept is full
+__global__ __launch_bounds__(kT) void ransac_hyp_kernel(Hyp h, int it0, int n_it, const int* __restrict__ n_kept, int max_validation,
+                                                        int* __restrict__ blist, int* __restrict__ bcount)
+{
+    if (*n_kept >= max_validation) return;
+    __shared__ int wc[kT / 64];
+    const int gid = blockIdx.x * kT + threadIdx.x;
+    double T[12];
+    const bool pass = gid < n_it && ransac_hypothesis(h, it0 + gid, true, T);
+    const unsigned long long m = __ballot(pass);
+    const int wave = threadIdx.x / 64, wl = threadIdx.x % 64;
+    if (wl == 0) wc[wave] = __popcll(m);
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int w = 0; w < kT / 64; ++w) { off += w < wave ? wc[w] : 0; tot += wc[w]; }
+    if (pass) blist[(size_t)blockIdx.x * kT + off + __popcll(m & ((1ULL << wl) - 1ULL))] = it0 + gid;
+    if (threadIdx.x == 0) bcount[blockIdx.x] = tot;
+}
+
+// one block: appends the blocks' lists in block order to kept[*n_kept ..] up to max_validation entries
+__global__ __launch_bounds__(kT) void ransac_append_kernel(const int* __restrict__ blist, const int* __restrict__ bcount, int nb, int max_validation,
+                                                           int* __restrict__ kept, int* __restrict__ n_kept)
+{
+    const int base = *n_kept;
+    if (base >= max_validation) return;
+    __shared__ int pre[kT + 1];
+    const int per = (nb + kT - 1) / kT;
+    const int b0 = min(nb, (int)threadIdx.x * per), b1 = min(nb, b0 + per);
+    int s = 0;
+    for (int b = b0; b < b1; ++b) s += bcount[b];
+    pre[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int k = 0; k < kT; ++k) { const int v = pre[k]; pre[k] = run; run += v; }
+        pre[kT] = run;
+    }
+    __syncthreads();
+    int off = base + pre[threadIdx.x];
+    for (int b = b0; b < b1 && off < max_validation; ++b) {
+        const int c = bcount[b];
+        for (int r = 0; r < c && off + r < max_validation; ++r) kept[off + r] = blist[(size_t)b * kT + r];
+        off += c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) *n_kept = min(max_validation, base + pre[kT]);
+}
+
+// the transformation of every kept iteration (rows 0..2)
+__global__ void ransac_models_kernel(Hyp h, const int* __restrict__ kept, int nh, double* __restrict__ T12)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nh) return;
+    double T[12];
+    ransac_hypothesis(h, kept[k], false, T);
+    for (int e = 0; e < 12; ++e) T12[(size_t)k * 12 + e] = T[e];
+}
+
+// blockIdx.y = hypothesis, blockIdx.x strides over the source (kGroups points per pass, kG lanes each, as nn1_group_kernel); the group's
+// lane 0 accumulates its points' count / sum d^2 in order, the block reduces its groups in order -> part[h][bx][2]
+__global__ __launch_bounds__(kT) void ransac_validate_kernel(Grid g, const double* __restrict__ src, int ns, const double* __restrict__ T12, double r2,
+                                                             double* __restrict__ part)
+{
+    __shared__ double sc[kGroups], sd[kGroups];
+    const int lane = threadIdx.x % kG, grp = threadIdx.x / kG;
+    const double* T = T12 + (size_t)blockIdx.y * 12;
+    double cnt = 0.0, sum = 0.0;
+    for (int base = blockIdx.x * kGroups; base < ns; base += gridDim.x * kGroups) {
+        const int i = base + grp;
+        if (i >= ns) continue;
+        const double x = src[(size_t)i * 3], y = src[(size_t)i * 3 + 1], z = src[(size_t)i * 3 + 2];
+        double q[3];
+        for (int r = 0; r < 3; ++r) q[r] = ((T[r * 4] * x + T[r * 4 + 1] * y) + T[r * 4 + 2] * z) + T[r * 4 + 3];
+        double best = r2;
+        bool found = false;
+        for_my_cell(g, q, lane, [&](int, double d2) { if (d2 < best) { best = d2; found = true; } });
+        for (int m = kG / 2; m >= 1; m >>= 1) {
+            const double ob = __shfl_xor(best, m, kG);
+            const int of = __shfl_xor((int)found, m, kG);
+            if (of && (!found || ob < best)) { best = ob; found = true; }
+        }
+        if (found) { cnt += 1.0; sum += best; }
+    }
+    if (lane == 0) { sc[grp] = cnt; sd[grp] = sum; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double c = 0.0, s = 0.0;
+        for (int k = 0; k < kGroups; ++k) { c += sc[k]; s += sd[k]; }
+        part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2] = c;
+        part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 + 1] = s;
+    }
+}
+
+// one block: fitness / rmse of every hypothesis (partials summed in block order), then the winner in iteration order, replaced only by a
+// strictly better one (open3d IsBetterRANSACThan) starting from (identity, 0, 0).  out: [0..15] T, [16] fitness, [17] rmse,
+// [18] correspondences, [19] winner's position in `kept` (-1: none), [20] its iteration index (-1: none)
+__global__ __launch_bounds__(kT) void ransac_select_kernel(const double* __restrict__ part, int G, int nh, int ns, const double* __restrict__ T12,
+                                                           const int* __restrict__ kept, double* __restrict__ fr, double* __restrict__ out)
+{
+    for (int k = threadIdx.x; k < nh; k += kT) {
+        double c = 0.0, s = 0.0;
+        for (int b = 0; b < G; ++b) { c += part[((size_t)k * G + b) * 2]; s += part[((size_t)k * G + b) * 2 + 1]; }
+        fr[(size_t)k * 3] = c / (double)ns;
+        fr[(size_t)k * 3 + 1] = c > 0.0 ? sqrt(s / c) : 0.0;
+        fr[(size_t)k * 3 + 2] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double bf = 0.0, br = 0.0, bc = 0.0;
+    int bk = -1;
+    for (int k = 0; k < nh; ++k) {
+        const double f = fr[(size_t)k * 3], r = fr[(size_t)k * 3 + 1];
+        if (f > bf || (f == bf && r < br)) { bf = f; br = r; bc = fr[(size_t)k * 3 + 2]; bk = k; }
+    }
+    for (int e = 0; e < 16; ++e) out[e] = (e % 5 == 0) ? 1.0 : 0.0;
+    if (bk >= 0) for (int e = 0; e < 12; ++e) out[e] = T12[(size_t)bk * 12 + e];
+    out[16] = bf; out[17] = br; out[18] = bc; out[19] = bk; out[20] = bk >= 0 ? (double)kept[bk] : -1.0;
+}
+
+int validate_blocks(int ns)
+{
+    const int g = ape::ceil_div(ns, kGroups);
+    return g < 1 ? 1 : (g > 64 ? 64 : g);
+}
+
+int nn_slices(int ns, int nt)
+{
+    const int bx = ape::ceil_div(ns, kNNT);
+    const int max_s = ape::ceil_div(nt, kNNTile);
+    int s = ape::ceil_div(2048, bx);
+    return s < 1 ? 1 : (s > max_s ? max_s : s);
+}
+
+}  // namespace
+
+#define GRID_ARGS const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n, double cell
+#define MAKE_GRID Grid g{sorted, (const u64*)keys, order, origin3, n, cell}
+
+extern "C" size_t ape_fpfh_workspace_bytes(int n, int max_nn)
+{
+    if (n < 1) n = 1;
+    if (max_nn < 1) max_nn = 1;
+    return align_up((size_t)n * max_nn * 4) + align_up((size_t)n * max_nn * 8) + align_up((size_t)n * 4) + align_up((size_t)n * kBins * 8);
+}
+
+extern "C" int ape_fpfh_f64(GRID_ARGS, const double* pts, const double* normals, double radius, int max_nn, double* feature, void* ws,
+                            size_t ws_bytes, void* stream)
+{
+    if (!sorted || !keys || !order || !origin3 || !pts || !normals || !feature || !ws || n < 1 || !(radius > 0) || radius > cell ||
+        max_nn < 1 || max_nn > kFeatMaxNN)
+        return APE_EINVAL;
+    if (ws_bytes < ape_fpfh_workspace_bytes(n, max_nn)) return APE_EWORKSPACE;
+    MAKE_GRID;
+    char* p = (char*)ws;
+    int* nbr = (int*)p;          p += align_up((size_t)n * max_nn * 4);
+    double* nbr_d2 = (double*)p; p += align_up((size_t)n * max_nn * 8);
+    int* cnt = (int*)p;          p += align_up((size_t)n * 4);
+    double* spfh = (double*)p;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = ape::ceil_div((long)n * kG, (long)kT);
+    hipLaunchKernelGGL(fpfh_spfh_kernel, dim3(blocks), dim3(kT), 0, st, g, pts, normals, n, radius * radius, max_nn, nbr, nbr_d2, cnt, spfh);
+    hipLaunchKernelGGL(fpfh_kernel, dim3(blocks), dim3(kT), 0, st, (const int*)nbr, (const double*)nbr_d2, (const int*)cnt, (const double*)spfh,
+                       n, max_nn, feature);
+    return ape::check_launch("ape_fpfh_f64");
+}
+
+extern "C" size_t ape_feature_nn1_workspace_bytes(int ns, int nt)
+{
+    if (ns < 1) ns = 1;
+    if (nt < 1) nt = 1;
+    const size_t s = (size_t)nn_slices(ns, nt);
+    return align_up(s * ns * 8) + align_up(s * ns * 4);
+}
+
+extern "C" int ape_feature_nn1_f64(const double* src_feature, int ns, const double* tgt_feature, int nt, int* nn, void* ws, size_t ws_bytes,
+                                   void* stream)
+{
+    if (!src_feature || !tgt_feature || !nn || !ws || ns < 0 || nt < 1) return APE_EINVAL;
+    if (ns == 0) return APE_OK;
+    if (ws_bytes < ape_feature_nn1_workspace_bytes(ns, nt)) return APE_EWORKSPACE;
+    const int nslice0 = nn_slices(ns, nt);
+    const int slice = ape::ceil_div(ape::ceil_div(nt, nslice0), kNNTile) * kNNTile;
+    const int nslice = ape::ceil_div(nt, slice);
+    double* part_d = (double*)ws;
+    int* part_i = (int*)((char*)ws + align_up((size_t)nslice0 * ns * 8));
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(feature_nn_kernel, dim3(ape::ceil_div(ns, kNNT), nslice), dim3(kNNT), 0, st, src_feature, ns, tgt_feature, nt, slice, part_d, part_i);
+    hipLaunchKernelGGL(feature_nn_merge_kernel, dim3(ape::ceil_div(ns, kT) > 1024 ? 1024 : ape::ceil_div(ns, kT)), dim3(kT), 0, st,
+                       (const double*)part_d, (const int*)part_i, ns, nslice, nn);
+    return ape::check_launch("ape_feature_nn1_f64");
+}
+
+extern "C" size_t ape_ransac_workspace_bytes(int ns, int chunk, int max_validation)
+{
+    if (ns < 1) ns = 1;
+    if (chunk < 1) chunk = 1;
+    if (max_validation < 1) max_validation = 1;
+    const size_t nb = (size_t)ape::ceil_div(chunk, kT);
+    return align_up(nb * kT * 4) + align_up(nb * 4) + align_up((size_t)max_validation * 12 * 8) +
+           align_up((size_t)max_validation * validate_blocks(ns) * 2 * 8) + align_up((size_t)max_validation * 3 * 8);
+}
+
+extern "C" int ape_ransac_hypotheses_f64(const double* src, int ns, const double* tgt, int nt, const int* nn, int ransac_n, long seed,
+                                         double edge_sim, double dist_thr, int it_begin, int n_it, int max_validation, int* kept, int* n_kept,
+                                         void* ws, size_t ws_bytes, void* stream)
+{
+    if (!src || !tgt || !nn || !kept || !n_kept || !ws || ns < 1 || nt < 1 || ransac_n < 3 || ransac_n > kMaxRansacN || it_begin < 0 ||
+        n_it < 0 || max_validation < 1)
+        return APE_EINVAL;
+    if (n_it == 0) return APE_OK;
+    if (ws_bytes < ape_ransac_workspace_bytes(ns, n_it, max_validation)) return APE_EWORKSPACE;
+    const int nb = ape::ceil_div(n_it, kT);
+    int* blist = (int*)ws;
+    int* bcount = (int*)((char*)ws + align_up((size_t)nb * kT * 4));
+    const Hyp h{src, ns, tgt, nt, nn, ransac_n, (u64)seed, edge_sim, dist_thr};
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ransac_hyp_kernel, dim3(nb), dim3(kT), 0, st, h, it_begin, n_it, (const int*)n_kept, max_validation, blist, bcount);
+    hipLaunchKernelGGL(ransac_append_kernel, dim3(1), dim3(kT), 0, st, (const int*)blist, (const int*)bcount, nb, max_validation, kept, n_kept);
+    return ape::check_launch("ape_ransac_hypotheses_f64");
+}
+
+extern "C" int ape_ransac_validate_f64(GRID_ARGS, const double* src, int ns, const double* tgt, int nt, const int* nn, int ransac_n,
+                                       long seed, const int* kept, int n_kept, double max_dist, double* result, double* fit_rmse,
+                                       void* ws, size_t ws_bytes, void* stream)
+{
+    if (!sorted || !keys || !order || !origin3 || !src || !tgt || !nn || !result || !ws || n < 1 || ns < 1 || nt != n || ransac_n < 3 ||
+        ransac_n > kMaxRansacN || n_kept < 0 || n_kept > 65535 || (n_kept > 0 && !kept) || !(max_dist > 0) || max_dist > cell)
+        return APE_EINVAL;
+    const int mv = n_kept < 1 ? 1 : n_kept;
+    if (ws_bytes < ape_ransac_workspace_bytes(ns, 1, mv)) return APE_EWORKSPACE;
+    char* p = (char*)ws + align_up((size_t)kT * 4) + align_up(4);
+    double* T12 = (double*)p;  p += align_up((size_t)mv * 12 * 8);
+    double* part = (double*)p; p += align_up((size_t)mv * validate_blocks(ns) * 2 * 8);
+    double* fr = fit_rmse ? fit_rmse : (double*)p;
+    MAKE_GRID;
+    const Hyp h{src, ns, tgt, nt, nn, ransac_n, (u64)seed, -1.0, -1.0};
+    hipStream_t st = (hipStream_t)stream;
+    const int G = validate_blocks(ns);
+    if (n_kept > 0) {
+        hipLaunchKernelGGL(ransac_models_kernel, dim3(ape::ceil_div(n_kept, 64)), dim3(64), 0, st, h, kept, n_kept, T12);
+        hipLaunchKernelGGL(ransac_validate_kernel, dim3(G, n_kept), dim3(kT), 0, st, g, src, ns, (const double*)T12, max_dist * max_dist, part);
+    }
+    hipLaunchKernelGGL(ransac_select_kernel, dim3(1), dim3(kT), 0, st, (const double*)part, G, n_kept, ns, (const double*)T12, kept, fr, result);
+    return ape::check_launch("ape_ransac_validate_f64");
+}

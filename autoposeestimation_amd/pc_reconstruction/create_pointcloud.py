@@ -65,12 +65,13 @@ def fuse_direction(views, intr, point_cloud_tf=None, **kw):
     return cloud, tfs
 
 
-def finish_object(point_clouds, min_friends=20, min_dist=5, nb_neighbors=20, voxel_size=2, voxel_size_out=5, threshold=10):
+def finish_object(point_clouds, min_friends=20, min_dist=5, nb_neighbors=20, voxel_size=2, voxel_size_out=5, threshold=10,
+                  global_regression=False):
     """reference :331-376: align the per-directory clouds, then derive the three exported clouds: `<obj>_out` (robot
     frame), `<obj>` (centred, voxel_size_out) and the >= 1000-point `<obj>.xyz` model cloud used by DenseFusion (voxel grown
     in 0.1 steps until fewer than 1000 points would remain).  Returns (out, centred_down, xyz ndarray)."""
     out = utils.align_point_clouds(point_clouds, min_friends=min_friends, min_dist=min_dist, nb_neighbors=nb_neighbors,
-                                   voxel_size=voxel_size, threshold=threshold)
+                                   voxel_size=voxel_size, threshold=threshold, global_regression=global_regression)
     down = out.voxel_down_sample(voxel_size=voxel_size_out)
     down.translate(translation=-utils.get_my_source_center(down))
     big = out.clone()
@@ -149,7 +150,7 @@ def load_point_cloud(object_name, save_dir, root, reference_point=np.array([0, 0
     # all directories at once: per-view work of every chain over all ranks, one all-gather, then the owners fuse side by side
     fused = utils.fuse_chains(chains, intr, voxel_size=voxel_size, threshold=threshold, min_friends=min_friends, min_dist=min_dist,
                               nb_neighbors=nb_neighbors, icp_point2point=icp_point2point, icp_point2plane=icp_point2plane,
-                              dist=dist if dist_on else None)
+                              dist=dist if dist_on else None, global_regression=global_regression)
     def export_mine():
         mine = []
         for di in sorted(fused):
@@ -170,7 +171,8 @@ def load_point_cloud(object_name, save_dir, root, reference_point=np.array([0, 0
         return None
     point_clouds = [pc.PointCloud(p) for p in sets]
     out, down, xyz = finish_object(point_clouds, min_friends=min_friends, min_dist=min_dist, nb_neighbors=nb_neighbors,
-                                   voxel_size=voxel_size, voxel_size_out=voxel_size_out, threshold=threshold)
+                                   voxel_size=voxel_size, voxel_size_out=voxel_size_out, threshold=threshold,
+                                   global_regression=global_regression)
     for ext in ("pcd", "ply"):
         pc.write_point_cloud(os.path.join(pcd_path, "{}_out.{}".format(object_name, ext)), out)
         pc.write_point_cloud(os.path.join(pcd_path, "{}.{}".format(object_name, ext)), down)

@@ -56,11 +56,29 @@ from autoposeestimation_amd.pc_reconstruction import pointcloud as _pc  # noqa: 
 
 def preprocess_point_cloud(pcd, voxel_size):
     """reference :19-33.  Down-sample + normals (hybrid radius 2*voxel, max_nn 30).  The FPFH feature the reference also
-    computes (:29-32) is only consumed by the global RANSAC registration, which every caller disables
-    (main.py:177, create_labels.py:229) -- it is returned as None."""
+    computes (:29-32) is only consumed by the global RANSAC registration, which the callers disable by default
+    (main.py:177, create_labels.py:229) -- it is returned as None, and execute_global_registration computes it
+    when it is needed."""
     pcd_down = pcd.voxel_down_sample(voxel_size)
     pcd_down.estimate_normals(_pc.KDTreeSearchParamHybrid(radius=voxel_size * 2, max_nn=30))
     return pcd_down, None
+
+
+def execute_global_registration(source_down, target_down, source_fpfh, target_fpfh, voxel_size):
+    """reference :36-49: RANSAC on FPFH matches, distance threshold 1.5 * voxel, ransac_n 4, edge-length (0.9) and distance checkers,
+    4 000 000 iterations / 500 validations.  A None feature is computed here (radius 5 * voxel, max_nn 100, as :28-32), so
+    reference-shaped code that passes preprocess_point_cloud's features works.  Seeded and reproducible (pointcloud.
+    registration_ransac_based_on_feature_matching)."""
+    distance_threshold = voxel_size * 1.5
+    param = _pc.KDTreeSearchParamHybrid(radius=voxel_size * 5, max_nn=100)
+    if source_fpfh is None:
+        source_fpfh = _pc.compute_fpfh_feature(source_down, param)
+    if target_fpfh is None:
+        target_fpfh = _pc.compute_fpfh_feature(target_down, param)
+    return _pc.registration_ransac_based_on_feature_matching(
+        source_down, target_down, source_fpfh, target_fpfh, distance_threshold, _pc.TransformationEstimationPointToPoint(False), 4,
+        [_pc.CorrespondenceCheckerBasedOnEdgeLength(0.9), _pc.CorrespondenceCheckerBasedOnDistance(distance_threshold)],
+        _pc.RANSACConvergenceCriteria(4000000, 500))
 
 
 def refine_registration(source, target, result_ransac, voxel_size):
@@ -72,12 +90,13 @@ def refine_registration(source, target, result_ransac, voxel_size):
 def icp_regression(target, source, voxel_size=5, threshold=100, global_regression=False, icp_point2point=True,
                    icp_point2plane=True, plot=False):
     """reference :63-122.  Returns (target_down, source_down, T); like the reference, `target` is copied and `source` is not
-    (both are only read).  global_regression (FPFH + RANSAC) is not provided."""
-    if global_regression:
-        raise NotImplementedError("global RANSAC registration is disabled by every caller of the reference and is not built")
+    (both are only read).  global_regression: FPFH features of both down-sampled clouds and RANSAC on their matches
+    (execute_global_registration) give the initial guess of the ICP stages, or the result when both are off."""
     target, _ = preprocess_point_cloud(target.clone(), voxel_size)
     source, _ = preprocess_point_cloud(source, voxel_size)
     init_tf = np.identity(4)
+    if global_regression:
+        init_tf = execute_global_registration(source, target, None, None, voxel_size).transformation
     criteria = _pc.ICPConvergenceCriteria(relative_fitness=1e-2, relative_rmse=1e-2, max_iteration=100)
     if icp_point2point:
         init_tf = _pc.registration_icp(source, target, threshold, init_tf, _pc.TransformationEstimationPointToPoint(),
@@ -126,7 +145,8 @@ def get_surface(label, depth_frame, intr, robot2Cam_ft, min_friends, min_dist, n
     return _post_filter(surface, min_friends, min_dist, nb_neighbors, voxel_size)
 
 
-def fuse_surfaces(surfaces, voxel_size=2, threshold=10, voxel_size_out=None, icp_point2point=True, icp_point2plane=False):
+def fuse_surfaces(surfaces, voxel_size=2, threshold=10, voxel_size_out=None, icp_point2point=True, icp_point2plane=False,
+                  global_regression=False):
     """The sequential accumulation at the heart of load_point_cloud (pc_reconstruction/create_pointcloud.py:288-312) over already
     pre-processed surfaces (PointClouds in view order, empty ones skipped): each is registered to the accumulating cloud, merged, and
     the union is voxel down-sampled.  Order-dependent: one rank runs a chain.  Returns (cloud, [T per surface])."""
@@ -139,7 +159,7 @@ def fuse_surfaces(surfaces, voxel_size=2, threshold=10, voxel_size_out=None, icp
             acc = source
             tfs.append(np.identity(4))
             continue
-        _, _, T = icp_regression(acc, source, voxel_size=voxel_size, threshold=threshold, global_regression=False,
+        _, _, T = icp_regression(acc, source, voxel_size=voxel_size, threshold=threshold, global_regression=global_regression,
                                  icp_point2point=icp_point2point, icp_point2plane=icp_point2plane)
         tfs.append(T)
         merged = _pc.PointCloud(device=acc.device)
@@ -151,14 +171,14 @@ def fuse_surfaces(surfaces, voxel_size=2, threshold=10, voxel_size_out=None, icp
 
 
 def fuse_views(views, intr, voxel_size=2, threshold=10, min_friends=20, min_dist=5, nb_neighbors=20, voxel_size_out=None,
-               icp_point2point=True, icp_point2plane=False, dist=None, owner=0):
+               icp_point2point=True, icp_point2plane=False, dist=None, owner=0, global_regression=False):
     """`views` = sequence of (label u8[H,W], depth [H,W], robot2cam 4x4) of ONE (object, direction) chain (create_pointcloud.py:276-312):
     get_surface per view, then fuse_surfaces.  With a torch.distributed group (`dist`) the per-view get_surface work is sharded over the
     ranks and one padded all-gather hands the surfaces to the chain's `owner`, which fuses them (SURVEY.md 8e; sharding.sharded_chain);
     the other ranks return (None, None).  The result on the owner is bit-identical to the single-rank call."""
     from autoposeestimation_amd import sharding
     make_set, fuse = _chain_workers(intr, voxel_size, threshold, min_friends, min_dist, nb_neighbors, voxel_size_out, icp_point2point,
-                                    icp_point2plane)
+                                    icp_point2plane, global_regression)
     res = sharding.sharded_chain(list(views), make_set, fuse, owner, dist, load=_load_view)
     return res if res is not None else (None, None)
 
@@ -168,7 +188,8 @@ def _load_view(view):
     return view() if callable(view) else view
 
 
-def _chain_workers(intr, voxel_size, threshold, min_friends, min_dist, nb_neighbors, voxel_size_out, icp_point2point, icp_point2plane):
+def _chain_workers(intr, voxel_size, threshold, min_friends, min_dist, nb_neighbors, voxel_size_out, icp_point2point, icp_point2plane,
+                   global_regression=False):
     def make_set(view):
         view = view() if callable(view) else view                           # (already decoded when it came through _load_view)
         label, depth, robot2cam = view[:3]
@@ -183,20 +204,22 @@ def _chain_workers(intr, voxel_size, threshold, min_friends, min_dist, nb_neighb
             c.points = p.to(dev)
             clouds.append(c)
         return fuse_surfaces(clouds, voxel_size=voxel_size, threshold=threshold, voxel_size_out=voxel_size_out,
-                             icp_point2point=icp_point2point, icp_point2plane=icp_point2plane)
+                             icp_point2point=icp_point2point, icp_point2plane=icp_point2plane, global_regression=global_regression)
     return make_set, fuse
 
 
 def fuse_chains(chains, intr, voxel_size=2, threshold=10, min_friends=20, min_dist=5, nb_neighbors=20, voxel_size_out=None,
-                icp_point2point=True, icp_point2plane=False, dist=None):
+                icp_point2point=True, icp_point2plane=False, dist=None, global_regression=False):
     """`fuse_views` for several (object, direction) chains at once (`chains` = list of view lists): the get_surface work of all views
     of all chains is spread over the ranks, one padded all-gather, then every rank runs the sequential fusion of the chains it owns
     (chain i -> rank i % world) -- the chains' ICP sequences proceed in parallel on different GPUs.
-    Returns {chain index: (cloud, [T per view])} for this rank's chains; each is bit-identical to the single-rank fuse_views of it."""
+    Returns {chain index: (cloud, [T per view])} for this rank's chains; each is bit-identical to the single-rank fuse_views of it.
+    global_regression=True runs FPFH + RANSAC before every registration (icp_regression) and takes the sequential per-chain route:
+    the batched lock-step form is ICP only."""
     from autoposeestimation_amd import sharding
     make_set, fuse = _chain_workers(intr, voxel_size, threshold, min_friends, min_dist, nb_neighbors, voxel_size_out, icp_point2point,
-                                    icp_point2plane)
-    if not USE_BATCHED:
+                                    icp_point2plane, global_regression)
+    if not USE_BATCHED or global_regression:
         return sharding.sharded_chains([list(v) for v in chains], make_set, fuse, dist, load=_load_view)
     # lock-step batched form (pc_reconstruction/batched.py): one host thread, one launch per step for all of this rank's views / chains
     from autoposeestimation_amd.pc_reconstruction import batched as B

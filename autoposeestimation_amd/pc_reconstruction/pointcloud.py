@@ -427,6 +427,146 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
     return RegistrationResult(T, fitness, rmse, n_corr)
 
 
+# ---- global registration: FPFH + RANSAC on feature matches (reference open3d_utils.py:19-49; csrc/registration.hip) ------------------
+class Feature:
+    """open3d.registration.Feature: `t` is the device [n, 33] float64 tensor; `.data` copies it to the host as open3d's [33, n]."""
+
+    def __init__(self, t=None, device="cuda"):
+        self.t = torch.zeros(0, 33, dtype=_D, device=device) if t is None else t
+
+    @property
+    def data(self):
+        return np.ascontiguousarray(self.t.cpu().numpy().T)
+
+    def dimension(self):
+        return int(self.t.shape[1])
+
+    def num(self):
+        return int(self.t.shape[0])
+
+
+def compute_fpfh_feature(pcd, search_param):
+    """open3d 0.9 registration::ComputeFPFHFeature with KDTreeSearchParamHybrid(radius, max_nn <= 128); the cloud needs normals.
+    The neighbour list of a point is every point with d^2 < radius^2, ordered by (d^2, index), first max_nn (ape_fpfh_f64)."""
+    n = len(pcd)
+    if n == 0:
+        return Feature(device=pcd.device)
+    if not pcd.has_normals():
+        raise RuntimeError("compute_fpfh_feature requires normals (estimate_normals first)")
+    radius, max_nn = float(search_param.radius), int(search_param.max_nn)
+    g = pcd._grid(radius)
+    out = torch.empty(n, 33, dtype=_D, device=pcd.device)
+    L = _lib.lib()
+    ws = torch.empty(L.ape_fpfh_workspace_bytes(n, max_nn), dtype=torch.uint8, device=pcd.device)
+    _lib.check(L.ape_fpfh_f64(*PointCloud._gargs(g), _lib.dptr(pcd._p, _D), _lib.dptr(pcd._n, _D), radius, max_nn, _lib.dptr(out),
+                              _lib.dptr(ws), ws.numel(), _st()), "ape_fpfh_f64")
+    return Feature(out)
+
+
+class RANSACConvergenceCriteria:
+    def __init__(self, max_iteration=1000, max_validation=1000):
+        self.max_iteration, self.max_validation = max_iteration, max_validation
+
+
+class CorrespondenceCheckerBasedOnEdgeLength:
+    def __init__(self, similarity_threshold=0.9):
+        self.similarity_threshold = similarity_threshold
+
+
+class CorrespondenceCheckerBasedOnDistance:
+    def __init__(self, distance_threshold):
+        self.distance_threshold = distance_threshold
+
+
+_RANSAC_CHUNK = (1 << 14, 1 << 20)   # iterations of the first hypothesis chunk, and the cap the chunk doubles up to
+
+
+def feature_nn(source_feature, target_feature):
+    """index of the nearest target feature of every source feature (squared L2 over the 33 dimensions, ties -> lowest index)"""
+    ns, nt = source_feature.num(), target_feature.num()
+    dev = source_feature.t.device
+    nn = torch.empty(ns, dtype=torch.int32, device=dev)
+    if ns == 0 or nt == 0:
+        return nn.fill_(-1)
+    L = _lib.lib()
+    ws = torch.empty(L.ape_feature_nn1_workspace_bytes(ns, nt), dtype=torch.uint8, device=dev)
+    _lib.check(L.ape_feature_nn1_f64(_lib.dptr(source_feature.t.contiguous(), _D), ns, _lib.dptr(target_feature.t.contiguous(), _D), nt,
+                                     _lib.dptr(nn), _lib.dptr(ws), ws.numel(), _st()), "ape_feature_nn1_f64")
+    return nn
+
+
+def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature, max_correspondence_distance,
+                                                  estimation_method=None, ransac_n=4, checkers=(), criteria=None, seed=0):
+    """open3d 0.9 registration::RegistrationRANSACBasedOnFeatureMatching (reference open3d_utils.py:36-49), on the device.
+
+    Every source point is matched to its nearest target feature once (open3d looks the same mapping up lazily).  Iteration i draws
+    `ransac_n` source indices with replacement, s_ij = splitmix64((seed << 32) ^ (i * ransac_n + j)) mod Ns, and pairs each with its
+    match; the edge-length checkers run, then Umeyama without scaling, then the distance checkers.  The first
+    `criteria.max_validation` passing iterations IN ITERATION ORDER are validated against the whole source cloud (fitness, inlier rmse
+    within max_correspondence_distance); the winner has the highest fitness, then the lowest rmse, then the lowest iteration, and the
+    identity with fitness 0 stands when nothing beats it.  open3d draws with rand() seeded from the clock and its result depends on the
+    thread order; this sampler is seeded and the result reproducible: the same `seed` gives the same transformation bit for bit.
+
+    Only point-to-point estimation without scaling and the edge-length / distance checkers are supported.  The result carries, beside
+    open3d's fields, `validated` (kept iteration indices, host array) and `iterations` (iterations drawn before the last kept one, or
+    all of max_iteration when fewer passed)."""
+    estimation_method = estimation_method if estimation_method is not None else TransformationEstimationPointToPoint(False)
+    if not isinstance(estimation_method, TransformationEstimationPointToPoint):
+        raise NotImplementedError("RANSAC supports TransformationEstimationPointToPoint only")
+    criteria = criteria if criteria is not None else RANSACConvergenceCriteria()
+    edge_sim, dist_thr = -1.0, -1.0
+    for c in checkers:
+        if isinstance(c, CorrespondenceCheckerBasedOnEdgeLength):
+            edge_sim = max(edge_sim, float(c.similarity_threshold))      # every checker must pass: the strictest one decides
+        elif isinstance(c, CorrespondenceCheckerBasedOnDistance):
+            dist_thr = float(c.distance_threshold) if dist_thr < 0 else min(dist_thr, float(c.distance_threshold))
+        else:
+            raise NotImplementedError("correspondence checker %s" % type(c).__name__)
+    empty = RegistrationResult(np.eye(4), 0.0, 0.0, 0)
+    empty.validated, empty.iterations = np.zeros(0, np.int64), 0
+    ransac_n, max_dist = int(ransac_n), float(max_correspondence_distance)
+    if ransac_n < 3 or max_dist <= 0.0:
+        return empty
+    if ransac_n > 16:
+        raise ValueError("ransac_n > 16 is not supported")
+    ns, nt = len(source), len(target)
+    if source_feature.num() != ns or target_feature.num() != nt:
+        raise ValueError("features and clouds differ in size")
+    max_it, max_val = int(criteria.max_iteration), int(criteria.max_validation)
+    if max_val > 65535:
+        raise ValueError("max_validation > 65535 is not supported")
+    if ns == 0 or nt == 0 or max_it <= 0 or max_val <= 0:
+        return empty
+    dev = source.device
+    L = _lib.lib()
+    nn = feature_nn(source_feature, target_feature)
+    chunk, cap = min(_RANSAC_CHUNK[0], max_it), min(_RANSAC_CHUNK[1], max_it)
+    ws = torch.empty(L.ape_ransac_workspace_bytes(ns, max(chunk, cap), max_val), dtype=torch.uint8, device=dev)
+    kept = torch.empty(max_val, dtype=torch.int32, device=dev)
+    n_kept = torch.zeros(1, dtype=torch.int32, device=dev)
+    src, tgt = _lib.dptr(source._p, _D), _lib.dptr(target._p, _D)
+    it, k = 0, 0
+    while it < max_it:                                  # bounded by max_iteration; the device list stops growing once full
+        c = min(chunk, max_it - it)
+        _lib.check(L.ape_ransac_hypotheses_f64(src, ns, tgt, nt, _lib.dptr(nn), ransac_n, int(seed), edge_sim, dist_thr, it, c, max_val,
+                                               _lib.dptr(kept), _lib.dptr(n_kept), _lib.dptr(ws), ws.numel(), _st()),
+                   "ape_ransac_hypotheses_f64")
+        it += c
+        k = int(n_kept.item())
+        if k >= max_val:
+            break
+        chunk = min(chunk * 2, cap)
+    grid = target._grid(max_dist)
+    out = torch.empty(24, dtype=_D, device=dev)
+    _lib.check(L.ape_ransac_validate_f64(*PointCloud._gargs(grid), src, ns, tgt, nt, _lib.dptr(nn), ransac_n, int(seed), _lib.dptr(kept), k,
+                                         max_dist, _lib.dptr(out), None, _lib.dptr(ws), ws.numel(), _st()), "ape_ransac_validate_f64")
+    r = out.cpu().numpy()
+    res = RegistrationResult(r[:16].reshape(4, 4).copy(), float(r[16]), float(r[17]), int(round(r[18])))
+    res.validated = kept[:k].cpu().numpy().astype(np.int64)
+    res.iterations = int(res.validated[-1]) + 1 if k >= max_val else it
+    return res
+
+
 def surface_points(label, depth, intr, robot2cam, device="cuda"):
     """label u8[H,W], depth (integer sensor units) [H,W] -> PointCloud of the valid pixels in the robot frame (mm)."""
     dev = torch.device(device)

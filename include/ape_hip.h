@@ -453,6 +453,40 @@ int ape_icp_run_batch_f64(int kind, int nb, const double* const* sorted, const u
                           int first_call, int* const* corr, double* const* dist2, double* const* sums, double* const* state, void* ws,
                           size_t ws_bytes, void* stream);
 
+/* ---- global registration (reference pc_reconstruction/open3d_utils.py:19-49; open3d 0.9 compute_fpfh_feature and
+ * registration_ransac_based_on_feature_matching), float64, autoposeestimation_amd/csrc/registration.hip ----------------------------
+ * Workspace of ape_fpfh_f64 for a cloud of n points and the given max_nn. */
+size_t ape_fpfh_workspace_bytes(int n, int max_nn);
+/* FPFH feature[n][33] of a cloud with normals (pts / normals [n][3] in the cloud's own order) through its search grid (the GRID args of
+ * ape_grid_build_f64 over the same n points, cell >= radius): hybrid neighbour list d^2 < radius^2, ordered by (d^2, index), first max_nn
+ * (<= 128); SPFH over the list without its entry 0, then FPFH = per 11-bin block normalised sum_k SPFH_k / d^2_k (d^2 != 0) + SPFH_i.
+ * Points with at most one list entry get zeros.  Two launches. */
+int ape_fpfh_f64(const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n, double cell,
+                 const double* pts, const double* normals, double radius, int max_nn, double* feature, void* ws, size_t ws_bytes, void* stream);
+size_t ape_feature_nn1_workspace_bytes(int ns, int nt);
+/* nn[s] = argmin_t sum_j (src_feature[s][j] - tgt_feature[t][j])^2 over the 33 dimensions in j order, fp64, ties -> lowest t. */
+int ape_feature_nn1_f64(const double* src_feature, int ns, const double* tgt_feature, int nt, int* nn, void* ws, size_t ws_bytes, void* stream);
+/* Workspace of the two RANSAC calls below: hypotheses in chunks of up to `chunk` iterations, up to max_validation kept. */
+size_t ape_ransac_workspace_bytes(int ns, int chunk, int max_validation);
+/* RANSAC iterations [it_begin, it_begin + n_it): iteration i draws source s_j = splitmix64(((uint64_t)seed << 32) ^ (i * ransac_n + j)) mod ns,
+ * j < ransac_n (3..16), pairs it with nn[s_j], runs the edge-length checker (edge_sim < 0: none), Umeyama without scaling and the
+ * distance checker (dist_thr < 0: none).  The passing iteration indices are appended IN ITERATION ORDER to kept[*n_kept ..] until
+ * max_validation are kept (kept / n_kept on the device, the caller zeroes *n_kept before the first chunk; a full list makes the call
+ * a no-op).  Two launches. */
+int ape_ransac_hypotheses_f64(const double* src, int ns, const double* tgt, int nt, const int* nn, int ransac_n, long seed,
+                              double edge_sim, double dist_thr, int it_begin, int n_it, int max_validation, int* kept, int* n_kept, void* ws,
+                              size_t ws_bytes, void* stream);
+/* Validation of the n_kept (host count, <= 65535) kept iterations: each one's transformation recomputed, every source point moved by it
+ * and matched to its nearest target within max_dist (d^2 < max_dist^2; the GRID args are the target's, cell >= max_dist, n = nt);
+ * fitness = count / ns, rmse = sqrt(sum d^2 / count) (0 without matches), fixed-order sums.  result[24] on the device: [0..15] the
+ * winner's 4x4 (row major), [16] fitness, [17] rmse, [18] correspondences, [19] its position in kept, [20] its iteration (-1 / -1 and
+ * the identity with fitness 0 when nothing is better than that); the winner has the highest fitness, then the lowest rmse, then the
+ * lowest iteration.  fit_rmse (optional, [n_kept][3] on the device): fitness, rmse, correspondences of every kept iteration. */
+int ape_ransac_validate_f64(const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n,
+                            double cell, const double* src, int ns, const double* tgt, int nt, const int* nn, int ransac_n,
+                            long seed, const int* kept, int n_kept, double max_dist, double* result, double* fit_rmse,
+                            void* ws, size_t ws_bytes, void* stream);
+
 /* ape_conv3x3_halo_bf16 for a 64-channel layer (the segmentor's up_3, pspnet.py:51) with ape_seg_head_f32 fused into its
  * epilogue: the [B][H][W][64] activation is never written, label[B][H][W] u8 / score[B][H][W] f32 are (bit-identical to the
  * unfused pair).  params->Cout must be 64, no residual; params->ups as in ape_conv3x3_halo_bf16. */
