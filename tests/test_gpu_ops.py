@@ -25,9 +25,11 @@ def test_psp_prior_sum_equals_four_accumulating_resizes(shape):
     assert (got.cpu().permute(0, 3, 1, 2) - want).abs().max().item() <= 1e-5
 
 
-@pytest.mark.parametrize("shape", [(3, 1000, 1024), (2, 500, 128), (2, 77, 12), (1, 64, 256), (2, 1000, 6)])
+@pytest.mark.parametrize("shape", [(3, 1000, 1024), (2, 500, 128), (2, 77, 12), (1, 64, 256), (2, 1000, 6),
+                                   (2, 63, 256), (2, 64, 256), (2, 63, 4100), (1, 200, 4100), (2, 64, 10), (1, 100, 4098)])
 def test_mean_rows(shape):
-    """nn.AvgPool1d(num_points) (network.py:51,65,149,166): both the 16-wave float4 kernel and the dword fallback."""
+    """nn.AvgPool1d(num_points) (network.py:51,65,149,166): both the 16-wave float4 kernel and the dword fallback, on both
+    sides of the n = 64 switch, with a ragged last channel chunk (C = 4100) and C % 4 != 0 at n >= 64."""
     from autoposeestimation_amd import engine as E
     b, n, c = shape
     x = torch.randn(b, n, c, generator=torch.Generator().manual_seed(n))
