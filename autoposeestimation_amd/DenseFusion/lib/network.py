@@ -330,8 +330,9 @@ def _dropout2d(x, masks, key, p):
     return x * m[:, None, None, :]
 
 
-def _pspnet_train(mod, prefix, backend, x, masks, precision):
-    """x[B,H,W,4] -> log-softmax embedding [B,H,W,32] (pspnet.py:64-77 in train mode)"""
+def _pspnet_train(mod, prefix, backend, x, masks, precision, logits_only=False):
+    """x[B,H,W,4] -> log-softmax embedding [B,H,W,32] (pspnet.py:64-77 in train mode); logits_only: the `final` conv's output before the
+    log-softmax (the segmentor's head, segmentation/utils.py)"""
     from autoposeestimation_amd import autograd as A
     P = lambda k: mod.param(prefix + k)  # noqa: E731
     cv = lambda *a, **k: A.conv(*a, precision=precision, **k)  # noqa: E731
@@ -358,7 +359,8 @@ def _pspnet_train(mod, prefix, backend, x, masks, precision):
         p = A.PReLUFn.apply(u, P(name + ".conv.2.weight"))
         if dkey is not None:
             p = _dropout2d(p, masks, dkey, 0.15)
-    return A.LogSoftmaxRowsFn.apply(cv(p, P("final.0.weight"), P("final.0.bias")))
+    final = cv(p, P("final.0.weight"), P("final.0.bias"))
+    return final if logits_only else A.LogSoftmaxRowsFn.apply(final)
 
 
 def _feat_train(mod, x4, emb, refine, precision):

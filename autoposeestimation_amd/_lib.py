@@ -143,6 +143,18 @@ SIGNATURES = {
     "ape_ransac_workspace_bytes": [_I, _I, _I],
     "ape_ransac_hypotheses_f64": [_P, _I, _P, _I, _P, _I, _c.c_long, _D, _D, _I, _I, _I, _P, _P, _P, _c.c_size_t, _P],
     "ape_ransac_validate_f64": [_P, _P, _P, _P, _I, _D, _P, _I, _P, _I, _P, _I, _c.c_long, _P, _I, _D, _P, _P, _P, _c.c_size_t, _P],
+    # segmentor training (csrc/segtrain.hip)
+    "ape_bn_workspace_bytes": [_I],
+    "ape_bn_train_fwd_f32": [_P] * 10 + [_c.c_long, _I, _F, _F, _I, _P, _c.c_size_t, _P],
+    "ape_bn_train_bwd_f32": [_P] * 10 + [_c.c_long, _I, _P, _c.c_size_t, _P],
+    "ape_upsample_nearest2x_bwd_f32": [_P, _I, _I, _P, _I, _I, _I, _I, _P],
+    "ape_softmax_rows_f32": [_P, _P, _c.c_long, _I, _P],
+    "ape_softmax_rows_bwd_f32": [_P, _P, _P, _c.c_long, _I, _P],
+    "ape_jaccard_workspace_bytes": [_I, _I],
+    "ape_jaccard_fwd_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _c.c_size_t, _P],
+    "ape_jaccard_bwd_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _c.c_size_t, _P],
+    "ape_confusion_add": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "ape_sgd_step_multi_f32": [_I, _P, _F, _F, _F, _F, _I, _P],
 }
 
 
@@ -150,6 +162,12 @@ class AdamJob(_c.Structure):
     """Mirror of `ape_adam_job` (include/ape_hip.h)."""
     _fields_ = [("param", _c.c_void_p), ("grad", _c.c_void_p), ("exp_avg", _c.c_void_p), ("exp_avg_sq", _c.c_void_p), ("n", _c.c_long),
                 ("bc1", _c.c_float), ("bc2_sqrt", _c.c_float)]
+
+
+class SgdJob(_c.Structure):
+    """Mirror of `ape_sgd_job` (include/ape_hip.h)."""
+    _fields_ = [("param", _c.c_void_p), ("grad", _c.c_void_p), ("momentum_buffer", _c.c_void_p), ("n", _c.c_long), ("first", _c.c_int32),
+                ("reserved", _c.c_int32)]
 
 
 class PackJob(_c.Structure):
@@ -169,7 +187,8 @@ ACT_NONE, ACT_RELU, ACT_PRELU, ACT_SIGMOID = 0, 1, 2, 3
 _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspace_bytes": _c.c_size_t, "ape_seg_components_workspace_bytes": _c.c_size_t,
              "ape_packed_weights_bf16_elems": _c.c_long, "ape_pc_workspace_bytes": _c.c_size_t, "ape_pc_batch_workspace_bytes": _c.c_size_t,
              "ape_conv2d_wgrad_workspace_bytes": _c.c_size_t, "ape_conv_gemm_splitk_workspace_bytes": _c.c_size_t,
-             "ape_fpfh_workspace_bytes": _c.c_size_t, "ape_feature_nn1_workspace_bytes": _c.c_size_t, "ape_ransac_workspace_bytes": _c.c_size_t}
+             "ape_fpfh_workspace_bytes": _c.c_size_t, "ape_feature_nn1_workspace_bytes": _c.c_size_t, "ape_ransac_workspace_bytes": _c.c_size_t,
+             "ape_bn_workspace_bytes": _c.c_size_t, "ape_jaccard_workspace_bytes": _c.c_size_t}
 
 _lib = None
 

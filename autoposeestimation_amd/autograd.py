@@ -483,3 +483,196 @@ class Adam:
                                                 float(self.weight_decay), _st())
         _lib.check(rc, "ape_adam_step_multi_f32")
         refresh_banks(live)          # the conv operands of the updated parameters, one launch
+
+
+# ---- segmentor training (csrc/segtrain.hip): smp 0.1.3 Unet in train mode, jaccard_loss ------------------------------------------------
+def _strides4(t):
+    return (ctypes.c_long * 4)(*[int(s) for s in t.stride()])
+
+
+class BatchNormFn(torch.autograd.Function):
+    """nn.BatchNorm2d in train mode (batch statistics over B*H*W, biased variance) with the activation and residual of its site fused:
+    y = act(bn(x) + residual), act in {ACT_NONE, ACT_RELU}.  x[B,H,W,C] NHWC; running_mean / running_var / num_batches_tracked are
+    updated on the device (momentum 0.1, unbiased variance), as torch does.  Backward: the ReLU mask from the saved output, one fixed-order
+    reduction for sum(g) and sum(g * x_hat), then dx; the residual receives the masked gradient."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, running_mean, running_var, num_batches_tracked, act, eps=1e-5, momentum=0.1):
+        x = _c(x)
+        b, h, w, c = x.shape
+        rows = b * h * w
+        if rows < 2:
+            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+        y = torch.empty_like(x)
+        mean = torch.empty(2 * c, dtype=torch.float32, device=x.device)          # (hi, lo) pairs
+        invstd = torch.empty(c, dtype=torch.float32, device=x.device)
+        ws = _ws(_lib.lib().ape_bn_workspace_bytes(c), x.device)
+        res = None if residual is None else _c(residual)
+        rc = _lib.lib().ape_bn_train_fwd_f32(_lib.dptr(x, torch.float32), _lib.dptr(_c(gamma.detach()), torch.float32),
+                                             _lib.dptr(_c(beta.detach()), torch.float32), _lib.dptr(res, torch.float32), _lib.dptr(y),
+                                             _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(running_mean, torch.float32),
+                                             _lib.dptr(running_var, torch.float32), _lib.dptr(num_batches_tracked, torch.int64), rows, c,
+                                             float(eps), float(momentum), act, _lib.dptr(ws), ws.numel(), _st())
+        _lib.check(rc, "ape_bn_train_fwd_f32")
+        ctx.save_for_backward(x, gamma, mean, invstd, y if act == E.ACT_RELU else None)
+        ctx.has_res = residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, mean, invstd, y = ctx.saved_tensors
+        dy = _c(dy)
+        b, h, w, c = x.shape
+        need_x, need_g, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        need_r = ctx.has_res and ctx.needs_input_grad[3]
+        dx = torch.empty_like(x) if need_x else None
+        dg = torch.empty_like(invstd) if need_g else None
+        db = torch.empty_like(invstd) if need_b else None
+        dres = (torch.empty_like(x) if y is not None else dy) if need_r else None
+        ws = _ws(_lib.lib().ape_bn_workspace_bytes(c) + 8 * c, x.device)
+        rc = _lib.lib().ape_bn_train_bwd_f32(_lib.dptr(dy, torch.float32), _lib.dptr(y), _lib.dptr(x), _lib.dptr(mean), _lib.dptr(invstd),
+                                             _lib.dptr(_c(gamma.detach()), torch.float32), _lib.dptr(dx), _lib.dptr(dg), _lib.dptr(db),
+                                             _lib.dptr(dres if (need_r and y is not None) else None), b * h * w, c, _lib.dptr(ws),
+                                             ws.numel(), _st())
+        _lib.check(rc, "ape_bn_train_bwd_f32")
+        return dx, dg, db, dres, None, None, None, None, None, None
+
+
+def batch_norm(x, bn_module, act=E.ACT_NONE, residual=None):
+    """BatchNormFn over an nn.BatchNorm2d's parameters and buffers (its eps and momentum)"""
+    return BatchNormFn.apply(x, bn_module.weight, bn_module.bias, residual, bn_module.running_mean, bn_module.running_var,
+                             bn_module.num_batches_tracked, act, bn_module.eps, bn_module.momentum)
+
+
+class UpsampleNearest2xFn(torch.autograd.Function):
+    """F.interpolate(x, scale_factor=2, mode='nearest') followed, when `skip` is given, by torch.cat([up, skip], channels) (smp's
+    DecoderBlock, written as one buffer: engine.nearest_up2 fills both channel windows).  Backward: 2x2 sums read from the up-sampled
+    channel window of the concatenation gradient (ld, offset) -- no slice copy -- and the skip's window handed on as a view."""
+
+    @staticmethod
+    def forward(ctx, x, skip=None):
+        x = _c(x)
+        b, h, w, c = x.shape
+        cs = 0 if skip is None else skip.shape[3]
+        if skip is not None and tuple(skip.shape[:3]) != (b, 2 * h, 2 * w):
+            raise ValueError("skip %s does not match the up-sampled %s" % (tuple(skip.shape), (b, 2 * h, 2 * w)))
+        out = torch.empty(b, 2 * h, 2 * w, c + cs, dtype=torch.float32, device=x.device)
+        E.nearest_up2(x, out, 0)
+        if skip is not None:
+            E.nearest_up2(_c(skip), out, c, scale=1)
+        ctx.shape, ctx.cs = (b, h, w, c), cs
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        b, h, w, c = ctx.shape
+        dout = _c(dout)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(b, h, w, c, dtype=torch.float32, device=dout.device)
+            rc = _lib.lib().ape_upsample_nearest2x_bwd_f32(_lib.dptr(dout, torch.float32), c + ctx.cs, 0, _lib.dptr(dx), b, h, w, c, _st())
+            _lib.check(rc, "ape_upsample_nearest2x_bwd_f32")
+        dskip = dout[..., c:] if (ctx.cs and ctx.needs_input_grad[1]) else None
+        return dx, dskip
+
+
+class SoftmaxChannelsFn(torch.autograd.Function):
+    """softmax over the channel (last NHWC) axis: smp 0.1.3's SegmentationHead activation 'softmax' / 'softmax2d'"""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _c(x)
+        c = x.shape[-1]
+        y = torch.empty_like(x)
+        _lib.check(_lib.lib().ape_softmax_rows_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), x.numel() // c, c, _st()), "ape_softmax_rows_f32")
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        c = y.shape[-1]
+        dx = torch.empty_like(y)
+        rc = _lib.lib().ape_softmax_rows_bwd_f32(_lib.dptr(_c(dy), torch.float32), _lib.dptr(y), _lib.dptr(dx), y.numel() // c, c, _st())
+        _lib.check(rc, "ape_softmax_rows_bwd_f32")
+        return dx
+
+
+class JaccardLossFn(torch.autograd.Function):
+    """jaccard_loss(true, logits, eps) of the reference's segmentation/utils.py:71-114 on the device: logits[B,C,H,W] fp32 at any strides
+    (the channels-last view the segmentors return is read in place; its gradient is written in the same layout), labels i64 [B,H,W] or
+    [B,1,H,W].  Like the reference, whose sums run over dims (0,) + range(2, true.ndim): [B,1,H,W] labels sum over (B, H, W), [B,H,W]
+    labels over (B, H) only, one IoU per (class, column) averaged (what its driver's [B,H,W] labels get).  A label outside the classes gives a
+    NaN loss (the reference's one-hot raises) -- no host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, eps):
+        b, c, h, w = logits.shape
+        ncol = w if labels.dim() == 3 else 1
+        lab = labels.reshape(b, h, w)
+        if not lab.is_contiguous():
+            lab = lab.contiguous()
+        ws = _ws(_lib.lib().ape_jaccard_workspace_bytes(c, ncol), logits.device)
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        st = _strides4(logits)
+        rc = _lib.lib().ape_jaccard_fwd_f32(ctypes.c_void_p(logits.data_ptr()), st, _lib.dptr(lab, torch.int64), b, c, h, w, ncol, float(eps),
+                                            _lib.dptr(loss), _lib.dptr(ws), ws.numel(), _st())
+        _lib.check(rc, "ape_jaccard_fwd_f32")
+        ctx.save_for_backward(logits, lab, ws)
+        ctx.ncol = ncol
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, lab, ws = ctx.saved_tensors
+        b, c, h, w = logits.shape
+        dlogits = torch.empty_strided(logits.shape, logits.stride(), dtype=torch.float32, device=logits.device)
+        rc = _lib.lib().ape_jaccard_bwd_f32(ctypes.c_void_p(logits.data_ptr()), _strides4(logits), _lib.dptr(lab, torch.int64), b, c, h, w,
+                                            ctx.ncol, _lib.dptr(_c(g.detach().float().reshape(1))), ctypes.c_void_p(dlogits.data_ptr()),
+                                            _strides4(dlogits), _lib.dptr(ws), ws.numel(), _st())
+        _lib.check(rc, "ape_jaccard_bwd_f32")
+        return dlogits, None, None
+
+
+class SGD:
+    """torch.optim.SGD(params, lr, momentum, dampening, weight_decay, nesterov) on ape_sgd_step_multi_f32 (the reference's driver takes it
+    when training_config['optimizer'] != 'Adam', segmentation/__init__.py:96-101).  Like Adam: `step()` skips parameters whose .grad is
+    None and re-packs the conv operands of the updated parameters; `zero_grad()` drops the gradients."""
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False):
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self.params = [p for p in params]
+        self.lr, self.momentum, self.dampening, self.weight_decay, self.nesterov = lr, momentum, dampening, weight_decay, nesterov
+        self.state = {}
+
+    def zero_grad(self):
+        for p in self.params:
+            p.grad = None
+
+    @torch.no_grad()
+    def step(self):
+        live = [p for p in self.params if p.grad is not None]
+        if not live:
+            return
+        jobs = (_lib.SgdJob * len(live))()
+        keep = []
+        for i, p in enumerate(live):
+            if not p.data.is_contiguous():
+                raise RuntimeError("SGD needs contiguous parameters")
+            g = p.grad
+            if g.dtype != torch.float32 or not g.is_contiguous():
+                g = _c(g.float())
+                keep.append(g)
+            buf, first = None, 0
+            if self.momentum != 0:
+                buf = self.state.get(p)
+                if buf is None:
+                    buf = self.state[p] = torch.empty_like(p.data)
+                    first = 1
+            jobs[i] = _lib.SgdJob(param=_lib.dptr(p.data, torch.float32), grad=_lib.dptr(g), momentum_buffer=_lib.dptr(buf), n=p.numel(),
+                                  first=first, reserved=0)
+        rc = _lib.lib().ape_sgd_step_multi_f32(len(live), jobs, float(self.lr), float(self.momentum), float(self.dampening),
+                                               float(self.weight_decay), int(bool(self.nesterov)), _st())
+        _lib.check(rc, "ape_sgd_step_multi_f32")
+        refresh_banks(live)

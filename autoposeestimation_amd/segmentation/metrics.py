@@ -1,0 +1,237 @@
+"""The segmentor's training loss and metric with the reference's signatures (segmentation/utils.py:71-296): `jaccard_loss`, `Metric`,
+`ConfusionMatrix`, `IoU`.  segmentation/utils.py re-exports them, so `install_dropin(reference_root=...)` no longer copies the
+reference's own in.
+
+Device tensors take the kernels of csrc/segtrain.hip (autograd.JaccardLossFn, ape_confusion_add): the loss never leaves the device and
+`IoU.add` does no host synchronisation -- the confusion matrix accumulates in device memory until `value()` reads it.  NumPy arrays and
+CPU tensors given to the metric keep the reference's NumPy arithmetic (its contract accepts them); the loss needs device tensors.
+
+One deliberate difference: the confusion matrix counts in int64.  The reference's is np.int32 and wraps after 2^31 pixels in one
+matrix (about 7000 frames of 480 x 640 in an epoch).
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from autoposeestimation_amd import _lib
+
+_MAX_LOSS_CLASSES = 32           # csrc/segtrain.hip kJacMax
+_MAX_METRIC_CLASSES = 64         # csrc/segtrain.hip kConfMax
+
+
+def _strides4(t):
+    return (ctypes.c_long * 4)(*[int(s) for s in t.stride()])
+
+
+def _as_i64(t):
+    if t.dtype == torch.int64:
+        return t.contiguous()
+    if t.is_floating_point() or t.is_complex():
+        raise TypeError("labels must be an integer tensor, got %s" % t.dtype)
+    return t.long().contiguous()
+
+
+def jaccard_loss(true, logits, eps=1e-7):
+    """segmentation/utils.py:71-114 on the device: `1 - mean_{c in unique(true)} I_c / (S_c - I_c + eps)` with I_c = sum(p * onehot),
+    S_c = sum(p + onehot) and p = softmax(logits, dim=1), or, for one channel, the pair (sigmoid, 1 - sigmoid) against the one-hot in
+    swapped order.  The sums run over the reference's dims (0,) + range(2, true.ndim): (B, H, W) for [B,1,H,W] labels, but (B, H) for
+    [B,H,W] labels -- one IoU per (class, column w), all averaged; its driver passes [B,H,W] labels, so that is what it minimises.  true: i64 [B,H,W] or [B,1,H,W]; logits: fp32 [B,C,H,W] at any strides (C <= 32).  The reference's
+    driver feeds it the softmax output of smp's head, so the loss sees a double softmax; that is restated, not changed.  A label outside
+    0..C-1 (0..1 for C == 1) makes the loss NaN -- the reference's one-hot raises instead, which would need a host synchronisation."""
+    from autoposeestimation_amd import autograd as A
+    if not (torch.is_tensor(true) and torch.is_tensor(logits)):
+        raise TypeError("jaccard_loss takes tensors")
+    if not (true.is_cuda and logits.is_cuda):
+        raise _lib.ApeError("jaccard_loss runs on the device: got labels on %s and logits on %s (no CPU fallback)" % (true.device, logits.device))
+    if logits.dim() != 4:
+        raise ValueError("logits must be [B,C,H,W], got %s" % (tuple(logits.shape),))
+    b, c, h, w = logits.shape
+    if tuple(true.shape) not in ((b, h, w), (b, 1, h, w)):
+        raise ValueError("labels %s do not match logits %s: expected [B,H,W] or [B,1,H,W]" % (tuple(true.shape), tuple(logits.shape)))
+    if logits.dtype != torch.float32:
+        raise TypeError("logits must be float32, got %s" % logits.dtype)
+    if not 1 <= c <= _MAX_LOSS_CLASSES:
+        raise ValueError("jaccard_loss supports 1..%d channels, got %d" % (_MAX_LOSS_CLASSES, c))
+    return A.JaccardLossFn.apply(logits, _as_i64(true), float(eps))
+
+
+class Metric(object):
+    """base class of the metrics (reference segmentation/utils.py:117-129)"""
+
+    def reset(self):
+        pass
+
+    def add(self):
+        pass
+
+    def value(self):
+        pass
+
+
+class ConfusionMatrix(Metric):
+    """K x K confusion matrix, rows = target, columns = prediction (reference segmentation/utils.py:132-196).
+
+    `add(predicted, target)`: predicted N x K scores or N class indices, target N class indices or an N x K one-hot.  Device tensors are
+    counted by one kernel launch into a device-resident matrix (arg-max with the first maximum on ties, as CPU torch / NumPy); NumPy
+    arrays and CPU tensors by NumPy, as the reference does.  Out-of-range classes raise ValueError: at once on the NumPy path, at the next
+    `value()` on the device path (checking earlier would synchronise every batch).
+    `value()` returns the counts as np.int64 (the reference's np.int32 overflows after 2^31 pixels), or the row-normalised float32 matrix
+    when `normalized`."""
+
+    def __init__(self, num_classes, normalized=False):
+        super().__init__()
+        self.conf = np.zeros((num_classes, num_classes), dtype=np.int64)
+        self.normalized = normalized
+        self.num_classes = num_classes
+        self._dev = None            # (u64 counts [K,K] as int64, out-of-range flag) on the device of the first device add
+        self.reset()
+
+    def reset(self):
+        self.conf.fill(0)
+        if self._dev is not None:
+            self._dev[0].zero_()
+            self._dev[1].zero_()
+
+    def _add_device(self, pred, target):
+        """pred [B,K,H,W] scores or [B,H,W] labels, target likewise, both on the device"""
+        k = self.num_classes
+        if k > _MAX_METRIC_CLASSES:
+            raise ValueError("the device confusion matrix supports up to %d classes, got %d" % (_MAX_METRIC_CLASSES, k))
+        dev = pred.device
+        if self._dev is None or self._dev[0].device != dev:
+            if self._dev is not None:
+                self._fold()
+            self._dev = (torch.zeros(k, k, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+
+        def src(t, what):
+            if t.dim() == 4:
+                if t.shape[1] != k:
+                    raise ValueError("number of %s scores does not match size of confusion matrix (%d != %d)" % (what, t.shape[1], k))
+                if t.dtype != torch.float32:
+                    t = t.float()
+                return t, _strides4(t), None, (t.shape[0], t.shape[2], t.shape[3])
+            lab = _as_i64(t)
+            return None, None, lab, tuple(lab.shape)
+
+        ps, pst, pl, pshape = src(pred, "predicted")
+        ts, tst, tl, tshape = src(target, "target")
+        if pshape != tshape:
+            raise ValueError("predicted %s and target %s cover different pixels" % (tuple(pred.shape), tuple(target.shape)))
+        b, h, w = pshape
+        if b * h * w == 0:
+            return
+        rc = _lib.lib().ape_confusion_add(ctypes.c_void_p(ps.data_ptr() if ps is not None else 0), pst, _lib.dptr(pl),
+                                          ctypes.c_void_p(ts.data_ptr() if ts is not None else 0), tst, _lib.dptr(tl), b, h, w, k,
+                                          _lib.dptr(self._dev[0]), _lib.dptr(self._dev[1]), _lib.stream_ptr())
+        _lib.check(rc, "ape_confusion_add")
+
+    def _fold(self):
+        """device counts -> self.conf (one synchronisation)"""
+        if self._dev is None:
+            return
+        counts, bad = self._dev
+        if int(bad.item()):
+            bad.zero_()
+            counts.zero_()
+            raise ValueError("predicted or target values are not between 0 and k-1")
+        self.conf += counts.cpu().numpy()
+        counts.zero_()
+
+    def add(self, predicted, target):
+        if torch.is_tensor(predicted) and torch.is_tensor(target) and predicted.is_cuda and target.is_cuda:
+            if predicted.shape[0] != target.shape[0]:
+                raise ValueError("number of targets and predicted outputs do not match")
+            # N x K scores -> [N,K,1,1], N indices -> [N,1,1]: one pixel per example
+            as_px = lambda t: t[:, :, None, None] if t.dim() == 2 else t[:, None, None]  # noqa: E731
+            if predicted.dim() not in (1, 2) or target.dim() not in (1, 2):
+                raise ValueError("ConfusionMatrix.add takes N x K scores or N class indices")
+            self._add_device(as_px(predicted), as_px(target))
+            return
+        if torch.is_tensor(predicted):
+            predicted = predicted.cpu().numpy()
+        if torch.is_tensor(target):
+            target = target.cpu().numpy()
+        predicted, target = np.asarray(predicted), np.asarray(target)
+        k = self.num_classes
+        if predicted.shape[0] != target.shape[0]:
+            raise ValueError("number of targets and predicted outputs do not match")
+        if predicted.ndim != 1:
+            if predicted.shape[1] != k:
+                raise ValueError("number of predictions does not match size of confusion matrix")
+            predicted = np.argmax(predicted, 1)
+        elif predicted.size and not (predicted.max() < k and predicted.min() >= 0):
+            raise ValueError("predicted values are not between 0 and k-1")
+        if target.ndim != 1:
+            if target.shape[1] != k:
+                raise ValueError("Onehot target does not match size of confusion matrix")
+            if not ((target >= 0).all() and (target <= 1).all()):
+                raise ValueError("in one-hot encoding, target values should be 0 or 1")
+            if not (target.sum(1) == 1).all():
+                raise ValueError("multi-label setting is not supported")
+            target = np.argmax(target, 1)
+        elif target.size and not (target.max() < k and target.min() >= 0):
+            raise ValueError("target values are not between 0 and k-1")
+        idx = predicted.astype(np.int64) + k * target.astype(np.int64)
+        self.conf += np.bincount(idx, minlength=k * k).reshape(k, k)
+
+    def value(self):
+        """rows = targets, columns = predictions: np.int64 counts, or float32 rows normalised to sum 1 when `normalized`"""
+        self._fold()
+        if self.normalized:
+            conf = self.conf.astype(np.float32)
+            return conf / conf.sum(1).clip(min=1e-12)[:, None]
+        return self.conf
+
+
+class IoU(Metric):
+    """Per-class intersection over union and its mean (reference segmentation/utils.py:199-291): TP / (TP + FP + FN) from the confusion
+    matrix; `value()` -> (iou[K], nanmean(iou[1:])) -- the reference leaves class 0 (background) out of the mean.  A class with
+    TP + FP + FN = 0 gives NaN.  ignore_index: an int or an iterable of ints whose rows and columns are zeroed first (in the accumulated
+    matrix itself, as the reference does when not normalized)."""
+
+    def __init__(self, num_classes, normalized=False, ignore_index=None):
+        super().__init__()
+        self.conf_metric = ConfusionMatrix(num_classes, normalized)
+        if ignore_index is None:
+            self.ignore_index = None
+        elif isinstance(ignore_index, int):
+            self.ignore_index = (ignore_index,)
+        else:
+            try:
+                self.ignore_index = tuple(ignore_index)
+            except TypeError:
+                raise ValueError("'ignore_index' must be an int or iterable")
+
+    def reset(self):
+        self.conf_metric.reset()
+
+    def add(self, predicted, target):
+        """predicted: [N,K,H,W] scores or [N,H,W] class indices; target likewise"""
+        if predicted.shape[0] != target.shape[0]:
+            raise ValueError("number of targets and predicted outputs do not match")
+        if predicted.dim() not in (3, 4):
+            raise ValueError("predictions must be of dimension (N, H, W) or (N, K, H, W)")
+        if target.dim() not in (3, 4):
+            raise ValueError("targets must be of dimension (N, H, W) or (N, K, H, W)")
+        if predicted.is_cuda and target.is_cuda:
+            self.conf_metric._add_device(predicted, target)
+            return
+        if predicted.dim() == 4:
+            predicted = predicted.argmax(1)
+        if target.dim() == 4:
+            target = target.argmax(1)
+        self.conf_metric.add(predicted.reshape(-1), target.reshape(-1))
+
+    def value(self):
+        conf = self.conf_metric.value()
+        if self.ignore_index is not None:
+            for i in self.ignore_index:
+                conf[:, i] = 0
+                conf[i, :] = 0
+        tp = np.diag(conf)
+        fp = conf.sum(0) - tp
+        fn = conf.sum(1) - tp
+        with np.errstate(divide="ignore", invalid="ignore"):
+            iou = tp / (tp + fp + fn)
+        return iou, np.nanmean(iou[1:])

@@ -10,7 +10,10 @@ constructor keywords and state-dict keys (278 for resnet34 with the BatchNorm `n
   * head = conv3x3 (16 -> classes, bias) + the activation (softmax over channels, or none).
 Parity with smp itself cannot be pinned offline; the tests hold it to an fp64 restatement of the architecture above.
 
-All BatchNorm layers run in eval mode (running statistics) and are folded into their convolution (engine.bn_fold).  The encoder runs
+In eval mode all BatchNorm layers use their running statistics and are folded into their convolution (engine.bn_fold).  In train mode
+(`train(True)`) forward() builds smp's training graph on the tape of autoposeestimation_amd/autograd.py instead: ConvFn + BatchNormFn
+(batch statistics, running buffers updated) per BN site, MaxPoolFn, UpsampleNearest2xFn (up-sample + concatenation), the head conv and
+SoftmaxChannelsFn; segmentation/train.py drives it.  The encoder runs
 through engine.Conv.  Each decoder layer takes one of two routes, chosen from its shape by measurement (FUSED_LAYERS / FUSED_HEAD below):
   * fused (bf16 precisions): csrc/unet.hip reads the up-sampled / concatenated input virtually -- nothing is written but the output;
   * materialised: the nearest up-sample written into the first channels of a concatenation buffer whose skip half the encoder wrote in
@@ -214,7 +217,7 @@ class UnetSegmentor(_HipModule):
         self.decoder = _Decoder()
         self.segmentation_head = nn.Sequential(nn.Conv2d(DECODER_CHANNELS[-1], classes, 3, 1, 1))
         for p in self.parameters():
-            p.requires_grad_(False)
+            p.requires_grad_(False)           # leaves of the tape only in train mode (train(True))
         # 'imagenet' (what the reference's saved segmentation_config says, main.py:609) would be downloaded by smp; here the weights must come
         # from load_state_dict before the first run
         self._weights_loaded = encoder_weights is None
@@ -225,9 +228,12 @@ class UnetSegmentor(_HipModule):
         return r
 
     def train(self, mode=True):
+        """train(True): the parameters become leaves of the tape and forward() builds the training graph (BatchNorm on batch statistics);
+        either way the cached inference plan is dropped, so eval() re-folds the BatchNorm layers with the updated running statistics"""
         super().train(mode)
-        for p in self.parameters():
-            p.requires_grad_(False)
+        if not mode:
+            for p in self.parameters():
+                p.requires_grad_(False)
         return self
 
     def _build_plan(self, sd, dev):
@@ -309,5 +315,50 @@ class UnetSegmentor(_HipModule):
 
     def forward(self, x):
         if self.training:
-            raise NotImplementedError("UnetSegmentor runs inference only (eval mode: BatchNorm running statistics)")
+            return self._forward_train(x)
         return self.predict(x)
+
+    def _forward_train(self, x):
+        """smp 0.1.3 Unet in train mode on the tape (autoposeestimation_amd/autograd.py): x[B,in_channels,H,W] cuda -> [B,classes,H,W], a
+        view of the NHWC result (channels-last strides).  Every BatchNorm2d uses the batch's statistics and updates its running buffers."""
+        from autoposeestimation_amd import autograd as A
+        if not self._weights_loaded:
+            self.plan()                       # raises: the imagenet encoder cannot be downloaded
+        _need_cuda(x, "input")
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise ValueError("expected [B,%d,H,W], got %s" % (self.in_channels, tuple(x.shape)))
+        b, _, h, w = x.shape
+        if h % 32 or w % 32:
+            raise ValueError("Unet input height and width must be multiples of 32, got %dx%d" % (h, w))
+        if b * h * w * 32 >= 1 << 31:
+            # the largest tensors of the step (the 32-channel full-resolution decoder input, the 16-channel map and their gradients) are
+            # indexed with 32 bits; BatchNorm needs the whole batch, so it cannot be sliced
+            raise ValueError("batch %s is too large for one training step: B*H*W*32 must stay below 2^31" % (tuple(x.shape),))
+        self.sync_banks()
+        x4 = torch.zeros(b, h, w, (self.in_channels + 3) // 4 * 4, dtype=torch.float32, device=x.device)
+        x4[..., :self.in_channels] = x.detach().permute(0, 2, 3, 1)
+        pr = self.precision
+
+        def cbn(t, conv, bn, stride=1, pad=1, act=E.ACT_RELU, residual=None):
+            return A.batch_norm(A.conv(t, conv.weight, stride=stride, pad=pad, precision=pr), bn, act, residual)
+
+        enc = self.encoder
+        f = [cbn(x4, enc.conv1, enc.bn1, stride=2, pad=3)]
+        y = A.MaxPoolFn.apply(f[0])
+        for li in range(1, 5):
+            for bi, blk in enumerate(getattr(enc, "layer%d" % li)):
+                s = 2 if (bi == 0 and li > 1) else 1
+                res = y if not hasattr(blk, "downsample") else cbn(y, blk.downsample[0], blk.downsample[1], stride=s, pad=0, act=E.ACT_NONE)
+                t = cbn(y, blk.conv1, blk.bn1, stride=s)
+                y = cbn(t, blk.conv2, blk.bn2, residual=res)
+            f.append(y)
+        y = f[4]
+        for blk, skip in zip(self.decoder.blocks, (f[3], f[2], f[1], f[0], None)):
+            y = A.UpsampleNearest2xFn.apply(y, skip)
+            y = cbn(y, blk.conv1[0], blk.conv1[1])
+            y = cbn(y, blk.conv2[0], blk.conv2[1])
+        head = self.segmentation_head[0]
+        y = A.conv(y, head.weight, head.bias, pad=1, precision=pr)
+        if self.activation in ("softmax", "softmax2d"):
+            y = A.SoftmaxChannelsFn.apply(y)
+        return y.permute(0, 3, 1, 2)

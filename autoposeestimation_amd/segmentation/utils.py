@@ -8,13 +8,15 @@ kernels; `predict()` returns the first `classes` channels of its `final` 1x1 con
 `get_model('Unet', cfg)` returns segmentation/unet.py's UnetSegmentor, a restatement of smp 0.1.3's Unet (resnet18 / resnet34
 encoder) with smp's state-dict keys, so the reference's `Unet_resnet34.ckpt` files load; LinkNet raises NotImplementedError.
 
-Training-only symbols of the reference module (jaccard_loss, IoU, ConfusionMatrix, transforms, animate*) are outside the
-hot path and are not provided.
+The training loss and metric (jaccard_loss, Metric, ConfusionMatrix, IoU) live in segmentation/metrics.py and are re-exported here under
+the reference's names; in train mode both segmentors' forward() builds a training graph on the tape (segmentation/train.py drives them).
+The reference's transforms and animate* stay outside the package.
 """
 import torch
 
 from autoposeestimation_amd import engine as E
-from autoposeestimation_amd.DenseFusion.lib.network import PSPNet, _need_cuda
+from autoposeestimation_amd.DenseFusion.lib.network import PSPNet, _need_cuda, _pspnet_train
+from autoposeestimation_amd.segmentation.metrics import ConfusionMatrix, IoU, Metric, jaccard_loss  # noqa: F401
 
 
 class PsPNetSegmentor(PSPNet):
@@ -72,6 +74,27 @@ class PsPNetSegmentor(PSPNet):
         if self.activation in ("softmax", "softmax2d"):
             return torch.softmax(logits, dim=1)
         return logits
+
+    def forward(self, x):
+        """train mode: x[B,in_channels,H,W] -> [B,classes,H,W] (a view of the NHWC result) through the PSPNet training graph (dropout
+        masks included, set_dropout_masks) up to the `final` conv, its first `classes` channels, then the activation -- the head predict()
+        uses.  eval mode: PSPNet.forward (unchanged)."""
+        if not self.training:
+            return super().forward(x)
+        from autoposeestimation_amd import autograd as A
+        _need_cuda(x, "input")
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise ValueError("expected [B,%d,H,W], got %s" % (self.in_channels, tuple(x.shape)))
+        b, _, h, w = x.shape
+        if b * h * w * 64 >= 1 << 31:
+            raise ValueError("batch %s is too large for one training step: B*H*W*64 must stay below 2^31" % (tuple(x.shape),))
+        self.sync_banks()
+        x4 = torch.zeros(b, h, w, (self.in_channels + 3) // 4 * 4, dtype=torch.float32, device=x.device)
+        x4[..., :self.in_channels] = x.detach().permute(0, 2, 3, 1)
+        y = _pspnet_train(self, "", self.backend, x4, self._drop, self.precision, logits_only=True)[..., :self.classes]
+        if self.activation in ("softmax", "softmax2d"):
+            y = A.SoftmaxChannelsFn.apply(y)
+        return y.permute(0, 3, 1, 2)
 
 
 def _unavailable(name):

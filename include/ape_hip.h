@@ -594,6 +594,56 @@ typedef struct ape_pack_job {
 } ape_pack_job;
 int ape_pack_train_weights(int n, const ape_pack_job* jobs_device, long max_elems, void* stream);
 
+/* ---- Segmentor training (csrc/segtrain.hip; reference segmentation/__init__.py:134-156 over smp 0.1.3's Unet) ----------------------
+ * BatchNorm2d in train mode over x[rows][C] (rows = B*H*W, NHWC): mean[2 * C] (the batch mean as a float pair hi[C], lo[C]) and invstd[C]
+ * (biased variance, eps) of the batch, running_mean /
+ * running_var updated with `momentum` (unbiased variance, rows / (rows - 1)), num_batches_tracked[0] += 1 (i64; the three may be NULL),
+ * then y = act((x - mean) * invstd * gamma + beta [+ residual]), act = APE_ACT_NONE | APE_ACT_RELU.  rows < 2 is refused (torch raises).
+ * Workspace: ape_bn_workspace_bytes(C) for the forward, that plus 2 * C floats for the backward.  Deterministic (fixed-order partials). */
+size_t ape_bn_workspace_bytes(int C);
+int ape_bn_train_fwd_f32(const float* x, const float* gamma, const float* beta, const float* residual, float* y, float* mean, float* invstd,
+                         float* running_mean, float* running_var, long long* num_batches_tracked, long rows, int C, float eps, float momentum,
+                         int act, void* ws, size_t ws_bytes, void* stream);
+/* Backward of the above: g = dy, masked by y > 0 when the saved output y is given (ReLU); dres = g (residual gradient, may be NULL),
+ * dbeta = sum g, dgamma = sum g * x_hat, dx = gamma * invstd * (g - mean(g) - x_hat * mean(g * x_hat)) (dx / dgamma / dbeta may be NULL) */
+int ape_bn_train_bwd_f32(const float* dy, const float* y, const float* x, const float* mean, const float* invstd, const float* gamma,
+                         float* dx, float* dgamma, float* dbeta, float* dres, long rows, int C, void* ws, size_t ws_bytes, void* stream);
+/* F.interpolate(scale_factor=2, mode='nearest') backward: dx[B][h][w][C] = 2x2 sums of dy[B][2h][2w][ld] channels off..off+C */
+int ape_upsample_nearest2x_bwd_f32(const float* dy, int ld, int off, float* dx, int B, int h, int w, int C, void* stream);
+/* softmax over the last (channel) axis of x[rows][C] and its backward dx = y * (dy - sum(dy * y)) */
+int ape_softmax_rows_f32(const float* x, float* y, long rows, int C, void* stream);
+int ape_softmax_rows_bwd_f32(const float* dy, const float* y, float* dx, long rows, int C, void* stream);
+/* jaccard_loss(true, logits, eps) of segmentation/utils.py:71-114: logits[B][C][H][W] at element strides strides_host[4] (a channels-last
+ * view is read in place), labels i64 [B*H*W], C in 1..32 (C == 1: the sigmoid pair with the swapped one-hot).  ncol = 1: intersections
+ * and cardinalities summed over (B, H, W) (the reference's [B,1,H,W] labels); ncol = W: over (B, H) per column (its [B,H,W] labels, whose
+ * reduction dims are (0, 2)).  loss[0] = 1 - mean over the label values present (and the columns) of I/(S - I + eps); NaN when a label is
+ * outside the classes.  The workspace keeps the per-class terms the backward reads: pass the same one to ape_jaccard_bwd_f32, which writes
+ * dlogits (at dstrides_host) times the device scalar gscale[0]. */
+size_t ape_jaccard_workspace_bytes(int C, int ncol);
+int ape_jaccard_fwd_f32(const float* logits, const long* strides_host, const long long* labels, int B, int C, int H, int W, int ncol,
+                        float eps, float* loss, void* ws, size_t ws_bytes, void* stream);
+int ape_jaccard_bwd_f32(const float* logits, const long* strides_host, const long long* labels, int B, int C, int H, int W, int ncol,
+                        const float* gscale, float* dlogits, const long* dstrides_host, const void* ws, size_t ws_bytes, void* stream);
+/* ConfusionMatrix.add of segmentation/utils.py:151-191: prediction and target each either scores[B][K][H][W] (strides_host; arg-max, first
+ * maximum) or i64 labels [B*H*W] (exactly one of the two non-NULL); conf[K][K] u64 (rows = target, columns = prediction) accumulated with
+ * integer atomics; bad_flag[0] |= 1 when a class falls outside 0..K-1 (that pixel is not counted).  K <= 64. */
+int ape_confusion_add(const float* pred_scores, const long* pred_strides_host, const long long* pred_labels, const float* tgt_scores,
+                      const long* tgt_strides_host, const long long* tgt_labels, int B, int H, int W, int K, unsigned long long* conf,
+                      unsigned* bad_flag, void* stream);
+/* torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov) over n parameter buffers (64 per launch): d = g + wd * p; buf = d on a
+ * buffer's first step (first = 1), else momentum * buf + (1 - dampening) * d; d = nesterov ? d + momentum * buf : buf; p -= lr * d.
+ * momentum_buffer may be NULL when momentum == 0. */
+typedef struct ape_sgd_job {
+    float* param;
+    const float* grad;
+    float* momentum_buffer;
+    long n;
+    int first;
+    int reserved;
+} ape_sgd_job;
+int ape_sgd_step_multi_f32(int n, const ape_sgd_job* jobs_host, float lr, float momentum, float dampening, float weight_decay, int nesterov,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
