@@ -10,6 +10,10 @@ over one batch of synthetic frames (BASELINE config 3: batch=64 640x480 frames p
 By default the loop is software-pipelined (pose stage of step i on a second HIP stream beside the segmentation of step i+1; every
 step still does all of its work between the fences): about +4 % frames/s over `--no-overlap`, whose per-kernel event timings are
 the kernels' own (with the overlap they include what the co-running small pose launches cost them).
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line (headline figures + the roofline of the
+timed region's five heaviest kernels).  `--full` adds everything that takes work of its own after the timed region: the CPU
+baseline and parity blocks, the single-stream re-run of every timed step, the isolated kernel pass, the secondary legs (`modes`,
+`staged`, `sweep`, `latency`, `pose`, `label`); the --no-* options switch single parts of it off.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -513,7 +517,8 @@ def label_main(args, rank, world, device, dist, embedded=False):
     """configs[4]: pose-label generation.  A step = `--views` synthetic 640x480 views in chains of 25 (one chain = one (object,
     direction) sequence of create_pointcloud.py:276-312): get_surface (back-projection, voxel / radius / statistical filters) for every
     view, spread over the ranks; one padded all-gather; then the sequential p2p + point-to-plane ICP fusion of each chain on its
-    owner rank (chain i -> rank i % world).  Total work is fixed as ranks are added (strong scaling).  Views are resident in HBM."""
+    owner rank (chain i -> rank i % world).  Total work is fixed as ranks are added (strong scaling).  Views are resident in HBM.
+    --full: the CPU baseline and the parity block on the first views of chain 0."""
     from autoposeestimation_amd.pc_reconstruction import open3d_utils as U
     from autoposeestimation_amd.pc_reconstruction import pointcloud as PC
     per_chain = 25
@@ -596,7 +601,7 @@ def label_main(args, rank, world, device, dist, embedded=False):
                                      "of the chain is a few microseconds of work behind a dependent launch, so this stage is latency-bound by "
                                      "construction and sits far below the HBM roofline; chains run side by side to use the GPU(s)"
                                      % (ICP_BYTES_PER_PAIR[0], ICP_BYTES_PER_PAIR[1])}}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"], acc = label_cpu_baseline(chains_np[0])
             # parity on the sample: the GPU fusion of the same first views against the oracle's
             g, _ = U.fuse_views(chains[0][:6], S.LABEL_INTR, **LABEL_KW)
@@ -625,7 +630,8 @@ def pose_main(args, rank, world, device, dist, embedded=False):
     eval_linemod.py:118-130).  A step = FramePipeline.poses (choose / back-projection / crop normalisation / PoseNet / pose selection /
     two refiner passes / float64 composition) + ape_adds_dis_batched_f32 + the single all_gather of (class, q, t, ADD-S) per crop.
     Inputs (u8 frames, u16 depth, the object map and its detections) are resident in HBM; crops shard over the ranks (weak scaling).
-    Secondary object `knn_training_size`: ape_knn_f32 at the training loss's size, 10^6 queries x 1000 refs (loss.py:38-47)."""
+    --full: the conv kernels of one more step timed (`roofline.kernels`), the CPU baseline and parity blocks, and the secondary object
+    `knn_training_size`: ape_knn_f32 at the training loss's size, 10^6 queries x 1000 refs (loss.py:38-47)."""
     from autoposeestimation_amd.pipeline.utils import FramePipeline
     from autoposeestimation_amd.DenseFusion.lib.network import PoseNet, PoseRefineNet
     from autoposeestimation_amd.DenseFusion.lib.knn import KNearestNeighbor
@@ -703,31 +709,6 @@ def pose_main(args, rank, world, device, dist, embedded=False):
         m = model.shape[1]
         pairs = n * m * m
         ach = pairs * KNN_LANE_OPS_PER_PAIR / (adds_ms * 1e-3) / 1e12
-        # after the timed region: every conv launch of one step timed (the MFMA side of the workload), and the k-NN kernel at training size
-        prof = E.LaunchProfile()
-        E.PROFILE = prof
-        step(args.warmup + args.steps, target, gather=False)
-        torch.cuda.synchronize()
-        E.PROFILE = None
-        top = sorted(prof.summary().items(), key=lambda kv: -kv[1]["ms"])[:3]
-        mfma = []
-        for lab, d in top:
-            bound, peak, unit = kernel_peak(lab)
-            a_ = (d["bytes"] / (d["ms"] * 1e-3) / 1e9) if bound == "hbm" else (d["flop"] / (d["ms"] * 1e-3) / 1e12)
-            mfma.append({"kernel": lab, "bound": bound, "launches": d["launches"], "ms_per_step": round(d["ms"], 3), "achieved": round(a_, 2),
-                         "peak": round(peak, 1), "unit": unit, "frac": round(a_ / peak, 4)})
-        knn = KNearestNeighbor(1)
-        kref, kqry = torch.randn(1, 3, 1000, device=device), torch.randn(1, 3, 1_000_000, device=device)
-        knn(kref, kqry)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            knn(kref, kqry)
-        e1.record()
-        torch.cuda.synchronize()
-        knn_ms = e0.elapsed_time(e1) / 10
-        knn_ach = 1e9 * KNN_LANE_OPS_PER_PAIR / (knn_ms * 1e-3) / 1e12
         line = {"metric": "crops/sec (PoseNet + 2 x PoseRefineNet + ADD-S via the HIP k-NN / ADD-S kernel), 160x160 crops, N=1000",
                 "value": round(n * world * args.steps / dt, 2), "unit": "crops/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -745,14 +726,41 @@ def pose_main(args, rank, world, device, dist, embedded=False):
                                      "selects: the reference's arithmetic, which the bit-exact index contract fixes); peak = 256 CUs x 4 SIMD-32 x 2.4 GHz; "
                                      "time = HIP events around the two launches, every step of the timed region, on their stream.  %d objects x "
                                      "10^6 pairs are ~10 us of vector work for the whole chip: the pair of launches is latency-bound -- "
-                                     "`knn_training_size` is the same arithmetic at a size that fills the chip"
-                                     % (KNN_LANE_OPS_PER_PAIR, n),
-                             "kernels": mfma},
-                "knn_training_size": {"kernel": "knn1_d3_q<2, 8>", "refs": 1000, "queries": 1000000, "ms": round(knn_ms, 4),
-                                      "pairs_per_s": round(1e9 / (knn_ms * 1e-3), 0), "bound": "valu", "achieved": round(knn_ach, 3),
-                                      "peak": round(PEAK_F32_LANE_OPS, 1), "unit": "T lane-op/s", "frac": round(knn_ach / PEAK_F32_LANE_OPS, 4)},
+                                     "`knn_training_size` (--full) is the same arithmetic at a size that fills the chip"
+                                     % (KNN_LANE_OPS_PER_PAIR, n)},
                 "adds_mean_m": round(float(dis.mean()), 6)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            # after the timed region: every conv launch of one step timed (the MFMA side of the workload), and the k-NN kernel at training size
+            prof = E.LaunchProfile()
+            E.PROFILE = prof
+            step(args.warmup + args.steps, target, gather=False)
+            torch.cuda.synchronize()
+            E.PROFILE = None
+            top = sorted(prof.summary().items(), key=lambda kv: -kv[1]["ms"])[:3]
+            mfma = []
+            for lab, d in top:
+                bound, peak, unit = kernel_peak(lab)
+                a_ = (d["bytes"] / (d["ms"] * 1e-3) / 1e9) if bound == "hbm" else (d["flop"] / (d["ms"] * 1e-3) / 1e12)
+                mfma.append({"kernel": lab, "bound": bound, "launches": d["launches"], "ms_per_step": round(d["ms"], 3), "achieved": round(a_, 2),
+                             "peak": round(peak, 1), "unit": unit, "frac": round(a_ / peak, 4)})
+            knn = KNearestNeighbor(1)
+            kref, kqry = torch.randn(1, 3, 1000, device=device), torch.randn(1, 3, 1_000_000, device=device)
+            knn(kref, kqry)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                knn(kref, kqry)
+            e1.record()
+            torch.cuda.synchronize()
+            knn_ms = e0.elapsed_time(e1) / 10
+            knn_ach = 1e9 * KNN_LANE_OPS_PER_PAIR / (knn_ms * 1e-3) / 1e12
+            line["roofline"]["kernels"] = mfma
+            line["knn_training_size"] = {"kernel": "knn1_d3_q<2, 8>", "refs": 1000, "queries": 1000000, "ms": round(knn_ms, 4),
+                                         "pairs_per_s": round(1e9 / (knn_ms * 1e-3), 0), "bound": "valu", "achieved": round(knn_ach, 3),
+                                         "peak": round(PEAK_F32_LANE_OPS, 1), "unit": "T lane-op/s", "frac": round(knn_ach / PEAK_F32_LANE_OPS, 4)}
+            line["adds_mean_m"] = line.pop("adds_mean_m")
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"], line["parity"] = pose_cpu_baseline(frames, objects, est_sd, ref_sd, choose.cpu().numpy(), pose.cpu().numpy(),
                                                                      dis.cpu().numpy(), targets, device)
         if embedded:
@@ -848,7 +856,12 @@ def main():
                          "PoseNet + 2 x PoseRefineNet + ADD-S (HIP k-NN / ADD-S kernel) on --crops 160x160 crops per GPU")
     ap.add_argument("--views", type=int, default=200, help="--workload label: views per step (one (object, direction) chain)")
     ap.add_argument("--crops", type=int, default=32, help="--workload pose (BASELINE configs[1]): 160x160 crops per GPU and step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run what the headline figure does not need: the CPU baseline and parity blocks, "
+                         "the single-stream re-run of every timed step, the isolated pass of the five kernels, the secondary legs (modes, "
+                         "staged, sweep, latency, pose, label); --workload pose / label: their CPU baseline, parity, per-kernel and k-NN "
+                         "figures.  Off by default: a plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full / --mixed: skip the CPU baseline and the parity blocks it checks")
     ap.add_argument("--unfiltered-frames", action="store_true",
                     help="time the first --batch random frames of each rank as they come (about 1 in 100 carries a stray blob or a clipped "
                          "120x160 crop) instead of selecting frames with exactly one 160x160 detection (configs[2], the default)")
@@ -865,16 +878,16 @@ def main():
                     help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, "
                          "at most 64 MB in all; a larger output as a fixed seeded sample): the same arguments give the same inputs in every "
                          "run, so two builds can be compared output for output")
-    ap.add_argument("--no-staged", action="store_true", help="skip the secondary `staged` leg (the same loop fed from pinned host memory through a copy stream)")
-    ap.add_argument("--no-modes", action="store_true", help="skip the secondary `modes` leg (two steps of the exact-fp32 operand mode after the timed region)")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the compact secondary `sweep` leg (4 steps of the --mixed frames, no parity block)")
-    ap.add_argument("--no-latency", action="store_true", help="skip the compact secondary `latency` leg (50 runs of the batch-1 live loop)")
-    ap.add_argument("--no-step-check", action="store_true", help="skip the re-run of every timed step on one stream after the timed region "
+    ap.add_argument("--no-staged", action="store_true", help="--full: skip the secondary `staged` leg (the same loop fed from pinned host memory through a copy stream)")
+    ap.add_argument("--no-modes", action="store_true", help="--full: skip the secondary `modes` leg (two steps of the exact-fp32 operand mode after the timed region)")
+    ap.add_argument("--no-sweep", action="store_true", help="--full: skip the compact secondary `sweep` leg (4 steps of the --mixed frames, no parity block)")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the compact secondary `latency` leg (50 runs of the batch-1 live loop)")
+    ap.add_argument("--no-step-check", action="store_true", help="--full: skip the re-run of every timed step on one stream after the timed region "
                     "(`parity.steps_bitwise_equal`; the profile passes of tools/make_profiles.sh skip it: their traces count steps)")
-    ap.add_argument("--no-pose-leg", action="store_true", help="skip the compact secondary `pose` leg (BASELINE configs[1]: 10 steps of --workload pose)")
-    ap.add_argument("--no-label-leg", action="store_true", help="skip the compact secondary `label` leg (BASELINE configs[4]: 1 step of --workload label, 200 views)")
+    ap.add_argument("--no-pose-leg", action="store_true", help="--full: skip the compact secondary `pose` leg (BASELINE configs[1]: 10 steps of --workload pose)")
+    ap.add_argument("--no-label-leg", action="store_true", help="--full: skip the compact secondary `label` leg (BASELINE configs[4]: 1 step of --workload label, 200 views)")
     ap.add_argument("--mixed", action="store_true",
-                    help="the full `sweep` leg (--mixed-steps steps + its own parity block; the default line carries a compact one: 4 steps, no "
+                    help="the full `sweep` leg (--mixed-steps steps + its own parity block, with or without --full; the --full line carries a compact one: 4 steps, no "
                          "parity block).  `sweep`: --batch frames with 1-3 painted objects each, sizes drawn from SURVEY.md 8d's crop "
                          "sweep {80x80, 120x160, 160x160, 240x240, 320x400}, through the same path (several crop-size buckets per step); run after the "
                          "timed region, never part of `value`")
@@ -882,7 +895,7 @@ def main():
     ap.add_argument("--no-pose-graphs", action="store_true",
                     help="--mixed: enqueue every crop-size bucket's ~90 pose-stage launches one by one instead of replaying one captured HIP graph per bucket")
     ap.add_argument("--latency", action="store_true",
-                    help="the full `latency` leg (--latency-runs runs; the default line carries a compact one of 50 runs).  `latency`: ONE resident 640x480 frame with one object through the whole path (what the reference's live "
+                    help="the full `latency` leg (--latency-runs runs, with or without --full; the --full line carries a compact one of 50 runs).  `latency`: ONE resident 640x480 frame with one object through the whole path (what the reference's live "
                          "loop does per frame, main.py:517-553), host wall clock from the call to the pose on the host, p50 / p99 over --latency-runs "
                          "runs; after the timed region, never part of `value`")
     ap.add_argument("--latency-runs", type=int, default=200)
@@ -1032,7 +1045,9 @@ def main():
             with open(args.dump_launches, "w") as f:
                 json.dump([[r[0], r[1]] for r in E.PROFILE.records], f)
     prof = E.PROFILE = E.LaunchProfile(only=top_only)
-    keep_steps.update(range(args.warmup, args.warmup + args.steps))
+    check_steps = args.full and not args.no_step_check
+    if check_steps:
+        keep_steps.update(range(args.warmup, args.warmup + args.steps))
     t0 = time.perf_counter()
     out = run_steps(args.warmup, args.steps)
     fence()
@@ -1053,13 +1068,13 @@ def main():
         dump_outputs(args.dump_outputs, {"poses": out["gathered"], "pose": out["pose"], "objects": out["objects"], "n_cand": out["n_cand"],
                                          "choose": out["choose"], "objmap": out["objmap"]})
 
-    # Every TIMED step's result block against the same step (same frames, same sampling seed) run again on ONE stream after the timed
+    # --full: every TIMED step's result block against the same step (same frames, same sampling seed) run again on ONE stream after the timed
     # region: the overlapped loop must give the single-stream bits (round 5 found a co-stream fault in this arrangement; the parity block
     # below only sees the last step).  Rank 0 reports `parity.steps_bitwise_equal`; any rank that differs fails the whole run.
     timed_blocks = dict(kept)
     kept.clear()
     steps_equal = None
-    if not args.no_step_check:
+    if check_steps:
         pipe_chk = FramePipeline(seg, est, ref, CLASSES, num_points=N_POINTS, refine_mode="live_compat", pose_stream=False)
         steps_equal = 0
         for i in range(args.warmup, args.warmup + args.steps):
@@ -1076,10 +1091,10 @@ def main():
 
     # With the software-pipelined loop the pose stage of the previous batch runs BESIDE the timed kernels on a second stream, so their
     # HIP-event durations in the timed region include what the co-running launches cost them (throughput goes up, every kernel takes
-    # longer).  A short single-stream pass AFTER the timed region (not part of `value`) times the same five kernels alone; both sets
+    # longer).  With --full a short single-stream pass AFTER the timed region (not part of `value`) times the same five kernels alone; both sets
     # are reported (`frac` / `avg_launch_us` = timed region, `isolated_*` = alone).
     iso_summ = iso_by_shape = None
-    if args.overlap and top_only:
+    if args.full and args.overlap and top_only:
         pipe_iso = FramePipeline(seg, est, ref, CLASSES, num_points=N_POINTS, refine_mode="live_compat", pose_stream=False)
         E.PROFILE = E.LaunchProfile(only=top_only)
         for i in range(3):
@@ -1090,11 +1105,11 @@ def main():
         iso_by_shape = E.PROFILE.summary(by_shape=True)
         E.PROFILE = None
 
-    # Secondary, AFTER the timed region (not part of `value`): the same step with exact-fp32 operands on the matrix cores -- what the
+    # --full, secondary, AFTER the timed region (not part of `value`): the same step with exact-fp32 operands on the matrix cores -- what the
     # default mode's split-bf16 operands (three products per term, ~2^-16 operand error, inside the 1e-4 parity bar) buy.  Two
     # single-stream steps behind one warm-up step; every rank runs them (the step's gather is a collective), rank 0 reports.
     modes = None
-    if not args.no_modes and (args.seg_precision, args.pose_precision) == ("bf16x3", "bf16x3"):
+    if args.full and not args.no_modes and (args.seg_precision, args.pose_precision) == ("bf16x3", "bf16x3"):
         for m in (seg, est, ref):
             m.set_precision("f32")
         pipe_f = FramePipeline(seg, est, ref, CLASSES, num_points=N_POINTS, refine_mode="live_compat", pose_stream=False)
@@ -1120,12 +1135,12 @@ def main():
         ref.set_precision(args.pose_precision)
         del pipe_f
 
-    # Secondary, AFTER the timed region (not part of `value`): the live loop receives its frames on the HOST (main.py:517-553,
+    # --full, secondary, AFTER the timed region (not part of `value`): the live loop receives its frames on the HOST (main.py:517-553,
     # pipeline/utils.py:421-427,556-560).  `staged`: every step takes a batch from pinned host memory through a COPY stream into one of two
     # device buffer pairs while the previous batch is being segmented (1.5 MB per frame: 98 MB per 64-frame step), then runs the same
     # software-pipelined loop on it.  value is the resident-input rate; this leg shows what the staging costs beside it.
     staged = None
-    if not args.no_staged and not args.frames:
+    if args.full and not args.no_staged and not args.frames:
         copy_stream = torch.cuda.Stream()
         host = [(torch.from_numpy(np.stack([f[0] for f in frames])).pin_memory(), torch.from_numpy(np.stack([f[1] for f in frames])).pin_memory())]
         host.append((host[0][0].flip(0).contiguous().pin_memory(), host[0][1].flip(0).contiguous().pin_memory()))        # a second, different batch
@@ -1181,24 +1196,24 @@ def main():
                           "batch's segmentation; same loop otherwise; after the timed region, never part of `value`"}
         del pipe_s
 
-    # Secondary, AFTER the timed region (not part of `value`): what real frames look like (pipeline/utils.py:444-470, 522-561: every detected
+    # --full, secondary, AFTER the timed region (not part of `value`): what real frames look like (pipeline/utils.py:444-470, 522-561: every detected
     # class of a frame gets its own crop, crops of one size go through the pose stage together) -- 1-3 objects per frame, five crop sizes.
     sweep = None
-    if (args.mixed or not args.no_sweep) and not args.frames:
+    if (args.mixed or (args.full and not args.no_sweep)) and not args.frames:
         sweep = mixed_sweep(args, rank, world, device, dist, seg, est, ref, seg_sd, est_sd, ref_sd, fence,
                             steps=args.mixed_steps if args.mixed else 4, with_parity=args.mixed)
 
     latency = None
-    want_latency = (args.latency or not args.no_latency) and not args.frames
+    want_latency = (args.latency or (args.full and not args.no_latency)) and not args.frames
     if want_latency and rank == 0:
         latency = latency_leg(args, device, seg, est, ref, frames[0], runs=args.latency_runs if args.latency else 50)
     if dist and want_latency:
         dist.barrier()
 
-    # Secondary, AFTER the timed region (not part of `value`): BASELINE configs[1] and configs[4] through the same code as --workload pose /
+    # --full, secondary, AFTER the timed region (not part of `value`): BASELINE configs[1] and configs[4] through the same code as --workload pose /
     # --workload label (every rank takes part: both have their own collectives), compact: 10 steps of 32 crops, 1 step of 200 views
     pose_leg = label_leg = None
-    if not args.frames:
+    if args.full and not args.frames:
         import copy
         torch.cuda.synchronize()
         if not args.no_pose_leg:
@@ -1292,8 +1307,10 @@ def main():
                                 "roofline_frac price the launch against the slower of its two limits (algorithmic flop at the matrix peak, algorithmic bytes "
                                 "at 8 TB/s), hbm_frac = the byte limit alone"
                                 + ("; the loop is software-pipelined (pose stage of the previous batch on a second stream beside these kernels), so the "
-                                   "timed-region durations include the co-running launches; isolated_* = the same kernels in a single-stream pass "
-                                   "of 3 steps after the timed region" if args.overlap else ""))
+                                   "timed-region durations include the co-running launches" if args.overlap else "")
+                                + ("; isolated_* = the same kernels in a single-stream pass of 3 steps after the timed region" if iso_summ else
+                                   "; ranked by timed-region time (--full adds the isolated_* figures of a single-stream pass and ranks by them)"
+                                   if args.overlap else ""))
         total_frames = per_rank * world * args.steps
         line = {
             "metric": "RGB-D frames/sec (seg+DenseFusion+2-refine), 640x480 N=1000",
@@ -1330,7 +1347,7 @@ def main():
             line["sweep"] = sweep
         if latency is not None:
             line["latency"] = latency
-        if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (the other ranks would idle at the barrier)
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (the other ranks would idle at the barrier)
             if out.get("stream") is not None:
                 out["stream"].synchronize()
             choose_h = out["choose"].cpu().numpy()

@@ -33,7 +33,7 @@ def _common(d, steps, warmup):
 
 
 def test_default_line_has_roofline_cpu_baseline_and_parity(tmp_path):
-    d = _run("--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    d = _run("--full", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path))
     _common(d, 2, 1)
     # --dump-outputs: what the last timed step returned, float32 / float64, 64 MB at most
     dumped = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
@@ -50,7 +50,7 @@ def test_default_line_has_roofline_cpu_baseline_and_parity(tmp_path):
     st = d["staged"]
     assert st["unit"] == "frames/s" and st["host_bytes_per_step"] == 64 * 480 * 640 * 5 and st["objects_found_last_step"] == 64
     assert st["value"] >= 0.9 * d["value"]              # the 98 MB per step hide behind the segmentation (within 3 % on a quiet box; 10 % here: short runs)
-    # compact secondary legs the plain command carries: four steps of the 1-3-objects / five-crop-sizes frames, 50 runs of the batch-1 live loop
+    # compact secondary legs the --full command carries: four steps of the 1-3-objects / five-crop-sizes frames, 50 runs of the batch-1 live loop
     sw, lat = d["sweep"], d["latency"]
     assert sw["steps"] == 4 and sw["unit"] == "frames/s" and 0 < sw["value"] < d["value"] * 1.2 and len(sw["crop_buckets_last_step"]) >= 4
     assert "parity" not in sw and sw["pose_graphs"] is True
@@ -101,10 +101,36 @@ def test_default_line_has_roofline_cpu_baseline_and_parity(tmp_path):
     assert sec["label"]["views_s"] == la["value"] and sec["label"]["max_nn_distance_mm"] == la["parity"]["max_nn_distance_mm"]
 
 
+def test_plain_line_carries_the_headline_and_nothing_that_runs_after_the_timed_region(tmp_path):
+    """Without --full the run sets up, warms up, times the steps, writes --dump-outputs and prints the line: the headline fields and the
+    roofline of the timed region's five kernels, none of the legs that take work of their own"""
+    d = _run("--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    _common(d, 2, 1)
+    assert d["unit"] == "frames/s" and d["scaling"] == "weak" and d["dtype"] == "bf16x3" and "resident in HBM" in d["config"]["inputs"]
+    assert abs(d["value"] - 64 * 2 / (d["ms_per_step"] * 2e-3)) < 0.02 * d["value"]
+    assert d["config"]["objects_found_last_step"] == 64 and d["config"]["crop_buckets_last_step"] == {"160x160": 64}
+    dumped = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(dumped) == {"poses", "pose", "objects", "n_cand", "choose", "objmap"} and dumped["poses"].shape == (64, 1, 8)
+    ks = d["roofline"]["kernels"]
+    assert len(ks) == 5 and d["roofline"]["kernel"] == ks[0]["kernel"]
+    for k in ks:
+        assert k["launches"] > 0 and 0 < k["frac"] < 1 and k["shapes"] and "isolated_frac" not in k
+    assert d["modes"] is None and d["staged"] is None and d["parity"]["steps_bitwise_equal"] == "skipped"
+    for k in ("sweep", "latency", "cpu_baseline", "pose", "label"):
+        assert k not in d, k
+    assert d["secondary"] == {"steps_bitwise_equal": "skipped"}
+    # the pose workload's plain line: the timed ADD-S launches priced, no extra profiled step, k-NN leg, CPU baseline or parity block
+    p = _run("--workload", "pose", "--steps", "2", "--warmup", "1")
+    assert p["unit"] == "crops/s" and p["steps"] == 2 and p["roofline"]["bound"] == "valu" and 0 < p["roofline"]["frac"] < 1
+    for k in ("knn_training_size", "cpu_baseline", "parity"):
+        assert k not in p, k
+    assert "kernels" not in p["roofline"]
+
+
 def test_frames_1024_line():
     """BASELINE configs[3] at its own size: 1024 frames per step (16 sub-batches of 64 on the one GPU), parity block kept (the oracle
     runs 16 frames of the last sub-batch)"""
-    d = _run("--frames", "1024", "--batch", "64", "--steps", "1", "--warmup", "1", "--baseline-frames", "16")
+    d = _run("--full", "--frames", "1024", "--batch", "64", "--steps", "1", "--warmup", "1", "--baseline-frames", "16")
     _common(d, 1, 1)
     assert d["scaling"] == "strong" and d["config"]["frames_per_gpu_per_step"] == 1024 and "configs[3]" in d["config"]["workload"]
     assert abs(d["value"] - 1024 / (d["ms_per_step"] * 1e-3)) < 0.02 * d["value"]
@@ -135,7 +161,7 @@ def test_mixed_sweep_and_latency_line():
 
 
 def test_label_line():
-    d = _run("--workload", "label", "--steps", "1", "--warmup", "1")
+    d = _run("--full", "--workload", "label", "--steps", "1", "--warmup", "1")
     _common(d, 1, 1)
     assert d["unit"] == "views/s" and d["scaling"] == "strong" and d["dtype"] == "f64" and "configs[4]" in d["config"]["workload"]
     assert d["icp"]["registrations_per_s"] > 0 and d["icp"]["point_pairs_per_s"] > 0
@@ -146,7 +172,7 @@ def test_label_line():
 def test_pose_line():
     """BASELINE configs[1]: PoseNet + 2 refiner passes + ADD-S through the HIP k-NN / ADD-S kernel on 32 crops; the line prices the pair
     evaluations against the fp32 vector rate, carries the k-NN kernel at the training loss's size, a CPU baseline and the parity block"""
-    d = _run("--workload", "pose", "--steps", "3", "--warmup", "1")
+    d = _run("--full", "--workload", "pose", "--steps", "3", "--warmup", "1")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline", "cpu_baseline", "parity", "knn_training_size"):
         assert k in d, k
@@ -192,7 +218,7 @@ def test_two_rank_rehearsal_on_one_gpu(flags):
     port = 29900 + os.getpid() % 90
     env = dict(os.environ, APE_DIST_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--no-cpu-baseline", *flags],
+                          "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--full", "--no-cpu-baseline", *flags],
                          capture_output=True, text=True, timeout=900, cwd=REPO, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]

@@ -15,8 +15,8 @@ $T rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_no -- python3
 cp $O/prof_no/*/*_kernel_stats.csv $O/${R}_bf16x3_kernel_stats.csv
 python tools/prof_summary.py $O/prof_no/*/*_kernel_trace.csv --steps $PSTEPS --warmup 2 > $O/${R}_bf16x3_timed_region.json || exit 1
 python tools/prof_step_list.py $O/prof_no/*/*_kernel_trace.csv > $O/${R}_step_launch_list.txt || exit 1
-# 2. the DEFAULT command (software-pipelined loop) under the kernel trace
-$T rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_def -- python3 bench.py --steps $PSTEPS --warmup 1 --no-cpu-baseline --no-modes --no-staged --no-sweep --no-latency --no-pose-leg --no-label-leg --no-step-check > $O/prof_def.log 2>&1 || exit 1
+# 2. the default software-pipelined loop under the kernel trace, with --full's isolated pass of the five kernels after the timed region
+$T rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_def -- python3 bench.py --full --steps $PSTEPS --warmup 1 --no-cpu-baseline --no-modes --no-staged --no-sweep --no-latency --no-pose-leg --no-label-leg --no-step-check > $O/prof_def.log 2>&1 || exit 1
 cp $O/prof_def/*/*_kernel_stats.csv $O/${R}_default_overlap_kernel_stats.csv
 python tools/prof_summary.py $O/prof_def/*/*_kernel_trace.csv --steps $PSTEPS --warmup 2 --tail-steps 3 > $O/${R}_default_overlap_timed_region.json || exit 1
 # 3. HBM traffic: FETCH_SIZE and WRITE_SIZE in separate passes, split per layer shape
@@ -31,10 +31,10 @@ python tools/pmc_big3.py --reduce $O/pmc_util/*/*_counter_collection.csv > $O/${
 $T rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_label -- python3 bench.py --workload label --steps 3 --warmup 1 --no-cpu-baseline > $O/prof_label.log 2>&1 || exit 1
 cp $O/prof_label/*/*_kernel_stats.csv $O/${R}_label_kernel_stats.csv
 # 5b. the pose workload (BASELINE configs[1]: 32 crops -> PoseNet + 2 refiner passes + ADD-S, and the k-NN kernel at the training loss's size)
-$T rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_pose -- python3 bench.py --workload pose --steps 20 --warmup 3 --no-cpu-baseline > $O/prof_pose.log 2>&1 || exit 1
+$T rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_pose -- python3 bench.py --full --workload pose --steps 20 --warmup 3 --no-cpu-baseline > $O/prof_pose.log 2>&1 || exit 1
 cp $O/prof_pose/*/*_kernel_stats.csv $O/${R}_pose_kernel_stats.csv
-# 6. the un-profiled default line of the same tree (with the CPU baseline and the parity block) and the freshness stamp
-$T python3 bench.py --steps 20 --warmup 5 > $O/bench_default.log 2>&1 || exit 1
+# 6. the un-profiled --full line of the same tree (with the CPU baseline and the parity block) and the freshness stamp
+$T python3 bench.py --full --steps 20 --warmup 5 > $O/bench_default.log 2>&1 || exit 1
 python - "$O" "$R" "$PSTEPS" <<'PY'
 import json, sys, os
 sys.path.insert(0, "tools")
