@@ -230,7 +230,8 @@ __global__ void maxpool3x3s2_bwd_kernel(const float* __restrict__ x, const float
     }
 }
 
-// adaptive average pool backward, gather form (bins [floor(o*H/S), ceil((o+1)*H/S)) may overlap by one pixel)
+// adaptive average pool backward, gather form.  Bin o is [floor(o*H/S), ceil((o+1)*H/S)); the bins holding pixel iy are exactly
+// o = floor(iy*S/H) .. ceil((iy+1)*S/H) - 1 (more than three of them when S > 2H)
 __global__ void adaptive_avgpool_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int B, int H, int W, int C, int S)
 {
     const long total = (long)B * H * W * C;
@@ -241,12 +242,13 @@ __global__ void adaptive_avgpool_bwd_kernel(const float* __restrict__ dy, float*
         const int iy = t % H;
         const int b = t / H;
         float g = 0.f;
-        const int oy_c = (int)(((long)iy * S) / H), ox_c = (int)(((long)ix * S) / W);
-        for (int oy = oy_c - 1; oy <= oy_c + 1; ++oy) {
+        const int oy_b = (int)(((long)iy * S) / H), ox_b = (int)(((long)ix * S) / W);
+        const int oy_e = (int)(((long)(iy + 1) * S + H - 1) / H), ox_e = (int)(((long)(ix + 1) * S + W - 1) / W);
+        for (int oy = oy_b; oy < oy_e; ++oy) {
             if (oy < 0 || oy >= S) continue;
             const int y0 = (oy * H) / S, y1 = ((oy + 1) * H + S - 1) / S;
             if (iy < y0 || iy >= y1) continue;
-            for (int ox = ox_c - 1; ox <= ox_c + 1; ++ox) {
+            for (int ox = ox_b; ox < ox_e; ++ox) {
                 if (ox < 0 || ox >= S) continue;
                 const int x0 = (ox * W) / S, x1 = ((ox + 1) * W + S - 1) / S;
                 if (ix < x0 || ix >= x1) continue;
@@ -299,7 +301,8 @@ __global__ void log_softmax_bwd_kernel(const float* __restrict__ dy, const float
     }
 }
 
-// gather_rows backward: dx[b][index[b][j]][:] += dy[b][j][:]  (dx zeroed by the caller; indices may repeat -> atomics)
+// gather_rows backward: dx[b][index[b][j]][:] += dy[b][j][:]  (dx zeroed by the caller; indices may repeat -> atomics).  An index
+// out of range is clamped to row 0 / rows_in - 1 exactly as the forward gather_rows_kernel clamps it: the adjoint of that forward.
 __global__ void scatter_add_rows_kernel(const float* __restrict__ dy, const int64_t* __restrict__ index, float* __restrict__ dx, int B,
                                         int rows_in, int n, int C)
 {
@@ -308,8 +311,8 @@ __global__ void scatter_add_rows_kernel(const float* __restrict__ dy, const int6
         const int c = i % C;
         const long r = i / C;
         const int b = r / n;
-        const long src = index[r];
-        if (src < 0 || src >= rows_in) continue;
+        long src = index[r];
+        src = src < 0 ? 0 : (src >= rows_in ? rows_in - 1 : src);
         atomicAdd(dx + ((long)b * rows_in + src) * C + c, dy[i]);
     }
 }

@@ -554,7 +554,8 @@ int ape_bilinear_bwd_nhwc_f32(const float* dy, float* dx, int B, int H, int W, i
                               void* stream);
 /* nn.LogSoftmax backward per row (pspnet.py:55) */
 int ape_log_softmax_bwd_rows_f32(const float* dy, const float* y, float* dx, long rows, int C, void* stream);
-/* torch.gather backward (network.py:100-102): dx[B][rows_in][C] = scatter-add of dy[B][n][C] at index[B][n] */
+/* torch.gather backward (network.py:100-102): dx[B][rows_in][C] = scatter-add of dy[B][n][C] at index[B][n]; an index outside
+ * 0..rows_in-1 is clamped as ape_gather_rows_f32 clamps it (the adjoint of that forward) */
 int ape_scatter_add_rows_f32(const float* dy, const int64_t* index, float* dx, int B, int rows_in, int n, int C, void* stream);
 /* AvgPool1d(num_points) backward (network.py:64): dx[B][n][C] = dy[B][C] / n */
 int ape_mean_rows_bwd_f32(const float* dy, float* dx, int B, int n, int C, void* stream);
