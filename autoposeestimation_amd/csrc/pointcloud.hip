@@ -12,7 +12,7 @@
 //   icp_*_sums         one-pass reductions for the two ICP estimators: Umeyama sums (point-to-point) and the 6x6 normal
 //                      equations J^T J, J^T r with r = (s - t).n_t, J = [s x n_t, n_t] (point-to-plane).
 // All of it is HBM/latency-bound index work, all of it hand written (the sort: seg_sort_batch / seg_merge_batch; the scans and the
-// ordered compactions: scan_block / compact_block); the one-cloud entry points are the batched ones called with one cloud.
+// ordered compactions: scan_block / compact_block).  Every `*_body` below has ONE kernel, its `*_batch` form: a cloud alone is a batch of one.
 // Reductions use fixed-order two-stage trees => bitwise reproducible.
 #include "common.h"
 #include "pc_grid.h"
@@ -52,11 +52,6 @@ __device__ __forceinline__ void transform_kernel_body(double* __restrict__ pts, 
             for (int r = 0; r < 3; ++r) normals[i * 3 + r] = (T.m[r * 4] * a + T.m[r * 4 + 1] * b) + T.m[r * 4 + 2] * c;
         }
     }
-}
-
-__global__ void transform_kernel(double* __restrict__ pts, int n, Mat4 T, double* __restrict__ normals)
-{
-    transform_kernel_body(pts, n, T, normals, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -146,40 +141,6 @@ __device__ __forceinline__ void radius_count_group_kernel_body(Grid g, const dou
     if (i < nq && lane == 0) count[i] = c;
 }
 
-__global__ __launch_bounds__(kT) void radius_count_group_kernel(Grid g, const double* __restrict__ q, int nq, double r2, int* __restrict__ count)
-{
-    radius_count_group_kernel_body(g, q, nq, r2, count, blockIdx.x, gridDim.x);
-}
-
-__device__ __forceinline__ void nn1_group_kernel_body(Grid g, const double* __restrict__ q, int nq, double r2, int* __restrict__ idx, double* __restrict__ dist2, const double* __restrict__ skip, const int bx, const int gx)
-{
-    if (skip && skip[0] != 0.0) return;
-    const int lane = threadIdx.x % kG;
-    const int i = (bx * kT + threadIdx.x) / kG;
-    double best = r2;
-    unsigned bi = 0xffffffffu;
-    if (i < nq)
-        for_my_cell(g, q + (size_t)i * 3, lane, [&](int j, double d2) {
-            const unsigned o = g.order[j];
-            if (d2 < best || (d2 == best && bi != 0xffffffffu && o < bi)) { best = d2; bi = o; }   // ties: lowest original index
-        });
-    for (int m = kG / 2; m >= 1; m >>= 1) {
-        const double ob = __shfl_xor(best, m, kG);
-        const unsigned oi = __shfl_xor(bi, m, kG);
-        if (oi != 0xffffffffu && (bi == 0xffffffffu || ob < best || (ob == best && oi < bi))) { best = ob; bi = oi; }
-    }
-    if (i < nq && lane == 0) {
-        idx[i] = bi == 0xffffffffu ? -1 : (int)bi;
-        dist2[i] = bi == 0xffffffffu ? 0.0 : best;
-    }
-}
-
-__global__ __launch_bounds__(kT) void nn1_group_kernel(Grid g, const double* __restrict__ q, int nq, double r2, int* __restrict__ idx,
-                                                       double* __restrict__ dist2, const double* __restrict__ skip)
-{
-    nn1_group_kernel_body(g, q, nq, r2, idx, dist2, skip, blockIdx.x, gridDim.x);
-}
-
 // `skip` (optional, in the kernels of the ICP loop): a device word that, once non-zero, turns the launch into a no-op -- the loop runs
 // a fixed number of enqueued iterations and the device decides when it has converged (icp_step)
 
@@ -228,7 +189,7 @@ __device__ void normal_from_selection(const Grid& g, const int* bj, int cnt, dou
     if (nrm[2] < 0) for (int d = 0; d < 3; ++d) nrm[d] = -nrm[d];
 }
 
-// kG lanes per query (see nn1_group_kernel): the in-radius candidates of the 27 cells go to the group's LDS list, then min(max_nn,
+// kG lanes per query (see icp_move_nn1_kernel_body): the in-radius candidates of the 27 cells go to the group's LDS list, then min(max_nn,
 // candidates) rounds take the smallest (d^2, sorted position) after the last one taken -- the order an insertion sort over the cells
 // in key order produces (its ties keep the first visited = lower sorted position) -- and lane 0 runs the covariance / eigenvector
 // part on the selection in that order.  More than kNrmCand candidates: the rounds re-walk each lane's cell instead of the list.
@@ -283,11 +244,6 @@ __device__ __forceinline__ void normals_kernel_body(Grid g, const double* __rest
     }
 }
 
-__global__ __launch_bounds__(kT) void normals_kernel(Grid g, const double* __restrict__ q, int nq, double r2, int max_nn, double* __restrict__ normals)
-{
-    normals_kernel_body(g, q, nq, r2, max_nn, normals, blockIdx.x, gridDim.x);
-}
-
 // brute-force k-NN (self included, like KDTree SearchKNN on the cloud itself): mean of the k smallest distances
 __global__ __launch_bounds__(kT) void knn_mean_kernel(const double* __restrict__ pts, int n, int k, double* __restrict__ mean)
 {
@@ -325,7 +281,7 @@ __global__ __launch_bounds__(kT) void knn_mean_kernel(const double* __restrict__
     }
 }
 
-// The same through the uniform grid, kG lanes per query (see nn1_group_kernel; the queries are the grid's own points in key order).
+// The same through the uniform grid, kG lanes per query (see icp_move_nn1_kernel_body; the queries are the grid's own points in key order).
 // For R = 1, 2, 3: the lanes share the cells of the (2R+1)^3 block around the query's cell and drop their squared distances into the
 // group's LDS list; if the block holds the k nearest for certain (k-th smallest inside R cell sizes: every point outside the block is
 // at least R cells away), k rounds of "smallest entry after the last one taken" (each lane scans its share, the group reduces by
@@ -423,11 +379,6 @@ __device__ __forceinline__ void knn_mean_grid_kernel_body(Grid g, int k, double*
     if (lane == 0) mean[g.order[i]] = sum / (double)k;
 }
 
-__global__ __launch_bounds__(kT) void knn_mean_grid_kernel(Grid g, int k, double* __restrict__ mean)
-{
-    knn_mean_grid_kernel_body(g, k, mean, blockIdx.x, gridDim.x);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // generic fixed-order reduction of NV doubles per element: stage 1 -> part[blocks][NV], stage 2 -> out[NV]
 template <int NV, class F>
@@ -456,11 +407,6 @@ __device__ __forceinline__ void reduce_stage2_body(const double* __restrict__ pa
     if (v < nv) { double s = 0; for (int b = 0; b < g; ++b) s += part[b * nv + v]; out[v] = s; }
 }
 
-__global__ void reduce_stage2(const double* __restrict__ part, int g, int nv, double* __restrict__ out, const double* __restrict__ skip = nullptr)
-{
-    reduce_stage2_body(part, g, nv, out, skip, blockIdx.x, gridDim.x);
-}
-
 // out: [0] count, [1] sum d^2, [2..4] sum s, [5..7] sum t, [8..16] sum s_a t_b (row a, col b)
 __device__ __forceinline__ void p2p_sums_kernel_body(const double* __restrict__ src, const double* __restrict__ tgt, const int* __restrict__ corr, const double* __restrict__ d2, int n, double* __restrict__ part, const double* __restrict__ skip, const int bx, const int gx)
 {
@@ -474,13 +420,6 @@ __device__ __forceinline__ void p2p_sums_kernel_body(const double* __restrict__ 
         for (int a = 0; a < 3; ++a) { e[2 + a] = s[a]; e[5 + a] = t[a]; for (int b = 0; b < 3; ++b) e[8 + a * 3 + b] = s[a] * t[b]; }
         return true;
     }, part, bx, gx);
-}
-
-__global__ __launch_bounds__(kT) void p2p_sums_kernel(const double* __restrict__ src, const double* __restrict__ tgt, const int* __restrict__ corr,
-                                                      const double* __restrict__ d2, int n, double* __restrict__ part,
-                                                      const double* __restrict__ skip = nullptr)
-{
-    p2p_sums_kernel_body(src, tgt, corr, d2, n, part, skip, blockIdx.x, gridDim.x);
 }
 
 // out: [0] count, [1] sum d^2, [2..22] upper triangle of J^T J (row major), [23..28] J^T r
@@ -503,14 +442,6 @@ __device__ __forceinline__ void p2plane_sums_kernel_body(const double* __restric
     }, part, bx, gx);
 }
 
-__global__ __launch_bounds__(kT) void p2plane_sums_kernel(const double* __restrict__ src, const double* __restrict__ tgt,
-                                                          const double* __restrict__ tn, const int* __restrict__ corr,
-                                                          const double* __restrict__ d2, int n, double* __restrict__ part,
-                                                          const double* __restrict__ skip = nullptr)
-{
-    p2plane_sums_kernel_body(src, tgt, tn, corr, d2, n, part, skip, blockIdx.x, gridDim.x);
-}
-
 // out: [0..2] sum p, [3..8] sum p_a p_b upper triangle
 __device__ __forceinline__ void moments_kernel_body(const double* __restrict__ pts, int n, double* __restrict__ part, const int bx, const int gx)
 {
@@ -520,11 +451,6 @@ __device__ __forceinline__ void moments_kernel_body(const double* __restrict__ p
         e[3] = p[0] * p[0]; e[4] = p[0] * p[1]; e[5] = p[0] * p[2]; e[6] = p[1] * p[1]; e[7] = p[1] * p[2]; e[8] = p[2] * p[2];
         return true;
     }, part, bx, gx);
-}
-
-__global__ __launch_bounds__(kT) void moments_kernel(const double* __restrict__ pts, int n, double* __restrict__ part)
-{
-    moments_kernel_body(pts, n, part, blockIdx.x, gridDim.x);
 }
 
 struct Vec12 { double v[12]; };
@@ -538,11 +464,6 @@ __device__ __forceinline__ void mahalanobis_kernel_body(const double* __restrict
         for (int a = 0; a < 3; ++a) s += e[a] * ((mc.v[3 + a * 3] * e[0] + mc.v[3 + a * 3 + 1] * e[1]) + mc.v[3 + a * 3 + 2] * e[2]);
         out[i] = sqrt(s);
     }
-}
-
-__global__ void mahalanobis_kernel(const double* __restrict__ pts, int n, Vec12 mc, double* __restrict__ out)
-{
-    mahalanobis_kernel_body(pts, n, mc, out, blockIdx.x, gridDim.x);
 }
 
 __device__ __forceinline__ void select_rows_kernel_body(const double* __restrict__ pts, const int* __restrict__ sel, const int* __restrict__ n_sel, double* __restrict__ out, const int bx, const int gx)
@@ -564,45 +485,6 @@ Mat4 load_mat(const double* T16_host) { Mat4 m; for (int i = 0; i < 16; ++i) m.m
 
 }  // namespace
 
-extern "C" int ape_transform_points_f64(double* pts, double* normals_or_null, int n, const double* T16_host, void* stream)
-{
-    if (!pts || !T16_host || n < 0) return APE_EINVAL;
-    if (n == 0) return APE_OK;
-    hipLaunchKernelGGL(transform_kernel, dim3(grid_for(n)), dim3(kT), 0, (hipStream_t)stream, pts, n, load_mat(T16_host), normals_or_null);
-    return ape::check_launch("ape_transform_points_f64");
-}
-
-#define GRID_ARGS const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n, double cell
-#define MAKE_GRID Grid g{sorted, (const u64*)keys, order, origin3, n, cell}
-
-extern "C" int ape_grid_radius_count_f64(GRID_ARGS, const double* q, int nq, double radius, int* count, void* stream)
-{
-    if (!sorted || !keys || !order || !origin3 || !q || !count || n < 1 || nq < 0 || radius > cell) return APE_EINVAL;
-    if (nq == 0) return APE_OK;
-    MAKE_GRID;
-    hipLaunchKernelGGL(radius_count_group_kernel, dim3(ape::ceil_div((long)nq * kG, (long)kT)), dim3(kT), 0, (hipStream_t)stream, g, q, nq, radius * radius, count);
-    return ape::check_launch("ape_grid_radius_count_f64");
-}
-
-extern "C" int ape_grid_nn1_f64(GRID_ARGS, const double* q, int nq, double max_dist, int* idx, double* dist2, void* stream)
-{
-    if (!sorted || !keys || !order || !origin3 || !q || !idx || !dist2 || n < 1 || nq < 0 || max_dist > cell) return APE_EINVAL;
-    if (nq == 0) return APE_OK;
-    MAKE_GRID;
-    hipLaunchKernelGGL(nn1_group_kernel, dim3(ape::ceil_div((long)nq * kG, (long)kT)), dim3(kT), 0, (hipStream_t)stream, g, q, nq, max_dist * max_dist, idx, dist2, (const double*)nullptr);
-    return ape::check_launch("ape_grid_nn1_f64");
-}
-
-extern "C" int ape_grid_normals_f64(GRID_ARGS, const double* q, int nq, double radius, int max_nn, double* normals, void* stream)
-{
-    if (!sorted || !keys || !order || !origin3 || !q || !normals || n < 1 || nq < 0 || radius > cell || max_nn < 3 || max_nn > kMaxNN)
-        return APE_EINVAL;
-    if (nq == 0) return APE_OK;
-    MAKE_GRID;
-    hipLaunchKernelGGL(normals_kernel, dim3(ape::ceil_div((long)nq * kG, (long)kT)), dim3(kT), 0, (hipStream_t)stream, g, q, nq, radius * radius, max_nn, normals);
-    return ape::check_launch("ape_grid_normals_f64");
-}
-
 extern "C" int ape_knn_mean_dist_f64(const double* pts, int n, int k, double* mean, void* stream)
 {
     if (!pts || !mean || n < 1 || k < 1 || k > kMaxNN) return APE_EINVAL;
@@ -610,48 +492,11 @@ extern "C" int ape_knn_mean_dist_f64(const double* pts, int n, int k, double* me
     return ape::check_launch("ape_knn_mean_dist_f64");
 }
 
-extern "C" int ape_grid_knn_mean_dist_f64(GRID_ARGS, int k, double* mean, void* stream)
-{
-    if (!sorted || !keys || !order || !origin3 || !mean || n < 1 || k < 1 || k > kMaxNN || k > n || !(cell > 0)) return APE_EINVAL;
-    MAKE_GRID;
-    hipLaunchKernelGGL(knn_mean_grid_kernel, dim3(ape::ceil_div((long)n * kG, (long)kT)), dim3(kT), 0, (hipStream_t)stream, g, k, mean);
-    return ape::check_launch("ape_grid_knn_mean_dist_f64");
-}
-
-/* kind 0: point-to-point sums out[17]; kind 1: point-to-plane out[29] (needs tgt_normals); kind 2: moments of src, out[9] */
-extern "C" int ape_icp_sums_f64(int kind, const double* src, const double* tgt, const double* tgt_normals, const int* corr,
-                                const double* dist2, int n, double* out, void* ws, size_t ws_bytes, void* stream)
-{
-    if (!src || !out || !ws || n < 0 || kind < 0 || kind > 2) return APE_EINVAL;
-    if (kind < 2 && (!tgt || !corr || !dist2)) return APE_EINVAL;
-    if (kind == 1 && !tgt_normals) return APE_EINVAL;
-    const int nv = kind == 0 ? 17 : kind == 1 ? 29 : 9;
-    const int g = grid_for(n, 512);
-    if (ws_bytes < (size_t)g * nv * 8) return APE_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    double* part = (double*)ws;
-    if (kind == 0) hipLaunchKernelGGL(p2p_sums_kernel, dim3(g), dim3(kT), 0, st, src, tgt, corr, dist2, n, part);
-    else if (kind == 1) hipLaunchKernelGGL(p2plane_sums_kernel, dim3(g), dim3(kT), 0, st, src, tgt, tgt_normals, corr, dist2, n, part);
-    else hipLaunchKernelGGL(moments_kernel, dim3(g), dim3(kT), 0, st, src, n, part);
-    hipLaunchKernelGGL(reduce_stage2, dim3(1), dim3(64), 0, st, part, g, nv, out);
-    return ape::check_launch("ape_icp_sums_f64");
-}
-
-extern "C" int ape_mahalanobis_f64(const double* pts, int n, const double* mean_cinv12_host, double* out, void* stream)
-{
-    if (!pts || !mean_cinv12_host || !out || n < 0) return APE_EINVAL;
-    if (n == 0) return APE_OK;
-    Vec12 mc;
-    for (int i = 0; i < 12; ++i) mc.v[i] = mean_cinv12_host[i];
-    hipLaunchKernelGGL(mahalanobis_kernel, dim3(grid_for(n)), dim3(kT), 0, (hipStream_t)stream, pts, n, mc, out);
-    return ape::check_launch("ape_mahalanobis_f64");
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // ICP iteration entirely on the device (open3d 0.9 RegistrationICP as called at pc_reconstruction/open3d_utils.py:96-117): the
 // correspondence search and the 17 / 29 reduced sums were device work already; here the 3x3 SVD (Umeyama, point-to-point) / the 6x6
 // solve (point-to-plane), the composition T <- update . T, the fitness / rmse bookkeeping and the convergence test run on the tail of
-// the reduction kernel (icp_reduce_step_kernel), so a registration needs ONE device-to-host copy (its result) instead of one per
+// the reduction kernel (icp_reduce_step_batch), so a registration needs ONE device-to-host copy (its result) instead of one per
 // iteration, and an iteration is three launches: [apply the pending update +] correspondence search, partial sums, reduce + step.
 // state[40]: [0] done, [1] updates applied, [2] fitness, [3] inlier rmse, [4] correspondences, [5..20] T (row major), [21..36] the
 // last update, [37] 1 = converged by the relative criteria, 2 = too few correspondences, 3 = iteration limit.
@@ -740,17 +585,13 @@ __device__ __forceinline__ void icp_reduce_step_kernel_body(const double* __rest
     if (v == 0) icp_step(kind, tot, st, ns, rel_fitness, rel_rmse, max_iteration);
 }
 
-__global__ __launch_bounds__(64) void icp_reduce_step_kernel(const double* __restrict__ part, int g, int nv, double* __restrict__ sums, int kind,
-                                                             double* __restrict__ st, int ns, double rel_fitness, double rel_rmse, int max_iteration)
-{
-    icp_reduce_step_kernel_body(part, g, nv, sums, kind, st, ns, rel_fitness, rel_rmse, max_iteration, blockIdx.x, gridDim.x);
-}
-
-// correspondence search of the ICP loop with the pending update applied on the way: the query is moved by state[21..36] (the update the
-// previous step computed), written back, and searched -- kG lanes per query as in nn1_group_kernel (every lane moves its copy)
+// correspondence search (nearest grid point within sqrt(r2), -1 if none), kG lanes per query: each lane walks its share of the 27 cells,
+// the group reduces by shuffles.  In the ICP loop (apply = 1) the pending update is applied on the way: the query is moved by
+// state[21..36] (the update the previous step computed; every lane moves its copy), written back, and searched.  `st` may be null
+// (apply = 0): a plain search that no state word can switch off
 __device__ __forceinline__ void icp_move_nn1_kernel_body(Grid g, double* __restrict__ src, int nq, double r2, int* __restrict__ idx, double* __restrict__ dist2, const double* __restrict__ st, int apply, const int bx, const int gx)
 {
-    if (st[0] != 0.0) return;
+    if (st && st[0] != 0.0) return;
     const int lane = threadIdx.x % kG;
     const int i = (bx * kT + threadIdx.x) / kG;
     double q[3] = {0, 0, 0};
@@ -767,7 +608,7 @@ __device__ __forceinline__ void icp_move_nn1_kernel_body(Grid g, double* __restr
     if (i < nq)
         for_my_cell(g, q, lane, [&](int j, double d2) {
             const unsigned o = g.order[j];
-            if (d2 < best || (d2 == best && bi != 0xffffffffu && o < bi)) { best = d2; bi = o; }
+            if (d2 < best || (d2 == best && bi != 0xffffffffu && o < bi)) { best = d2; bi = o; }   // ties: lowest original index
         });
     for (int m = kG / 2; m >= 1; m >>= 1) {
         const double ob = __shfl_xor(best, m, kG);
@@ -781,45 +622,7 @@ __device__ __forceinline__ void icp_move_nn1_kernel_body(Grid g, double* __restr
     }
 }
 
-__global__ __launch_bounds__(kT) void icp_move_nn1_kernel(Grid g, double* __restrict__ src, int nq, double r2, int* __restrict__ idx,
-                                                          double* __restrict__ dist2, const double* __restrict__ st, int apply)
-{
-    icp_move_nn1_kernel_body(g, src, nq, r2, idx, dist2, st, apply, blockIdx.x, gridDim.x);
-}
-
 }  // namespace
-
-/* Enqueue `n_iter` ICP iterations (kind 0 point-to-point, 1 point-to-plane) with everything on the device; see the block comment above.
- * `src` [ns][3] is the source ALREADY transformed by the initial guess and is updated in place; `state` [40] doubles on the device: the
- * caller zeroes it and writes the initial T into state[5..20] before the FIRST call of a registration (first_call = 1 also runs the
- * evaluation that precedes open3d's loop and the step that computes the first update), and reads it back (one copy) after each call:
- * state[0] != 0 means finished.  An iteration = apply the pending update, evaluate, step; `max_iteration` of them exhaust the limit.  Grid arguments:
- * the target's search grid from ape_grid_build_f64 (cell >= max_dist).  ws: n-blocks x 29 doubles as for ape_icp_sums_f64. */
-extern "C" int ape_icp_run_f64(int kind, GRID_ARGS, double* src, int ns, const double* tgt, const double* tgt_normals, double max_dist,
-                               double rel_fitness, double rel_rmse, int max_iteration, int n_iter, int first_call, int* corr, double* dist2,
-                               double* sums, double* state, void* ws, size_t ws_bytes, void* stream)
-{
-    if (kind < 0 || kind > 1 || !sorted || !keys || !order || !origin3 || !src || !tgt || !corr || !dist2 || !sums || !state || !ws) return APE_EINVAL;
-    if (kind == 1 && !tgt_normals) return APE_EINVAL;
-    if (n < 1 || ns < 1 || max_dist > cell || n_iter < 0 || max_iteration < 0) return APE_EINVAL;
-    const int nv = kind == 0 ? 17 : 29;
-    const int nb = grid_for(ns, 512);
-    if (ws_bytes < (size_t)nb * nv * 8) return APE_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    MAKE_GRID;
-    double* part = (double*)ws;
-    auto block = [&](int apply) {         // [move +] search, sums, reduce + step: three launches
-        hipLaunchKernelGGL(icp_move_nn1_kernel, dim3(ape::ceil_div((long)ns * kG, (long)kT)), dim3(kT), 0, st, g, src, ns, max_dist * max_dist, corr, dist2,
-                           (const double*)state, apply);
-        if (kind == 0) hipLaunchKernelGGL(p2p_sums_kernel, dim3(nb), dim3(kT), 0, st, (const double*)src, tgt, (const int*)corr, (const double*)dist2, ns, part, (const double*)state);
-        else hipLaunchKernelGGL(p2plane_sums_kernel, dim3(nb), dim3(kT), 0, st, (const double*)src, tgt, tgt_normals, (const int*)corr, (const double*)dist2, ns, part, (const double*)state);
-        hipLaunchKernelGGL(icp_reduce_step_kernel, dim3(1), dim3(64), 0, st, (const double*)part, nb, nv, sums, kind, state, ns, rel_fitness, rel_rmse, max_iteration);
-    };
-    if (first_call) block(0);
-    for (int it = 0; it < n_iter; ++it) block(1);
-    return ape::check_launch("ape_icp_run_f64");
-}
-
 
 // =====================================================================================================================================
 // BATCHED forms (`*_batch_f64`): the label path's clouds are tiny (10^3..10^4 points) and every step of a chain depends on the one before,
@@ -827,8 +630,8 @@ extern "C" int ape_icp_run_f64(int kind, GRID_ARGS, double* src, int ns, const d
 // step in round 2, three host threads fighting over the GIL to keep the GPU fed.  The (object, direction) chains are independent of each
 // other (create_pointcloud.py:276-312: one sequential fusion per rotation directory), so here ONE launch advances up to kMaxBatch chains:
 // blockIdx.y selects the chain's argument record (passed by value in the kernel arguments), blockIdx.x walks that chain's own grid -- the
-// SAME `*_body` device code with the SAME per-chain grid size as the one-cloud entry points above (the fixed-order two-stage reductions
-// keep their partial layout), hence bit-identical results.  hipCUB's sort becomes ONE segmented radix sort over all chains (same stable
+// `*_body` device code above with a per-chain grid size that depends on that chain's point count alone (the fixed-order two-stage
+// reductions keep their partial layout), hence a chain's result does not depend on its slot or its neighbours in the batch.  hipCUB's sort becomes ONE segmented radix sort over all chains (same stable
 // LSD radix per segment); its select / scan calls become a single-workgroup ordered compaction / scan per chain.
 namespace {
 
@@ -907,7 +710,7 @@ struct BKeys { const double* pts; const double* bounds6; u64* keys; unsigned* id
 struct BVox { const double* pts; const u64* keys; const unsigned* order; int* head; int* scan; double* out; int* n_out; int n, gx; };
 struct BGather { const double* pts; const unsigned* order; double* out; int n, gx; };
 struct BGridQ { Grid g; const double* q; int nq, gx; double r2; int* count; double* normals; int max_nn; double* mean; int k; };
-struct BSel { const double* pts; const int* count; const double* mean; int* sel; int* n_out; double* out; int n, gx, thr_count; double thr_mean; int mode; const uint8_t* keep; };
+struct BSel { const double* pts; const int* count; const double* mean; int* sel; int* n_out; double* out; int n, gx, thr_count; double thr_mean; int mode; };
 struct BMom { const double* pts; double* part; double* out; int n, gx; };
 struct BMaha { const double* pts; double* out; int n, gx; Vec12 mc; };
 struct BXform { double* pts; double* normals; Mat4 T; int n, gx; };
@@ -987,13 +790,12 @@ __global__ __launch_bounds__(kT) void knn_mean_batch(const Batch<BGridQ> b)
     knn_mean_grid_kernel_body(a.g, a.k, a.mean, blockIdx.x, a.gx);
 }
 // keep rule evaluated on the device: mode 0: count[i] > thr_count (RemoveRadiusOutliers); mode 1: mean[i] > 0 && mean[i] < thr_mean
-// (RemoveStatisticalOutliers; the threshold comes from the host's float64 statistics of the means, as in the one-cloud path)
+// (RemoveStatisticalOutliers; the threshold comes from the host's float64 statistics of the means)
 __global__ __launch_bounds__(kCT) void select_compact_batch(const Batch<BSel> b)
 {
     const BSel& a = b.t[blockIdx.y];
     if (a.n <= 0) return;
     if (a.mode == 0) compact_block(a.n, [&](int i) { return a.count[i] > a.thr_count; }, a.sel, a.n_out);
-    else if (a.mode == 2) compact_block(a.n, [&](int i) { return a.keep[i] != 0; }, a.sel, a.n_out);
     else compact_block(a.n, [&](int i) { const double m = a.mean[i]; return m > 0.0 && m < a.thr_mean; }, a.sel, a.n_out);
 }
 __global__ void select_rows_batch(const Batch<BSel> b)
@@ -1008,11 +810,11 @@ __global__ __launch_bounds__(kT) void moments1_batch(const Batch<BMom> b)
     if ((int)blockIdx.x >= a.gx) return;
     moments_kernel_body(a.pts, a.n, a.part, blockIdx.x, a.gx);
 }
-__global__ void moments2_batch(const Batch<BMom> b)
+__global__ void moments2_batch(const Batch<BMom> b, int nv)
 {
     const BMom& a = b.t[blockIdx.y];
     if (a.gx <= 0) return;
-    reduce_stage2_body(a.part, a.gx, 9, a.out, nullptr, 0, 1);
+    reduce_stage2_body(a.part, a.gx, nv, a.out, nullptr, 0, 1);
 }
 __global__ void mahalanobis_batch(const Batch<BMaha> b)
 {
@@ -1332,8 +1134,9 @@ extern "C" size_t ape_pc_batch_workspace_bytes(int nb, long n_total)
 
 #define APE_BATCH_CHECK(nb) if ((nb) < 1 || (nb) > kMaxBatch) return APE_EINVAL
 
-/* ape_surface_points_f64 for nb views at once: label[c] / depth[c] [H][W], T16_host [nb][16], points[c] capacity H*W rows,
- * n_out [nb] on the device; pix_ws: nb * H * W ints */
+/* get_surface's pixel loop for nb views at once: the pixels with label != 0 and depth != 0 in raster order, back-projected (mm) and moved
+ * to the robot frame.  label[c] / depth[c] [H][W], T16_host [nb][16], points[c] capacity H*W rows, n_out [nb] on the device;
+ * pix_ws: nb * H * W ints */
 extern "C" int ape_surface_points_batch_f64(int nb, const uint8_t* const* label, const uint16_t* const* depth, int H, int W, const double* intr4_host,
                                             const double* T16_host, double* const* points, int* n_out, int* pix_ws, void* stream)
 {
@@ -1350,7 +1153,7 @@ extern "C" int ape_surface_points_batch_f64(int nb, const uint8_t* const* label,
     return ape::check_launch("ape_surface_points_batch_f64");
 }
 
-/* ape_voxel_down_sample_f64 for nb clouds: out[c] capacity n[c] rows, n_out [nb] on the device; n / out pointers are host arrays */
+/* per-voxel means of nb clouds, ordered by voxel key: out[c] capacity n[c] rows, n_out [nb] on the device; n / out pointers are host arrays */
 extern "C" int ape_voxel_down_sample_batch_f64(int nb, const double* const* pts, const int* n, double voxel, double* const* out, int* n_out, void* ws,
                                                size_t ws_bytes, void* stream)
 {
@@ -1385,7 +1188,8 @@ extern "C" int ape_voxel_down_sample_batch_f64(int nb, const double* const* pts,
     return ape::check_launch("ape_voxel_down_sample_batch_f64");
 }
 
-/* ape_grid_build_f64 for nb clouds; sorted / keys / order / origin: per-cloud device buffers (host arrays of pointers) */
+/* the search grids of nb clouds (points sorted by cell key); sorted / keys / order / origin: per-cloud caller-owned device buffers (host
+ * arrays of pointers) */
 extern "C" int ape_grid_build_batch_f64(int nb, const double* const* pts, const int* n, double cell, double* const* sorted,
                                         unsigned long long* const* keys, unsigned* const* order, double* const* origin3, void* ws, size_t ws_bytes,
                                         void* stream)
@@ -1463,7 +1267,7 @@ extern "C" int ape_select_points_batch_f64(int mode, int nb, const double* const
     for (int c = 0; c < nb; ++c) {
         if (n[c] < 0) return APE_EINVAL;
         b.t[c] = BSel{pts[c], mode == 0 ? count[c] : nullptr, mode == 1 ? mean[c] : nullptr, sel_ws + off, n_out + c, out[c], n[c], n[c] > 0 ? grid_for(n[c]) : 0,
-                      thr_count, mode == 1 ? thr_mean_host[c] : 0.0, mode, nullptr};
+                      thr_count, mode == 1 ? thr_mean_host[c] : 0.0, mode};
         off += n[c];
         mg = b.t[c].gx > mg ? b.t[c].gx : mg;
     }
@@ -1473,7 +1277,7 @@ extern "C" int ape_select_points_batch_f64(int mode, int nb, const double* const
     return ape::check_launch("ape_select_points_batch_f64");
 }
 
-/* ape_icp_sums_f64(kind 2) for nb clouds: out9 [nb][9] on the device; ws: nb * 512 * 9 doubles */
+/* moments of nb clouds (sum p[3], upper triangle of sum p_a p_b [6]): out9 [nb][9] on the device; ws: nb * 512 * 9 doubles */
 extern "C" int ape_moments_batch_f64(int nb, const double* const* pts, const int* n, double* out9, void* ws, size_t ws_bytes, void* stream)
 {
     APE_BATCH_CHECK(nb);
@@ -1487,11 +1291,11 @@ extern "C" int ape_moments_batch_f64(int nb, const double* const* pts, const int
     }
     hipStream_t st = (hipStream_t)stream;
     launch_batch(moments1_batch, b, nb, mg, kT, st);
-    launch_batch(moments2_batch, b, nb, 1, 64, st);
+    launch_batch(moments2_batch, b, nb, 1, 64, st, 9);
     return ape::check_launch("ape_moments_batch_f64");
 }
 
-/* ape_mahalanobis_f64 for nb clouds: mc12_host [nb][12] */
+/* sqrt((p - mu)^T Cinv (p - mu)) per point of nb clouds: mc12_host [nb][12] = (mu[3], Cinv[9]) */
 extern "C" int ape_mahalanobis_batch_f64(int nb, const double* const* pts, const int* n, const double* mc12_host, double* const* out, void* stream)
 {
     APE_BATCH_CHECK(nb);
@@ -1512,7 +1316,7 @@ extern "C" int ape_mahalanobis_batch_f64(int nb, const double* const* pts, const
     return ape::check_launch("ape_mahalanobis_batch_f64");
 }
 
-/* ape_transform_points_f64 for nb clouds in place: T16_host [nb][16]; normals[c] may be null */
+/* p <- T p (normals: rotation part) for nb clouds in place: T16_host [nb][16]; normals[c] may be null */
 extern "C" int ape_transform_points_batch_f64(int nb, double* const* pts, double* const* normals, const int* n, const double* T16_host, void* stream)
 {
     APE_BATCH_CHECK(nb);
@@ -1547,9 +1351,13 @@ extern "C" int ape_concat_points_batch_f64(int nb, const double* const* a, const
     return ape::check_launch("ape_concat_points_batch_f64");
 }
 
-/* ape_icp_run_f64 for nb registrations of the same kind advancing together: per chain the target's grid, the moved source src[c] (ns[c]
- * rows, updated in place), target points / normals, scratch corr[c] / dist2[c] / sums[c] (29) and state[c] (40 doubles on the device, set
- * up as for ape_icp_run_f64); chains with ns[c] == 0 or gn[c] == 0 are skipped.  ws: nb * 512 * 29 doubles. */
+/* Enqueue `n_iter` ICP iterations (kind 0 point-to-point, 1 point-to-plane) of nb registrations advancing together, everything on the
+ * device; see the block comment above icp_step.  Per chain: the target's search grid (cell >= max_dist), src[c] [ns[c]][3] = the source
+ * ALREADY transformed by the initial guess, updated in place, target points / normals, scratch corr[c] / dist2[c] / sums[c] (29) and
+ * state[c], 40 doubles on the device: the caller zeroes it and writes the initial T into state[5..20] before the FIRST call of a
+ * registration (first_call = 1 also runs the evaluation that precedes open3d's loop and the step that computes the first update), and
+ * reads it back (one copy) after each call: state[0] != 0 means finished.  An iteration = apply the pending update, evaluate, step;
+ * `max_iteration` of them exhaust the limit.  Chains with ns[c] == 0 or gn[c] == 0 are skipped.  ws: nb * 512 * 29 doubles. */
 extern "C" int ape_icp_run_batch_f64(int kind, int nb, BGRID_ARGS, double* const* src, const int* ns, const double* const* tgt,
                                      const double* const* tgt_normals, double max_dist, double rel_fitness, double rel_rmse, int max_iteration, int n_iter,
                                      int first_call, int* const* corr, double* const* dist2, double* const* sums, double* const* state, void* ws,
@@ -1582,50 +1390,42 @@ extern "C" int ape_icp_run_batch_f64(int kind, int nb, BGRID_ARGS, double* const
 
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The one-cloud entry points: the batched ones above with one cloud (same kernels, same results as a batch slot)
-extern "C" size_t ape_pc_workspace_bytes(int n)
+// The two steps of an ICP evaluation as calls of their own, for a loop that solves on the host (registration_icp(host_solve=True), the
+// LAPACK check of icp_step): the batch kernels above with ONE record and no state word -- same per-cloud grid sizes, same bits.
+#define GRID_ARGS const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n, double cell
+
+extern "C" int ape_grid_nn1_f64(GRID_ARGS, const double* q, int nq, double max_dist, int* idx, double* dist2, void* stream)
 {
-    if (n < 1) n = 1;
-    return ape_pc_batch_workspace_bytes(1, n) + align_up((size_t)n * 4);
+    if (!sorted || !keys || !order || !origin3 || !q || !idx || !dist2 || n < 1 || nq < 0 || max_dist > cell) return APE_EINVAL;
+    if (nq == 0) return APE_OK;
+    Batch<BIcp> b{};
+    b.t[0] = BIcp{Grid{sorted, (const u64*)keys, order, origin3, n, cell}, const_cast<double*>(q), nullptr, nullptr, idx, dist2, nullptr, nullptr, nullptr,
+                  nq, ape::ceil_div((long)nq * kG, (long)kT), 0};
+    launch_batch(icp_move_nn1_batch, b, 1, b.t[0].gx_nn, kT, (hipStream_t)stream, max_dist * max_dist, 0);       // apply = 0: q is only read
+    return ape::check_launch("ape_grid_nn1_f64");
 }
 
-/* label[H][W] u8, depth[H][W] u16 -> points[n][3] f64 in raster order (capacity H*W), *n_out on the device */
-extern "C" int ape_surface_points_f64(const uint8_t* label, const uint16_t* depth, int H, int W, double fx, double fy, double ppx,
-                                      double ppy, const double* T16_host, double* points, int* n_out, void* ws, size_t ws_bytes,
-                                      void* stream)
+/* kind 0: point-to-point sums out[17]; kind 1: point-to-plane out[29] (needs tgt_normals); kind 2: moments of src, out[9] */
+extern "C" int ape_icp_sums_f64(int kind, const double* src, const double* tgt, const double* tgt_normals, const int* corr,
+                                const double* dist2, int n, double* out, void* ws, size_t ws_bytes, void* stream)
 {
-    if (!label || !depth || !T16_host || !points || !n_out || !ws || H < 1 || W < 1) return APE_EINVAL;
-    if (ws_bytes < (size_t)H * W * 4) return APE_EWORKSPACE;
-    const double intr[4] = {fx, fy, ppx, ppy};
-    return ape_surface_points_batch_f64(1, &label, &depth, H, W, intr, T16_host, &points, n_out, (int*)ws, stream);
-}
-
-/* out capacity n points; *n_out on the device */
-extern "C" int ape_voxel_down_sample_f64(const double* pts, int n, double voxel, double* out, int* n_out, void* ws, size_t ws_bytes,
-                                         void* stream)
-{
-    if (!pts || !out || !n_out || !ws || n < 1 || !(voxel > 0)) return APE_EINVAL;
-    return ape_voxel_down_sample_batch_f64(1, &pts, &n, voxel, &out, n_out, ws, ws_bytes, stream);
-}
-
-/* Build the search grid of a cloud: sorted[n][3], keys[n], order[n], origin[3] (all caller-owned device buffers). */
-extern "C" int ape_grid_build_f64(const double* pts, int n, double cell, double* sorted, unsigned long long* keys, unsigned* order,
-                                  double* origin3, void* ws, size_t ws_bytes, void* stream)
-{
-    if (!pts || !sorted || !keys || !order || !origin3 || !ws || n < 1 || !(cell > 0)) return APE_EINVAL;
-    return ape_grid_build_batch_f64(1, &pts, &n, cell, &sorted, &keys, &order, &origin3, ws, ws_bytes, stream);
-}
-
-/* out[i] = pts[sel[i]] for the rows with keep[i] != 0, in order (capacity n); *n_out on the device */
-extern "C" int ape_select_points_f64(const double* pts, const uint8_t* keep, int n, double* out, int* sel_idx, int* n_out, void* ws,
-                                     size_t ws_bytes, void* stream)
-{
-    (void)ws; (void)ws_bytes;
-    if (!pts || !keep || !out || !sel_idx || !n_out || n < 1) return APE_EINVAL;
-    Batch<BSel> b{};
-    b.t[0] = BSel{pts, nullptr, nullptr, sel_idx, n_out, out, n, grid_for(n), 0, 0.0, 2, keep};
+    if (!src || !out || !ws || n < 0 || kind < 0 || kind > 2) return APE_EINVAL;
+    if (kind < 2 && (!tgt || !corr || !dist2)) return APE_EINVAL;
+    if (kind == 1 && !tgt_normals) return APE_EINVAL;
+    const int nv = kind == 0 ? 17 : kind == 1 ? 29 : 9;
+    const int g = grid_for(n, 512);
+    if (ws_bytes < (size_t)g * nv * 8) return APE_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    launch_batch(select_compact_batch, b, 1, 1, kCT, st);
-    launch_batch(select_rows_batch, b, 1, b.t[0].gx, kT, st);
-    return ape::check_launch("ape_select_points_f64");
+    double* part = (double*)ws;
+    Batch<BMom> bm{};
+    bm.t[0] = BMom{src, part, out, n, g};
+    if (kind == 2) {
+        launch_batch(moments1_batch, bm, 1, g, kT, st);
+    } else {
+        Batch<BIcp> b{};
+        b.t[0] = BIcp{Grid{}, const_cast<double*>(src), tgt, tgt_normals, const_cast<int*>(corr), const_cast<double*>(dist2), part, nullptr, nullptr, n, 0, g};
+        launch_batch(icp_sums_batch, b, 1, g, kT, st, kind);
+    }
+    launch_batch(moments2_batch, bm, 1, 1, 64, st, nv);
+    return ape::check_launch("ape_icp_sums_f64");
 }

@@ -3,9 +3,10 @@
 A chain by itself is a string of tiny dependent kernels (10^3..10^4 points, float64): round 2 drove three chains side by side from three
 host threads and still spent its time in launch latency (38.6 k launches and 13.6 k small copies per 200-view step, the threads fighting
 over the GIL).  Here ONE host thread advances up to 16 clouds per call: every primitive below takes a LIST of clouds and issues ONE launch
-(`blockIdx.y` = cloud, csrc/pointcloud.hip "BATCHED forms") with ONE device-to-host copy of the counts it needs -- the same `*_body`
-device code with the same per-cloud grid sizes as the one-cloud methods of `PointCloud`, and the same host float64 arithmetic between
-the launches, so every cloud comes out BIT-IDENTICAL to the one-cloud path (tests/test_gpu_pointcloud.py compares them).
+(`blockIdx.y` = cloud, csrc/pointcloud.hip "BATCHED forms") with ONE device-to-host copy of the counts it needs.  A cloud's grid sizes
+and the host float64 arithmetic between the launches depend on that cloud alone, so its result does not depend on its slot or its
+neighbours in a batch (tests/test_gpu_pointcloud.py compares batches of 16 + 3 with every cloud alone), and this is the ONLY
+implementation: the methods of `PointCloud` and `pointcloud.registration_icp` call the primitives below with a one-element list.
 
     get_surface_batch(views, ...)          = [open3d_utils.get_surface(v) for v in views]              (reference open3d_utils.py:171-213)
     fuse_surfaces_batch(chains, ...)       = [open3d_utils.fuse_surfaces(c) for c in chains]           (create_pointcloud.py:288-312)
@@ -57,7 +58,8 @@ def _cloud(points, device):
 
 # ---- primitives over lists of clouds ----------------------------------------------------------------------------------------------------
 def surface_points(views, intr_default, device="cuda"):
-    """[pointcloud.surface_points(label, depth, intr, robot2cam)] for resident views (label u8 / depth u16 CUDA tensors of ONE image size)"""
+    """views = [(label u8[H,W], depth (integer sensor units) [H,W], robot2cam 4x4[, intr])] of ONE image size -> PointClouds of the valid
+    pixels in the robot frame (mm); resident views (label u8 / depth u16 CUDA tensors) are used in place, others are uploaded"""
     out = [None] * len(views)
     for idx in _chunks(views):
         labs, deps, intrs, Ts = [], [], [], []
@@ -117,7 +119,8 @@ def voxel_down_sample(clouds, voxel_size):
 
 
 def build_grids(clouds, cell):
-    """the search grid of every cloud for ONE cell size (PointCloud._grid, cached on the cloud like the one-cloud path does); empty clouds get None"""
+    """the search grid of every cloud for ONE cell size; the last one is kept on the cloud while its coordinates stay the same tensor,
+    unchanged (`_epoch`: in-place transforms); empty clouds get None"""
     grids = [None] * len(clouds)
     todo = []
     for i, c in enumerate(clouds):
@@ -152,13 +155,18 @@ def _grid_args(grids):
             _ints([0 if g is None else g["n"] for g in grids]))
 
 
-def _select(clouds, mode, counts=None, thr_count=0, means=None, thr_means=None):
-    """ordered row selection with the keep rule on the device -> new clouds"""
-    out = [None] * len(clouds)
+def _select(clouds, mode, counts=None, thr_count=0, means=None, thr_means=None, indices=False):
+    """ordered row selection with the keep rule on the device -> new clouds; indices=True: -> (clouds, [kept row indices per cloud]), one
+    more copy per batch (the `sel` buffer the kernel fills anyway)"""
+    out, kept_idx = [None] * len(clouds), [[] for _ in clouds]
     for idx in _chunks(clouds):
         ns = [len(clouds[i]) for i in idx]
         dev = clouds[idx[0]].device
         nb = len(idx)
+        if sum(ns) == 0:                                 # empty clouds cost no launch
+            for i in idx:
+                out[i] = PC.PointCloud(device=dev)
+            continue
         bufs = [torch.empty(max(n, 1), 3, dtype=_D, device=dev) for n in ns]
         cnt = torch.zeros(nb, dtype=torch.int32, device=dev)
         sel = torch.empty(max(sum(ns), 1), dtype=torch.int32, device=dev)
@@ -168,15 +176,22 @@ def _select(clouds, mode, counts=None, thr_count=0, means=None, thr_means=None):
                                                     _dbls([thr_means[i] for i in idx]) if mode == 1 else None, _ptrs(bufs), _lib.dptr(cnt), _lib.dptr(sel), _st())
         _lib.check(rc, "ape_select_points_batch_f64")
         kept = cnt.cpu().numpy()
+        if indices:
+            sel_host, offs = sel.cpu().numpy(), np.concatenate([[0], np.cumsum(ns)])
         for k, i in enumerate(idx):
             out[i] = _cloud(bufs[k][:int(kept[k])].contiguous(), dev) if ns[k] else PC.PointCloud(device=dev)
-    return out
+            if indices:
+                kept_idx[i] = sel_host[offs[k]:offs[k] + int(kept[k])].tolist()
+    return (out, kept_idx) if indices else out
 
 
-def remove_radius_outlier(clouds, nb_points, radius):
+def remove_radius_outlier(clouds, nb_points, radius, indices=False):
+    """keeps points with MORE than nb_points neighbours (self included) at distance < radius"""
     grids = build_grids(clouds, radius)
     counts = [None] * len(clouds)
     for idx in _chunks(clouds):
+        if not any(len(clouds[i]) for i in idx):
+            continue
         dev = clouds[idx[0]].device
         cs = [torch.empty(max(len(clouds[i]), 1), dtype=torch.int32, device=dev) for i in idx]
         rc = _lib.lib().ape_grid_query_batch_f64(0, len(idx), *_grid_args([grids[i] for i in idx]), float(radius), _ptrs([clouds[i]._p for i in idx]),
@@ -184,15 +199,17 @@ def remove_radius_outlier(clouds, nb_points, radius):
         _lib.check(rc, "ape_grid_query_batch_f64")
         for k, i in enumerate(idx):
             counts[i] = cs[k]
-    return _select(clouds, 0, counts=counts, thr_count=int(nb_points))
+    return _select(clouds, 0, counts=counts, thr_count=int(nb_points), indices=indices)
 
 
 def moments(clouds):
-    """[PointCloud._moments()] -> (mean[3], covariance[3,3]) per cloud (None for an empty one)"""
+    """(mean[3], population covariance[3,3]) per cloud, as open3d's ComputeMeanAndCovariance (None for an empty one)"""
     out = [None] * len(clouds)
     for idx in _chunks(clouds):
         dev = clouds[idx[0]].device
         ns = [len(clouds[i]) for i in idx]
+        if sum(ns) == 0:
+            continue
         o9 = torch.zeros(len(idx), 9, dtype=_D, device=dev)
         ws = torch.empty(len(idx) * 512 * 9 * 8, dtype=torch.uint8, device=dev)
         rc = _lib.lib().ape_moments_batch_f64(len(idx), _ptrs([clouds[i]._p for i in idx]), _ints(ns), _lib.dptr(o9), _lib.dptr(ws), ws.numel(), _st())
@@ -209,7 +226,7 @@ def moments(clouds):
 
 
 def mahalanobis(clouds):
-    """[np.array(c.compute_mahalanobis_distance())] (host arrays, like the one-cloud method)"""
+    """sqrt((p - mean)^T cov^-1 (p - mean)) of every point, per cloud, as host arrays"""
     mom = moments(clouds)
     out = [np.zeros(0)] * len(clouds)
     for idx in _chunks(clouds):
@@ -234,52 +251,64 @@ def mahalanobis(clouds):
     return out
 
 
-def remove_statistical_outlier(clouds, nb_neighbors, std_ratios, cell_hint):
-    """PointCloud.remove_statistical_outlier per cloud (its own std_ratio each), one k-NN launch, one copy of the means, the float64 threshold
-    statistics on the host exactly as the one-cloud method computes them, the keep rule evaluated on the device"""
-    out = [None] * len(clouds)
-    live = [i for i, c in enumerate(clouds) if len(c) > 0]
-    for i in range(len(clouds)):
-        if i not in live:
-            out[i] = PC.PointCloud(device=clouds[i].device)
-    # the k-NN grid's cell: _safe_cell(cell_hint) per cloud; clouds that need another cell than the common one go through the one-cloud method
-    common = float(cell_hint)
-    odd = [i for i in live if clouds[i]._safe_cell(common) != common or min(nb_neighbors, len(clouds[i])) != nb_neighbors]
-    for i in odd:
-        out[i] = clouds[i].remove_statistical_outlier(nb_neighbors, std_ratios[i], cell_hint=cell_hint)[0]
-    live = [i for i in live if i not in odd]
-    if not live:
-        return out
-    sub = [clouds[i] for i in live]
-    grids = build_grids(sub, common)
-    means = [None] * len(sub)
-    for idx in _chunks(sub):
-        dev = sub[idx[0]].device
-        ns = [len(sub[j]) for j in idx]
-        offs = np.concatenate([[0], np.cumsum(ns)])
-        flat = torch.empty(int(offs[-1]), dtype=_D, device=dev)
-        views = [flat[offs[k]:offs[k + 1]] for k in range(len(idx))]
-        rc = _lib.lib().ape_grid_query_batch_f64(2, len(idx), *_grid_args([grids[j] for j in idx]), common, None, None, 0.0, int(nb_neighbors), None, None,
-                                                 _ptrs(views), _st())
-        _lib.check(rc, "ape_grid_query_batch_f64")
-        host = flat.cpu().numpy()
-        for k, j in enumerate(idx):
-            means[j] = (views[k], host[offs[k]:offs[k + 1]])
-    thr = []
-    for j, (_, m) in enumerate(means):
-        valid = m >= 0
-        cloud_mean = m[valid].sum() / max(int(valid.sum()), 1)
-        std = math.sqrt(((m[valid] - cloud_mean) ** 2).sum() / max(int(valid.sum()) - 1, 1))
-        thr.append(cloud_mean + float(std_ratios[live[j]]) * std)
-    kept = _select(sub, 1, means=[mv[0] for mv in means], thr_means=thr)
-    for j, i in enumerate(live):
-        out[i] = kept[j]
-    return out
+def remove_statistical_outlier(clouds, nb_neighbors, std_ratios, cell_hint=None, indices=False):
+    """open3d 0.9 RemoveStatisticalOutliers per cloud (its own std_ratio each): the mean distance to the nb_neighbors nearest (self included)
+    must be < cloud mean + std_ratio * sample std.  One k-NN launch, one copy of the means, the float64 threshold statistics on the host,
+    the keep rule evaluated on the device.  `cell_hint` = a radius expected to hold the k neighbours (speed only: the grid search is exact
+    for any cell), None: derived from each cloud's extent and point count.  Clouds that share (cell, k) advance together."""
+    out, kept_idx = [None] * len(clouds), [[] for _ in clouds]
+    groups = {}                                          # (k-NN cell, k) -> positions of the clouds that take it, in order
+    for i, c in enumerate(clouds):
+        n = len(c)
+        if n == 0:
+            out[i] = PC.PointCloud(device=c.device)
+            continue
+        k = int(min(nb_neighbors, n))
+        hint = cell_hint
+        if hint is None:
+            ext = (c._p.max(0).values - c._p.min(0).values).cpu().numpy()
+            area = ext[0] * ext[1] + ext[1] * ext[2] + ext[0] * ext[2]       # a surface scan: ~n / area points per unit area
+            hint = math.sqrt(max(k * area / (3.0 * n), 1e-300))
+            if not (hint > 0 and math.isfinite(hint)):
+                hint = 1.0
+        groups.setdefault((c._safe_cell(hint), k), []).append(i)
+    for (cell, k), live in groups.items():
+        sub = [clouds[i] for i in live]
+        grids = build_grids(sub, cell)
+        means = [None] * len(sub)
+        for idx in _chunks(sub):
+            dev = sub[idx[0]].device
+            ns = [len(sub[j]) for j in idx]
+            offs = np.concatenate([[0], np.cumsum(ns)])
+            flat = torch.empty(int(offs[-1]), dtype=_D, device=dev)
+            views = [flat[offs[m]:offs[m + 1]] for m in range(len(idx))]
+            rc = _lib.lib().ape_grid_query_batch_f64(2, len(idx), *_grid_args([grids[j] for j in idx]), cell, None, None, 0.0, k, None, None,
+                                                     _ptrs(views), _st())
+            _lib.check(rc, "ape_grid_query_batch_f64")
+            host = flat.cpu().numpy()
+            for m, j in enumerate(idx):
+                means[j] = (views[m], host[offs[m]:offs[m + 1]])
+        thr = []
+        for j, (_, m) in enumerate(means):
+            valid = m >= 0
+            cloud_mean = m[valid].sum() / max(int(valid.sum()), 1)
+            std = math.sqrt(((m[valid] - cloud_mean) ** 2).sum() / max(int(valid.sum()) - 1, 1))
+            thr.append(cloud_mean + float(std_ratios[live[j]]) * std)
+        res = _select(sub, 1, means=[mv[0] for mv in means], thr_means=thr, indices=indices)
+        kept, kept_rows = res if indices else (res, None)
+        for j, i in enumerate(live):
+            out[i] = kept[j]
+            if indices:
+                kept_idx[i] = kept_rows[j]
+    return (out, kept_idx) if indices else out
 
 
 def estimate_normals(clouds, radius, max_nn):
+    """KDTreeSearchParamHybrid(radius, max_nn) normals, set on the clouds"""
     grids = build_grids(clouds, radius)
     for idx in _chunks(clouds):
+        if not any(len(clouds[i]) for i in idx):
+            continue
         dev = clouds[idx[0]].device
         nrm = [torch.empty(max(len(clouds[i]), 1), 3, dtype=_D, device=dev) for i in idx]
         rc = _lib.lib().ape_grid_query_batch_f64(1, len(idx), *_grid_args([grids[i] for i in idx]), float(radius), _ptrs([clouds[i]._p for i in idx]),
@@ -292,7 +321,7 @@ def estimate_normals(clouds, radius, max_nn):
 
 
 def transform(clouds, Ts):
-    """in place, like PointCloud.transform"""
+    """in place (points, and normals where a cloud has them); bumps the clouds' `_epoch` so that their cached search grids go stale"""
     for idx in _chunks(clouds):
         live = [i for i in idx if len(clouds[i])]
         if not live:
@@ -322,15 +351,17 @@ def concat(a_list, b_list=None):
     return out
 
 
-def registration_icp(sources, targets, max_correspondence_distance, inits, kind, criteria):
-    """[pointcloud.registration_icp(s, t, dist, init, estimator(kind), criteria).transformation] for pairs advancing together: one launch triple
-    per iteration for all pairs, one copy of all 40-double states per chunk of iterations; a pair that has converged turns its launches
-    into no-ops (its device `done` word), exactly as in the one-pair loop."""
+def icp_states(sources, targets, max_correspondence_distance, inits, kind, criteria):
+    """open3d 0.9 RegistrationICP (estimator `kind`: 0 point-to-point, 1 point-to-plane) for pairs advancing together: one launch triple per
+    iteration for all pairs, one copy of all 40-double states per chunk of iterations; a pair that has converged turns its launches into
+    no-ops (its device `done` word).  -> the final state of every pair (ape_icp_run_batch_f64: [2] fitness, [3] inlier rmse,
+    [4] correspondences, [5..20] T), None for a pair with an empty cloud.  The sources are not modified."""
     n = len(sources)
     Ts = [np.eye(4) if inits[i] is None else np.array(inits[i], dtype=np.float64) for i in range(n)]
+    states = [None] * n
     live = [i for i in range(n) if len(sources[i]) and len(targets[i])]
     if not live:
-        return Ts
+        return states
     moved = transform(concat([sources[i] for i in live]), [Ts[i] for i in live])      # open3d works on a transformed copy
     tg = [targets[i] for i in live]
     grids = build_grids(tg, max_correspondence_distance)
@@ -377,8 +408,15 @@ def registration_icp(sources, targets, max_correspondence_distance, inits, kind,
                     PC.ICP_STATS["kind%d" % kind] = PC.ICP_STATS.get("kind%d" % kind, 0) + ev * ns[k]
                 PC.ICP_STATS["events"].append((ev0, ev1))
         for k, j in enumerate(idx):
-            Ts[live[j]] = out[k, 5:21].reshape(4, 4).copy()
-    return Ts
+            states[live[j]] = out[k]
+    return states
+
+
+def registration_icp(sources, targets, max_correspondence_distance, inits, kind, criteria):
+    """[transformation of the pair's registration]; a pair with an empty cloud keeps its initial guess"""
+    states = icp_states(sources, targets, max_correspondence_distance, inits, kind, criteria)
+    return [(np.eye(4) if inits[i] is None else np.array(inits[i], dtype=np.float64)) if st is None else st[5:21].reshape(4, 4).copy()
+            for i, st in enumerate(states)]
 
 
 # ---- the two stages of the label path, in lock step over chains -------------------------------------------------------------------------

@@ -6,7 +6,6 @@ scipy/numpy restatement (oracle/pointcloud_oracle.py) plus recover-a-known-trans
 
 Points live on the GPU as a contiguous float64 [n,3] tensor; `np.array(pcd.points)` / `np.asarray(pcd.points)` copies to
 the host like open3d's Vector3dVector does; assigning `pcd.points = array` uploads.  No CPU fallback."""
-import ctypes
 import threading
 import math
 import os
@@ -21,16 +20,6 @@ _D = torch.float64
 
 def _st():
     return _lib.stream_ptr()
-
-
-def _ws(n, device):
-    nbytes = _lib.lib().ape_pc_workspace_bytes(int(max(n, 1)))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
-
-
-def _host16(T):
-    T = np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(16))
-    return T, T.ctypes.data_as(ctypes.c_void_p)
 
 
 class _Points:
@@ -103,17 +92,9 @@ class PointCloud:
     __deepcopy__ = lambda self, memo: self.clone()   # noqa: E731  (copy.deepcopy(target), open3d_utils.py:72)
 
     # -- moments ---------------------------------------------------------------------------------------------------
+    # Every kernel-backed method below is the list primitive of batched.py called with this one cloud: a cloud alone is a batch of one.
     def _moments(self):
-        n = len(self)
-        out = torch.empty(9, dtype=_D, device=self.device)
-        ws = torch.empty(512 * 29 * 8, dtype=torch.uint8, device=self.device)
-        rc = _lib.lib().ape_icp_sums_f64(2, _lib.dptr(self._p, _D), None, None, None, None, n, _lib.dptr(out), _lib.dptr(ws),
-                                         ws.numel(), _st())
-        _lib.check(rc, "ape_icp_sums_f64")
-        m = out.cpu().numpy()
-        mean = m[:3] / n
-        s2 = np.array([[m[3], m[4], m[5]], [m[4], m[6], m[7]], [m[5], m[7], m[8]]]) / n
-        return mean, s2 - np.outer(mean, mean)      # open3d ComputeMeanAndCovariance: population covariance
+        return _B.moments([self])[0]                # (mean, population covariance): open3d ComputeMeanAndCovariance
 
     def get_center(self):
         if len(self) == 0:
@@ -121,23 +102,11 @@ class PointCloud:
         return self._moments()[0]
 
     def compute_mahalanobis_distance(self):
-        n = len(self)
-        if n == 0:
-            return np.zeros(0)
-        mean, cov = self._moments()
-        mc = np.ascontiguousarray(np.concatenate([mean, np.linalg.inv(cov).reshape(9)]))
-        out = torch.empty(n, dtype=_D, device=self.device)
-        rc = _lib.lib().ape_mahalanobis_f64(_lib.dptr(self._p, _D), n, mc.ctypes.data_as(ctypes.c_void_p), _lib.dptr(out), _st())
-        _lib.check(rc, "ape_mahalanobis_f64")
-        return out.cpu().numpy()
+        return _B.mahalanobis([self])[0]
 
     # -- rigid motions (in place, return self like open3d) ------------------------------------------------------------
     def transform(self, T):
-        if len(self):
-            self._epoch += 1
-            T, ptr = _host16(T)
-            rc = _lib.lib().ape_transform_points_f64(_lib.dptr(self._p, _D), _lib.dptr(self._n), len(self), ptr, _st())
-            _lib.check(rc, "ape_transform_points_f64")
+        _B.transform([self], [T])
         return self
 
     def translate(self, translation, relative=True):
@@ -156,40 +125,12 @@ class PointCloud:
 
     # -- filters ---------------------------------------------------------------------------------------------------
     def voxel_down_sample(self, voxel_size):
-        n = len(self)
-        out = PointCloud(device=self.device)
-        if n == 0:
-            return out
-        buf = torch.empty(n, 3, dtype=_D, device=self.device)
-        cnt = torch.zeros(1, dtype=torch.int32, device=self.device)
-        ws = _ws(n, self.device)
-        rc = _lib.lib().ape_voxel_down_sample_f64(_lib.dptr(self._p, _D), n, float(voxel_size), _lib.dptr(buf), _lib.dptr(cnt),
-                                                  _lib.dptr(ws), ws.numel(), _st())
-        _lib.check(rc, "ape_voxel_down_sample_f64")
-        out._p = buf[:int(cnt.item())].contiguous()
-        return out
+        return _B.voxel_down_sample([self], voxel_size)[0]
 
     def _grid(self, cell):
         """search grid of this cloud for cell size `cell`; the last one is kept while the coordinates stay the same tensor, unchanged
-        (icp_regression registers two estimators against the same target)"""
-        c = self._gcache
-        if c is not None and c[0] is self._p and c[1] == float(cell) and c[2] == self._epoch:
-            return c[3]
-        g = self._build_grid(cell)
-        self._gcache = (self._p, float(cell), self._epoch, g)
-        return g
-
-    def _build_grid(self, cell):
-        n = len(self)
-        g = {"sorted": torch.empty(n, 3, dtype=_D, device=self.device),
-             "keys": torch.empty(n, dtype=torch.int64, device=self.device),
-             "order": torch.empty(n, dtype=torch.int32, device=self.device),
-             "origin": torch.empty(3, dtype=_D, device=self.device), "n": n, "cell": float(cell)}
-        ws = _ws(n, self.device)
-        rc = _lib.lib().ape_grid_build_f64(_lib.dptr(self._p, _D), n, float(cell), _lib.dptr(g["sorted"]), _lib.dptr(g["keys"]),
-                                           _lib.dptr(g["order"]), _lib.dptr(g["origin"]), _lib.dptr(ws), ws.numel(), _st())
-        _lib.check(rc, "ape_grid_build_f64")
-        return g
+        (icp_regression registers two estimators against the same target): batched.build_grids"""
+        return _B.build_grids([self], cell)[0]
 
     def _safe_cell(self, cell):
         """a k-NN cell size that keeps every cell coordinate inside the 21-bit key range (the shell bound needs unclamped cells)"""
@@ -203,69 +144,24 @@ class PointCloud:
     def _gargs(g):
         return (_lib.dptr(g["sorted"]), _lib.dptr(g["keys"]), _lib.dptr(g["order"]), _lib.dptr(g["origin"]), g["n"], g["cell"])
 
-    def _select(self, keep):
-        n = len(self)
-        out = PointCloud(device=self.device)
-        buf = torch.empty(n, 3, dtype=_D, device=self.device)
-        sel = torch.empty(n, dtype=torch.int32, device=self.device)
-        cnt = torch.zeros(1, dtype=torch.int32, device=self.device)
-        ws = _ws(n, self.device)
-        rc = _lib.lib().ape_select_points_f64(_lib.dptr(self._p, _D), _lib.dptr(keep, torch.uint8), n, _lib.dptr(buf), _lib.dptr(sel),
-                                              _lib.dptr(cnt), _lib.dptr(ws), ws.numel(), _st())
-        _lib.check(rc, "ape_select_points_f64")
-        k = int(cnt.item())
-        out._p = buf[:k].contiguous()
-        return out, sel[:k].cpu().numpy().tolist()
-
     def remove_radius_outlier(self, nb_points, radius):
         """keeps points with MORE than nb_points neighbours (self included) at distance < radius; -> (cloud, kept indices)"""
-        n = len(self)
-        if n == 0:
-            return PointCloud(device=self.device), []
-        g = self._grid(radius)
-        count = torch.empty(n, dtype=torch.int32, device=self.device)
-        rc = _lib.lib().ape_grid_radius_count_f64(*self._gargs(g), _lib.dptr(self._p, _D), n, float(radius), _lib.dptr(count), _st())
-        _lib.check(rc, "ape_grid_radius_count_f64")
-        return self._select((count > int(nb_points)).to(torch.uint8))
+        clouds, kept = _B.remove_radius_outlier([self], nb_points, radius, indices=True)
+        return clouds[0], kept[0]
 
     def remove_statistical_outlier(self, nb_neighbors, std_ratio, cell_hint=None):
         """open3d 0.9 RemoveStatisticalOutliers: mean distance to the nb_neighbors nearest (self included) must be
         < cloud mean + std_ratio * sample std; -> (cloud, kept indices).  The k-NN search walks a uniform grid (exact for any cell
-        size, ape_grid_knn_mean_dist_f64); `cell_hint` = a radius expected to hold the k neighbours (get_surface passes the radius of
-        the radius-outlier filter that ran just before), otherwise it is derived from the cloud's extent and point count."""
-        n = len(self)
-        if n == 0:
-            return PointCloud(device=self.device), []
-        k = int(min(nb_neighbors, n))
-        mean = torch.empty(n, dtype=_D, device=self.device)
-        if cell_hint is None:
-            ext = (self._p.max(0).values - self._p.min(0).values).cpu().numpy()
-            area = ext[0] * ext[1] + ext[1] * ext[2] + ext[0] * ext[2]       # a surface scan: ~n / area points per unit area
-            cell_hint = math.sqrt(max(k * area / (3.0 * n), 1e-300))
-            if not (cell_hint > 0 and math.isfinite(cell_hint)):
-                cell_hint = 1.0
-        g = self._grid(self._safe_cell(cell_hint))
-        rc = _lib.lib().ape_grid_knn_mean_dist_f64(*self._gargs(g), k, _lib.dptr(mean), _st())
-        _lib.check(rc, "ape_grid_knn_mean_dist_f64")
-        m = mean.cpu().numpy()
-        valid = m >= 0
-        cloud_mean = m[valid].sum() / max(int(valid.sum()), 1)
-        std = math.sqrt(((m[valid] - cloud_mean) ** 2).sum() / max(int(valid.sum()) - 1, 1))
-        thr = cloud_mean + float(std_ratio) * std
-        keep = torch.from_numpy(((m > 0) & (m < thr)).astype(np.uint8)).to(self.device)
-        return self._select(keep)
+        size, ape_grid_query_batch_f64 op 2); `cell_hint` = a radius expected to hold the k neighbours (get_surface passes the radius
+        of the radius-outlier filter that ran just before), otherwise it is derived from the cloud's extent and point count."""
+        clouds, kept = _B.remove_statistical_outlier([self], nb_neighbors, [std_ratio], cell_hint, indices=True)
+        return clouds[0], kept[0]
 
     def estimate_normals(self, search_param=None, radius=None, max_nn=30):
         """KDTreeSearchParamHybrid(radius, max_nn) semantics (open3d_utils.py:25-27)"""
         if search_param is not None:
             radius, max_nn = search_param.radius, search_param.max_nn
-        n = len(self)
-        if n == 0:
-            return self
-        g = self._grid(radius)
-        self._n = torch.empty(n, 3, dtype=_D, device=self.device)
-        rc = _lib.lib().ape_grid_normals_f64(*self._gargs(g), _lib.dptr(self._p, _D), n, float(radius), int(max_nn), _lib.dptr(self._n), _st())
-        _lib.check(rc, "ape_grid_normals_f64")
+        _B.estimate_normals([self], radius, max_nn)
         return self
 
 
@@ -345,14 +241,14 @@ def _point_to_plane(s):
 
 ICP_STATS = None          # bench.py --workload label sets a dict here: registrations, evaluations, point pairs, (start, end) events
 _ICP_STATS_LOCK = threading.Lock()     # registrations of different chains run on different host threads (sharding.run_side_by_side)
-_ICP_CHUNK = 5            # iterations enqueued per device round trip (3 launches each); the reference's criteria (1e-2) stop after 2-4
+_ICP_CHUNK = 5            # batched.icp_states: iterations enqueued per device round trip (3 launches each); the reference's criteria (1e-2) stop after 2-4
 
 
 def registration_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None, host_solve=False):
     """open3d 0.9 registration::RegistrationICP (call sites open3d_utils.py:56-58,98-117).  The source cloud is NOT
     modified (open3d works on a transformed copy).  The whole iteration -- correspondence search, the 17/29 reduced sums, the
-    3x3 SVD / 6x6 solve, T <- update . T and the convergence test -- runs on the device (ape_icp_run_f64): a chunk of iterations
-    is enqueued at once, launches after convergence are no-ops, and the 40-double state comes back once per chunk (normally once
+    3x3 SVD / 6x6 solve, T <- update . T and the convergence test -- runs on the device (batched.icp_states with this one pair): a chunk of
+    iterations is enqueued at once, launches after convergence are no-ops, and the 40-double state comes back once per chunk (normally once
     per registration).  `host_solve=True` keeps the round-1 loop (numpy SVD / solve, one D2H per iteration) for the parity tests."""
     estimation_method = estimation_method or TransformationEstimationPointToPoint()
     criteria = criteria or ICPConvergenceCriteria()
@@ -362,6 +258,9 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
         return RegistrationResult(T, 0.0, 0.0, 0)
     if estimation_method.kind == 1 and not target.has_normals():
         raise RuntimeError("TransformationEstimationPointToPlane requires target normals")
+    if not host_solve:
+        out = _B.icp_states([source], [target], max_correspondence_distance, [T], estimation_method.kind, criteria)[0]
+        return RegistrationResult(out[5:21].reshape(4, 4).copy(), float(out[2]), float(out[3]), int(out[4]))
     dev = source.device
     pcd = source.clone().transform(T)
     grid = target._grid(max_correspondence_distance)
@@ -370,36 +269,6 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
     sums = torch.empty(29, dtype=_D, device=dev)
     ws = torch.empty(512 * 29 * 8, dtype=torch.uint8, device=dev)
     L = _lib.lib()
-    if not host_solve:
-        st0 = np.zeros(40)
-        st0[5:21] = T.reshape(-1)
-        state = torch.from_numpy(st0).to(dev)
-        left, first, chunk = int(criteria.max_iteration), 1, _ICP_CHUNK         # the first call's block already holds one step
-        if ICP_STATS is not None:
-            ev0 = torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        while True:
-            n_it = min(chunk, left)
-            _lib.check(L.ape_icp_run_f64(estimation_method.kind, *PointCloud._gargs(grid), _lib.dptr(pcd._p, _D), ns, _lib.dptr(target._p, _D),
-                                         _lib.dptr(target._n), float(max_correspondence_distance), float(criteria.relative_fitness),
-                                         float(criteria.relative_rmse), int(criteria.max_iteration), n_it, first, _lib.dptr(corr), _lib.dptr(d2),
-                                         _lib.dptr(sums), _lib.dptr(state, _D), _lib.dptr(ws), ws.numel(), _st()), "ape_icp_run_f64")
-            out = state.cpu().numpy()
-            left -= n_it
-            first = 0
-            if out[0] != 0.0 or left <= 0:
-                break
-            chunk *= 2
-        if ICP_STATS is not None:
-            ev1 = torch.cuda.Event(enable_timing=True)
-            ev1.record()
-            with _ICP_STATS_LOCK:
-                ICP_STATS["registrations"] += 1
-                ICP_STATS["evaluations"] += int(out[1]) + 1
-                ICP_STATS["pairs"] += (int(out[1]) + 1) * ns
-                ICP_STATS["kind%d" % estimation_method.kind] = ICP_STATS.get("kind%d" % estimation_method.kind, 0) + (int(out[1]) + 1) * ns
-                ICP_STATS["events"].append((ev0, ev1))
-        return RegistrationResult(out[5:21].reshape(4, 4).copy(), float(out[2]), float(out[3]), int(out[4]))
 
     def evaluate():
         _lib.check(L.ape_grid_nn1_f64(*PointCloud._gargs(grid), _lib.dptr(pcd._p, _D), ns, float(max_correspondence_distance),
@@ -569,32 +438,9 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
 
 def surface_points(label, depth, intr, robot2cam, device="cuda"):
     """label u8[H,W], depth (integer sensor units) [H,W] -> PointCloud of the valid pixels in the robot frame (mm)."""
-    dev = torch.device(device)
-    if torch.is_tensor(label) and torch.is_tensor(depth) and label.is_cuda and depth.is_cuda:
-        # views already resident in HBM
-        if label.dtype != torch.uint8 or depth.dtype != torch.uint16:
-            raise ValueError("resident views must be uint8 labels and uint16 depth")
-        lab, dep, dev = label.contiguous(), depth.contiguous(), label.device
-    else:
-        lab = torch.as_tensor(np.ascontiguousarray(np.asarray(label, dtype=np.uint8))).to(dev)
-        d = np.asarray(depth)
-        if d.dtype != np.uint16:
-            if (d < 0).any() or (d > 65535).any() or (d != np.floor(d)).any():
-                raise ValueError("depth must hold integer sensor units in 0..65535")
-            d = d.astype(np.uint16)
-        dep = torch.from_numpy(np.ascontiguousarray(d)).to(dev)
-    h, w = lab.shape
-    buf = torch.empty(h * w, 3, dtype=_D, device=dev)
-    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = _ws(h * w, dev)
-    T, ptr = _host16(robot2cam)
-    rc = _lib.lib().ape_surface_points_f64(_lib.dptr(lab, torch.uint8), _lib.dptr(dep, torch.uint16), h, w, float(intr.get("fx")),
-                                           float(intr.get("fy")), float(intr.get("ppx")), float(intr.get("ppy")), ptr, _lib.dptr(buf),
-                                           _lib.dptr(cnt), _lib.dptr(ws), ws.numel(), _st())
-    _lib.check(rc, "ape_surface_points_f64")
-    out = PointCloud(device=dev)
-    out._p = buf[:int(cnt.item())].contiguous()
-    return out
+    if torch.is_tensor(label) and torch.is_tensor(depth) and label.is_cuda and depth.is_cuda and (label.dtype != torch.uint8 or depth.dtype != torch.uint16):
+        raise ValueError("resident views must be uint8 labels and uint16 depth")             # views already resident in HBM
+    return _B.surface_points([(label, depth, robot2cam)], intr, device)[0]
 
 
 # ---- o3d.io stand-ins: .ply / .pcd point clouds, xyz only -----------------------------------------------------------------------
@@ -708,3 +554,7 @@ def read_point_cloud(path, device="cuda"):
     else:
         raise ValueError("unsupported point-cloud format %r" % ext)
     return PointCloud(np.ascontiguousarray(pts, dtype=np.float64), device=device)
+
+
+# the kernel-backed methods above are the list primitives of batched.py (which builds PointClouds, hence imports this module) with one cloud
+from autoposeestimation_amd.pc_reconstruction import batched as _B  # noqa: E402

@@ -357,96 +357,74 @@ int ape_preprocess_u8_nhwc4(const uint8_t* rgb, const int* rects, float* out, in
                             int div255, void* stream);
 
 /* ---- pose-label path: point clouds in float64 (pc_reconstruction/open3d_utils.py, open3d 0.9 semantics) -------
- * Workspace for any of the calls below on clouds of up to n points (H*W for ape_surface_points_f64). */
-size_t ape_pc_workspace_bytes(int n);
-/* get_surface's pixel loop        pc_reconstruction/open3d_utils.py:171-192: pixels with label != 0 and depth != 0, in raster
- * order, back-projected (mm, no depth scale) and moved to the robot frame by T (row-major 4x4, HOST pointer).
- * points[H*W][3] capacity, *n_out (device int). */
-int ape_surface_points_f64(const uint8_t* label, const uint16_t* depth, int H, int W, double fx, double fy, double ppx,
-                           double ppy, const double* T16_host, double* points, int* n_out, void* ws, size_t ws_bytes,
-                           void* stream);
-/* PointCloud.transform            in place; normals (may be NULL) get the rotation part */
-int ape_transform_points_f64(double* pts, double* normals_or_null, int n, const double* T16_host, void* stream);
-/* PointCloud.voxel_down_sample    open3d_utils.py:21,198,157: per-voxel mean, output ordered by voxel key */
-int ape_voxel_down_sample_f64(const double* pts, int n, double voxel, double* out, int* n_out, void* ws, size_t ws_bytes,
-                              void* stream);
-/* Uniform search grid over a cloud (cell >= every radius later asked of it): caller-owned sorted[n][3], keys[n],
- * order[n], origin3[3].  Replaces open3d's KDTreeFlann for the bounded-radius searches of the path. */
-int ape_grid_build_f64(const double* pts, int n, double cell, double* sorted, unsigned long long* keys, unsigned* order,
-                       double* origin3, void* ws, size_t ws_bytes, void* stream);
-/* remove_radius_outlier's neighbour count (d < radius, self included)   open3d_utils.py:203 */
-int ape_grid_radius_count_f64(const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3,
-                              int n, double cell, const double* q, int nq, double radius, int* count, void* stream);
+ * The path's primitives are the `*_batch_f64` calls further down (a cloud alone is a batch of one); here: the all-pairs k-NN that the
+ * grid search is tested against, and the two steps of one ICP evaluation as calls of their own for a loop that solves on the host (the
+ * LAPACK check of the device step): one-record calls of the kernels of ape_icp_run_batch_f64 over ONE cloud's grid. */
 /* registration_icp's correspondence search: nearest target point within max_dist, idx = -1 if none   :98-117 */
 int ape_grid_nn1_f64(const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3,
                      int n, double cell, const double* q, int nq, double max_dist, int* idx, double* dist2, void* stream);
-/* estimate_normals(KDTreeSearchParamHybrid(radius, max_nn))   open3d_utils.py:25-27; normals oriented towards +z */
-int ape_grid_normals_f64(const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3,
-                         int n, double cell, const double* q, int nq, double radius, int max_nn, double* normals, void* stream);
 /* remove_statistical_outlier's per-point mean distance to its k nearest neighbours (self included)   :208-211 */
 int ape_knn_mean_dist_f64(const double* pts, int n, int k, double* mean, void* stream);
-/* The same means for the points of a grid-indexed cloud (the grid's own points are the queries), searched shell by shell through the
- * uniform grid instead of over all pairs: bitwise equal to ape_knn_mean_dist_f64 for any cell size; fastest when a cell holds a few
- * points (cell ~ the radius that contains k neighbours).  k <= 64, k <= n. */
-int ape_grid_knn_mean_dist_f64(const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3,
-                               int n, double cell, int k, double* mean, void* stream);
 /* One-pass ICP reductions (bitwise reproducible).  kind 0: point-to-point (Umeyama) out[17] = count, sum d^2, sum s[3],
  * sum t[3], sum s_a t_b[9];  kind 1: point-to-plane out[29] = count, sum d^2, upper triangle of J^T J[21], J^T r[6];
- * kind 2: moments of src, out[9] = sum p[3], sum p_a p_b upper triangle[6] (get_center / compute_mahalanobis_distance). */
+ * kind 2: moments of src, out[9] = sum p[3], sum p_a p_b upper triangle[6] (get_center / compute_mahalanobis_distance).
+ * ws: 512 x 29 doubles. */
 int ape_icp_sums_f64(int kind, const double* src, const double* tgt, const double* tgt_normals, const int* corr,
                      const double* dist2, int n, double* out, void* ws, size_t ws_bytes, void* stream);
-/* registration_icp's LOOP on the device (open3d_utils.py:96-117; open3d 0.9 RegistrationICP): `n_iter` iterations of
- * [move src by the pending update + correspondence search] -> partial sums -> [reduce + step: fitness / rmse / convergence test, Umeyama
- * 3x3 SVD (kind 0) or 6x6 solve (kind 1), T <- update . T], three launches each, enqueued at once; every launch is a no-op once
- * state[0] != 0.  first_call = 1 prepends the evaluation before open3d's loop and the step that computes the first update.  `src` is the
- * source already moved by the initial guess, updated in place.  state[40] doubles on the device: [0] done, [1] updates applied,
- * [2] fitness, [3] inlier rmse, [4] correspondences, [5..20] T row major, [21..36] last update, [37] stop reason (1 converged,
- * 2 too few correspondences, 3 iteration limit), [38] internal.  Before the first call of a registration (first_call = 1) the caller
- * zeroes it and writes the initial T; one copy of it back per call tells whether to enqueue more.  Grid arguments as above
- * (cell >= max_dist); ws: 512 x 29 doubles.  sums[29], corr[ns], dist2[ns]: caller-owned scratch. */
-int ape_icp_run_f64(int kind, const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n,
-                    double cell, double* src, int ns, const double* tgt, const double* tgt_normals, double max_dist, double rel_fitness,
-                    double rel_rmse, int max_iteration, int n_iter, int first_call, int* corr, double* dist2, double* sums, double* state,
-                    void* ws, size_t ws_bytes, void* stream);
-/* compute_mahalanobis_distance    mean_cinv12_host = (mean[3], inverse covariance[9]) */
-int ape_mahalanobis_f64(const double* pts, int n, const double* mean_cinv12_host, double* out, void* stream);
-/* ordered row selection (outlier filters): out = pts[keep != 0], sel_idx = kept indices, *n_out on the device */
-int ape_select_points_f64(const double* pts, const uint8_t* keep, int n, double* out, int* sel_idx, int* n_out, void* ws,
-                          size_t ws_bytes, void* stream);
 
-/* ---- BATCHED forms of the point-cloud kernels above (pose-label path, SURVEY.md 8e: the (object, direction) chains of
+/* ---- the point-cloud primitives, BATCHED (pose-label path, SURVEY.md 8e: the (object, direction) chains of
  * pc_reconstruction/create_pointcloud.py:276-312 are independent of each other).  ONE launch advances up to 16 clouds: blockIdx.y selects
- * the cloud's argument record, blockIdx.x walks that cloud's own grid -- the same device code with the same per-cloud grid sizes as the
- * one-cloud entry points, hence bit-identical results per cloud.  Per-cloud arguments are HOST arrays (of device pointers / sizes) of
+ * the cloud's argument record, blockIdx.x walks that cloud's own grid, whose size depends on that cloud's point count alone -- a cloud's
+ * result does not depend on its slot or its neighbours in the batch.  Per-cloud arguments are HOST arrays (of device pointers / sizes) of
  * length nb <= 16; clouds with n = 0 are skipped.  hipCUB's radix sort becomes a single-workgroup LDS sort per cloud (the cell keys re-coded
  * as a 32-bit lexicographic rank, packed with the index: stable, the same permutation), its select / scan calls a single-workgroup ordered
  * compaction / scan per cloud. */
 size_t ape_pc_batch_workspace_bytes(int nb, long n_total);
-/* label[c] / depth[c] [H][W]; intr4_host [nb][4] = fx, fy, ppx, ppy; T16_host [nb][16]; points[c] capacity H*W rows;
+/* get_surface's pixel loop        pc_reconstruction/open3d_utils.py:171-192: pixels with label != 0 and depth != 0, in raster
+ * order, back-projected (mm, no depth scale) and moved to the robot frame by T (row-major 4x4).
+ * label[c] / depth[c] [H][W]; intr4_host [nb][4] = fx, fy, ppx, ppy; T16_host [nb][16]; points[c] capacity H*W rows;
  * n_out [nb] on the device; pix_ws: nb * H * W ints of scratch */
 int ape_surface_points_batch_f64(int nb, const uint8_t* const* label, const uint16_t* const* depth, int H, int W, const double* intr4_host,
                                  const double* T16_host, double* const* points, int* n_out, int* pix_ws, void* stream);
+/* PointCloud.voxel_down_sample    open3d_utils.py:21,198,157: per-voxel mean, output ordered by voxel key; out[c] capacity n[c] rows */
 int ape_voxel_down_sample_batch_f64(int nb, const double* const* pts, const int* n, double voxel, double* const* out, int* n_out, void* ws,
                                     size_t ws_bytes, void* stream);
+/* Uniform search grid over a cloud (cell >= every radius later asked of it): caller-owned sorted[c][n][3], keys[c][n],
+ * order[c][n], origin3[c][3].  Replaces open3d's KDTreeFlann for the bounded-radius searches of the path. */
 int ape_grid_build_batch_f64(int nb, const double* const* pts, const int* n, double cell, double* const* sorted, unsigned long long* const* keys,
                              unsigned* const* order, double* const* origin3, void* ws, size_t ws_bytes, void* stream);
-/* op 0: ape_grid_radius_count_f64 (count[c][nq[c]]); op 1: ape_grid_normals_f64 (normals[c][nq[c]][3], max_nn); op 2:
- * ape_grid_knn_mean_dist_f64 (mean[c][gn[c]], k; q / nq unused) */
+/* op 0: remove_radius_outlier's neighbour count (d < radius, self included; open3d_utils.py:203) -> count[c][nq[c]];
+ * op 1: estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) (:25-27), normals oriented towards +z -> normals[c][nq[c]][3];
+ * op 2: the means of ape_knn_mean_dist_f64 for the grid's own points, searched shell by shell through the grid instead of over all
+ *       pairs: bitwise equal for any cell size; fastest when a cell holds a few points (cell ~ the radius that contains k neighbours).
+ *       k <= 64, k <= gn[c] -> mean[c][gn[c]]; q / nq unused */
 int ape_grid_query_batch_f64(int op, int nb, const double* const* sorted, const unsigned long long* const* keys, const unsigned* const* order,
                              const double* const* origin3, const int* gn, double cell, const double* const* q, const int* nq, double radius,
                              int max_nn_or_k, int* const* count, double* const* normals, double* const* mean, void* stream);
-/* ape_select_points_f64 with the keep rule evaluated on the device: mode 0 count[c][i] > thr_count (RemoveRadiusOutliers), mode 1
- * mean[c][i] > 0 && mean[c][i] < thr_mean_host[c] (RemoveStatisticalOutliers); sel_ws: sum n ints; n_out [nb] on the device */
+/* ordered row selection (outlier filters) with the keep rule evaluated on the device: mode 0 count[c][i] > thr_count
+ * (RemoveRadiusOutliers), mode 1 mean[c][i] > 0 && mean[c][i] < thr_mean_host[c] (RemoveStatisticalOutliers).  out[c] = the kept rows
+ * (capacity n[c]), n_out [nb] on the device; sel_ws: sum n ints, cloud c's kept indices at offset n[0] + .. + n[c-1] */
 int ape_select_points_batch_f64(int mode, int nb, const double* const* pts, const int* n, const int* const* count, int thr_count,
                                 const double* const* mean, const double* thr_mean_host, double* const* out, int* n_out, int* sel_ws, void* stream);
-/* ape_icp_sums_f64(kind 2): out9 [nb][9] on the device; ws: nb * 512 * 9 doubles */
+/* the moments of ape_icp_sums_f64(kind 2): out9 [nb][9] on the device; ws: nb * 512 * 9 doubles */
 int ape_moments_batch_f64(int nb, const double* const* pts, const int* n, double* out9, void* ws, size_t ws_bytes, void* stream);
+/* compute_mahalanobis_distance    mc12_host [nb][12] = (mean[3], inverse covariance[9]) */
 int ape_mahalanobis_batch_f64(int nb, const double* const* pts, const int* n, const double* mc12_host, double* const* out, void* stream);
+/* PointCloud.transform            in place, T16_host [nb][16]; normals (may be NULL, per cloud too) get the rotation part */
 int ape_transform_points_batch_f64(int nb, double* const* pts, double* const* normals, const int* n, const double* T16_host, void* stream);
 /* out[c] = [a[c] | b[c]] (b may be NULL: copies) */
 int ape_concat_points_batch_f64(int nb, const double* const* a, const int* na, const double* const* b, const int* nb_rows, double* const* out,
                                 void* stream);
-/* ape_icp_run_f64 for nb registrations of one kind advancing together (state[c]: 40 doubles on the device each); ws: nb * 512 * 29 doubles */
+/* registration_icp's LOOP on the device (open3d_utils.py:96-117; open3d 0.9 RegistrationICP) for nb registrations of one kind advancing
+ * together: `n_iter` iterations of [move src by the pending update + correspondence search] -> partial sums -> [reduce + step: fitness /
+ * rmse / convergence test, Umeyama 3x3 SVD (kind 0) or 6x6 solve (kind 1), T <- update . T], three launches each, enqueued at once; for a
+ * registration every launch is a no-op once its state[0] != 0.  first_call = 1 prepends the evaluation before open3d's loop and the step
+ * that computes the first update.  `src[c]` is the source already moved by the initial guess, updated in place.  state[c]: 40 doubles on
+ * the device: [0] done, [1] updates applied, [2] fitness, [3] inlier rmse, [4] correspondences, [5..20] T row major, [21..36] last
+ * update, [37] stop reason (1 converged, 2 too few correspondences, 3 iteration limit), [38] internal.  Before the first call of a
+ * registration (first_call = 1) the caller zeroes it and writes the initial T; one copy of it back per call tells whether to enqueue
+ * more.  Grid arguments: the targets' grids (cell >= max_dist); ws: nb * 512 * 29 doubles.  sums[c][29], corr[c][ns], dist2[c][ns]:
+ * caller-owned scratch. */
 int ape_icp_run_batch_f64(int kind, int nb, const double* const* sorted, const unsigned long long* const* keys, const unsigned* const* order,
                           const double* const* origin3, const int* gn, double cell, double* const* src, const int* ns, const double* const* tgt,
                           const double* const* tgt_normals, double max_dist, double rel_fitness, double rel_rmse, int max_iteration, int n_iter,
@@ -457,8 +435,8 @@ int ape_icp_run_batch_f64(int kind, int nb, const double* const* sorted, const u
  * registration_ransac_based_on_feature_matching), float64, autoposeestimation_amd/csrc/registration.hip ----------------------------
  * Workspace of ape_fpfh_f64 for a cloud of n points and the given max_nn. */
 size_t ape_fpfh_workspace_bytes(int n, int max_nn);
-/* FPFH feature[n][33] of a cloud with normals (pts / normals [n][3] in the cloud's own order) through its search grid (the GRID args of
- * ape_grid_build_f64 over the same n points, cell >= radius): hybrid neighbour list d^2 < radius^2, ordered by (d^2, index), first max_nn
+/* FPFH feature[n][33] of a cloud with normals (pts / normals [n][3] in the cloud's own order) through its search grid (one cloud's buffers of
+ * ape_grid_build_batch_f64 over the same n points, cell >= radius): hybrid neighbour list d^2 < radius^2, ordered by (d^2, index), first max_nn
  * (<= 128); SPFH over the list without its entry 0, then FPFH = per 11-bin block normalised sum_k SPFH_k / d^2_k (d^2 != 0) + SPFH_i.
  * Points with at most one list entry get zeros.  Two launches. */
 int ape_fpfh_f64(const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n, double cell,

@@ -1,4 +1,4 @@
-"""Timing of ape_grid_knn_mean_dist_f64 on one view's surface for several cell sizes, with the share of points whose k-th neighbour
+"""Timing of the grid k-NN mean distance (ape_grid_query_batch_f64 op 2, one cloud) on one view's surface for several cell sizes, with the share of points whose k-th neighbour
 lies outside one cell (those take the serial fallback).  python tools/mb_knn_grid.py"""
 import sys
 import time
@@ -9,6 +9,7 @@ from scipy.spatial import cKDTree
 
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
 from autoposeestimation_amd import _lib, synthetic as S  # noqa: E402
+from autoposeestimation_amd.pc_reconstruction import batched as B  # noqa: E402
 from autoposeestimation_amd.pc_reconstruction import pointcloud as PC  # noqa: E402
 
 label, depth, cam = S.label_views(1, seed=0)[0]
@@ -26,7 +27,7 @@ for cell in (5.0, 7.57, 10.0, 15.0):
     for _ in range(2):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        _lib.check(_lib.lib().ape_grid_knn_mean_dist_f64(*PC.PointCloud._gargs(g), k, _lib.dptr(mean), None), "knn")
+        _lib.check(_lib.lib().ape_grid_query_batch_f64(2, 1, *B._grid_args([g]), cell, None, None, 0.0, k, None, None, B._ptrs([mean]), None), "knn")
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
     print("cell %5.2f: %7.1f us   outside-one-cell share %.4f   points per occupied cell %.1f" % (cell, dt * 1e6, (dk >= cell).mean(), n / occ))
