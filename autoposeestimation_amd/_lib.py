@@ -144,6 +144,8 @@ SIGNATURES = {
     "ape_jaccard_bwd_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _c.c_size_t, _P],
     "ape_confusion_add": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "ape_sgd_step_multi_f32": [_I, _P, _F, _F, _F, _F, _I, _P],
+    "ape_bgsub_train_workspace_bytes": [_I],
+    "ape_bgsub_train_samples": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P],
 }
 
 
@@ -172,12 +174,21 @@ class ConvParams(_c.Structure):
                [("alpha", _c.c_float), ("bias_bstride", _c.c_int32), ("ldr", _c.c_int32), ("roff", _c.c_int32), ("ups", _c.c_int32)]
 
 
+class BgsubTrainJob(_c.Structure):
+    """Mirror of `ape_bgsub_train_job` (include/ape_hip.h)."""
+    _fields_ = [("f_rgb", _c.c_void_p), ("b_rgb", _c.c_void_p), ("f_depth", _c.c_void_p), ("b_depth", _c.c_void_p), ("label", _c.c_void_p),
+                ("a", _c.c_double * 6), ("fa", _c.c_int32 * 6), ("rot_mode", _c.c_int32), ("hflip", _c.c_int32), ("vflip", _c.c_int32),
+                ("n_ops", _c.c_int32 * 2), ("op_code", (_c.c_int32 * 4) * 2), ("op_factor", (_c.c_float * 4) * 2),
+                ("op_shift", (_c.c_int32 * 4) * 2), ("reserved", _c.c_int32)]
+
+
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_SIGMOID = 0, 1, 2, 3
 _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspace_bytes": _c.c_size_t, "ape_seg_components_workspace_bytes": _c.c_size_t,
              "ape_packed_weights_bf16_elems": _c.c_long, "ape_pc_batch_workspace_bytes": _c.c_size_t,
              "ape_conv2d_wgrad_workspace_bytes": _c.c_size_t, "ape_conv_gemm_splitk_workspace_bytes": _c.c_size_t,
              "ape_fpfh_workspace_bytes": _c.c_size_t, "ape_feature_nn1_workspace_bytes": _c.c_size_t, "ape_ransac_workspace_bytes": _c.c_size_t,
-             "ape_bn_workspace_bytes": _c.c_size_t, "ape_jaccard_workspace_bytes": _c.c_size_t}
+             "ape_bn_workspace_bytes": _c.c_size_t, "ape_jaccard_workspace_bytes": _c.c_size_t,
+             "ape_bgsub_train_workspace_bytes": _c.c_size_t}
 
 _lib = None
 

@@ -11,15 +11,32 @@ largest summed probability.  Only the final uint8 labels come back for PNG encod
 Network: the reference hard-codes smp's Unet-resnet34 with in_channels = 7 (third-party, unavailable: segmentation/utils.py)
 -> the default here is the in-repo PSPNet ('PsPNet', resnet34 encoder, 7 input channels, 2 classes), checkpoint
 `<root>/background_subtraction/trained_models/<name>_<encoder>.ckpt` holding {'state_dict': ...} like the reference's.
-Training-side symbols of the reference module (load_subtraction, augment, metrics, transforms) are not provided."""
+
+Training side (reference :63-384, :414-646): `load_subtraction` and `augment` build ONE sample through the device batch builder
+(background_subtraction/augment.py, csrc/bgsub_train.hip); `IoU_cca` is the metric behind `do_cca`, entirely on the device;
+`jaccard_loss`, `Metric`, `ConfusionMatrix`, `IoU` and `get_model` are the segmentation package's (segmentation/metrics.py,
+segmentation/utils.py).  The reference keeps a second copy of them in this module; checked against :63-384: `Metric`,
+`ConfusionMatrix`, `IoU` and `get_model` are the same functions, and both modules' `IoU.value()` and `IoU_cca.value()` average `iou[1:]`.
+`jaccard_loss` is NOT the same: this module's (:63-99) ends in `jacc_loss[1:].mean()` -- every class but the first, so with two classes
+only the object's IoU term -- where segmentation/utils.py:110-111 averages `jacc_loss[unique(true)]`, the classes present in the batch,
+background included.  The name exported here is the segmentation package's device kernel (`ape_jaccard_fwd_f32`), so the driver of this
+build minimises `1 - mean(J_background, J_object)` where the reference minimises `1 - J_object`; a `[1:]` variant of the kernel is not
+built yet and the logged losses are therefore not comparable with the reference's.  The torchvision
+wrapper classes (HFlipDefault, colorJitter, normalize, toTensor, :16-58) are unused by the reference's own driver and not provided;
+`animate` is a matplotlib view and not provided."""
 import json
 import os
+import random
 
 import numpy as np
 import torch
+from PIL import Image
 
 from autoposeestimation_amd import engine as E
+from autoposeestimation_amd.background_subtraction import augment as G
+from autoposeestimation_amd.background_subtraction.augment import ColorJitterPIL  # noqa: F401
 from autoposeestimation_amd.data_generation import sample_io
+from autoposeestimation_amd.segmentation.metrics import ConfusionMatrix, IoU, Metric, jaccard_loss  # noqa: F401
 from autoposeestimation_amd.segmentation.utils import get_model
 
 DEFAULT_MEAN = [0.040278014, 0.04060352, 0.038310923, 0.0381776, 0.03656849, 0.03636289, 0.03556486]      # :670-673
@@ -133,3 +150,108 @@ def get_mask_prediction(object_name, root, mean=None, std=None, reference_point=
                 sample_io.write_label(save_dir, s, "pred", lab)
             counter += len(ids)
             print("number = {}/{}".format(counter, ns))
+
+
+class IoU_cca(IoU):
+    """reference :225-301: IoU of the prediction AFTER `do_cca` -- softmax again, arg-max, 8-connected components of the non-zero labels,
+    keep the one with the largest summed probability (component 1 when there is none) -- against the target.  `add` runs on the device
+    (`ape_seg_argmax_f32`, `ape_seg_components_scored(APE_SEG_SCORE_SUM)`, `ape_confusion_add`) and does not synchronise; `value()` reads
+    the confusion matrix once.  predicted[N,K,H,W] f32 scores, target[N,H,W] integer labels, both on the device (the reference's `do_cca`
+    cannot take [N,H,W] predictions either, and its `target.view(-1)` rules out [N,K,H,W] targets)."""
+
+    def add(self, predicted, target):
+        if predicted.shape[0] != target.shape[0]:
+            raise ValueError("number of targets and predicted outputs do not match")
+        if predicted.dim() != 4:
+            raise ValueError("IoU_cca takes (N, K, H, W) scores: do_cca needs the class probabilities")
+        if target.dim() != 3:
+            raise ValueError("IoU_cca takes (N, H, W) integer targets")
+        if not (predicted.is_cuda and target.is_cuda):
+            raise RuntimeError("IoU_cca runs on the GPU only (no CPU fallback in this build)")
+        b, k, h, w = predicted.shape
+        nhwc = predicted.permute(0, 2, 3, 1).contiguous().float()
+        label, score = E.seg_argmax(nhwc, k, double_softmax=False)          # F.softmax(predicted, dim=1) (:200) + argmax / max
+        self.conf_metric._add_device(_biggest_component(label.view(b, h, w), score.view(b, h, w)), target)
+
+
+def _open(root, key, sub, name, idx):
+    return Image.open(os.path.join(root, key, sub, name.format(idx)))
+
+
+def read_sample(root, key, idx):
+    """the five files of one training sample (:443-447, :457-461, :499-503, :513-517, :597-601) -> (f_rgb[H,W,3] u8, b_rgb, f_depth[H,W]
+    u16, b_depth, label[H,W] u8); refuses what the device builder cannot take"""
+    b_rgb = np.array(_open(root, key, "background", "img{:06d}.png", idx).convert("RGB"))
+    f_rgb = np.array(_open(root, key, "foreground", "img{:06d}.png", idx).convert("RGB"))
+    depths = []
+    for sub in ("foreground", "background"):
+        d = _open(root, key, sub, "depth{:06d}.png", idx)
+        if d.mode != "I;16":
+            raise TypeError("%s depth of %s/%d is a %r image; the builder takes 16-bit depth (Pillow mode I;16)" % (sub, key, idx, d.mode))
+        depths.append(np.array(d))
+    y = _open(root, key, "groundtruth", "img{:06d}.mask.0.png", idx)
+    if len(y.getbands()) != 1:
+        raise ValueError("label of %s/%d has %d bands %r; one band expected" % (key, idx, len(y.getbands()), y.getbands()))
+    if y.mode not in ("L", "P", "1"):
+        raise TypeError("label of %s/%d is a %r image; an 8-bit label expected" % (key, idx, y.mode))
+    label = np.array(y).astype(np.uint8)
+    if not (f_rgb.shape == b_rgb.shape and f_rgb.shape[:2] == depths[0].shape == depths[1].shape == label.shape):
+        raise ValueError("the five frames of %s/%d differ in size" % (key, idx))
+    return f_rgb, b_rgb, depths[0], depths[1], label
+
+
+def _flag_params(angle, resize, rotate, colorJitter, hflip, vflip, size):
+    if resize is not None and resize is not False:
+        want = tuple(getattr(resize, "size", ()))
+        if want != tuple(size):
+            raise ValueError("resize to %r of %r frames: only the identity is provided (the reference's Resize([480, 640]) of its 480 x 640 "
+                             "frames; bilinear resizing of other sizes is not restated)" % (want, tuple(size)))
+    if colorJitter is not None and colorJitter is not False and not isinstance(colorJitter, ColorJitterPIL):
+        raise TypeError("colorJitter must be a ColorJitterPIL (the draws are made on the host, the jitter runs on the device)")
+    return {"angle": angle if rotate else None, "hflip": bool(hflip), "vflip": bool(vflip)}
+
+
+def load_subtraction(root, key, idx, resize=None, rotate=None, colorJitter=None, hflip=None, vflip=None, plot=False, abs=True):
+    """reference :414-626 for one sample, through the batch builder with a batch of one: -> x[H,W,7] uint8 difference channels,
+    y[H,W] float64.  Draws as the reference: `random.uniform(-180, 180)` when `rotate`, `np.random.rand()` per requested flip (dropped
+    when <= 0.5), then the jitter of the background, then of the foreground.  `rotate` / `hflip` / `vflip` are used as flags, `resize`
+    must carry `.size` equal to the frames', `colorJitter` is a ColorJitterPIL.  One difference: y is the BINARISED label (0. / 1.), not
+    the rotated raw values -- dataset.py:76, the reference's only consumer, binarises at once."""
+    if plot:
+        raise NotImplementedError("plot=True is a matplotlib debugging view of the reference; not provided")
+    if not abs:
+        raise NotImplementedError("abs=False (signed differences cast to uint8) is not provided; the reference's dataset never asks for it")
+    if not torch.cuda.is_available():
+        raise RuntimeError("load_subtraction runs on the GPU only (no CPU fallback in this build)")
+    p = G.draw_params(rotate=rotate, hflip=hflip, vflip=vflip, jitter=None)
+    frames = read_sample(root, key, idx)
+    _flag_params(p["angle"], resize, rotate, colorJitter, hflip, vflip, frames[4].shape)
+    if colorJitter:
+        p["ops_b"] = colorJitter.params()
+        p["ops_f"] = colorJitter.params()
+    dev = torch.device("cuda:0")
+    _, lab, u8 = G.build_samples([tuple(torch.from_numpy(a).to(dev) for a in frames)], [p], DEFAULT_MEAN, DEFAULT_STD, want_u8=True)
+    return u8[0].cpu().numpy(), lab[0].cpu().numpy().astype(np.float64)
+
+
+def augment(x, angle=0, resize=None, rotate=None, colorJitter=None, hflip=None, vflip=None):
+    """reference :629-646 on ONE image given as a device tensor: [H,W,3] u8 (RGB: rotate -> jitter -> flips) or
+    [H,W] u8 (label): geometry only, returned binarised (0 / 1).  Same flag conventions as load_subtraction; the jitter draws its parameters when called.  The image
+    goes through the sample builder beside blank companions and is read back from its difference against them."""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError("augment takes a device tensor (no CPU fallback in this build)")
+    h, w = x.shape[:2]
+    p = _flag_params(angle, resize, rotate, colorJitter, hflip, vflip, (h, w))
+    p["ops_f"] = colorJitter.params() if colorJitter else []
+    z = lambda dt, *sh: torch.zeros(*sh, dtype=dt, device=x.device)  # noqa: E731
+    if x.dtype == torch.uint8 and x.dim() == 3 and x.shape[2] == 3:
+        frames = (x.contiguous(), z(torch.uint8, h, w, 3), z(torch.uint16, h, w), z(torch.uint16, h, w), z(torch.uint8, h, w))
+        _, _, u8 = G.build_samples([frames], [p], [0.0] * 7, [1.0] * 7, want_u8=True)
+        return u8[0, :, :, :3].contiguous()                 # |f - 0|
+    if x.dtype == torch.uint8 and x.dim() == 2:
+        frames = (z(torch.uint8, h, w, 3), z(torch.uint8, h, w, 3), z(torch.uint16, h, w), z(torch.uint16, h, w), x.contiguous())
+        p["ops_f"] = []
+        _, lab = G.build_samples([frames], [p], [0.0] * 7, [1.0] * 7)
+        return lab[0].to(torch.uint8)                       # binarised, as the builder emits labels
+    raise TypeError("augment takes [H,W,3] uint8 or [H,W] uint8 images, got %s %s (depth frames are augmented inside load_subtraction: their "
+                    "difference, not the frame, leaves the builder)" % (x.dtype, tuple(x.shape)))

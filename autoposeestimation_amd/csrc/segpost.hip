@@ -23,6 +23,7 @@
 //   crop_normalize u8 RGB -> NHWC4 f32 (x[/255] - mean) / std
 #include "common.h"
 #include "seg_head.h"
+#include "bgsub_px.h"
 
 namespace {
 
@@ -419,27 +420,7 @@ struct BgsubArgs {
     float mean[7], stdv[7];
 };
 
-// Pillow's rgb2hsv_row (Convert.c, follows colorsys.py): float divisions, the hue wrap and the * 255.0 in double, truncation.
-// Pinned bit for bit against PIL over all 2^24 colours (tools/gen_golden_bgsub.py).
-__device__ __forceinline__ void pil_hsv(int r, int g, int b, int& uh, int& us, int& uv)
-{
-    const int maxc = max(r, max(g, b)), minc = min(r, min(g, b));
-    uv = maxc;
-    if (minc == maxc) { uh = 0; us = 0; return; }
-    const float cr = (float)(maxc - minc);
-    const float s = cr / (float)maxc;
-    const float rc = (float)(maxc - r) / cr, gc = (float)(maxc - g) / cr, bc = (float)(maxc - b) / cr;
-    float h;
-    if (r == maxc) h = bc - gc;
-    else if (g == maxc) h = (float)(2.0 + (double)rc - (double)bc);
-    else h = (float)(4.0 + (double)gc - (double)rc);
-    const double hw = (double)h / 6.0 + 1.0;
-    h = (float)(hw - floor(hw));                    // fmod(., 1.0) of a positive double: exact
-    const int ih = (int)((double)h * 255.0), is = (int)((double)s * 255.0);
-    uh = ih < 0 ? 0 : (ih > 255 ? 255 : ih);
-    us = is < 0 ? 0 : (is > 255 ? 255 : is);
-}
-
+// pil_hsv: Pillow's rgb2hsv_row, bgsub_px.h (shared with the training-sample builder, bgsub_train.hip)
 __global__ void bgsub_features_kernel(const uint8_t* __restrict__ f_rgb, const uint8_t* __restrict__ b_rgb,
                                       const uint16_t* __restrict__ f_depth, const uint16_t* __restrict__ b_depth,
                                       const double* __restrict__ gate /*[B][2] min,max*/, BgsubArgs a, float4* __restrict__ out,

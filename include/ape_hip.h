@@ -623,6 +623,43 @@ typedef struct ape_sgd_job {
 int ape_sgd_step_multi_f32(int n, const ape_sgd_job* jobs_host, float lr, float momentum, float dampening, float weight_decay, int nesterov,
                            void* stream);
 
+/* ---- Background-subtraction training samples (csrc/bgsub_train.hip; reference background_subtraction/utils.py:414-646 load_subtraction +
+ * augment, dataset.py:60-86) ---------------------------------------------------------------------------------------------------------
+ * One job per sample of the batch: DEVICE pointers to the raw frames (any frames of a resident set: a batch is a table of pointers, not a
+ * copy) and the augmentation the host drew.  Order per image: rotate -> colour jitter (RGB only) -> h-flip -> v-flip.
+ * rot_mode: APE_ROT_NONE, APE_ROT_180, APE_ROT_90 / APE_ROT_270 (Pillow's transposes, square frames only) or APE_ROT_AFFINE = Pillow's
+ * Image.rotate through its AFFINE nearest-neighbour transform with zero fill: `a` is the inverse matrix Image.rotate hands the transform
+ * (output pixel -> source position), read in double precision at the pixel centre for the 16-bit depth, and `fa` its 16.16 fixed-point
+ * form FLOOR(v * 65536 + 0.5) of (a0, a1, a2 + a0/2 + a1/2, a3, a4, a5 + a3/2 + a4/2) that the 8-bit images (RGB, label) walk.
+ * Colour ops: image 0 = foreground, 1 = background, each with its own ordered list of up to four ops APE_JIT_*: brightness / contrast /
+ * saturation blend towards black / the rounded mean of L over the whole image as it is at that point / L by `op_factor` (C float,
+ * truncated, clipped outside [0, 1]); hue adds `op_shift` (0..255) to H of Pillow's HSV, wrapping.  At most one contrast per list. */
+enum { APE_ROT_NONE = 0, APE_ROT_180 = 1, APE_ROT_AFFINE = 2, APE_ROT_90 = 3, APE_ROT_270 = 4 };
+enum { APE_JIT_END = 0, APE_JIT_BRIGHTNESS = 1, APE_JIT_CONTRAST = 2, APE_JIT_SATURATION = 3, APE_JIT_HUE = 4 };
+typedef struct ape_bgsub_train_job {
+    const uint8_t* f_rgb;      /* [H][W][3] */
+    const uint8_t* b_rgb;
+    const uint16_t* f_depth;   /* [H][W] */
+    const uint16_t* b_depth;
+    const uint8_t* label;      /* [H][W] */
+    double a[6];
+    int fa[6];
+    int rot_mode, hflip, vflip;
+    int n_ops[2];
+    int op_code[2][4];
+    float op_factor[2][4];
+    int op_shift[2][4];
+    int reserved;
+} ape_bgsub_train_job;
+/* x8[B][H][W][8] f32 NHWC: |f - b| of RGB (3), of Pillow's HSV (3) and of the depth after `f_depth[b_depth == 0] = 0` then
+ * `b_depth[f_depth == 0] = 0` (no distance gate), each cast to uint8 as numpy does (the depth difference wraps mod 256), / 255, then
+ * (x - mean7) / std7 (HOST pointers); channel 7 = 0.  label[B][H][W] i64 in {0, 1} (non-zero -> 1).  u8_or_null[B][H][W][7] receives the
+ * uint8 channels.  Two launches (the L sums of the contrast ops, then everything), none when B == 0; bit-reproducible.  The workspace
+ * (ape_bgsub_train_workspace_bytes(B)) carries the sums between the two and must not be shared by batches in flight at once. */
+size_t ape_bgsub_train_workspace_bytes(int B);
+int ape_bgsub_train_samples(const ape_bgsub_train_job* jobs_host, int B, int H, int W, const float* mean7_host, const float* std7_host,
+                            float* x8, long long* label, uint8_t* u8_or_null, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,101 @@
+"""tests/bgsub_train_reference.py (the CPU restatement of the training-sample builder on Pillow + numpy) against
+tests/golden/bgsub_train.npz, which tools/gen_golden_bgsub_train.py made by running the reference's load_subtraction,
+SegmentationDataset.__getitem__ and IoU_cca.  Everything is compared exactly.  No GPU."""
+import os
+import random
+
+import numpy as np
+import pytest
+
+import bgsub_train_reference as R
+from autoposeestimation_amd.background_subtraction import augment as G
+from autoposeestimation_amd.background_subtraction import dataset as D                      # noqa: F401  (absent before this feature)
+from autoposeestimation_amd.background_subtraction.utils import IoU_cca, load_subtraction   # noqa: F401
+from conftest import REPO
+
+GOLDEN = np.load(os.path.join(REPO, "tests", "golden", "bgsub_train.npz"))
+CASES = [str(c) for c in GOLDEN["cases"]]
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_restatement_equals_reference_case(name):
+    frames, params, x, y = R.golden_case(GOLDEN, name)
+    got_x, got_y = R.build_sample(frames, params)
+    assert got_x.dtype == np.uint8 and np.array_equal(got_x, x)
+    assert np.array_equal(got_y, y.astype(np.int64))
+
+
+def test_cases_cover_every_op_order_and_flip_outcome():
+    orders, flips = set(), set()
+    for name in CASES:
+        if name.startswith("all"):
+            _, p, _, _ = R.golden_case(GOLDEN, name)
+            orders |= {tuple(n for n, _ in p["ops_f"]), tuple(n for n, _ in p["ops_b"])}
+            flips.add((p["hflip"], p["vflip"]))
+    assert len(orders) == 24 and len(flips) == 4
+
+
+def test_seeded_items_equal_reference_getitem():
+    """SegmentationDataset.__getitem__ of the reference, seeded: the draws of consecutive samples come from one stream, in its order"""
+    jit = G.ColorJitterPIL(0.05, 0.05, 0.05, 0.02)
+    mean, std = GOLDEN["mean"], GOLDEN["std"]
+    seed_now = None
+    for seed, index in GOLDEN["items"]:
+        if seed != seed_now:
+            random.seed(int(seed))
+            np.random.seed(int(seed))
+            seed_now = seed
+        params = G.draw_params(rotate=True, hflip=True, vflip=True, jitter=jit)
+        u8, y = R.build_sample(R.golden_frames(GOLDEN, "ds_k%d" % (index // 2), index % 2), params)
+        x = R.normalise(u8, mean, std)
+        assert x.dtype == np.float32 and np.array_equal(x, GOLDEN["item_%d_%d_x" % (seed, index)])
+        assert np.array_equal(y, GOLDEN["item_%d_%d_y" % (seed, index)])
+    u8, y = R.build_sample(R.golden_frames(GOLDEN, "ds_k0", 1), {"angle": None})          # test mode, index 1: the key comes from `classes`
+    assert np.array_equal(R.normalise(u8, mean, std), GOLDEN["item_test_1_x"]) and np.array_equal(y, GOLDEN["item_test_1_y"])
+
+
+def test_statistics_pass_equals_reference():
+    """mean=None: per sample the mean / std of x[:, :, i] of the CHW tensor (image column i), averaged over 23 samples, in fp32"""
+    import torch
+    means, stds = [], []
+    for i in range(23):
+        u8, _ = R.build_sample(R.golden_frames(GOLDEN, "stat", i), {"angle": None})
+        x = torch.from_numpy(np.ascontiguousarray(u8.transpose(2, 0, 1))).float().div(255)       # ToTensor: contiguous CHW
+        means.append([torch.mean(x[:, :, c]).numpy() for c in range(7)])
+        stds.append([torch.std(x[:, :, c]).numpy() for c in range(7)])
+    assert np.array_equal(np.mean(np.array(means), axis=0), GOLDEN["stat_mean"])
+    assert np.array_equal(np.mean(np.array(stds), axis=0), GOLDEN["stat_std"])
+
+
+def _cca_host(pred):
+    """do_cca's rule in numpy / scipy for the confusion counts below"""
+    import scipy.ndimage as ndi
+    e = np.exp(pred - pred.max(1, keepdims=True))
+    sm = e / e.sum(1, keepdims=True)
+    out = np.zeros((pred.shape[0],) + pred.shape[2:], np.int64)
+    for i, p in enumerate(sm):
+        lab, n = ndi.label(p.argmax(0) != 0, structure=np.ones((3, 3), bool))
+        mx = p.max(0)
+        best, best_score = 1, 0
+        for u in range(1, n + 1):
+            s = np.sum(mx[lab == u])
+            if s > best_score:
+                best, best_score = u, s
+        out[i] = lab == best
+    return out
+
+
+@pytest.mark.parametrize("tag,k", [("k2", 2), ("k3", 3)])
+def test_cca_confusion_counts_equal_reference(tag, k):
+    pred, target = GOLDEN["cca_%s_pred" % tag], GOLDEN["cca_%s_target" % tag].astype(np.int64)
+    conf = np.bincount((_cca_host(pred) + k * target).reshape(-1), minlength=k * k).reshape(k, k)
+    assert np.array_equal(conf, GOLDEN["cca_%s_conf" % tag])
+    assert int(GOLDEN["cca_%s_conf" % tag].sum()) == target.size
+
+
+def test_job_table_refuses_what_the_kernel_cannot_take():
+    with pytest.raises(ValueError, match="at most 4"):
+        G.make_job({"angle": None, "ops_f": [("hue", 0.01)] * 5}, 8, 8, 0, 0, 0, 0, 0)
+    with pytest.raises(ValueError, match="one contrast"):
+        G.make_job({"angle": None, "ops_b": [("contrast", 0.9), ("contrast", 1.1)]}, 8, 8, 0, 0, 0, 0, 0)
+    assert G.rotation(-180.0, 48, 64)[0] == G.ROT_180 and G.rotation(90.0, 48, 64)[0] == G.ROT_AFFINE and G.rotation(90.0, 40, 40)[0] == G.ROT_90

@@ -1,0 +1,230 @@
+"""The training-sample builder (csrc/bgsub_train.hip), SegmentationDataset, IoU_cca and the training driver of the background-subtraction
+segmentor on the GPU, against tests/golden/bgsub_train.npz (made by running the reference) and tests/bgsub_train_reference.py (Pillow).
+Every comparison of samples is exact: u8 channels, the fp32 tensor and the labels with np.array_equal, no pixel excused."""
+import json
+import os
+import random
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+import bgsub_train_reference as R
+from conftest import REPO
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = np.load(os.path.join(REPO, "tests", "golden", "bgsub_train.npz"))
+CASES = [str(c) for c in GOLDEN["cases"]]
+DEV = "cuda:0"
+
+
+def _up(frames):
+    return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in frames)
+
+
+def _build(frames_list, params_list, mean, std):
+    from autoposeestimation_amd.background_subtraction import augment as G
+    x8, lab, u8 = G.build_samples([_up(f) for f in frames_list], params_list, mean, std, want_u8=True)
+    assert x8.shape[-1] == 8 and float(x8[..., 7].abs().max()) == 0.0
+    return x8[..., :7].permute(0, 3, 1, 2).cpu().numpy(), lab.cpu().numpy(), u8.cpu().numpy()
+
+
+def _write_tree(root, key, frames_list):
+    for sub in ("background", "foreground", "groundtruth"):
+        os.makedirs(os.path.join(root, key, sub), exist_ok=True)
+    for i, (f_rgb, b_rgb, f_depth, b_depth, label) in enumerate(frames_list):
+        Image.fromarray(f_rgb, "RGB").save(os.path.join(root, key, "foreground", "img%06d.png" % i))
+        Image.fromarray(b_rgb, "RGB").save(os.path.join(root, key, "background", "img%06d.png" % i))
+        Image.fromarray(f_depth).save(os.path.join(root, key, "foreground", "depth%06d.png" % i))
+        Image.fromarray(b_depth).save(os.path.join(root, key, "background", "depth%06d.png" % i))
+        Image.fromarray(label, "L").save(os.path.join(root, key, "groundtruth", "img%06d.mask.0.png" % i))
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_builder_equals_reference_case(name):
+    frames, params, x, y = R.golden_case(GOLDEN, name)
+    mean, std = GOLDEN["mean"], GOLDEN["std"]
+    gx, gy, gu8 = _build([frames], [params], mean, std)
+    bad = int((gu8[0] != x).any(-1).sum())
+    print("%s: %d of %d pixels differ in the u8 channels, %d labels" % (name, bad, x.shape[0] * x.shape[1], int((gy[0] != y).sum())))
+    assert np.array_equal(gu8[0], x)
+    assert np.array_equal(gy[0], y.astype(np.int64)) and gy.dtype == np.int64
+    assert np.array_equal(gx[0], R.normalise(x, mean, std))
+
+
+@pytest.mark.parametrize("seed", [11, 12, 13])
+def test_builder_equals_restatement_480x640_batch5(seed):
+    from autoposeestimation_amd.background_subtraction import augment as G
+    rng = np.random.default_rng(seed)
+    frames = [R.synthetic_frames(rng, 480, 640) for _ in range(5)]
+    random.seed(seed)
+    np.random.seed(seed)
+    params = [G.draw_params(True, True, True, G.ColorJitterPIL(0.2, 0.2, 0.2, 0.05) if i % 2 else G.ColorJitterPIL(0.05, 0.05, 0.05, 0.02))
+              for i in range(5)]
+    mean, std = GOLDEN["mean"], GOLDEN["std"]
+    wx, wy, wu8 = R.build_batch(frames, params, mean, std)
+    gx, gy, gu8 = _build(frames, params, mean, std)
+    print("seed %d: %d u8 values, %d labels, %d fp32 values differ" % (seed, int((gu8 != wu8).sum()), int((gy != wy).sum()), int((gx != wx).sum())))
+    assert np.array_equal(gu8, wu8) and np.array_equal(gy, wy) and np.array_equal(gx, wx)
+    # the same batch again is bit-identical, and a sample does not depend on its batch
+    gx2, gy2, gu82 = _build(frames, params, mean, std)
+    assert np.array_equal(gx, gx2) and np.array_equal(gy, gy2) and np.array_equal(gu8, gu82)
+    ax, ay, au8 = _build(frames[3:4], params[3:4], mean, std)
+    assert np.array_equal(ax[0], gx[3]) and np.array_equal(ay[0], gy[3]) and np.array_equal(au8[0], gu8[3])
+
+
+def test_more_samples_than_one_launch_takes():
+    """the job table travels 16 samples per launch: 19 samples cross the chunk boundary"""
+    from autoposeestimation_amd.background_subtraction import augment as G
+    rng = np.random.default_rng(3)
+    frames = [R.synthetic_frames(rng, 37, 53) for _ in range(19)]
+    random.seed(3)
+    np.random.seed(3)
+    params = [G.draw_params(True, True, True, G.ColorJitterPIL(0.2, 0.2, 0.2, 0.05)) for _ in range(19)]
+    wx, wy, wu8 = R.build_batch(frames, params, GOLDEN["mean"], GOLDEN["std"])
+    gx, gy, gu8 = _build(frames, params, GOLDEN["mean"], GOLDEN["std"])
+    assert np.array_equal(gu8, wu8) and np.array_equal(gy, wy) and np.array_equal(gx, wx)
+
+
+@pytest.fixture(scope="module")
+def ds_tree(tmp_path_factory):
+    root = str(tmp_path_factory.mktemp("bgsub_ds"))
+    for k in ("k0", "k1"):
+        _write_tree(root, k, [R.golden_frames(GOLDEN, "ds_" + k, i) for i in range(2)])
+    return root
+
+
+def test_seeded_dataset_items_equal_reference(ds_tree):
+    from autoposeestimation_amd.background_subtraction.dataset import SegmentationDataset
+    mean, std = [float(v) for v in GOLDEN["mean"]], [float(v) for v in GOLDEN["std"]]
+    ds = SegmentationDataset("train", ds_tree, {"k0": [0, 1], "k1": [0, 1]}, ["k0", "k1"], mean=mean, std=std, size=(37, 53))
+    assert len(ds) == 4
+    seed_now = None
+    for seed, index in GOLDEN["items"]:
+        if seed != seed_now:
+            random.seed(int(seed))
+            np.random.seed(int(seed))
+            seed_now = seed
+        x, y = ds[int(index)]
+        assert x.is_cuda and tuple(x.shape) == (7, 37, 53) and y.dtype == torch.int64
+        assert np.array_equal(x.cpu().numpy(), GOLDEN["item_%d_%d_x" % (seed, index)])
+        assert np.array_equal(y.cpu().numpy(), GOLDEN["item_%d_%d_y" % (seed, index)])
+    dt = SegmentationDataset("test", ds_tree, {"k1": [0, 1]}, ["k0", "k1"], mean=mean, std=std, size=(37, 53))
+    x, y = dt[1]
+    assert np.array_equal(x.cpu().numpy(), GOLDEN["item_test_1_x"]) and np.array_equal(y.cpu().numpy(), GOLDEN["item_test_1_y"])
+    # a batch draws per sample in index order: the same stream as item after item
+    random.seed(2)
+    np.random.seed(2)
+    xb, yb = ds.batch([0, 3, 2])
+    for j, index in enumerate((0, 3, 2)):
+        assert np.array_equal(xb[j].cpu().numpy(), GOLDEN["item_2_%d_x" % index])
+
+
+def test_statistics_pass_equals_reference(tmp_path):
+    from autoposeestimation_amd.background_subtraction.dataset import SegmentationDataset
+    _write_tree(str(tmp_path), "s0", [R.golden_frames(GOLDEN, "stat", i) for i in range(23)])
+    ds = SegmentationDataset("test", str(tmp_path), {"s0": list(range(23))}, ["s0"], mean=None, std=None, size=(16, 24))
+    assert np.array_equal(np.array(ds.mean, np.float32), GOLDEN["stat_mean"]) and np.array_equal(np.array(ds.std, np.float32), GOLDEN["stat_std"])
+
+
+@pytest.mark.parametrize("tag,k", [("k2", 2), ("k3", 3)])
+def test_iou_cca_counts_equal_reference_without_sync(tag, k):
+    from autoposeestimation_amd.background_subtraction.utils import IoU_cca
+    pred = torch.from_numpy(GOLDEN["cca_%s_pred" % tag]).to(DEV)
+    target = torch.from_numpy(GOLDEN["cca_%s_target" % tag].astype(np.int64)).to(DEV)
+    m = IoU_cca(num_classes=k)
+    half = pred.shape[0] // 2
+    m.add(pred[:half], target[:half])           # warm: first-use allocations
+    m.reset()
+    torch.cuda.synchronize()
+    prev = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        m.add(pred[:half], target[:half])
+        m.add(pred[half:], target[half:])
+    finally:
+        torch.cuda.set_sync_debug_mode(prev)
+    iou, miou = m.value()
+    assert np.array_equal(m.conf_metric.value(), GOLDEN["cca_%s_conf" % tag])
+    assert np.array_equal(iou, GOLDEN["cca_%s_iou" % tag], equal_nan=True) and miou == GOLDEN["cca_%s_miou" % tag]
+
+
+def test_refusals(ds_tree, tmp_path):
+    from autoposeestimation_amd.background_subtraction import augment as G
+    from autoposeestimation_amd.background_subtraction import utils as U
+    from autoposeestimation_amd.background_subtraction.dataset import SegmentationDataset
+    frames = R.golden_frames(GOLDEN, "set_a", 0)
+    f = _up(frames)
+    plain = {"angle": None}
+    with pytest.raises(ValueError, match="480"):                                    # wrong size
+        SegmentationDataset("test", ds_tree, {"k0": [0, 1]}, ["k0"], mean=[0.0] * 7, std=[1.0] * 7)
+    with pytest.raises(ValueError):
+        G.build_samples([f[:4] + (f[4][:, :-1].contiguous(),)], [plain], [0.0] * 7, [1.0] * 7)
+    with pytest.raises(TypeError, match="uint16"):                                  # wrong dtype
+        G.build_samples([f[:2] + (f[2].to(torch.int32), f[3], f[4])], [plain], [0.0] * 7, [1.0] * 7)
+    with pytest.raises(TypeError):
+        G.build_samples([(f[0].float(),) + f[1:]], [plain], [0.0] * 7, [1.0] * 7)
+    with pytest.raises(ValueError, match="at most 4"):                              # more than four colour ops
+        G.build_samples([f], [{"angle": None, "ops_f": [("brightness", 0.9)] * 5}], [0.0] * 7, [1.0] * 7)
+    root = str(tmp_path)
+    _write_tree(root, "c", [frames])
+    Image.fromarray(np.stack([frames[4]] * 3, -1), "RGB").save(os.path.join(root, "c", "groundtruth", "img000000.mask.0.png"))
+    with pytest.raises(ValueError, match="bands"):                                  # label with more than one band
+        U.load_subtraction(root, "c", 0)
+    with pytest.raises(NotImplementedError):
+        U.load_subtraction(ds_tree, "k0", 0, plot=True)
+    x, y = U.load_subtraction(ds_tree, "k0", 0)
+    wx, wy = R.build_sample(R.golden_frames(GOLDEN, "ds_k0", 0), plain)
+    assert np.array_equal(x, wx) and np.array_equal(y, wy.astype(np.float64)) and y.dtype == np.float64
+
+
+def test_plateau_drops_rate_after_sixth_bad_epoch():
+    from autoposeestimation_amd import autograd as A
+    from autoposeestimation_amd.background_subtraction.train import ReduceLROnPlateau
+    p = torch.nn.Parameter(torch.zeros(4, device=DEV))
+    opt = A.SGD([p], lr=5e-3, momentum=0.9, nesterov=True)
+    sch = ReduceLROnPlateau(opt, mode="max", factor=0.1, patience=5, threshold=1e-4)
+    rates = []
+    for _ in range(8):
+        sch.step(0.5)                          # the first call sets the best; six non-improving epochs follow
+        rates.append(opt.lr)
+    assert rates[:6] == [5e-3] * 6 and rates[6] == pytest.approx(5e-4, rel=1e-12) and rates[7] == rates[6]
+
+
+def test_driver_trains_and_the_checkpoint_labels(tmp_path):
+    """6 classes x 4 samples of 480 x 640 frames with a painted object, 3 epochs of Unet-resnet18"""
+    from autoposeestimation_amd.background_subtraction import segmentation_training
+    from autoposeestimation_amd.background_subtraction import utils as U
+    root = str(tmp_path)
+    bs_root = os.path.join(root, "background_subtraction")
+    rng = np.random.default_rng(7)
+    for c in range(6):
+        _write_tree(os.path.join(bs_root, "data"), "obj%d" % c, [R.synthetic_frames(rng, 480, 640) for _ in range(4)])
+    torch.manual_seed(0)
+    random.seed(0)
+    np.random.seed(0)
+    seg = {"name": "Unet", "encoder_name": "resnet18", "encoder_weights": None, "activation": "softmax", "in_channels": 7}
+    trn = {"epochs": 3, "batch_size": 5, "lr": 5e-3, "weight_decay": 0.0, "shuffle": True, "num_workers": 0, "momentum": 0.9}
+    logs = segmentation_training(trn, seg, root=bs_root, n_samples=4)
+    print("losses", logs["losses"], "mIoU", logs["iou_scores"], "mIoU cca", logs["iou_cca_scores"])
+    assert seg["name"] == "Unet"                                                    # the caller's dict is left alone
+    assert len(logs["losses"]) == 3 and logs["losses"][-1] < logs["losses"][0]
+    with open(os.path.join(bs_root, "logs", "Unet_resnet18.json")) as fh:
+        assert set(json.load(fh)) == {"best_iou_score", "best_iou_score_epoch", "iou_scores", "iou_cca_scores", "losses"}
+    cp = torch.load(os.path.join(bs_root, "trained_models", "Unet_resnet18.ckpt"), map_location="cpu")
+    assert set(cp) == {"state_dict", "epoch", "iou", "iou_scores", "losses", "loss", "iou_cca", "iou_cca_scores", "training_config", "name",
+                       "segmentation_config"}
+    model = U.get_default_model(root, name="Unet", encoder_name="resnet18")
+    obj = os.path.join(root, "data_generation", "data", "thing")
+    f_rgb, b_rgb, f_depth, b_depth, _ = R.synthetic_frames(rng, 480, 640)
+    for name, rgb, depth in (("background", b_rgb, b_depth), ("foreground", f_rgb, f_depth)):
+        os.makedirs(os.path.join(obj, name))
+        Image.fromarray(rgb, "RGB").save(os.path.join(obj, name, "000000.color.png"))
+        Image.fromarray(depth).save(os.path.join(obj, name, "000000.depth.png"))
+        with open(os.path.join(obj, name, "000000.meta.json"), "w") as fh:
+            json.dump({"robot2endEff_tf": np.eye(4).reshape(-1).tolist(), "hand_eye_calibration": np.eye(4).reshape(-1).tolist()}, fh)
+    U.get_mask_prediction("thing", root, model=model)
+    lab = np.array(Image.open(os.path.join(root, "label_generator", "data", "thing", "foreground", "000000.pred.label.png")))
+    assert lab.shape == (480, 640) and set(np.unique(lab)) <= {0, 255}
