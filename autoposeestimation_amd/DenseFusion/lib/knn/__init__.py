@@ -21,10 +21,9 @@ class _KnnPytorch:
         if ref.size(0) != query.size(0) or ref.size(1) != query.size(1) or idx.size(0) != ref.size(0) \
                 or idx.size(2) != query.size(2):
             raise ValueError("knn: inconsistent shapes %s %s %s" % (tuple(ref.shape), tuple(query.shape), tuple(idx.shape)))
-        rc = _lib.lib().ape_knn_f32(_lib.dptr(ref, torch.float32), _lib.dptr(query, torch.float32),
-                                    _lib.dptr(idx, torch.int64), ref.size(0), ref.size(1), ref.size(2),
-                                    query.size(2), idx.size(1), _lib.stream_ptr())
-        _lib.check(rc, "ape_knn_f32")
+        _lib.call.ape_knn_f32(_lib.dptr(ref, torch.float32), _lib.dptr(query, torch.float32),
+                              _lib.dptr(idx, torch.int64), ref.size(0), ref.size(1), ref.size(2),
+                              query.size(2), idx.size(1), _lib.stream_ptr())
         return 1  # knn.h:63
 
 

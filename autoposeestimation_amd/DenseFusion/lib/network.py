@@ -153,9 +153,11 @@ def _pspnet_param_shapes(backend, n_classes, in_channels=3):
 
 
 class _PSPPlan:
-    def __init__(self, sd, prefix, backend, dev, precision="f32"):
+    def __init__(self, sd, prefix, backend, dev, precision="f32", splitk=False):
+        """splitk: every layer may take the split-K form at small M inside E.low_latency() -- the pose networks' embedding CNN passes it,
+        the segmentor never does (its class maps must not depend on the batch a frame is in)"""
         g = lambda k: sd[prefix + k]  # noqa: E731
-        _Conv = lambda *a, **k: E.Conv(*a, precision=precision, **k)  # noqa: E731
+        _Conv = lambda *a, **k: E.Conv(*a, precision=precision, splitk=splitk, **k)  # noqa: E731
         self.precision = precision
         self.stem = _Conv(g("feats.conv1.weight"), None, 2, 3, 1, E.ACT_RELU, device=dev)
         self.blocks = []
@@ -185,20 +187,20 @@ class _PSPPlan:
         # up_1 / up_2: channel mixing at low resolution + tap gather (4x fewer flops, no upsampled tensor); up_3 (64 -> 64 at
         # full resolution) would write a 9 x 64-channel half-resolution tensor larger than what it saves, so it stays direct
         self.up = [E.UpConv(g(f"{n}.conv.1.weight"), g(f"{n}.conv.1.bias"), float(g(f"{n}.conv.2.weight").reshape(-1)[0]),
-                            device=dev, precision=precision) for n in ("up_1", "up_2")]
+                            device=dev, precision=precision, splitk=splitk) for n in ("up_1", "up_2")]
         self.up3 = _Conv(g("up_3.conv.1.weight"), g("up_3.conv.1.bias"), 1, 1, 1, E.ACT_PRELU,
                          alpha=float(g("up_3.conv.2.weight").reshape(-1)[0]), device=dev)
         # the segmentor's up_3 in up_1 / up_2's low-resolution form, ONE kernel with the head (engine.UpConv.seg_head, upconv_fused.hip):
         # 4x fewer matrix flops than the direct 3x3 conv on the up-sampled map
         self.up3_low = (E.UpConv(g("up_3.conv.1.weight"), g("up_3.conv.1.bias"), float(g("up_3.conv.2.weight").reshape(-1)[0]),
-                                 device=dev, precision=precision, fma=True) if precision == "bf16x3" else None)
+                                 device=dev, precision=precision, fma=True, splitk=splitk) if precision == "bf16x3" else None)
         self.final = _Conv(g("final.0.weight"), g("final.0.bias"), device=dev)
 
     def _s32_graph(self, x):
         """the S32 graph's 3x3 kernel tiles the 1/8-resolution map in 16x16 pixels: worth it only when those tiles are mostly full
         (the 480x640 segmentor: 60x80 -> 94 %; a 160x160 crop: 20x20 -> 39 %, which stays on the flattened-M kernels)"""
         h8, w8 = -(-x.shape[1] // 8), -(-x.shape[2] // 8)
-        return self.precision == "bf16x3" and E.USE_S32 and h8 * w8 >= 0.8 * (-(-h8 // 16) * -(-w8 // 16) * 256)
+        return self.precision == "bf16x3" and E.USE_S32 and E.tiles16_mostly_full(h8, w8)
 
     def label_score(self, x, head_w, head_b, double_softmax=True):
         """x[B,H,W,4] -> (label u8, score f32)[B,H,W]: features with the classification head (first C rows of the final 1x1 conv +
@@ -395,9 +397,9 @@ class _FeatPlan:
     """PoseNetFeat / PoseRefineNetFeat (network.py:39-68, 136-168) writing straight into the concatenated buffer
     pf[B*N, 384] = [conv1(x) 64 | e_conv1(emb) 64 | conv2 128 | e_conv2 128]."""
 
-    def __init__(self, sd, dev, refine, precision="f32"):
+    def __init__(self, sd, dev, refine, precision="f32", splitk=False):
         g = lambda k: (sd[f"feat.{k}.weight"], sd[f"feat.{k}.bias"])  # noqa: E731
-        kw = dict(act=E.ACT_RELU, device=dev, precision=precision)
+        kw = dict(act=E.ACT_RELU, device=dev, precision=precision, splitk=splitk)
         self.conv1 = E.Conv(*g("conv1"), **kw)
         self.e_conv1 = E.Conv(*g("e_conv1"), **kw)
         self.conv2 = E.Conv(*g("conv2"), **kw)
@@ -445,17 +447,17 @@ class PoseNet(_HipModule):
     def _build_plan(self, sd, dev):
         pl = type("Plan", (), {})()
         pr = self.precision
-        pl.cnn = _PSPPlan(sd, "cnn.model.module.", "resnet18", dev, pr)
-        pl.feat = _FeatPlan(sd, dev, refine=False, precision=pr)
+        kw = dict(device=dev, precision=pr, splitk=True)      # (batch-1 frames: the crop's small-M layers may split K; never the segmentor's)
+        pl.cnn = _PSPPlan(sd, "cnn.model.module.", "resnet18", dev, pr, splitk=True)
+        pl.feat = _FeatPlan(sd, dev, refine=False, precision=pr, splitk=True)
         w1 = torch.cat([sd[f"conv1_{h}.weight"] for h in "rtc"], 0)[:, :, 0]      # [1920, 1408]
         b1 = torch.cat([sd[f"conv1_{h}.bias"] for h in "rtc"], 0)
-        pl.l1_point = E.Conv(w1[:, :384], None, act=E.ACT_RELU, device=dev, precision=pr)           # per-point part
-        pl.l1_global = E.Conv(w1[:, 384:], b1, act=E.ACT_NONE, device=dev, precision=pr)            # per-crop bias from ap_x
-        pl.l2 = [E.Conv(sd[f"conv2_{h}.weight"], sd[f"conv2_{h}.bias"], act=E.ACT_RELU, device=dev, precision=pr) for h in "rtc"]
-        pl.l3 = [E.Conv(sd[f"conv3_{h}.weight"], sd[f"conv3_{h}.bias"], act=E.ACT_RELU, device=dev, precision=pr) for h in "rtc"]
+        pl.l1_point = E.Conv(w1[:, :384], None, act=E.ACT_RELU, **kw)           # per-point part
+        pl.l1_global = E.Conv(w1[:, 384:], b1, act=E.ACT_NONE, **kw)            # per-crop bias from ap_x
+        pl.l2 = [E.Conv(sd[f"conv2_{h}.weight"], sd[f"conv2_{h}.bias"], act=E.ACT_RELU, **kw) for h in "rtc"]
+        pl.l3 = [E.Conv(sd[f"conv3_{h}.weight"], sd[f"conv3_{h}.bias"], act=E.ACT_RELU, **kw) for h in "rtc"]
         pl.l4 = [t.detach().to(dev, torch.float32).reshape(t.shape[0], -1).contiguous()
                  for h in "rtc" for t in (sd[f"conv4_{h}.weight"], sd[f"conv4_{h}.bias"])]
-        E.allow_splitk(pl)          # (batch-1 frames: the crop's small-M layers may split K; never the segmentor's)
         return pl
 
     def forward_batch(self, img4, points4, choose, obj, taps=None):
@@ -555,14 +557,13 @@ class PoseRefineNet(_HipModule):
 
     def _build_plan(self, sd, dev):
         pl = type("Plan", (), {})()
-        pr = self.precision
-        pl.feat = _FeatPlan(sd, dev, refine=True, precision=pr)
+        kw = dict(act=E.ACT_RELU, device=dev, precision=self.precision, splitk=True)      # (as PoseNet's: may split K at batch 1)
+        pl.feat = _FeatPlan(sd, dev, refine=True, precision=self.precision, splitk=True)
         pl.l1 = E.Conv(torch.cat([sd["conv1_r.weight"], sd["conv1_t.weight"]], 0),
-                       torch.cat([sd["conv1_r.bias"], sd["conv1_t.bias"]], 0), act=E.ACT_RELU, device=dev, precision=pr)   # 1024 -> 512|512
-        pl.l2 = [E.Conv(sd[f"conv2_{h}.weight"], sd[f"conv2_{h}.bias"], act=E.ACT_RELU, device=dev, precision=pr) for h in "rt"]
+                       torch.cat([sd["conv1_r.bias"], sd["conv1_t.bias"]], 0), **kw)   # 1024 -> 512|512
+        pl.l2 = [E.Conv(sd[f"conv2_{h}.weight"], sd[f"conv2_{h}.bias"], **kw) for h in "rt"]
         pl.l3 = [t.detach().to(dev, torch.float32).contiguous()
                  for h in "rt" for t in (sd[f"conv3_{h}.weight"], sd[f"conv3_{h}.bias"])]
-        E.allow_splitk(pl)
         return pl
 
     def forward_batch(self, points4, emb, obj):

@@ -36,9 +36,7 @@ SIGNATURES = {
     "ape_conv_gemm_splitk_workspace_bytes": [_P],
     "ape_conv_gemm_bf16_splitk": [_P, _P, _P, _P, _P, _P, _I, _P, _c.c_size_t, _P],
     "ape_conv_gemm_bf16_multi": [_I, _P, _P, _P, _P, _P, _I, _P],
-    "ape_adaptive_avgpool_multi_nhwc_fmt": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _c.c_size_t, _P],
     "ape_adaptive_avgpool_multi_nhwc_ld": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _c.c_size_t, _P],
-    "ape_upconv3x3_gather_fmt": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "ape_upconv3x3_gather_ex": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P],
     "ape_upconv3x3_gather_strip_rows": [_I],
     "ape_upconv3x3_fused_supported": [_I, _I, _I, _I],
@@ -59,7 +57,6 @@ SIGNATURES = {
     "ape_maxpool3x3s2_nhwc_f32": [_P, _P, _I, _I, _I, _I, _P],
     "ape_adaptive_avgpool_nhwc_f32": [_P, _P, _I, _I, _I, _I, _I, _P],
     "ape_adaptive_avgpool_multi_workspace_bytes": [_I, _I],
-    "ape_adaptive_avgpool_multi_nhwc_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _c.c_size_t, _P],
     "ape_bilinear_nhwc_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "ape_psp_prior_sum_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "ape_upconv3x3_gather_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
@@ -79,7 +76,6 @@ SIGNATURES = {
     "ape_seg_argmax_f32": [_P, _I, _I, _P, _P, _c.c_long, _I, _P],
     "ape_seg_head_f32": [_P, _P, _P, _I, _P, _P, _c.c_long, _I, _P],
     "ape_seg_components_workspace_bytes": [_I, _I, _I, _I],
-    "ape_seg_components": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _c.c_size_t, _P],
     "ape_conv3x3_halo_seghead_bf16": [_P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P],
     "ape_unet_conv3x3_supported": [_I, _I, _I, _I],
     "ape_unet_conv3x3_bf16": [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -193,8 +189,11 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
 _lib = None
 
 
+ABI_VERSION = 6      # what ape_abi_version() of the library this table mirrors returns
+
+
 class ApeError(RuntimeError):
-    pass
+    code = None      # the status an entry point returned, when that is what failed
 
 
 def lib():
@@ -206,6 +205,10 @@ def lib():
                 "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C autoposeestimation_amd/csrc` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
         h = ctypes.CDLL(LIB_PATH)
+        h.ape_abi_version.restype = _c.c_int
+        if h.ape_abi_version() != ABI_VERSION:
+            raise ImportError("%s is ABI %d, this package expects ABI %d: a stale library -- rebuild it with "
+                              "`python -c 'import __graft_entry__ as g; g.build()'`" % (LIB_PATH, h.ape_abi_version(), ABI_VERSION))
         for name, argtypes in SIGNATURES.items():
             fn = getattr(h, name)  # AttributeError here = header and library disagree
             fn.argtypes = argtypes
@@ -240,7 +243,39 @@ def dptr(t, dtype=None):
     return _c.c_void_p(t.data_ptr())
 
 
+def _failed(what, rc):
+    msg = lib().ape_last_error()
+    err = ApeError("%s failed: code %d (%s)" % (what, rc, msg.decode() if msg else ""))
+    err.code = rc
+    return err
+
+
 def check(rc, what):
     if rc != 0:
-        msg = lib().ape_last_error()
-        raise ApeError("%s failed: code %d (%s)" % (what, rc, msg.decode() if msg else ""))
+        raise _failed(what, rc)
+
+
+class _Checked:
+    """`call.ape_x(args)`: the status-returning entry point ape_x with its status checked -- raises ApeError (symbol, `.code`,
+    ape_last_error) unless it returns APE_OK.  The checked form of a symbol is a ctypes function object of its own (the raw handle's
+    `lib().ape_x` stays unchecked: tests and tools assert on its return code) whose `errcheck` does the test; it is built on first use and
+    kept as an attribute.  Functions that return a value (*_supported, *_workspace_bytes, ...) are read through lib()."""
+
+    def __getattr__(self, name):
+        if name not in SIGNATURES or name in _RESTYPES or name.endswith(_QUERIES):
+            raise AttributeError("%s is not a status-returning entry point of include/ape_hip.h" % name)
+        fn = lib()[name]          # (item access makes a new function object; attribute access returns the cached raw one)
+        fn.argtypes, fn.restype = SIGNATURES[name], _c.c_int
+
+        def errcheck(rc, func, args):
+            if rc:
+                raise _failed(name, rc)
+            return rc
+
+        fn.errcheck = errcheck
+        setattr(self, name, fn)
+        return fn
+
+
+_QUERIES = ("_supported", "_elems", "_debug", "_strip_rows", "ape_abi_version")
+call = _Checked()

@@ -27,16 +27,14 @@ def _c(t):
 
 def act_bwd(dy, ref, act, alpha=0.0):
     dx = torch.empty_like(dy)
-    rc = _lib.lib().ape_act_bwd_f32(_lib.dptr(dy, torch.float32), _lib.dptr(ref), _lib.dptr(dx), dy.numel(), act, float(alpha), _st())
-    _lib.check(rc, "ape_act_bwd_f32")
+    _lib.call.ape_act_bwd_f32(_lib.dptr(dy, torch.float32), _lib.dptr(ref), _lib.dptr(dx), dy.numel(), act, float(alpha), _st())
     return dx
 
 
 def colsum(x2d_rows, c, ld, off, like):
     out = torch.empty(c, dtype=torch.float32, device=like.device)
     scratch = torch.empty(64 * c, dtype=torch.float32, device=like.device)
-    rc = _lib.lib().ape_colsum_f32(_lib.dptr(like, torch.float32), _lib.dptr(out), x2d_rows, c, ld, off, _lib.dptr(scratch), _st())
-    _lib.check(rc, "ape_colsum_f32")
+    _lib.call.ape_colsum_f32(_lib.dptr(like, torch.float32), _lib.dptr(out), x2d_rows, c, ld, off, _lib.dptr(scratch), _st())
     return out
 
 
@@ -51,14 +49,12 @@ def conv_wgrad(x, dy, cout, kh, kw, stride, pad, dil, param_shape=None):
     ws = _ws(nbytes, x.device)
     if param_shape is not None:
         dw = torch.empty(param_shape, dtype=torch.float32, device=x.device)
-        rc = _lib.lib().ape_conv2d_wgrad_param_f32(_lib.dptr(x, torch.float32), _lib.dptr(dy, torch.float32), _lib.dptr(dw), ctypes.byref(p),
-                                                   int(param_shape[1]), _lib.dptr(ws), ws.numel(), _st())
-        _lib.check(rc, "ape_conv2d_wgrad_param_f32")
+        _lib.call.ape_conv2d_wgrad_param_f32(_lib.dptr(x, torch.float32), _lib.dptr(dy, torch.float32), _lib.dptr(dw), ctypes.byref(p),
+                                             int(param_shape[1]), _lib.dptr(ws), ws.numel(), _st())
         return dw
     dw = torch.empty(cout, kh, kw, cx, dtype=torch.float32, device=x.device)
-    rc = _lib.lib().ape_conv2d_wgrad_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(dy, torch.float32), _lib.dptr(dw), ctypes.byref(p),
-                                              _lib.dptr(ws), ws.numel(), _st())
-    _lib.check(rc, "ape_conv2d_wgrad_nhwc_f32")
+    _lib.call.ape_conv2d_wgrad_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(dy, torch.float32), _lib.dptr(dw), ctypes.byref(p),
+                                        _lib.dptr(ws), ws.numel(), _st())
     return dw
 
 
@@ -117,7 +113,7 @@ class WeightBank:
         self.refresh()
 
     def refresh(self):
-        _lib.check(_lib.lib().ape_pack_train_weights(2, _lib.dptr(self.table), self.max_elems, _st()), "ape_pack_train_weights")
+        _lib.call.ape_pack_train_weights(2, _lib.dptr(self.table), self.max_elems, _st())
 
     def conv(self, transposed, stride, pad, dil, act):
         key = (transposed, stride, pad, dil, act)
@@ -182,7 +178,7 @@ def refresh_banks(params):
         if len(cache) >= 8:
             cache.clear()
         hit = cache[key] = (torch.cat([b.table for b in banks]), max(b.max_elems for b in banks), banks)
-    _lib.check(_lib.lib().ape_pack_train_weights(2 * len(banks), _lib.dptr(hit[0]), hit[1], _st()), "ape_pack_train_weights")
+    _lib.call.ape_pack_train_weights(2 * len(banks), _lib.dptr(hit[0]), hit[1], _st())
 
 
 refresh_banks.cache = {}
@@ -259,7 +255,7 @@ class PReLUFn(torch.autograd.Function):
         x = _c(x)
         y = torch.empty_like(x)
         a = float(alpha.detach().reshape(-1)[0])
-        _lib.check(_lib.lib().ape_prelu_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), x.numel(), a, _st()), "ape_prelu_f32")
+        _lib.call.ape_prelu_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), x.numel(), a, _st())
         ctx.save_for_backward(x, alpha)
         ctx.a = a
         return y
@@ -273,8 +269,7 @@ class PReLUFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             da = torch.empty(1, dtype=torch.float32, device=dy.device)
             scratch = torch.empty(1024, dtype=torch.float32, device=dy.device)
-            rc = _lib.lib().ape_prelu_dalpha_f32(_lib.dptr(dy, torch.float32), _lib.dptr(x), _lib.dptr(da), dy.numel(), _lib.dptr(scratch), _st())
-            _lib.check(rc, "ape_prelu_dalpha_f32")
+            _lib.call.ape_prelu_dalpha_f32(_lib.dptr(dy, torch.float32), _lib.dptr(x), _lib.dptr(da), dy.numel(), _lib.dptr(scratch), _st())
             da = da.reshape(alpha.shape)
         return dx, da
 
@@ -293,8 +288,7 @@ class MaxPoolFn(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         b, h, w, c = x.shape
         dx = torch.empty_like(x)
-        rc = _lib.lib().ape_maxpool3x3s2_bwd_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(_c(dy), torch.float32), _lib.dptr(dx), b, h, w, c, _st())
-        _lib.check(rc, "ape_maxpool3x3s2_bwd_nhwc_f32")
+        _lib.call.ape_maxpool3x3s2_bwd_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(_c(dy), torch.float32), _lib.dptr(dx), b, h, w, c, _st())
         return dx
 
 
@@ -310,8 +304,7 @@ class AdaptiveAvgPoolFn(torch.autograd.Function):
     def backward(ctx, dy):
         b, h, w, c = ctx.shape
         dx = torch.empty(ctx.shape, dtype=torch.float32, device=dy.device)
-        rc = _lib.lib().ape_adaptive_avgpool_bwd_nhwc_f32(_lib.dptr(_c(dy), torch.float32), _lib.dptr(dx), b, h, w, c, ctx.s, _st())
-        _lib.check(rc, "ape_adaptive_avgpool_bwd_nhwc_f32")
+        _lib.call.ape_adaptive_avgpool_bwd_nhwc_f32(_lib.dptr(_c(dy), torch.float32), _lib.dptr(dx), b, h, w, c, ctx.s, _st())
         return dx, None
 
 
@@ -327,8 +320,7 @@ class BilinearFn(torch.autograd.Function):
     def backward(ctx, dy):
         b, h, w, c = ctx.shape
         dx = torch.empty(ctx.shape, dtype=torch.float32, device=dy.device)
-        rc = _lib.lib().ape_bilinear_bwd_nhwc_f32(_lib.dptr(_c(dy), torch.float32), _lib.dptr(dx), b, h, w, c, ctx.o[0], ctx.o[1], ctx.ac, _st())
-        _lib.check(rc, "ape_bilinear_bwd_nhwc_f32")
+        _lib.call.ape_bilinear_bwd_nhwc_f32(_lib.dptr(_c(dy), torch.float32), _lib.dptr(dx), b, h, w, c, ctx.o[0], ctx.o[1], ctx.ac, _st())
         return dx, None, None, None
 
 
@@ -347,8 +339,7 @@ class LogSoftmaxRowsFn(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         c = y.shape[-1]
         dx = torch.empty_like(y)
-        rc = _lib.lib().ape_log_softmax_bwd_rows_f32(_lib.dptr(_c(dy), torch.float32), _lib.dptr(y), _lib.dptr(dx), y.numel() // c, c, _st())
-        _lib.check(rc, "ape_log_softmax_bwd_rows_f32")
+        _lib.call.ape_log_softmax_bwd_rows_f32(_lib.dptr(_c(dy), torch.float32), _lib.dptr(y), _lib.dptr(dx), y.numel() // c, c, _st())
         return dx
 
 
@@ -367,9 +358,8 @@ class GatherRowsFn(torch.autograd.Function):
         (index,) = ctx.saved_tensors
         b, r, c = ctx.shape
         dx = torch.empty(ctx.shape, dtype=torch.float32, device=dy.device)
-        rc = _lib.lib().ape_scatter_add_rows_f32(_lib.dptr(_c(dy), torch.float32), _lib.dptr(index, torch.int64), _lib.dptr(dx), b, r,
-                                                 index.shape[1], c, _st())
-        _lib.check(rc, "ape_scatter_add_rows_f32")
+        _lib.call.ape_scatter_add_rows_f32(_lib.dptr(_c(dy), torch.float32), _lib.dptr(index, torch.int64), _lib.dptr(dx), b, r,
+                                           index.shape[1], c, _st())
         return dx, None
 
 
@@ -385,7 +375,7 @@ class MeanRowsFn(torch.autograd.Function):
     def backward(ctx, dy):
         b, n, c = ctx.shape
         dx = torch.empty(ctx.shape, dtype=torch.float32, device=dy.device)
-        _lib.check(_lib.lib().ape_mean_rows_bwd_f32(_lib.dptr(_c(dy), torch.float32), _lib.dptr(dx), b, n, c, _st()), "ape_mean_rows_bwd_f32")
+        _lib.call.ape_mean_rows_bwd_f32(_lib.dptr(_c(dy), torch.float32), _lib.dptr(dx), b, n, c, _st())
         return dx
 
 
@@ -394,11 +384,10 @@ def _adds_grad(pred_r, pred_t, points, model, target, pred_c, dis, std, g, symme
     d_r, d_t = torch.empty_like(pred_r), torch.empty_like(pred_t)
     d_c = torch.empty(n, dtype=torch.float32, device=pred_r.device) if full else None
     g = _c(g.detach().float().reshape(1))
-    rc = _lib.lib().ape_adds_grad_f32(_lib.dptr(pred_r, torch.float32), _lib.dptr(pred_t, torch.float32), _lib.dptr(points),
-                                      _lib.dptr(model, torch.float32), _lib.dptr(target, torch.float32), _lib.dptr(pred_c),
-                                      _lib.dptr(dis, torch.float32), _lib.dptr(std), _lib.dptr(g), n, m, int(bool(symmetric)),
-                                      int(bool(full)), float(w), _lib.dptr(d_r), _lib.dptr(d_t), _lib.dptr(d_c), _st())
-    _lib.check(rc, "ape_adds_grad_f32")
+    _lib.call.ape_adds_grad_f32(_lib.dptr(pred_r, torch.float32), _lib.dptr(pred_t, torch.float32), _lib.dptr(points),
+                                _lib.dptr(model, torch.float32), _lib.dptr(target, torch.float32), _lib.dptr(pred_c),
+                                _lib.dptr(dis, torch.float32), _lib.dptr(std), _lib.dptr(g), n, m, int(bool(symmetric)),
+                                int(bool(full)), float(w), _lib.dptr(d_r), _lib.dptr(d_t), _lib.dptr(d_c), _st())
     return d_r, d_t, d_c
 
 
@@ -479,9 +468,8 @@ class Adam:
             jobs[i] = _lib.AdamJob(param=_lib.dptr(p.data, torch.float32), grad=_lib.dptr(g), exp_avg=_lib.dptr(st["exp_avg"]),
                                    exp_avg_sq=_lib.dptr(st["exp_avg_sq"]), n=p.numel(), bc1=1.0 - b1 ** st["step"],
                                    bc2_sqrt=math.sqrt(1.0 - b2 ** st["step"]))
-        rc = _lib.lib().ape_adam_step_multi_f32(len(live), jobs, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                                                float(self.weight_decay), _st())
-        _lib.check(rc, "ape_adam_step_multi_f32")
+        _lib.call.ape_adam_step_multi_f32(len(live), jobs, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                                          float(self.weight_decay), _st())
         refresh_banks(live)          # the conv operands of the updated parameters, one launch
 
 
@@ -508,12 +496,11 @@ class BatchNormFn(torch.autograd.Function):
         invstd = torch.empty(c, dtype=torch.float32, device=x.device)
         ws = _ws(_lib.lib().ape_bn_workspace_bytes(c), x.device)
         res = None if residual is None else _c(residual)
-        rc = _lib.lib().ape_bn_train_fwd_f32(_lib.dptr(x, torch.float32), _lib.dptr(_c(gamma.detach()), torch.float32),
-                                             _lib.dptr(_c(beta.detach()), torch.float32), _lib.dptr(res, torch.float32), _lib.dptr(y),
-                                             _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(running_mean, torch.float32),
-                                             _lib.dptr(running_var, torch.float32), _lib.dptr(num_batches_tracked, torch.int64), rows, c,
-                                             float(eps), float(momentum), act, _lib.dptr(ws), ws.numel(), _st())
-        _lib.check(rc, "ape_bn_train_fwd_f32")
+        _lib.call.ape_bn_train_fwd_f32(_lib.dptr(x, torch.float32), _lib.dptr(_c(gamma.detach()), torch.float32),
+                                       _lib.dptr(_c(beta.detach()), torch.float32), _lib.dptr(res, torch.float32), _lib.dptr(y),
+                                       _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(running_mean, torch.float32),
+                                       _lib.dptr(running_var, torch.float32), _lib.dptr(num_batches_tracked, torch.int64), rows, c,
+                                       float(eps), float(momentum), act, _lib.dptr(ws), ws.numel(), _st())
         ctx.save_for_backward(x, gamma, mean, invstd, y if act == E.ACT_RELU else None)
         ctx.has_res = residual is not None
         return y
@@ -530,11 +517,10 @@ class BatchNormFn(torch.autograd.Function):
         db = torch.empty_like(invstd) if need_b else None
         dres = (torch.empty_like(x) if y is not None else dy) if need_r else None
         ws = _ws(_lib.lib().ape_bn_workspace_bytes(c) + 8 * c, x.device)
-        rc = _lib.lib().ape_bn_train_bwd_f32(_lib.dptr(dy, torch.float32), _lib.dptr(y), _lib.dptr(x), _lib.dptr(mean), _lib.dptr(invstd),
-                                             _lib.dptr(_c(gamma.detach()), torch.float32), _lib.dptr(dx), _lib.dptr(dg), _lib.dptr(db),
-                                             _lib.dptr(dres if (need_r and y is not None) else None), b * h * w, c, _lib.dptr(ws),
-                                             ws.numel(), _st())
-        _lib.check(rc, "ape_bn_train_bwd_f32")
+        _lib.call.ape_bn_train_bwd_f32(_lib.dptr(dy, torch.float32), _lib.dptr(y), _lib.dptr(x), _lib.dptr(mean), _lib.dptr(invstd),
+                                       _lib.dptr(_c(gamma.detach()), torch.float32), _lib.dptr(dx), _lib.dptr(dg), _lib.dptr(db),
+                                       _lib.dptr(dres if (need_r and y is not None) else None), b * h * w, c, _lib.dptr(ws),
+                                       ws.numel(), _st())
         return dx, dg, db, dres, None, None, None, None, None, None
 
 
@@ -570,8 +556,7 @@ class UpsampleNearest2xFn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(b, h, w, c, dtype=torch.float32, device=dout.device)
-            rc = _lib.lib().ape_upsample_nearest2x_bwd_f32(_lib.dptr(dout, torch.float32), c + ctx.cs, 0, _lib.dptr(dx), b, h, w, c, _st())
-            _lib.check(rc, "ape_upsample_nearest2x_bwd_f32")
+            _lib.call.ape_upsample_nearest2x_bwd_f32(_lib.dptr(dout, torch.float32), c + ctx.cs, 0, _lib.dptr(dx), b, h, w, c, _st())
         dskip = dout[..., c:] if (ctx.cs and ctx.needs_input_grad[1]) else None
         return dx, dskip
 
@@ -584,7 +569,7 @@ class SoftmaxChannelsFn(torch.autograd.Function):
         x = _c(x)
         c = x.shape[-1]
         y = torch.empty_like(x)
-        _lib.check(_lib.lib().ape_softmax_rows_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), x.numel() // c, c, _st()), "ape_softmax_rows_f32")
+        _lib.call.ape_softmax_rows_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), x.numel() // c, c, _st())
         ctx.save_for_backward(y)
         return y
 
@@ -593,8 +578,7 @@ class SoftmaxChannelsFn(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         c = y.shape[-1]
         dx = torch.empty_like(y)
-        rc = _lib.lib().ape_softmax_rows_bwd_f32(_lib.dptr(_c(dy), torch.float32), _lib.dptr(y), _lib.dptr(dx), y.numel() // c, c, _st())
-        _lib.check(rc, "ape_softmax_rows_bwd_f32")
+        _lib.call.ape_softmax_rows_bwd_f32(_lib.dptr(_c(dy), torch.float32), _lib.dptr(y), _lib.dptr(dx), y.numel() // c, c, _st())
         return dx
 
 
@@ -615,9 +599,8 @@ class JaccardLossFn(torch.autograd.Function):
         ws = _ws(_lib.lib().ape_jaccard_workspace_bytes(c, ncol), logits.device)
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
         st = _strides4(logits)
-        rc = _lib.lib().ape_jaccard_fwd_f32(ctypes.c_void_p(logits.data_ptr()), st, _lib.dptr(lab, torch.int64), b, c, h, w, ncol, float(eps),
-                                            _lib.dptr(loss), _lib.dptr(ws), ws.numel(), _st())
-        _lib.check(rc, "ape_jaccard_fwd_f32")
+        _lib.call.ape_jaccard_fwd_f32(ctypes.c_void_p(logits.data_ptr()), st, _lib.dptr(lab, torch.int64), b, c, h, w, ncol, float(eps),
+                                      _lib.dptr(loss), _lib.dptr(ws), ws.numel(), _st())
         ctx.save_for_backward(logits, lab, ws)
         ctx.ncol = ncol
         return loss
@@ -627,10 +610,9 @@ class JaccardLossFn(torch.autograd.Function):
         logits, lab, ws = ctx.saved_tensors
         b, c, h, w = logits.shape
         dlogits = torch.empty_strided(logits.shape, logits.stride(), dtype=torch.float32, device=logits.device)
-        rc = _lib.lib().ape_jaccard_bwd_f32(ctypes.c_void_p(logits.data_ptr()), _strides4(logits), _lib.dptr(lab, torch.int64), b, c, h, w,
-                                            ctx.ncol, _lib.dptr(_c(g.detach().float().reshape(1))), ctypes.c_void_p(dlogits.data_ptr()),
-                                            _strides4(dlogits), _lib.dptr(ws), ws.numel(), _st())
-        _lib.check(rc, "ape_jaccard_bwd_f32")
+        _lib.call.ape_jaccard_bwd_f32(ctypes.c_void_p(logits.data_ptr()), _strides4(logits), _lib.dptr(lab, torch.int64), b, c, h, w,
+                                      ctx.ncol, _lib.dptr(_c(g.detach().float().reshape(1))), ctypes.c_void_p(dlogits.data_ptr()),
+                                      _strides4(dlogits), _lib.dptr(ws), ws.numel(), _st())
         return dlogits, None, None
 
 
@@ -672,7 +654,6 @@ class SGD:
                     first = 1
             jobs[i] = _lib.SgdJob(param=_lib.dptr(p.data, torch.float32), grad=_lib.dptr(g), momentum_buffer=_lib.dptr(buf), n=p.numel(),
                                   first=first, reserved=0)
-        rc = _lib.lib().ape_sgd_step_multi_f32(len(live), jobs, float(self.lr), float(self.momentum), float(self.dampening),
-                                               float(self.weight_decay), int(bool(self.nesterov)), _st())
-        _lib.check(rc, "ape_sgd_step_multi_f32")
+        _lib.call.ape_sgd_step_multi_f32(len(live), jobs, float(self.lr), float(self.momentum), float(self.dampening),
+                                         float(self.weight_decay), int(bool(self.nesterov)), _st())
         refresh_banks(live)

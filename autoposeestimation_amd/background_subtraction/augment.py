@@ -142,8 +142,7 @@ def build_samples(samples, params, mean, std, want_u8=False):
         _ws[key] = ws
     m = (ctypes.c_float * 7)(*[float(v) for v in mean])
     sd = (ctypes.c_float * 7)(*[float(v) for v in std])
-    rc = _lib.lib().ape_bgsub_train_samples(ctypes.cast(jobs, ctypes.c_void_p), b, h, w, ctypes.cast(m, ctypes.c_void_p),
-                                            ctypes.cast(sd, ctypes.c_void_p), _lib.dptr(x8), _lib.dptr(lab), _lib.dptr(u8) if want_u8 else None,
-                                            _lib.dptr(ws), ws.numel(), _lib.stream_ptr())
-    _lib.check(rc, "ape_bgsub_train_samples")
+    _lib.call.ape_bgsub_train_samples(ctypes.cast(jobs, ctypes.c_void_p), b, h, w, ctypes.cast(m, ctypes.c_void_p),
+                                      ctypes.cast(sd, ctypes.c_void_p), _lib.dptr(x8), _lib.dptr(lab), _lib.dptr(u8) if want_u8 else None,
+                                      _lib.dptr(ws), ws.numel(), _lib.stream_ptr())
     return (x8, lab, u8) if want_u8 else (x8, lab)

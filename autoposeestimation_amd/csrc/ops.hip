@@ -810,22 +810,9 @@ extern "C" size_t ape_adaptive_avgpool_multi_workspace_bytes(int B, int C)
     return (size_t)(B < 0 ? 0 : B) * kPoolMaxAtoms * kPoolMaxAtoms * (size_t)(C < 0 ? 0 : C) * sizeof(float);
 }
 
-/* nn.AdaptiveAvgPool2d((S_i, S_i)) for nsizes <= 4 sizes S_i <= 8 of the same map in one pass: x[B][H][W][C] -> ys[i][B][S_i][S_i][C].
+/* nn.AdaptiveAvgPool2d((S_i, S_i)) for nsizes <= 4 sizes S_i <= 8 of the same map in one pass: x[B][H][W][ldx] -> ys[i][B][S_i][S_i][C],
+ * of the first C channels of a map with ldx channels per pixel (ldx >= C), x in either activation format (APE_FMT_S32: both % 32 == 0).
  * Returns APE_EINVAL when the bin edges give more than 12 atoms per axis (call ape_adaptive_avgpool_nhwc_f32 per size then). */
-extern "C" int ape_adaptive_avgpool_multi_nhwc_f32(const float* x, float* const* ys_host, const int* sizes_host, int nsizes, int B, int H,
-                                                   int W, int C, void* workspace, size_t workspace_bytes, void* stream)
-{
-    return ape_adaptive_avgpool_multi_nhwc_fmt(x, APE_FMT_F32, ys_host, sizes_host, nsizes, B, H, W, C, workspace, workspace_bytes, stream);
-}
-
-/* the same with x in either activation format (APE_FMT_S32: C % 32 == 0); the pooled outputs are fp32 */
-extern "C" int ape_adaptive_avgpool_multi_nhwc_fmt(const void* x, int in_fmt, float* const* ys_host, const int* sizes_host, int nsizes, int B, int H,
-                                                   int W, int C, void* workspace, size_t workspace_bytes, void* stream)
-{
-    return ape_adaptive_avgpool_multi_nhwc_ld(x, in_fmt, ys_host, sizes_host, nsizes, B, H, W, C, C, workspace, workspace_bytes, stream);
-}
-
-/* ... of the first C channels of a map with ldx channels per pixel (ldx >= C; APE_FMT_S32: both % 32 == 0); outputs [B,s,s,C] */
 extern "C" int ape_adaptive_avgpool_multi_nhwc_ld(const void* x, int in_fmt, float* const* ys_host, const int* sizes_host, int nsizes, int B, int H,
                                                   int W, int C, int ldx, void* workspace, size_t workspace_bytes, void* stream)
 {
@@ -947,14 +934,7 @@ extern "C" int ape_head_select_f32(const float* h, int ldh, int off_r, int off_t
 extern "C" int ape_upconv3x3_gather_f32(const float* z, const float* bias, float* out, int B, int h, int w, int C, int act, float alpha,
                                         void* stream)
 {
-    return ape_upconv3x3_gather_fmt(z, bias, out, APE_FMT_F32, B, h, w, C, act, alpha, stream);
-}
-
-/* the same with the OUTPUT in either activation format (APE_FMT_S32: C % 32 == 0) */
-extern "C" int ape_upconv3x3_gather_fmt(const float* z, const float* bias, void* out, int out_fmt, int B, int h, int w, int C, int act,
-                                        float alpha, void* stream)
-{
-    return ape_upconv3x3_gather_ex(z, bias, out, out_fmt, B, h, w, C, act, alpha, 0, stream);
+    return ape_upconv3x3_gather_ex(z, bias, out, APE_FMT_F32, B, h, w, C, act, alpha, 0, stream);
 }
 
 // The strip kernel advances a tap's z row pair on a fixed schedule: the upper source row floor(sh * q) of up-sampled row q may change

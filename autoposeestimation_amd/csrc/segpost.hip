@@ -542,13 +542,6 @@ extern "C" size_t ape_seg_components_workspace_bytes(int B, int H, int W, int C)
 }
 
 /* label[B][H][W] u8, score[B][H][W] f32 -> objmap[B][H][W] u8, det[B][C][5] i32 (valid,rmin,rmax,cmin,cmax) */
-extern "C" int ape_seg_components(const uint8_t* label, const float* score, uint8_t* objmap, int* det, int B, int H, int W,
-                                  int C, int min_pixels, void* workspace, size_t workspace_bytes, void* stream)
-{
-    return ape_seg_components_scored(label, score, objmap, det, B, H, W, C, min_pixels, APE_SEG_SCORE_MEAN, workspace,
-                                     workspace_bytes, stream);
-}
-
 extern "C" int ape_seg_components_scored(const uint8_t* label, const float* score, uint8_t* objmap, int* det, int B, int H, int W,
                                          int C, int min_pixels, int score_mode, void* workspace, size_t workspace_bytes, void* stream)
 {
@@ -570,7 +563,7 @@ extern "C" int ape_seg_components_scored(const uint8_t* label, const float* scor
     int* tight = (int*)ws;
     const int g = grid_for(npix);
     // (sum / cnt are zeroed where they are used, at the component roots, by ccl_compress_kernel.  Kernels, not hipMemsetAsync: memset nodes of a
-    // captured HIP graph did not re-zero on replay -- tools/probes/graph_probe.py)
+    // captured HIP graph did not re-zero on replay -- tools/attic/probes/graph_probe.py)
     const int BC = B * C;
     hipLaunchKernelGGL(seg_small_init_kernel, dim3(ape::ceil_div(BC, kT)), dim3(kT), 0, st, hist, best_key, best_root, tight, BC);
     hipLaunchKernelGGL(ccl_init_kernel, dim3(g), dim3(kT), 0, st, label, L, W, npix);

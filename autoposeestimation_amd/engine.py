@@ -5,6 +5,8 @@ torch's current stream and returns without synchronising.  No function here has 
 Device layout (DESIGN.md "Data layout in HBM"): activations NHWC fp32 `[B,H,W,C]` (points are `[B,N,1,C]`),
 weights `[Cout][KH][KW][Cin4]` with Cin zero-padded to a multiple of 4.
 """
+import contextlib
+import contextvars
 import ctypes
 import os
 
@@ -82,7 +84,6 @@ PROFILE = None   # set to a LaunchProfile() to time conv launches
 #   "bf16x3" split-bf16, 3 products per term, ~2^-16 operand error      833 TFLOP/s effective peak
 #   "bf16"   plain bf16 operands (2^-8)                                 2.5 PFLOP/s peak
 PRECISIONS = ("f32", "bf16x3", "bf16")
-SPLITK_SMALL_M = False     # split-K for the pose networks' layers whose grid would not fill the chip: FramePipeline(low_latency=True) sets it around its pose stage (round 6)
 USE_HALO_KERNEL = True    # route eligible 3x3 convs of the bf16 paths to the LDS-halo kernel (conv3x3_halo.hip)
 USE_GEMM_KERNEL = os.environ.get("APE_USE_GEMM_KERNEL", "1") != "0"    # route Cin % 32 == 0 layers the halo kernel does not take to conv_gemm.hip (else conv_bf16.hip)
 USE_CONV_MULTI = os.environ.get("APE_USE_CONV_MULTI", "1") != "0"     # the PSP stage convolutions in one launch (conv1x1_multi); 0: one launch each (A/B)
@@ -118,14 +119,14 @@ class S32:
     def to_f32(self):
         y = torch.empty_like(self.t)
         c = self.t.shape[-1]
-        _lib.check(_lib.lib().ape_convert_s32(_lib.dptr(self.t, torch.float32), _lib.dptr(y), self.t.numel() // c, c, 0, _st()), "ape_convert_s32")
+        _lib.call.ape_convert_s32(_lib.dptr(self.t, torch.float32), _lib.dptr(y), self.t.numel() // c, c, 0, _st())
         return y
 
     @staticmethod
     def from_f32(x):
         y = torch.empty_like(x)
         c = x.shape[-1]
-        _lib.check(_lib.lib().ape_convert_s32(_lib.dptr(x, torch.float32), _lib.dptr(y), x.numel() // c, c, 1, _st()), "ape_convert_s32")
+        _lib.call.ape_convert_s32(_lib.dptr(x, torch.float32), _lib.dptr(y), x.numel() // c, c, 1, _st())
         return S32(y)
 
 
@@ -143,62 +144,109 @@ def pack_conv_weight(w, device):
     return out.contiguous()
 
 
-def allow_splitk(obj, _seen=None):
-    """mark every Conv reachable from `obj` (a plan object, a list / tuple / dict of them, an UpConv) as free to take the split-K form at small M"""
-    _seen = set() if _seen is None else _seen
-    if id(obj) in _seen or obj is None or isinstance(obj, (int, float, str, bytes, torch.Tensor)):
-        return
-    _seen.add(id(obj))
-    if isinstance(obj, Conv):
-        obj.allow_splitk = True
-        return
-    if isinstance(obj, (list, tuple)):
-        for o in obj:
-            allow_splitk(o, _seen)
-    elif isinstance(obj, dict):
-        for o in obj.values():
-            allow_splitk(o, _seen)
-    elif hasattr(obj, "__dict__") and type(obj).__module__.startswith("autoposeestimation_amd") or type(obj).__name__ == "Plan":
-        for o in vars(obj).values():
-            allow_splitk(o, _seen)
+# 3x3 layers on S32 inputs with these input channel counts take the half-pass kernel (fp16 main product + block-scaled e2m3 cross terms,
+# conv3x3_halo_mx.hip) instead of halo_s32's three bf16 products.  Off unless asked for: not bit-identical to bf16x3 (DESIGN.md 6e).
+USE_MX6 = os.environ.get("APE_USE_MX6", "0") != "0"
+MX6_CIN = tuple(int(v) for v in os.environ.get("APE_MX6_CIN", "512").split(","))
+
+
+_POSE_STAGE = contextvars.ContextVar("ape_low_latency_pose_stage", default=False)
+
+
+@contextlib.contextmanager
+def low_latency(on=True):
+    """Inside this block (of this thread / context only) the layers built with `Conv(..., splitk=True)` take the split-K form at small M:
+    the batch-1 pose stage of FramePipeline(low_latency=True).  Layers built without the keyword -- the segmentor's -- never do."""
+    token = _POSE_STAGE.set(bool(on))
+    try:
+        yield
+    finally:
+        _POSE_STAGE.reset(token)
+
+
+def _tf(v):
+    return "true" if v else "false"
+
+
+def tiles16_mostly_full(h, w):
+    """the LDS-halo kernels tile an h x w map in 16x16 pixels: worth it only when those tiles are mostly full (crop feature maps of
+    20x20 / 40x40 would waste 30..60 % of the MFMAs; the flattened-M kernels have no such edge effect)"""
+    return h * w >= 0.8 * (-(-h // 16) * -(-w // 16) * 256)
+
+
+# ---- profiling labels: the kernel names as rocprofv3 spells them (bench.py finds a kernel's HBM traffic in profiles/*_pmc_traffic.json by
+# them), one function per kernel family, and the shape string of a conv launch
+def halo_label(nsplit, dil, cout, ups, head=False):
+    return "conv3x3_halo_kernel<%d,%d,%d,%s,%s>" % (nsplit, dil, 64 if cout <= 64 else 128, _tf(ups), _tf(head))
+
+
+def halo_s32_label(dil):
+    return "halo_s32_kernel<%d, true>" % dil          # <dilation, ping-pong schedule>
+
+
+def halo_mx_label(dil):
+    return "halo_mx_kernel<%d>" % dil
+
+
+def gemm_s32_label(cout, residual=False):
+    bn = 128 if cout <= 128 else 192 if (-(-cout // 192) * 192 - cout) < (-(-cout // 256) * 256 - cout) else 256
+    return ("gemm_s32_res_kernel<%d, false>" if residual else "gemm_s32_kernel<%d, false>") % bn
+
+
+def conv_shape(conv, b, ho, wo, ups=False):
+    return "%dx%dx%d %d->%d k%d s%d d%d%s" % (b, ho, wo, conv.cin_real, conv.cout, conv.kh, conv.stride, conv.dil, " ups" if ups else "")
+
+
+def conv_params(conv, b, h, w, ldx, ldy, xoff=0, yoff=0, act=None, bias_bstride=0, ldr=0, roff=0, ups=False):
+    """the `ape_conv_params` of `conv` on a [b,h,w,ldx] input (h, w: of the up-sampled map when `ups`) writing a map of ldy channels;
+    ldr / roff: the residual's channels per pixel (0: none) and offset; act: None = the layer's own"""
+    ho, wo = conv.out_hw(h, w)
+    return ConvParams(B=b, H=h, W=w, Cin=conv.cin, ldx=ldx, xoff=xoff, Ho=ho, Wo=wo, Cout=conv.cout, ldy=ldy, yoff=yoff, KH=conv.kh, KW=conv.kw,
+                      stride=conv.stride, pad=conv.pad, dil=conv.dil, act=conv.act if act is None else act, alpha=conv.alpha,
+                      bias_bstride=bias_bstride, ldr=ldr, roff=roff, ups=int(bool(ups)))
+
+
+def _nsplit(precision):
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be one of %s" % (PRECISIONS,))
+    return {"f32": 0, "bf16x3": 3, "bf16": 1}[precision]
+
+
+# argument layouts of the conv entry points (Conv._make_plan picks one with the entry point, Conv.__call__ passes the operands accordingly)
+_ARGS_F32, _ARGS_BF16, _ARGS_GEMM, _ARGS_SPLITK, _ARGS_S32, _ARGS_MX = range(6)
 
 
 class Conv:
-    """One conv / 1x1 / Linear layer bound to ape_conv2d_nhwc_f32."""
+    """One conv / 1x1 / Linear layer bound to ape_conv2d_nhwc_f32 or, in the bf16 precisions, to the kernel of its family that takes the
+    call's geometry.  splitk: the layer may take the split-K form at small M inside `low_latency()` (the pose networks' layers)."""
 
-    def __init__(self, weight, bias=None, stride=1, pad=0, dil=1, act=ACT_NONE, alpha=0.0, device="cuda", precision="f32"):
-        if precision not in PRECISIONS:
-            raise ValueError("precision must be one of %s" % (PRECISIONS,))
-        self.w = pack_conv_weight(weight, device)
-        self.cout, self.kh, self.kw, self.cin = self.w.shape
-        self.cin_real = weight.shape[1]
-        self.precision = precision
-        self.nsplit = {"f32": 0, "bf16x3": 3, "bf16": 1}[precision]
-        if self.nsplit:
-            k = self.kh * self.kw * self.cin
-            n = _lib.lib().ape_packed_weights_bf16_elems(self.cout, k)
-            self.wp = torch.empty(n, dtype=torch.bfloat16, device=device)
-            _lib.check(_lib.lib().ape_pack_weights_bf16(_lib.dptr(self.w), _lib.dptr(self.wp), self.cout, k, _st()),
-                       "ape_pack_weights_bf16")
-            self.variant = "conv_bf16_kernel<%d,%s>" % (self.nsplit, "128,128,2,2,64,false" if self.cout > 64 else "128,64,4,1,32,true")
-        else:
-            self.variant = "conv_f32_kernel<%s>" % ("128,2,2" if self.cout > 64 else "64,4,1" if self.cout > 32 else "32,4,1")
+    def __init__(self, weight, bias=None, stride=1, pad=0, dil=1, act=ACT_NONE, alpha=0.0, device="cuda", precision="f32", splitk=False):
+        nsplit = _nsplit(precision)          # (refuses an unknown precision before anything is packed)
+        w, wp = pack_conv_weight(weight, device), None
+        if nsplit:
+            cout, kh, kw, cin = w.shape
+            wp = torch.empty(_lib.lib().ape_packed_weights_bf16_elems(cout, kh * kw * cin), dtype=torch.bfloat16, device=device)
+            _lib.call.ape_pack_weights_bf16(_lib.dptr(w), _lib.dptr(wp), cout, kh * kw * cin, _st())
+        self._bind(w, wp, weight.shape[1], stride, pad, dil, act, alpha, precision, splitk)
         self.bias = None if bias is None else bias.detach().to(device=device, dtype=torch.float32).contiguous()
-        self.stride, self.pad, self.dil, self.act, self.alpha = stride, pad, dil, act, float(alpha)
 
     @classmethod
-    def from_packed(cls, w, wp, cin_real, stride=1, pad=0, dil=1, act=ACT_NONE, alpha=0.0, precision="f32"):
+    def from_packed(cls, w, wp, cin_real, stride=1, pad=0, dil=1, act=ACT_NONE, alpha=0.0, precision="f32", splitk=False):
         """a layer over operands that are ALREADY packed (w: f32 [Cout,KH,KW,Cin4]; wp: the split-bf16 planes of the same weights, needed
         unless precision == 'f32'): the training tape keeps them per parameter and re-packs them after each optimizer step
         (autograd.WeightBank), instead of packing per call"""
-        if precision not in PRECISIONS:
-            raise ValueError("precision must be one of %s" % (PRECISIONS,))
         self = cls.__new__(cls)
+        self._bind(w, wp, cin_real, stride, pad, dil, act, alpha, precision, splitk)
+        self.bias = None
+        return self
+
+    def _bind(self, w, wp, cin_real, stride, pad, dil, act, alpha, precision, splitk):
+        """geometry, precision and kernel variant names of a layer over the packed operands (w, wp); its caches start empty"""
+        self.nsplit = _nsplit(precision)
+        self.precision = precision
         self.w = w
         self.cout, self.kh, self.kw, self.cin = w.shape
         self.cin_real = cin_real
-        self.precision = precision
-        self.nsplit = {"f32": 0, "bf16x3": 3, "bf16": 1}[precision]
         if self.nsplit:
             if wp is None:
                 raise ValueError("precision %s needs the packed bf16 planes" % precision)
@@ -206,29 +254,27 @@ class Conv:
             self.variant = "conv_bf16_kernel<%d,%s>" % (self.nsplit, "128,128,2,2,64,false" if self.cout > 64 else "128,64,4,1,32,true")
         else:
             self.variant = "conv_f32_kernel<%s>" % ("128,2,2" if self.cout > 64 else "64,4,1" if self.cout > 32 else "32,4,1")
-        self.bias = None
         self.stride, self.pad, self.dil, self.act, self.alpha = stride, pad, dil, act, float(alpha)
-        return self
+        self.splitk = bool(splitk)
+        self._plans, self._ws32, self._wmx6 = {}, None, None
 
     def s32k(self):
         """the weights in the S32K grouping ([Cout][K/32][hi 32 | lo 32] bf16) for the S32 consumers; built on first use"""
-        ws = getattr(self, "_ws32", None)
-        if ws is None:
+        if self._ws32 is None:
             k = self.kh * self.kw * self.cin
             ws = torch.empty(self.cout * k * 2, dtype=torch.bfloat16, device=self.w.device)
-            _lib.check(_lib.lib().ape_pack_weights_s32k(_lib.dptr(self.w), _lib.dptr(ws), self.cout, k, _st()), "ape_pack_weights_s32k")
+            _lib.call.ape_pack_weights_s32k(_lib.dptr(self.w), _lib.dptr(ws), self.cout, k, _st())
             self._ws32 = ws
-        return ws
+        return self._ws32
 
     def mx6k(self):
         """the weights as F16M6 lines ([Cout][9 * Cin / 32][128 B], mx6.pack_conv_weights) for ape_conv3x3_halo_mx; built on first use"""
-        wq = getattr(self, "_wmx6", None)
-        if wq is None:
+        if self._wmx6 is None:
             from . import mx6
             w = self.w.detach().float().cpu().numpy().reshape(self.cout, self.kh, self.kw, self.cin)       # (the unpacked layout: [Cout][kh][kw][Cin])
             lines = mx6.pack_lines(w.reshape(self.cout, self.kh * self.kw * (self.cin // 32), 32))
-            wq = self._wmx6 = torch.from_numpy(lines).to(self.w.device)
-        return wq
+            self._wmx6 = torch.from_numpy(lines).to(self.w.device)
+        return self._wmx6
 
     def _generic_variant(self, m):
         """name of the template instantiation ape_conv2d_nhwc_* dispatches to (mirrors the C++ rule; profiling label only)"""
@@ -262,17 +308,69 @@ class Conv:
         wo = (w + 2 * self.pad - self.dil * (self.kw - 1) - 1) // self.stride + 1
         return ho, wo
 
+    def _make_plan(self, key):
+        """The launch of one call signature (`key`: see __call__): the parameter block, the kernel family that takes it -- f32 generic, bf16
+        generic, LDS-halo, conv_gemm plain / _fmt / split-K for fp32 inputs; halo_mx, halo_s32, gemm_s32 for S32 inputs -- as (argument
+        layout, checked entry point), the launch's profiling label and shape string and its algorithmic cost.  Depends on shapes and on the
+        module switches in the key only: kept per signature (the training tape calls every layer with the same shapes step after step;
+        building the ctypes struct and asking the library twice cost ~15 us per call)."""
+        b, h, w, ldx, xoff, ldy, yoff, act, bias_bstride, ldr, roff, ups, splitk, in_fmt, out_fmt = key[:15]
+        p = conv_params(self, b, h, w, ldx, ldy, xoff, yoff, act, bias_bstride, ldr, roff, ups)
+        pref, L, m = ctypes.byref(p), _lib.lib(), b * p.Ho * p.Wo
+        sk_bytes = 0
+        if in_fmt == FMT_S32:
+            if self.kh != 3:
+                if not L.ape_conv_gemm_s32_supported(pref):
+                    raise ValueError("no S32 kernel for this layer geometry (%dx%d, stride %d, Cin %d, Cout %d)" % (self.kh, self.kw, self.stride, self.cin, self.cout))
+                args, entry, label = _ARGS_S32, "ape_conv_gemm_s32", gemm_s32_label(self.cout, ldr != 0)
+            elif (USE_MX6 and self.cin in MX6_CIN and self.cout >= 128 and self.stride == 1 and xoff == 0 and ldx == self.cin
+                  and L.ape_conv3x3_halo_mx_supported(pref)):
+                # half the matrix passes (conv3x3_halo_mx.hip): the S32 input is re-expressed once as F16M6 lines
+                args, entry, label = _ARGS_MX, "ape_conv3x3_halo_mx", halo_mx_label(self.dil)
+            else:
+                if not L.ape_conv3x3_halo_s32_supported(pref):
+                    raise ValueError("no S32 kernel for this layer geometry (3x3, stride %d, dil %d, Cin %d, Cout %d)" % (self.stride, self.dil, self.cin, self.cout))
+                args, entry, label = _ARGS_S32, "ape_conv3x3_halo_s32", halo_s32_label(self.dil)
+        else:
+            halo = bool(self.nsplit and USE_HALO_KERNEL and (ups or tiles16_mostly_full(h, w)) and L.ape_conv3x3_halo_supported(pref))
+            gemm = bool(not halo and self.nsplit and USE_GEMM_KERNEL and L.ape_conv_gemm_supported(pref))
+            if out_fmt == FMT_S32 and not gemm:
+                raise ValueError("an S32 output from an fp32 input exists only on the conv_gemm kernel (Cin % 32 == 0, not a halo layer)")
+            if halo:
+                args, entry, label = _ARGS_BF16, "ape_conv3x3_halo_bf16", halo_label(self.nsplit, self.dil, self.cout, ups)
+            elif gemm:
+                # k-tiles dealt to several workgroups per output tile where the library finds it worth it (fewer than 96 tiles and >= 8 k-tiles)
+                sk_bytes = int(L.ape_conv_gemm_splitk_workspace_bytes(pref)) if splitk and out_fmt == FMT_F32 else 0
+                args, entry = (_ARGS_SPLITK, "ape_conv_gemm_bf16_splitk") if sk_bytes else (_ARGS_GEMM, "ape_conv_gemm_bf16_fmt")
+                label = self._gemm_variant(m)
+            else:
+                args, entry = (_ARGS_BF16, "ape_conv2d_nhwc_bf16") if self.nsplit else (_ARGS_F32, "ape_conv2d_nhwc_f32")
+                label = self._generic_variant(m)
+        hin, win = (h // 2, w // 2) if ups else (h, w)
+        if len(self._plans) > 64:
+            self._plans.clear()
+        plan = self._plans[key] = (p, pref, args, getattr(_lib.call, entry), sk_bytes, label, conv_shape(self, b, p.Ho, p.Wo, ups),
+                                   *_conv_cost(self, b, hin, win, p.Ho, p.Wo, ldr != 0))
+        return plan
+
     def __call__(self, x, out=None, xoff=0, yoff=0, residual=None, roff=0, bias=None, bias_bstride=0, act=None, upsample2x=False,
                  out_fmt=FMT_F32, splitk=False):
         """x[B,H,W,ldx] (reads channels xoff..xoff+cin) -> out[B,Ho,Wo,ldy] (writes yoff..yoff+cout).
         upsample2x: the conv runs on the bilinear x2 (align_corners=True) up-sampling of x, fused into the LDS-halo kernel
         when it applies, otherwise materialised by ape_bilinear_nhwc_f32 first.
         x / residual may be `S32` (pre-split) tensors and out_fmt=FMT_S32 returns one: only on the split-bf16 kernels that
-        declare S32 operands (this never converts silently -- an unsupported combination raises)."""
-        if isinstance(x, S32) or isinstance(residual, S32):
-            return self._call_s32(x, out, xoff, yoff, residual, roff, bias, bias_bstride, act, out_fmt)
-        if out_fmt == FMT_S32 and isinstance(out, S32):
-            out = out.t
+        declare S32 operands (this never converts silently -- an unsupported combination raises).
+        splitk: take the split-K form if the library finds the shape worth it (the training tape); layers built with splitk=True also do
+        inside `low_latency()`."""
+        in_fmt = FMT_S32 if isinstance(x, S32) else FMT_F32
+        if in_fmt == FMT_S32 or isinstance(residual, S32):
+            if self.nsplit != 3:
+                raise ValueError("S32 operands exist only in the split-bf16 ('bf16x3') precision")
+            if in_fmt != FMT_S32:
+                raise ValueError("S32 output / residual needs an S32 input on this path")
+            if upsample2x:
+                raise ValueError("no S32 kernel up-samples its input")
+            x = x.t
         if upsample2x:
             can_fuse = (self.nsplit and USE_HALO_KERNEL and self.kh == 3 and self.kw == 3 and self.stride == 1 and self.pad == 1
                         and self.dil == 1 and self.cin % 32 == 0 and x.shape[3] == self.cin and xoff == 0)
@@ -284,145 +382,52 @@ class Conv:
         ho, wo = self.out_hw(h, w)
         if out is None:
             out = torch.empty(b, ho, wo, self.cout, dtype=torch.float32, device=x.device)
+        elif isinstance(out, S32):
+            out = out.t
         if tuple(out.shape[:3]) != (b, ho, wo):
             raise ValueError("conv output buffer %s does not match %s" % (tuple(out.shape), (b, ho, wo)))
-        if residual is not None and tuple(residual.shape[:3]) != (b, ho, wo):
-            raise ValueError("residual shape mismatch")
+        res_fmt = FMT_F32
+        if residual is not None:
+            if isinstance(residual, S32):
+                residual, res_fmt = residual.t, FMT_S32
+            if tuple(residual.shape[:3]) != (b, ho, wo):
+                raise ValueError("residual shape mismatch")
         bias = self.bias if bias is None else bias
         # small-M layers of the POSE networks (one crop's 20 x 20 maps: 4..16 output tiles walking K = 4608 alone on a 256-CU chip) take the split-K
-        # form whenever the library finds it worth it (ape_conv_gemm_splitk_workspace_bytes > 0: fewer than 96 tiles and >= 8 k-tiles) -- the
-        # batch-1 live loop of main.py:517-553; batches that fill the chip (the bench's 64 crops: 200+ tiles per layer) never do.  Opt-in per layer
-        # (`allow_splitk`, set by PoseNet / PoseRefineNet for their plans): the split changes the fp32 summation order, and the SEGMENTOR's class
-        # maps must stay bit-identical between a frame run alone and the same frame inside a batch (tests/test_gpu_bench_parity.py)
-        splitk = splitk or (SPLITK_SMALL_M and self.__dict__.get("allow_splitk", False))
-        # the parameter block and the kernel choice depend on shapes only: kept per call signature (the training tape calls every layer
-        # with the same shapes step after step; building the ctypes struct and asking the library twice cost ~15 us per call)
+        # form inside `low_latency()` -- the batch-1 live loop of main.py:517-553; batches that fill the chip (the bench's 64 crops: 200+ tiles per
+        # layer) never do.  Opt-in per layer (the `splitk` keyword of the constructor, passed by PoseNet / PoseRefineNet for their plans): the split
+        # changes the fp32 summation order, and the SEGMENTOR's class maps must stay bit-identical between a frame run alone and the same
+        # frame inside a batch (tests/test_gpu_bench_parity.py)
+        splitk = bool(splitk or (self.splitk and _POSE_STAGE.get()))
+        # the call signature: geometry and formats, then the module switches that take part in routing
         key = (b, h, w, ldx, xoff, out.shape[3], yoff, self.act if act is None else act, bias_bstride, 0 if residual is None else residual.shape[3], roff,
-               bool(upsample2x), splitk, USE_HALO_KERNEL, USE_GEMM_KERNEL)
-        plans = self.__dict__.get("_plans")
-        if plans is None:
-            plans = self.__dict__["_plans"] = {}
-        plan = plans.get(key)
-        if plan is None:
-            p = ConvParams(B=b, H=h, W=w, Cin=self.cin, ldx=ldx, xoff=xoff, Ho=ho, Wo=wo, Cout=self.cout,
-                           ldy=out.shape[3], yoff=yoff, KH=self.kh, KW=self.kw, stride=self.stride, pad=self.pad,
-                           dil=self.dil, act=self.act if act is None else act, alpha=self.alpha,
-                           bias_bstride=bias_bstride, ldr=0 if residual is None else residual.shape[3], roff=roff,
-                           ups=int(bool(upsample2x)))
-            # the halo kernel tiles the image in 16x16 pixels: use it only when those tiles are mostly full (crop feature maps of
-            # 20x20 / 40x40 would waste 30..60 % of the MFMAs; the flattened-M generic kernel has no such edge effect)
-            halo = bool(self.nsplit and USE_HALO_KERNEL and (upsample2x or (h * w) >= 0.8 * (-(-h // 16) * -(-w // 16) * 256))
-                        and _lib.lib().ape_conv3x3_halo_supported(ctypes.byref(p)))
-            gemm = bool(not halo and self.nsplit and USE_GEMM_KERNEL and _lib.lib().ape_conv_gemm_supported(ctypes.byref(p)))
-            sk_bytes = int(_lib.lib().ape_conv_gemm_splitk_workspace_bytes(ctypes.byref(p))) if (gemm and splitk) else 0
-            if len(plans) > 64:
-                plans.clear()
-            plan = plans[key] = (p, halo, gemm, sk_bytes)
-        p, halo, gemm, sk_bytes = plan
+               bool(upsample2x), splitk, in_fmt, out_fmt, USE_HALO_KERNEL, USE_GEMM_KERNEL, GEMM_VARIANT, USE_MX6, MX6_CIN)
+        plan = self._plans.get(key) or self._make_plan(key)
+        p, pref, args, fn, sk_bytes, label, shape, flop, nbytes = plan
         if p.alpha != self.alpha:
             p.alpha = self.alpha
-        if out_fmt == FMT_S32 and not gemm:
-            raise ValueError("an S32 output from an fp32 input exists only on the conv_gemm kernel (Cin % 32 == 0, not a halo layer)")
-        e0 = None
-        if PROFILE is not None:
-            label = ("conv3x3_halo_kernel<%d,%d,%d,%s,false>" % (self.nsplit, self.dil, 64 if self.cout <= 64 else 128, "true" if upsample2x else "false")
-                     if halo else self._gemm_variant(b * ho * wo) if gemm else self._generic_variant(b * ho * wo))
-            e0 = _prof_begin(label)
-        if halo:
-            rc = _lib.lib().ape_conv3x3_halo_bf16(_lib.dptr(x, torch.float32), _lib.dptr(self.wp), _lib.dptr(bias),
-                                                  _lib.dptr(residual), _lib.dptr(out, torch.float32), ctypes.byref(p),
-                                                  self.nsplit, _st())
-            _lib.check(rc, "ape_conv3x3_halo_bf16")
-        elif gemm and sk_bytes and out_fmt == FMT_F32:
-            # the training tape's batch-1 layers (autograd.ConvFn): k-tiles dealt to several workgroups per output tile
+        if args == _ARGS_MX:
+            xq = torch.empty_like(x)
+            _lib.call.ape_s32_to_f16m6(_lib.dptr(x, torch.float32), _lib.dptr(xq, torch.float32), b * h * w, ldx, _st())
+            x = xq
+        e0 = None if PROFILE is None else PROFILE.begin(label)
+        xp, bp, rp, yp = _lib.dptr(x, torch.float32), _lib.dptr(bias), _lib.dptr(residual), _lib.dptr(out, torch.float32)
+        if args == _ARGS_GEMM:
+            fn(xp, _lib.dptr(self.wp), bp, rp, yp, out_fmt, pref, self.nsplit, GEMM_VARIANT, _st())
+        elif args == _ARGS_BF16:
+            fn(xp, _lib.dptr(self.wp), bp, rp, yp, pref, self.nsplit, _st())
+        elif args == _ARGS_S32:
+            fn(xp, _lib.dptr(self.s32k()), bp, rp, res_fmt, yp, out_fmt, pref, _st())
+        elif args == _ARGS_SPLITK:
             ws = torch.empty(sk_bytes, dtype=torch.uint8, device=x.device)
-            rc = _lib.lib().ape_conv_gemm_bf16_splitk(_lib.dptr(x, torch.float32), _lib.dptr(self.wp), _lib.dptr(bias), _lib.dptr(residual),
-                                                      _lib.dptr(out, torch.float32), ctypes.byref(p), self.nsplit, _lib.dptr(ws), ws.numel(), _st())
-            _lib.check(rc, "ape_conv_gemm_bf16_splitk")
-        elif gemm:
-            rc = _lib.lib().ape_conv_gemm_bf16_fmt(_lib.dptr(x, torch.float32), _lib.dptr(self.wp), _lib.dptr(bias),
-                                                   _lib.dptr(residual), _lib.dptr(out, torch.float32), out_fmt, ctypes.byref(p),
-                                                   self.nsplit, GEMM_VARIANT, _st())
-            _lib.check(rc, "ape_conv_gemm_bf16_fmt")
-        elif self.nsplit:
-            rc = _lib.lib().ape_conv2d_nhwc_bf16(_lib.dptr(x, torch.float32), _lib.dptr(self.wp), _lib.dptr(bias),
-                                                 _lib.dptr(residual), _lib.dptr(out, torch.float32), ctypes.byref(p),
-                                                 self.nsplit, _st())
-            _lib.check(rc, "ape_conv2d_nhwc_bf16")
+            fn(xp, _lib.dptr(self.wp), bp, rp, yp, pref, self.nsplit, _lib.dptr(ws), sk_bytes, _st())
+        elif args == _ARGS_MX:
+            fn(xp, _lib.dptr(self.mx6k()), bp, rp, res_fmt, yp, out_fmt, pref, _st())
         else:
-            rc = _lib.lib().ape_conv2d_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(self.w), _lib.dptr(bias),
-                                                _lib.dptr(residual), _lib.dptr(out, torch.float32), ctypes.byref(p), _st())
-            _lib.check(rc, "ape_conv2d_nhwc_f32")
+            fn(xp, _lib.dptr(self.w), bp, rp, yp, pref, _st())
         if e0 is not None:
-            hin, win = (h // 2, w // 2) if upsample2x else (h, w)
-            _prof_end(e0, label, "%dx%dx%d %d->%d k%d s%d d%d%s" % (b, ho, wo, self.cin_real, self.cout, self.kh, self.stride, self.dil, " ups" if upsample2x else ""),
-                      *_conv_cost(self, b, hin, win, ho, wo, residual is not None))
+            _prof_end(e0, label, shape, flop, nbytes)
         return S32(out) if out_fmt == FMT_S32 else out
-
-
-# 3x3 layers on S32 inputs with these input channel counts take the half-pass kernel (fp16 main product + block-scaled e2m3 cross terms,
-# conv3x3_halo_mx.hip) instead of halo_s32's three bf16 products.  Off unless asked for: not bit-identical to bf16x3 (DESIGN.md 6e).
-USE_MX6 = os.environ.get("APE_USE_MX6", "0") != "0"
-MX6_CIN = tuple(int(v) for v in os.environ.get("APE_MX6_CIN", "512").split(","))
-
-
-def _conv_call_s32(self, x, out, xoff, yoff, residual, roff, bias, bias_bstride, act, out_fmt):
-    if self.nsplit != 3:
-        raise ValueError("S32 operands exist only in the split-bf16 ('bf16x3') precision")
-    if not isinstance(x, S32):
-        raise ValueError("S32 output / residual needs an S32 input on this path")
-    xt = x.t
-    b, h, w, ldx = xt.shape
-    ho, wo = self.out_hw(h, w)
-    if out is None:
-        out = torch.empty(b, ho, wo, self.cout, dtype=torch.float32, device=xt.device)
-    out_t = out.t if isinstance(out, S32) else out
-    if tuple(out_t.shape[:3]) != (b, ho, wo):
-        raise ValueError("conv output buffer %s does not match %s" % (tuple(out_t.shape), (b, ho, wo)))
-    res_t, res_fmt = None, FMT_F32
-    if residual is not None:
-        res_t, res_fmt = (residual.t, FMT_S32) if isinstance(residual, S32) else (residual, FMT_F32)
-        if tuple(res_t.shape[:3]) != (b, ho, wo):
-            raise ValueError("residual shape mismatch")
-    bias = self.bias if bias is None else bias
-    p = ConvParams(B=b, H=h, W=w, Cin=self.cin, ldx=ldx, xoff=xoff, Ho=ho, Wo=wo, Cout=self.cout, ldy=out_t.shape[3], yoff=yoff,
-                   KH=self.kh, KW=self.kw, stride=self.stride, pad=self.pad, dil=self.dil, act=self.act if act is None else act,
-                   alpha=self.alpha, bias_bstride=bias_bstride, ldr=0 if res_t is None else res_t.shape[3], roff=roff, ups=0)
-    is3 = self.kh == 3
-    if is3 and USE_MX6 and self.cin in MX6_CIN and self.cout >= 128 and self.stride == 1 and xoff == 0 and ldx == self.cin \
-            and _lib.lib().ape_conv3x3_halo_mx_supported(ctypes.byref(p)):
-        # half the matrix passes (conv3x3_halo_mx.hip): the S32 input is re-expressed once as F16M6 lines
-        xq = torch.empty_like(xt)
-        _lib.check(_lib.lib().ape_s32_to_f16m6(_lib.dptr(xt, torch.float32), _lib.dptr(xq, torch.float32), b * h * w, ldx, _st()), "ape_s32_to_f16m6")
-        label = "halo_mx_kernel<%d>" % self.dil
-        e0 = _prof_begin(label)
-        rc = _lib.lib().ape_conv3x3_halo_mx(_lib.dptr(xq, torch.float32), _lib.dptr(self.mx6k()), _lib.dptr(bias), _lib.dptr(res_t), res_fmt,
-                                            _lib.dptr(out_t, torch.float32), out_fmt, ctypes.byref(p), _st())
-        _lib.check(rc, "ape_conv3x3_halo_mx")
-        if e0 is not None:
-            _prof_end(e0, label, "%dx%dx%d %d->%d k%d s%d d%d" % (b, ho, wo, self.cin_real, self.cout, self.kh, self.stride, self.dil),
-                      *_conv_cost(self, b, h, w, ho, wo, residual is not None))
-        return S32(out_t) if out_fmt == FMT_S32 else out_t
-    if is3:
-        if not _lib.lib().ape_conv3x3_halo_s32_supported(ctypes.byref(p)):
-            raise ValueError("no S32 kernel for this layer geometry (3x3, stride %d, dil %d, Cin %d, Cout %d)" % (self.stride, self.dil, self.cin, self.cout))
-        label = "halo_s32_kernel<%d, true>" % self.dil          # (the kernel's name in a rocprofv3 trace: <dilation, ping-pong schedule>)
-    else:
-        if not _lib.lib().ape_conv_gemm_s32_supported(ctypes.byref(p)):
-            raise ValueError("no S32 kernel for this layer geometry (%dx%d, stride %d, Cin %d, Cout %d)" % (self.kh, self.kw, self.stride, self.cin, self.cout))
-        label = ("gemm_s32_res_kernel<%d, false>" if res_t is not None else "gemm_s32_kernel<%d, false>") % (128 if self.cout <= 128 else 192 if (-(-self.cout // 192) * 192 - self.cout) < (-(-self.cout // 256) * 256 - self.cout) else 256)
-    e0 = _prof_begin(label)
-    fn = _lib.lib().ape_conv3x3_halo_s32 if is3 else _lib.lib().ape_conv_gemm_s32
-    rc = fn(_lib.dptr(xt, torch.float32), _lib.dptr(self.s32k()), _lib.dptr(bias), _lib.dptr(res_t), res_fmt,
-            _lib.dptr(out_t, torch.float32), out_fmt, ctypes.byref(p), _st())
-    _lib.check(rc, "ape_conv3x3_halo_s32" if is3 else "ape_conv_gemm_s32")
-    if e0 is not None:
-        _prof_end(e0, label, "%dx%dx%d %d->%d k%d s%d d%d" % (b, ho, wo, self.cin_real, self.cout, self.kh, self.stride, self.dil),
-                  *_conv_cost(self, b, h, w, ho, wo, residual is not None))
-    return S32(out_t) if out_fmt == FMT_S32 else out_t
-
-
-Conv._call_s32 = _conv_call_s32
 
 
 def conv_seg_head(conv, x, head_w, head_b, double_softmax=True, upsample2x=False):
@@ -434,23 +439,21 @@ def conv_seg_head(conv, x, head_w, head_b, double_softmax=True, upsample2x=False
     c = head_w.shape[0]
     fusable = (conv.nsplit and USE_HALO_KERNEL and conv.cout == 64 and conv.kh == 3 and conv.kw == 3 and conv.stride == 1
                and conv.pad == 1 and conv.dil == 1 and conv.cin % 32 == 0 and ldx == conv.cin and c <= 16
-               and (upsample2x or (h * w) >= 0.8 * (-(-h // 16) * -(-w // 16) * 256)))
+               and (upsample2x or tiles16_mostly_full(h, w)))
     if not fusable:
         return seg_head(conv(x, upsample2x=upsample2x), head_w, head_b, double_softmax)
-    p = ConvParams(B=b, H=h, W=w, Cin=conv.cin, ldx=ldx, xoff=0, Ho=h, Wo=w, Cout=conv.cout, ldy=conv.cout, yoff=0, KH=3, KW=3,
-                   stride=1, pad=1, dil=1, act=conv.act, alpha=conv.alpha, bias_bstride=0, ldr=0, roff=0, ups=int(bool(upsample2x)))
+    p = conv_params(conv, b, h, w, ldx, conv.cout, ups=upsample2x)
     label = torch.empty(b, h, w, dtype=torch.uint8, device=x.device)
     score = torch.empty(b, h, w, dtype=torch.float32, device=x.device)
-    hlabel = "conv3x3_halo_kernel<%d,1,64,%s,true>" % (conv.nsplit, "true" if upsample2x else "false")
+    hlabel = halo_label(conv.nsplit, conv.dil, conv.cout, upsample2x, head=True)
     e0 = _prof_begin(hlabel)
-    rc = _lib.lib().ape_conv3x3_halo_seghead_bf16(_lib.dptr(x, torch.float32), _lib.dptr(conv.wp), _lib.dptr(conv.bias), ctypes.byref(p),
-                                                  conv.nsplit, _lib.dptr(head_w, torch.float32), _lib.dptr(head_b), c, _lib.dptr(label),
-                                                  _lib.dptr(score), int(bool(double_softmax)), _st())
-    _lib.check(rc, "ape_conv3x3_halo_seghead_bf16")
+    _lib.call.ape_conv3x3_halo_seghead_bf16(_lib.dptr(x, torch.float32), _lib.dptr(conv.wp), _lib.dptr(conv.bias), ctypes.byref(p),
+                                            conv.nsplit, _lib.dptr(head_w, torch.float32), _lib.dptr(head_b), c, _lib.dptr(label),
+                                            _lib.dptr(score), int(bool(double_softmax)), _st())
     if e0 is not None:
         hin, win = (h // 2, w // 2) if upsample2x else (h, w)
         # the 64-channel activation is never written: out = label (1 B) + score (4 B) per pixel
-        _prof_end(e0, hlabel, "%dx%dx%d %d->%d k3 s1 d1%s +head" % (b, h, w, conv.cin_real, conv.cout, " ups" if upsample2x else ""),
+        _prof_end(e0, hlabel, conv_shape(conv, b, h, w, upsample2x) + " +head",
                   2.0 * b * h * w * conv.cout * 9 * conv.cin_real,
                   4.0 * (b * hin * win * conv.cin_real + conv.cout * 9 * conv.cin_real) + 5.0 * b * h * w)
     return label, score
@@ -499,10 +502,9 @@ def unet_conv3x3(conv, a, b=None, ups=True, out=None, yoff=0):
     nc = 4 if conv.cout >= 64 else 2 if conv.cout in (32, 48) else 1
     label = "unet_conv3x3_kernel<%d,%s,%d,%d,false>" % (conv.nsplit, "true" if ups else "false", nc, 4 if nc == 4 else 8)
     e0 = _prof_begin(label)
-    rc = _lib.lib().ape_unet_conv3x3_bf16(_lib.dptr(a, torch.float32), a.shape[3], c1, _lib.dptr(b, torch.float32), ldb, c2,
-                                          _lib.dptr(conv.wp), _lib.dptr(conv.bias), _lib.dptr(out, torch.float32), out.shape[3], yoff,
-                                          bb, h, w, conv.cout, int(bool(ups)), conv.nsplit, _st())
-    _lib.check(rc, "ape_unet_conv3x3_bf16")
+    _lib.call.ape_unet_conv3x3_bf16(_lib.dptr(a, torch.float32), a.shape[3], c1, _lib.dptr(b, torch.float32), ldb, c2,
+                                    _lib.dptr(conv.wp), _lib.dptr(conv.bias), _lib.dptr(out, torch.float32), out.shape[3], yoff,
+                                    bb, h, w, conv.cout, int(bool(ups)), conv.nsplit, _st())
     if e0 is not None:
         m = bb * h * w
         lo = (bb * a.shape[1] * a.shape[2] * c1 + m * c2)
@@ -521,10 +523,9 @@ def unet_conv3x3_seghead(conv, a, b=None, ups=False, double_softmax=True):
     score = torch.empty(bb, h, w, dtype=torch.float32, device=a.device)
     klabel = "unet_conv3x3_kernel<%d,%s,1,8,true>" % (conv.nsplit, "true" if ups else "false")
     e0 = _prof_begin(klabel)
-    rc = _lib.lib().ape_unet_conv3x3_seghead_bf16(_lib.dptr(a, torch.float32), a.shape[3], c1, _lib.dptr(b, torch.float32),
-                                                  ldb, c2, _lib.dptr(conv.wp), _lib.dptr(conv.bias), conv.cout, _lib.dptr(label), _lib.dptr(score),
-                                                  bb, h, w, int(bool(ups)), conv.nsplit, int(bool(double_softmax)), _st())
-    _lib.check(rc, "ape_unet_conv3x3_seghead_bf16")
+    _lib.call.ape_unet_conv3x3_seghead_bf16(_lib.dptr(a, torch.float32), a.shape[3], c1, _lib.dptr(b, torch.float32),
+                                            ldb, c2, _lib.dptr(conv.wp), _lib.dptr(conv.bias), conv.cout, _lib.dptr(label), _lib.dptr(score),
+                                            bb, h, w, int(bool(ups)), conv.nsplit, int(bool(double_softmax)), _st())
     if e0 is not None:
         m = bb * h * w
         _prof_end(e0, klabel, "%dx%dx%d %d+%d->%d%s +head" % (bb, h, w, c1, c2, conv.cout, " ups" if ups else ""),
@@ -541,8 +542,7 @@ def nearest_up2(x, out=None, yoff=0, scale=2):
         out = torch.empty(b, scale * h, scale * w, c, dtype=torch.float32, device=x.device)
     if tuple(out.shape[:3]) != (b, scale * h, scale * w):
         raise ValueError("nearest_up2 output buffer mismatch")
-    rc = _lib.lib().ape_nearest_upsample_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(out, torch.float32), b, h, w, c, scale, out.shape[3], yoff, _st())
-    _lib.check(rc, "ape_nearest_upsample_nhwc_f32")
+    _lib.call.ape_nearest_upsample_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(out, torch.float32), b, h, w, c, scale, out.shape[3], yoff, _st())
     return out
 
 
@@ -591,9 +591,8 @@ def stem_pool(conv, x):
         n, h, w, _ = x.shape
         ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
         y = torch.empty(n, (ho - 1) // 2 + 1, (wo - 1) // 2 + 1, 64, dtype=torch.float32, device=x.device)
-        rc = _lib.lib().ape_stem_conv_pool_u8(_lib.dptr(x.rgb, torch.uint8), x.rgb.shape[0], _lib.dptr(x.rects, torch.int32), _lib.dptr(conv.w, torch.float32),
-                                              _lib.dptr(conv.bias), _lib.dptr(y), n, x.rgb.shape[1], x.rgb.shape[2], h, w, int(x.div255), conv.nsplit, _st())
-        _lib.check(rc, "ape_stem_conv_pool_u8")
+        _lib.call.ape_stem_conv_pool_u8(_lib.dptr(x.rgb, torch.uint8), x.rgb.shape[0], _lib.dptr(x.rects, torch.int32), _lib.dptr(conv.w, torch.float32),
+                                        _lib.dptr(conv.bias), _lib.dptr(y), n, x.rgb.shape[1], x.rgb.shape[2], h, w, int(x.div255), conv.nsplit, _st())
         return y
     b, h, w, ldx = x.shape
     fusable = (USE_FUSED_STEM and conv.nsplit and conv.cout == 64 and conv.cin == 4 and ldx == 4 and conv.kh == 7 and conv.kw == 7
@@ -602,25 +601,22 @@ def stem_pool(conv, x):
         return maxpool3x3s2(conv(x))
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     y = torch.empty(b, (ho - 1) // 2 + 1, (wo - 1) // 2 + 1, 64, dtype=torch.float32, device=x.device)
-    rc = _lib.lib().ape_stem_conv_pool_bf16(_lib.dptr(x, torch.float32), _lib.dptr(conv.w, torch.float32), _lib.dptr(conv.bias),
-                                            _lib.dptr(y), b, h, w, conv.nsplit, _st())
-    _lib.check(rc, "ape_stem_conv_pool_bf16")
+    _lib.call.ape_stem_conv_pool_bf16(_lib.dptr(x, torch.float32), _lib.dptr(conv.w, torch.float32), _lib.dptr(conv.bias),
+                                      _lib.dptr(y), b, h, w, conv.nsplit, _st())
     return y
 
 
 def maxpool3x3s2(x):
     b, h, w, c = x.shape
     y = torch.empty(b, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().ape_maxpool3x3s2_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), b, h, w, c, _st()),
-               "ape_maxpool3x3s2_nhwc_f32")
+    _lib.call.ape_maxpool3x3s2_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), b, h, w, c, _st())
     return y
 
 
 def adaptive_avgpool(x, s):
     b, h, w, c = x.shape
     y = torch.empty(b, s, s, c, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().ape_adaptive_avgpool_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), b, h, w, c, s, _st()),
-               "ape_adaptive_avgpool_nhwc_f32")
+    _lib.call.ape_adaptive_avgpool_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), b, h, w, c, s, _st())
     return y
 
 
@@ -636,13 +632,15 @@ def adaptive_avgpool_multi(x, sizes, channels=None):
     ws = _workspace(_lib.lib().ape_adaptive_avgpool_multi_workspace_bytes(b, c), xt.device)
     ptrs = (ctypes.c_void_p * len(sizes))(*[y.data_ptr() for y in ys])
     szs = (ctypes.c_int * len(sizes))(*sizes)
-    rc = _lib.lib().ape_adaptive_avgpool_multi_nhwc_ld(_lib.dptr(xt, torch.float32), fmt, ptrs, szs, len(sizes), b, h, w, c, ld, _lib.dptr(ws),
-                                                       ws.numel() * ws.element_size(), _st())
-    if rc == -1:      # APE_EINVAL: too many atoms for this geometry
-        xf = x.to_f32() if fmt == FMT_S32 else x
+    try:
+        _lib.call.ape_adaptive_avgpool_multi_nhwc_ld(_lib.dptr(xt, torch.float32), fmt, ptrs, szs, len(sizes), b, h, w, c, ld, _lib.dptr(ws),
+                                                     ws.numel() * ws.element_size(), _st())
+    except _lib.ApeError as e:
+        if e.code != -1:
+            raise
+        xf = x.to_f32() if fmt == FMT_S32 else x      # APE_EINVAL: too many atoms for this geometry
         xf = xf if c == ld else xf[..., :c].contiguous()
         return {s: adaptive_avgpool(xf, s) for s in sizes}
-    _lib.check(rc, "ape_adaptive_avgpool_multi_nhwc_ld")
     return dict(zip(sizes, ys))
 
 
@@ -658,15 +656,12 @@ def conv1x1_multi(convs, xs):
               and x.shape[3] == c.cin and x.is_contiguous() for c, x in zip(convs, xs)))
     if ok:
         outs = [torch.empty(x.shape[0], x.shape[1], x.shape[2], c.cout, dtype=torch.float32, device=x.device) for c, x in zip(convs, xs)]
-        ps = (ConvParams * n)(*[ConvParams(B=x.shape[0], H=x.shape[1], W=x.shape[2], Cin=c.cin, ldx=x.shape[3], xoff=0, Ho=x.shape[1], Wo=x.shape[2],
-                                           Cout=c.cout, ldy=c.cout, yoff=0, KH=1, KW=1, stride=1, pad=0, dil=1, act=c.act, alpha=c.alpha, bias_bstride=0,
-                                           ldr=0, roff=0, ups=0) for c, x in zip(convs, xs)])
+        ps = (ConvParams * n)(*[conv_params(c, x.shape[0], x.shape[1], x.shape[2], x.shape[3], c.cout) for c, x in zip(convs, xs)])
         ok = all(_lib.lib().ape_conv_gemm_supported(ctypes.byref(ps[i])) for i in range(n))
     if not ok:
         return [c(x) for c, x in zip(convs, xs)]
     arr = lambda ts: (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in ts])  # noqa: E731
-    rc = _lib.lib().ape_conv_gemm_bf16_multi(n, arr(xs), arr([c.wp for c in convs]), arr([c.bias for c in convs]), arr(outs), ps, convs[0].nsplit, _st())
-    _lib.check(rc, "ape_conv_gemm_bf16_multi")
+    _lib.call.ape_conv_gemm_bf16_multi(n, arr(xs), arr([c.wp for c in convs]), arr([c.bias for c in convs]), arr(outs), ps, convs[0].nsplit, _st())
     return outs
 
 
@@ -676,9 +671,8 @@ def bilinear(x, ho, wo, align_corners, out=None, yoff=0, accumulate=False):
         out = torch.empty(b, ho, wo, c, dtype=torch.float32, device=x.device)
     if tuple(out.shape[:3]) != (b, ho, wo):
         raise ValueError("bilinear output buffer mismatch")
-    rc = _lib.lib().ape_bilinear_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(out, torch.float32), b, h, w, c, c, ho, wo,
-                                          out.shape[3], yoff, int(bool(align_corners)), int(bool(accumulate)), _st())
-    _lib.check(rc, "ape_bilinear_nhwc_f32")
+    _lib.call.ape_bilinear_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(out, torch.float32), b, h, w, c, c, ho, wo,
+                                    out.shape[3], yoff, int(bool(align_corners)), int(bool(accumulate)), _st())
     return out
 
 
@@ -686,8 +680,7 @@ def psp_prior_sum(zs, h, w):
     """zs = [z1[B,1,1,C], z2[B,2,2,C], z3[B,3,3,C], z6[B,6,6,C]] -> sum of their bilinear (align_corners=False) resizes [B,h,w,C]"""
     b, c = zs[0].shape[0], zs[0].shape[3]
     out = torch.empty(b, h, w, c, dtype=torch.float32, device=zs[0].device)
-    rc = _lib.lib().ape_psp_prior_sum_f32(*[_lib.dptr(z, torch.float32) for z in zs], _lib.dptr(out), b, h, w, c, _st())
-    _lib.check(rc, "ape_psp_prior_sum_f32")
+    _lib.call.ape_psp_prior_sum_f32(*[_lib.dptr(z, torch.float32) for z in zs], _lib.dptr(out), b, h, w, c, _st())
     return out
 
 
@@ -702,20 +695,19 @@ def psp_bottleneck_folded(conv, x576, zs, out_fmt=FMT_S32):
     feats columns (Cin -> C, bias, ReLU).  No [B,h,w,C] prior-sum tensor is written or read (include/ape_hip.h ape_psp_fold_operands)."""
     xt = x576.t
     b, h, w, ld = xt.shape
-    if conv.nsplit != 3 or conv.kh != 1 or ld != conv.cin + PSP_FOLD_K or [tuple(z.shape) for z in zs] != [(b, s, s, conv.cout) for s in (1, 2, 3, 6)]:
+    if conv.nsplit != 3 or (conv.kh, conv.kw, conv.stride, conv.pad) != (1, 1, 1, 0) or ld != conv.cin + PSP_FOLD_K or [tuple(z.shape) for z in zs] != [(b, s, s, conv.cout) for s in (1, 2, 3, 6)]:
         raise ValueError("psp_bottleneck_folded: a split-bf16 1x1 layer, an S32 map of Cin + 64 channels and the four prior maps [B,s,s,Cout]")
     groups = conv.cin // 32 + 2
     wimg = torch.empty(b, conv.cout, groups * 64, dtype=torch.bfloat16, device=xt.device)
-    _lib.check(_lib.lib().ape_psp_fold_operands(_lib.dptr(conv.s32k()), *[_lib.dptr(z, torch.float32) for z in zs], _lib.dptr(wimg),
-                                                _lib.dptr(xt, torch.float32), b, h, w, ld, conv.cin, conv.cout, _st()), "ape_psp_fold_operands")
+    _lib.call.ape_psp_fold_operands(_lib.dptr(conv.s32k()), *[_lib.dptr(z, torch.float32) for z in zs], _lib.dptr(wimg),
+                                    _lib.dptr(xt, torch.float32), b, h, w, ld, conv.cin, conv.cout, _st())
     out = torch.empty(b, h, w, conv.cout, dtype=torch.float32, device=xt.device)
-    p = ConvParams(B=b, H=h, W=w, Cin=ld, ldx=ld, xoff=0, Ho=h, Wo=w, Cout=conv.cout, ldy=conv.cout, yoff=0, KH=1, KW=1, stride=1, pad=0, dil=1,
-                   act=conv.act, alpha=conv.alpha, bias_bstride=0, ldr=0, roff=0, ups=0)
-    label = "gemm_s32_kernel<%d, false>" % (128 if conv.cout <= 128 else 192 if (-(-conv.cout // 192) * 192 - conv.cout) < (-(-conv.cout // 256) * 256 - conv.cout) else 256)
+    p = conv_params(conv, b, h, w, ld, conv.cout)
+    p.Cin = ld                  # the contraction runs over K = Cin + 64
+    label = gemm_s32_label(conv.cout)
     e0 = _prof_begin(label)
-    rc = _lib.lib().ape_conv_gemm_s32_per_image(_lib.dptr(xt, torch.float32), _lib.dptr(wimg), conv.cout * groups * 128, _lib.dptr(conv.bias),
-                                                _lib.dptr(out), out_fmt, ctypes.byref(p), _st())
-    _lib.check(rc, "ape_conv_gemm_s32_per_image")
+    _lib.call.ape_conv_gemm_s32_per_image(_lib.dptr(xt, torch.float32), _lib.dptr(wimg), conv.cout * groups * 128, _lib.dptr(conv.bias),
+                                          _lib.dptr(out), out_fmt, ctypes.byref(p), _st())
     if e0 is not None:      # algorithmic: the layer's own contraction (K = Cin) + the prior sum's 50 coefficient columns; bytes: f in, out, per-frame weights
         _prof_end(e0, label, "%dx%dx%d %d+%d->%d k1 s1 d1 psp-fold" % (b, h, w, conv.cin, PSP_FOLD_K, conv.cout), 2.0 * b * h * w * conv.cout * ld,
                   4.0 * (b * h * w * ld + b * conv.cout * ld + b * h * w * conv.cout))
@@ -730,11 +722,11 @@ class UpConv:
     layer on an S32 input (up_3), as the ONE kernel of upconv_fused.hip that keeps the 9*Cout-channel tensor on the chip (bit-identical
     to the two calls).  fma: both interpolation steps as chained fused multiply-adds instead of separately rounded products."""
 
-    def __init__(self, weight, bias, alpha, device="cuda", precision="f32", fma=False):
+    def __init__(self, weight, bias, alpha, device="cuda", precision="f32", fma=False, splitk=False):
         cout, cin, kh, kw = weight.shape
         assert (kh, kw) == (3, 3)
         w9 = weight.detach().permute(2, 3, 0, 1).reshape(9 * cout, cin)            # row = (ky*3+kx)*Cout + co
-        self.mix = Conv(w9, None, device=device, precision=precision)
+        self.mix = Conv(w9, None, device=device, precision=precision, splitk=splitk)
         self.bias = bias.detach().to(device=device, dtype=torch.float32).contiguous()
         self.alpha, self.cout, self.cin, self.fma = float(alpha), cout, cin, bool(fma)
 
@@ -749,9 +741,8 @@ class UpConv:
         strip = self.cout % 64 == 0 and _lib.lib().ape_upconv3x3_gather_strip_rows(-1) > 0      # the library's own routing rule
         glabel = "upconv_gather_%skernel<%s,%s>" % ("strip_" if strip else "", "true" if out_fmt == FMT_S32 else "false", "true" if self.fma else "false")
         e0 = _prof_begin(glabel)
-        rc = _lib.lib().ape_upconv3x3_gather_ex(_lib.dptr(z, torch.float32), _lib.dptr(self.bias), _lib.dptr(out), out_fmt, b, h, w,
-                                                self.cout, ACT_PRELU, self.alpha, int(self.fma), _st())
-        _lib.check(rc, "ape_upconv3x3_gather_ex")
+        _lib.call.ape_upconv3x3_gather_ex(_lib.dptr(z, torch.float32), _lib.dptr(self.bias), _lib.dptr(out), out_fmt, b, h, w,
+                                          self.cout, ACT_PRELU, self.alpha, int(self.fma), _st())
         if e0 is not None:      # HBM-bound: z read once (9 * Cout channels at low resolution) + the output written once
             _prof_end(e0, glabel, "%dx%dx%d C%d" % (b, 2 * h, 2 * w, self.cout), 0.0, 4.0 * (b * h * w * 9 * self.cout + b * 4 * h * w * self.cout))
         return S32(out) if out_fmt == FMT_S32 else out
@@ -769,9 +760,8 @@ class UpConv:
         out = torch.empty(b, 2 * h, 2 * w, self.cout, dtype=torch.float32, device=x.device)
         label = "upconv_fused_kernel<%d,false,%s>" % (self.cin // 32, "true" if self.fma else "false")
         e0 = _prof_begin(label)
-        rc = _lib.lib().ape_upconv3x3_fused_s32(_lib.dptr(x.t, torch.float32), _lib.dptr(self.mix.s32k()), _lib.dptr(self.bias), _lib.dptr(out),
-                                                out_fmt, b, h, w, self.cin, ACT_PRELU, self.alpha, int(self.fma), _st())
-        _lib.check(rc, "ape_upconv3x3_fused_s32")
+        _lib.call.ape_upconv3x3_fused_s32(_lib.dptr(x.t, torch.float32), _lib.dptr(self.mix.s32k()), _lib.dptr(self.bias), _lib.dptr(out),
+                                          out_fmt, b, h, w, self.cin, ACT_PRELU, self.alpha, int(self.fma), _st())
         if e0 is not None:
             _prof_end(e0, label, "%dx%dx%d %d->%d up (executed flop; direct form x4)" % (b, 2 * h, 2 * w, self.cin, self.cout), *self._fused_cost(b, h, w, 4.0 * self.cout))
         return S32(out) if out_fmt == FMT_S32 else out
@@ -797,10 +787,9 @@ class UpConv:
         score = torch.empty(b, 2 * h, 2 * w, dtype=torch.float32, device=x.device)
         klabel = "upconv_fused_kernel<%d,true,%s>" % (self.cin // 32, "true" if self.fma else "false")
         e0 = _prof_begin(klabel)
-        rc = _lib.lib().ape_upconv3x3_fused_seghead_s32(_lib.dptr(x.t, torch.float32), _lib.dptr(self.mix.s32k()), _lib.dptr(self.bias), b, h, w,
-                                                        self.cin, ACT_PRELU, self.alpha, int(self.fma), _lib.dptr(head_w, torch.float32),
-                                                        _lib.dptr(head_b), c, _lib.dptr(label), _lib.dptr(score), int(bool(double_softmax)), _st())
-        _lib.check(rc, "ape_upconv3x3_fused_seghead_s32")
+        _lib.call.ape_upconv3x3_fused_seghead_s32(_lib.dptr(x.t, torch.float32), _lib.dptr(self.mix.s32k()), _lib.dptr(self.bias), b, h, w,
+                                                  self.cin, ACT_PRELU, self.alpha, int(self.fma), _lib.dptr(head_w, torch.float32),
+                                                  _lib.dptr(head_b), c, _lib.dptr(label), _lib.dptr(score), int(bool(double_softmax)), _st())
         if e0 is not None:
             _prof_end(e0, klabel, "%dx%dx%d %d->%d up +head (executed flop; direct form x4)" % (b, 2 * h, 2 * w, self.cin, self.cout), *self._fused_cost(b, h, w, 5.0))
         return label, score
@@ -811,8 +800,7 @@ def gather_rows(x, index):
     b, r, c = x.shape
     n = index.shape[1]
     y = torch.empty(b, n, c, dtype=torch.float32, device=x.device)
-    rc = _lib.lib().ape_gather_rows_f32(_lib.dptr(x, torch.float32), _lib.dptr(index, torch.int64), _lib.dptr(y), b, r, n, c, _st())
-    _lib.check(rc, "ape_gather_rows_f32")
+    _lib.call.ape_gather_rows_f32(_lib.dptr(x, torch.float32), _lib.dptr(index, torch.int64), _lib.dptr(y), b, r, n, c, _st())
     return y
 
 
@@ -821,21 +809,17 @@ def ups_patch_gather(x, index):
     b, h, w, c = x.shape
     n = index.shape[1]
     out = torch.empty(b * n, 1, 1, 9 * c, dtype=torch.float32, device=x.device)
-    rc = _lib.lib().ape_ups_patch_gather_f32(_lib.dptr(x, torch.float32), _lib.dptr(index, torch.int64), _lib.dptr(out), b, h, w, c, n, _st())
-    _lib.check(rc, "ape_ups_patch_gather_f32")
+    _lib.call.ape_ups_patch_gather_f32(_lib.dptr(x, torch.float32), _lib.dptr(index, torch.int64), _lib.dptr(out), b, h, w, c, n, _st())
     return out
 
 
 def conv3x3_as_matrix(conv):
-    """A 3x3 Conv viewed as the 1x1 contraction over its 9*Cin patch columns: shares the (already [Cout][KH][KW][Cin]) weights."""
+    """A 3x3 Conv viewed as the 1x1 contraction over its 9*Cin patch columns: a layer of its own (plan cache, lazily packed S32K / MX6
+    operands) over the 3x3 layer's weight storage (already [Cout][KH][KW][Cin]), bf16 planes and bias."""
     assert conv.kh == 3 and conv.kw == 3 and conv.cin == conv.cin_real
-    m = object.__new__(Conv)
-    m.__dict__.update(conv.__dict__)
-    m.kh = m.kw = 1
-    m.cin = m.cin_real = 9 * conv.cin
-    m.stride, m.pad, m.dil = 1, 0, 1
-    if conv.nsplit == 0:
-        m.w = conv.w.view(conv.cout, 1, 1, 9 * conv.cin)
+    m = Conv.from_packed(conv.w.view(conv.cout, 1, 1, 9 * conv.cin), conv.wp if conv.nsplit else None, 9 * conv.cin, act=conv.act, alpha=conv.alpha,
+                         precision=conv.precision, splitk=conv.splitk)
+    m.bias = conv.bias
     return m
 
 
@@ -843,8 +827,7 @@ def log_softmax_rows(x):
     c = x.shape[-1]
     rows = x.numel() // c
     y = torch.empty_like(x)
-    _lib.check(_lib.lib().ape_log_softmax_rows_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), rows, c, _st()),
-               "ape_log_softmax_rows_f32")
+    _lib.call.ape_log_softmax_rows_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), rows, c, _st())
     return y
 
 
@@ -852,7 +835,7 @@ def mean_rows(x):
     """x[B,n,C] -> [B,C]"""
     b, n, c = x.shape
     y = torch.empty(b, c, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().ape_mean_rows_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), b, n, c, _st()), "ape_mean_rows_f32")
+    _lib.call.ape_mean_rows_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), b, n, c, _st())
     return y
 
 
@@ -860,17 +843,16 @@ def pad3to4(x):
     """x[...,3] -> [...,4]"""
     rows = x.numel() // 3
     y = torch.empty(*x.shape[:-1], 4, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().ape_pad3to4_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), rows, _st()), "ape_pad3to4_f32")
+    _lib.call.ape_pad3to4_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), rows, _st())
     return y
 
 
 def head_select(h, off_r, off_t, off_c, wr, br, wt, bt, wc, bc, obj, b, n, k):
     """h[B*n, ldh] -> out[B,n,8]"""
     out = torch.empty(b, n, 8, dtype=torch.float32, device=h.device)
-    rc = _lib.lib().ape_head_select_f32(_lib.dptr(h, torch.float32), h.shape[-1], off_r, off_t, off_c, _lib.dptr(wr),
-                                        _lib.dptr(br), _lib.dptr(wt), _lib.dptr(bt), _lib.dptr(wc), _lib.dptr(bc),
-                                        _lib.dptr(obj, torch.int64), _lib.dptr(out), b, n, k, _st())
-    _lib.check(rc, "ape_head_select_f32")
+    _lib.call.ape_head_select_f32(_lib.dptr(h, torch.float32), h.shape[-1], off_r, off_t, off_c, _lib.dptr(wr),
+                                  _lib.dptr(br), _lib.dptr(wt), _lib.dptr(bt), _lib.dptr(wc), _lib.dptr(bc),
+                                  _lib.dptr(obj, torch.int64), _lib.dptr(out), b, n, k, _st())
     return out
 
 
@@ -880,26 +862,23 @@ def pose_select(heads, points4, want_new_points=True):
     pose = torch.empty(b, 7, dtype=torch.float64, device=heads.device)
     which = torch.empty(b, dtype=torch.int32, device=heads.device)
     newp = torch.empty(b, n, 4, dtype=torch.float32, device=heads.device) if want_new_points else None
-    rc = _lib.lib().ape_pose_select_f32(_lib.dptr(heads, torch.float32), _lib.dptr(points4, torch.float32), _lib.dptr(pose),
-                                        _lib.dptr(which), _lib.dptr(newp), b, n, _st())
-    _lib.check(rc, "ape_pose_select_f32")
+    _lib.call.ape_pose_select_f32(_lib.dptr(heads, torch.float32), _lib.dptr(points4, torch.float32), _lib.dptr(pose),
+                                  _lib.dptr(which), _lib.dptr(newp), b, n, _st())
     return pose, which, newp
 
 
 def pose_compose(pose, ref_r, ref_t):
     """in-place: pose[B,7] f64 <- pose o (ref_r[B,>=4], ref_t[B,>=3]) ; ref_* are (possibly strided) row views"""
     b = pose.shape[0]
-    rc = _lib.lib().ape_pose_compose_f64(_lib.dptr(pose, torch.float64), ctypes.c_void_p(ref_r.data_ptr()), ref_r.stride(0),
-                                         ctypes.c_void_p(ref_t.data_ptr()), ref_t.stride(0), b, _st())
-    _lib.check(rc, "ape_pose_compose_f64")
+    _lib.call.ape_pose_compose_f64(_lib.dptr(pose, torch.float64), ctypes.c_void_p(ref_r.data_ptr()), ref_r.stride(0),
+                                   ctypes.c_void_p(ref_t.data_ptr()), ref_t.stride(0), b, _st())
     return pose
 
 
 def pose_recentre(points4, pose):
     b, n, _ = points4.shape
     out = torch.empty_like(points4)
-    rc = _lib.lib().ape_pose_recentre_f32(_lib.dptr(points4, torch.float32), _lib.dptr(pose, torch.float64), _lib.dptr(out), b, n, _st())
-    _lib.check(rc, "ape_pose_recentre_f32")
+    _lib.call.ape_pose_recentre_f32(_lib.dptr(points4, torch.float32), _lib.dptr(pose, torch.float64), _lib.dptr(out), b, n, _st())
     return out
 
 
@@ -909,9 +888,8 @@ def preprocess_u8(rgb, rects, hc, wc, div255):
     b, h, w, _ = rgb.shape
     n = rects.shape[0]
     out = torch.empty(n, hc, wc, 4, dtype=torch.float32, device=rgb.device)
-    rc = _lib.lib().ape_preprocess_u8_nhwc4(_lib.dptr(rgb, torch.uint8), _lib.dptr(rects, torch.int32), _lib.dptr(out), n, h, w,
-                                            hc, wc, int(bool(div255)), _st())
-    _lib.check(rc, "ape_preprocess_u8_nhwc4")
+    _lib.call.ape_preprocess_u8_nhwc4(_lib.dptr(rgb, torch.uint8), _lib.dptr(rects, torch.int32), _lib.dptr(out), n, h, w,
+                                      hc, wc, int(bool(div255)), _st())
     return out
 
 
@@ -920,9 +898,8 @@ def seg_argmax(logits, n_classes, double_softmax=True):
     b, h, w, ld = logits.shape
     label = torch.empty(b, h, w, dtype=torch.uint8, device=logits.device)
     score = torch.empty(b, h, w, dtype=torch.float32, device=logits.device)
-    rc = _lib.lib().ape_seg_argmax_f32(_lib.dptr(logits, torch.float32), ld, n_classes, _lib.dptr(label), _lib.dptr(score),
-                                       b * h * w, int(bool(double_softmax)), _st())
-    _lib.check(rc, "ape_seg_argmax_f32")
+    _lib.call.ape_seg_argmax_f32(_lib.dptr(logits, torch.float32), ld, n_classes, _lib.dptr(label), _lib.dptr(score),
+                                 b * h * w, int(bool(double_softmax)), _st())
     return label, score
 
 
@@ -933,9 +910,8 @@ def seg_head(feat, w, bias, double_softmax=True):
         raise ValueError("seg_head expects the 64-channel up_3 activation")
     label = torch.empty(b, h, wd, dtype=torch.uint8, device=feat.device)
     score = torch.empty(b, h, wd, dtype=torch.float32, device=feat.device)
-    rc = _lib.lib().ape_seg_head_f32(_lib.dptr(feat, torch.float32), _lib.dptr(w, torch.float32), _lib.dptr(bias), w.shape[0],
-                                     _lib.dptr(label), _lib.dptr(score), b * h * wd, int(bool(double_softmax)), _st())
-    _lib.check(rc, "ape_seg_head_f32")
+    _lib.call.ape_seg_head_f32(_lib.dptr(feat, torch.float32), _lib.dptr(w, torch.float32), _lib.dptr(bias), w.shape[0],
+                               _lib.dptr(label), _lib.dptr(score), b * h * wd, int(bool(double_softmax)), _st())
     return label, score
 
 
@@ -965,10 +941,9 @@ def seg_components(label, score, n_classes, min_pixels=100, score_mode=SEG_SCORE
     det = torch.empty(b, n_classes, 5, dtype=torch.int32, device=label.device)
     nbytes = _lib.lib().ape_seg_components_workspace_bytes(b, h, w, n_classes)
     ws = _workspace(nbytes, label.device)
-    rc = _lib.lib().ape_seg_components_scored(_lib.dptr(label, torch.uint8), _lib.dptr(score, torch.float32), _lib.dptr(objmap),
-                                              _lib.dptr(det), b, h, w, n_classes, min_pixels, score_mode, _lib.dptr(ws),
-                                              ws.numel(), _st())
-    _lib.check(rc, "ape_seg_components_scored")
+    _lib.call.ape_seg_components_scored(_lib.dptr(label, torch.uint8), _lib.dptr(score, torch.float32), _lib.dptr(objmap),
+                                        _lib.dptr(det), b, h, w, n_classes, min_pixels, score_mode, _lib.dptr(ws),
+                                        ws.numel(), _st())
     return objmap, det
 
 
@@ -981,12 +956,11 @@ def bgsub_features(f_rgb, b_rgb, f_depth, b_depth, gate, mean, std, want_diff=Fa
     diff = torch.empty(b, h, w, 7, dtype=torch.uint8, device=f_rgb.device) if want_diff else None
     m = (ctypes.c_float * 7)(*[float(v) for v in mean])
     s = (ctypes.c_float * 7)(*[float(v) for v in std])
-    rc = _lib.lib().ape_bgsub_features_f32(_lib.dptr(f_rgb, torch.uint8), _lib.dptr(b_rgb, torch.uint8),
-                                           _lib.dptr(f_depth, torch.uint16), _lib.dptr(b_depth, torch.uint16),
-                                           _lib.dptr(gate, torch.float64), ctypes.cast(m, ctypes.c_void_p),
-                                           ctypes.cast(s, ctypes.c_void_p), _lib.dptr(out),
-                                           _lib.dptr(diff) if want_diff else None, b, h, w, _st())
-    _lib.check(rc, "ape_bgsub_features_f32")
+    _lib.call.ape_bgsub_features_f32(_lib.dptr(f_rgb, torch.uint8), _lib.dptr(b_rgb, torch.uint8),
+                                     _lib.dptr(f_depth, torch.uint16), _lib.dptr(b_depth, torch.uint16),
+                                     _lib.dptr(gate, torch.float64), ctypes.cast(m, ctypes.c_void_p),
+                                     ctypes.cast(s, ctypes.c_void_p), _lib.dptr(out),
+                                     _lib.dptr(diff) if want_diff else None, b, h, w, _st())
     return (out, diff) if want_diff else out
 
 
@@ -1000,14 +974,13 @@ def choose_points(objmap, depth, objects, n_points, seed=0):
     stride = h * w
     cand = torch.empty(n, stride, dtype=torch.int32, device=objmap.device)
     if isinstance(seed, torch.Tensor):
-        rc = _lib.lib().ape_choose_points_dseed(_lib.dptr(objmap, torch.uint8), _lib.dptr(depth, torch.uint16), _lib.dptr(objects, torch.int32),
-                                                n, h, w, n_points, _lib.dptr(seed, torch.int32), _lib.dptr(cand), stride, _lib.dptr(choose),
-                                                _lib.dptr(n_cand), _st())
-    else:
-        rc = _lib.lib().ape_choose_points(_lib.dptr(objmap, torch.uint8), _lib.dptr(depth, torch.uint16), _lib.dptr(objects, torch.int32),
-                                          n, h, w, n_points, seed & 0xFFFFFFFF, _lib.dptr(cand), stride, _lib.dptr(choose),
+        _lib.call.ape_choose_points_dseed(_lib.dptr(objmap, torch.uint8), _lib.dptr(depth, torch.uint16), _lib.dptr(objects, torch.int32),
+                                          n, h, w, n_points, _lib.dptr(seed, torch.int32), _lib.dptr(cand), stride, _lib.dptr(choose),
                                           _lib.dptr(n_cand), _st())
-    _lib.check(rc, "ape_choose_points")
+    else:
+        _lib.call.ape_choose_points(_lib.dptr(objmap, torch.uint8), _lib.dptr(depth, torch.uint16), _lib.dptr(objects, torch.int32),
+                                    n, h, w, n_points, seed & 0xFFFFFFFF, _lib.dptr(cand), stride, _lib.dptr(choose),
+                                    _lib.dptr(n_cand), _st())
     return choose, n_cand
 
 
@@ -1015,10 +988,9 @@ def backproject(depth, objects, choose, intr, depth_scale):
     b, h, w = depth.shape
     n, npts = choose.shape
     pts = torch.empty(n, npts, 4, dtype=torch.float32, device=depth.device)
-    rc = _lib.lib().ape_backproject_f32(_lib.dptr(depth, torch.uint16), _lib.dptr(objects, torch.int32), _lib.dptr(choose, torch.int64),
-                                        _lib.dptr(pts), n, h, w, npts, float(intr["fx"]), float(intr["fy"]), float(intr["ppx"]),
-                                        float(intr["ppy"]), float(depth_scale), _st())
-    _lib.check(rc, "ape_backproject_f32")
+    _lib.call.ape_backproject_f32(_lib.dptr(depth, torch.uint16), _lib.dptr(objects, torch.int32), _lib.dptr(choose, torch.int64),
+                                  _lib.dptr(pts), n, h, w, npts, float(intr["fx"]), float(intr["fy"]), float(intr["ppx"]),
+                                  float(intr["ppy"]), float(depth_scale), _st())
     return pts
 
 
@@ -1030,10 +1002,9 @@ def adds_dis(pred_r, pred_t, points, model, target, symmetric, want_pred=False, 
     dis = torch.empty(n, dtype=torch.float32, device=dev)
     std = torch.empty(n, dtype=torch.float32, device=dev) if want_std else None
     pred = torch.empty(n, m, 3, dtype=torch.float32, device=dev) if want_pred else None
-    rc = _lib.lib().ape_adds_dis_f32(_lib.dptr(pred_r, torch.float32), _lib.dptr(pred_t, torch.float32), _lib.dptr(points),
-                                     _lib.dptr(model, torch.float32), _lib.dptr(target, torch.float32), n, m,
-                                     int(bool(symmetric)), _lib.dptr(pred), _lib.dptr(dis), _lib.dptr(std), _st())
-    _lib.check(rc, "ape_adds_dis_f32")
+    _lib.call.ape_adds_dis_f32(_lib.dptr(pred_r, torch.float32), _lib.dptr(pred_t, torch.float32), _lib.dptr(points),
+                               _lib.dptr(model, torch.float32), _lib.dptr(target, torch.float32), n, m,
+                               int(bool(symmetric)), _lib.dptr(pred), _lib.dptr(dis), _lib.dptr(std), _st())
     return dis, std, pred
 
 
@@ -1042,9 +1013,8 @@ def adds_dis_batched(pred_r, pred_t, model, target, symmetric):
     b, m = model.shape[0], model.shape[1]
     dis = torch.empty(b, dtype=torch.float32, device=model.device)
     ws = torch.empty(b, m, dtype=torch.float32, device=model.device)          # per-point distances (the mean is a second launch)
-    rc = _lib.lib().ape_adds_dis_batched_f32(_lib.dptr(pred_r, torch.float32), _lib.dptr(pred_t, torch.float32), _lib.dptr(model, torch.float32),
-                                             _lib.dptr(target, torch.float32), b, m, int(bool(symmetric)), _lib.dptr(ws), _lib.dptr(dis), _st())
-    _lib.check(rc, "ape_adds_dis_batched_f32")
+    _lib.call.ape_adds_dis_batched_f32(_lib.dptr(pred_r, torch.float32), _lib.dptr(pred_t, torch.float32), _lib.dptr(model, torch.float32),
+                                       _lib.dptr(target, torch.float32), b, m, int(bool(symmetric)), _lib.dptr(ws), _lib.dptr(dis), _st())
     return dis
 
 
@@ -1052,17 +1022,15 @@ def adds_select(dis, std, pred_c, pred_r, pred_t, points, w):
     """-> out9 (loss, dis[which], q[4], t[3]) f32 on device, which i32[1]"""
     out = torch.empty(9, dtype=torch.float32, device=dis.device)
     which = torch.empty(1, dtype=torch.int32, device=dis.device)
-    rc = _lib.lib().ape_adds_select_f32(_lib.dptr(dis), _lib.dptr(std), _lib.dptr(pred_c, torch.float32), _lib.dptr(pred_r),
-                                        _lib.dptr(pred_t), _lib.dptr(points), dis.shape[0], float(w), _lib.dptr(out),
-                                        _lib.dptr(which), _st())
-    _lib.check(rc, "ape_adds_select_f32")
+    _lib.call.ape_adds_select_f32(_lib.dptr(dis), _lib.dptr(std), _lib.dptr(pred_c, torch.float32), _lib.dptr(pred_r),
+                                  _lib.dptr(pred_t), _lib.dptr(points), dis.shape[0], float(w), _lib.dptr(out),
+                                  _lib.dptr(which), _st())
     return out, which
 
 
 def recentre_qt(pts, qt7):
     """pts[n,3], qt7 (device f32 [7]: unnormalised quaternion + translation) -> (pts - t) . R(q)"""
     out = torch.empty_like(pts)
-    rc = _lib.lib().ape_recentre_qt_f32(_lib.dptr(pts, torch.float32), _lib.dptr(qt7, torch.float32), _lib.dptr(out),
-                                        pts.shape[0], _st())
-    _lib.check(rc, "ape_recentre_qt_f32")
+    _lib.call.ape_recentre_qt_f32(_lib.dptr(pts, torch.float32), _lib.dptr(qt7, torch.float32), _lib.dptr(out),
+                                  pts.shape[0], _st())
     return out

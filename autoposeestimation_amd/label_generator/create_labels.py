@@ -65,9 +65,8 @@ def relabel_frames(model, rgb, depth, robot2cam, reference_point, class_id, bs_l
     dist = np.linalg.norm(np.asarray(reference_point, dtype=np.float64)[None] - pos, axis=1)
     gate = torch.from_numpy(np.stack([dist - 150, dist + 150], 1).astype(np.float32)).to(dev)   # :107-109
     counts = torch.zeros(b, 6, dtype=torch.int32, device=dev)
-    rc = _lib.lib().ape_label_trust_counts(_lib.dptr(objmap, torch.uint8), target, _lib.dptr(bs_labels), _lib.dptr(depth, torch.uint16),
-                                           _lib.dptr(gate), b, h, w, 30, 50, _lib.dptr(counts), _lib.stream_ptr())
-    _lib.check(rc, "ape_label_trust_counts")
+    _lib.call.ape_label_trust_counts(_lib.dptr(objmap, torch.uint8), target, _lib.dptr(bs_labels), _lib.dptr(depth, torch.uint16),
+                                     _lib.dptr(gate), b, h, w, 30, 50, _lib.dptr(counts), _lib.stream_ptr())
     c = counts.cpu().numpy()
     labels = torch.where(objmap == target, torch.full_like(objmap, 255), torch.zeros_like(objmap))
     save = np.zeros(b, bool)

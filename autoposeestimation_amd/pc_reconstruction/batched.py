@@ -87,9 +87,8 @@ def surface_points(views, intr_default, device="cuda"):
         bufs = [torch.empty(h * w, 3, dtype=_D, device=dev) for _ in idx]
         cnt = torch.zeros(nb, dtype=torch.int32, device=dev)
         pix = torch.empty(nb * h * w, dtype=torch.int32, device=dev)
-        rc = _lib.lib().ape_surface_points_batch_f64(nb, _ptrs(labs), _ptrs(deps), h, w, _dbls(intrs), _dbls(np.stack(Ts).reshape(-1)), _ptrs(bufs), _lib.dptr(cnt),
-                                                     _lib.dptr(pix), _st())
-        _lib.check(rc, "ape_surface_points_batch_f64")
+        _lib.call.ape_surface_points_batch_f64(nb, _ptrs(labs), _ptrs(deps), h, w, _dbls(intrs), _dbls(np.stack(Ts).reshape(-1)), _ptrs(bufs), _lib.dptr(cnt),
+                                               _lib.dptr(pix), _st())
         counts = cnt.cpu().numpy()
         for k, i in enumerate(idx):
             out[i] = _cloud(bufs[k][:int(counts[k])].contiguous(), dev)
@@ -109,9 +108,8 @@ def voxel_down_sample(clouds, voxel_size):
         bufs = [torch.empty(max(n, 1), 3, dtype=_D, device=dev) for n in ns]
         cnt = torch.zeros(nb, dtype=torch.int32, device=dev)
         ws = _ws(nb, sum(ns), dev)
-        rc = _lib.lib().ape_voxel_down_sample_batch_f64(nb, _ptrs([clouds[i]._p for i in idx]), _ints(ns), float(voxel_size), _ptrs(bufs), _lib.dptr(cnt),
-                                                        _lib.dptr(ws), ws.numel(), _st())
-        _lib.check(rc, "ape_voxel_down_sample_batch_f64")
+        _lib.call.ape_voxel_down_sample_batch_f64(nb, _ptrs([clouds[i]._p for i in idx]), _ints(ns), float(voxel_size), _ptrs(bufs), _lib.dptr(cnt),
+                                                  _lib.dptr(ws), ws.numel(), _st())
         counts = cnt.cpu().numpy()
         for k, i in enumerate(idx):
             out[i] = _cloud(bufs[k][:int(counts[k])].contiguous(), dev) if ns[k] else PC.PointCloud(device=dev)
@@ -138,10 +136,9 @@ def build_grids(clouds, cell):
         gs = [{"sorted": torch.empty(n, 3, dtype=_D, device=dev), "keys": torch.empty(n, dtype=torch.int64, device=dev),
                "order": torch.empty(n, dtype=torch.int32, device=dev), "origin": torch.empty(3, dtype=_D, device=dev), "n": n, "cell": float(cell)} for n in ns]
         ws = _ws(len(sel), sum(ns), dev)
-        rc = _lib.lib().ape_grid_build_batch_f64(len(sel), _ptrs([clouds[i]._p for i in sel]), _ints(ns), float(cell), _ptrs([g["sorted"] for g in gs]),
-                                                 _ptrs([g["keys"] for g in gs]), _ptrs([g["order"] for g in gs]), _ptrs([g["origin"] for g in gs]),
-                                                 _lib.dptr(ws), ws.numel(), _st())
-        _lib.check(rc, "ape_grid_build_batch_f64")
+        _lib.call.ape_grid_build_batch_f64(len(sel), _ptrs([clouds[i]._p for i in sel]), _ints(ns), float(cell), _ptrs([g["sorted"] for g in gs]),
+                                           _ptrs([g["keys"] for g in gs]), _ptrs([g["order"] for g in gs]), _ptrs([g["origin"] for g in gs]),
+                                           _lib.dptr(ws), ws.numel(), _st())
         for g, i in zip(gs, sel):
             clouds[i]._gcache = (clouds[i]._p, float(cell), clouds[i]._epoch, g)
             grids[i] = g
@@ -170,11 +167,10 @@ def _select(clouds, mode, counts=None, thr_count=0, means=None, thr_means=None, 
         bufs = [torch.empty(max(n, 1), 3, dtype=_D, device=dev) for n in ns]
         cnt = torch.zeros(nb, dtype=torch.int32, device=dev)
         sel = torch.empty(max(sum(ns), 1), dtype=torch.int32, device=dev)
-        rc = _lib.lib().ape_select_points_batch_f64(mode, nb, _ptrs([clouds[i]._p for i in idx]), _ints(ns),
-                                                    _ptrs([counts[i] for i in idx]) if mode == 0 else None, int(thr_count),
-                                                    _ptrs([means[i] for i in idx]) if mode == 1 else None,
-                                                    _dbls([thr_means[i] for i in idx]) if mode == 1 else None, _ptrs(bufs), _lib.dptr(cnt), _lib.dptr(sel), _st())
-        _lib.check(rc, "ape_select_points_batch_f64")
+        _lib.call.ape_select_points_batch_f64(mode, nb, _ptrs([clouds[i]._p for i in idx]), _ints(ns),
+                                              _ptrs([counts[i] for i in idx]) if mode == 0 else None, int(thr_count),
+                                              _ptrs([means[i] for i in idx]) if mode == 1 else None,
+                                              _dbls([thr_means[i] for i in idx]) if mode == 1 else None, _ptrs(bufs), _lib.dptr(cnt), _lib.dptr(sel), _st())
         kept = cnt.cpu().numpy()
         if indices:
             sel_host, offs = sel.cpu().numpy(), np.concatenate([[0], np.cumsum(ns)])
@@ -194,9 +190,8 @@ def remove_radius_outlier(clouds, nb_points, radius, indices=False):
             continue
         dev = clouds[idx[0]].device
         cs = [torch.empty(max(len(clouds[i]), 1), dtype=torch.int32, device=dev) for i in idx]
-        rc = _lib.lib().ape_grid_query_batch_f64(0, len(idx), *_grid_args([grids[i] for i in idx]), float(radius), _ptrs([clouds[i]._p for i in idx]),
-                                                 _ints([len(clouds[i]) for i in idx]), float(radius), 0, _ptrs(cs), None, None, _st())
-        _lib.check(rc, "ape_grid_query_batch_f64")
+        _lib.call.ape_grid_query_batch_f64(0, len(idx), *_grid_args([grids[i] for i in idx]), float(radius), _ptrs([clouds[i]._p for i in idx]),
+                                           _ints([len(clouds[i]) for i in idx]), float(radius), 0, _ptrs(cs), None, None, _st())
         for k, i in enumerate(idx):
             counts[i] = cs[k]
     return _select(clouds, 0, counts=counts, thr_count=int(nb_points), indices=indices)
@@ -212,8 +207,7 @@ def moments(clouds):
             continue
         o9 = torch.zeros(len(idx), 9, dtype=_D, device=dev)
         ws = torch.empty(len(idx) * 512 * 9 * 8, dtype=torch.uint8, device=dev)
-        rc = _lib.lib().ape_moments_batch_f64(len(idx), _ptrs([clouds[i]._p for i in idx]), _ints(ns), _lib.dptr(o9), _lib.dptr(ws), ws.numel(), _st())
-        _lib.check(rc, "ape_moments_batch_f64")
+        _lib.call.ape_moments_batch_f64(len(idx), _ptrs([clouds[i]._p for i in idx]), _ints(ns), _lib.dptr(o9), _lib.dptr(ws), ws.numel(), _st())
         m_all = o9.cpu().numpy()
         for k, i in enumerate(idx):
             if ns[k] == 0:
@@ -242,9 +236,8 @@ def mahalanobis(clouds):
             continue
         flat = torch.empty(total, dtype=_D, device=dev)
         offs = np.concatenate([[0], np.cumsum(ns)])
-        rc = _lib.lib().ape_mahalanobis_batch_f64(len(idx), _ptrs([clouds[i]._p for i in idx]), _ints(ns), _dbls(mc.reshape(-1)),
-                                                  _ptrs([flat[offs[k]:offs[k + 1]] for k in range(len(idx))]), _st())
-        _lib.check(rc, "ape_mahalanobis_batch_f64")
+        _lib.call.ape_mahalanobis_batch_f64(len(idx), _ptrs([clouds[i]._p for i in idx]), _ints(ns), _dbls(mc.reshape(-1)),
+                                            _ptrs([flat[offs[k]:offs[k + 1]] for k in range(len(idx))]), _st())
         host = flat.cpu().numpy()                    # ONE device-to-host copy for the whole batch
         for k, i in enumerate(idx):
             out[i] = host[offs[k]:offs[k + 1]].copy()
@@ -282,9 +275,8 @@ def remove_statistical_outlier(clouds, nb_neighbors, std_ratios, cell_hint=None,
             offs = np.concatenate([[0], np.cumsum(ns)])
             flat = torch.empty(int(offs[-1]), dtype=_D, device=dev)
             views = [flat[offs[m]:offs[m + 1]] for m in range(len(idx))]
-            rc = _lib.lib().ape_grid_query_batch_f64(2, len(idx), *_grid_args([grids[j] for j in idx]), cell, None, None, 0.0, k, None, None,
-                                                     _ptrs(views), _st())
-            _lib.check(rc, "ape_grid_query_batch_f64")
+            _lib.call.ape_grid_query_batch_f64(2, len(idx), *_grid_args([grids[j] for j in idx]), cell, None, None, 0.0, k, None, None,
+                                               _ptrs(views), _st())
             host = flat.cpu().numpy()
             for m, j in enumerate(idx):
                 means[j] = (views[m], host[offs[m]:offs[m + 1]])
@@ -311,9 +303,8 @@ def estimate_normals(clouds, radius, max_nn):
             continue
         dev = clouds[idx[0]].device
         nrm = [torch.empty(max(len(clouds[i]), 1), 3, dtype=_D, device=dev) for i in idx]
-        rc = _lib.lib().ape_grid_query_batch_f64(1, len(idx), *_grid_args([grids[i] for i in idx]), float(radius), _ptrs([clouds[i]._p for i in idx]),
-                                                 _ints([len(clouds[i]) for i in idx]), float(radius), int(max_nn), None, _ptrs(nrm), None, _st())
-        _lib.check(rc, "ape_grid_query_batch_f64")
+        _lib.call.ape_grid_query_batch_f64(1, len(idx), *_grid_args([grids[i] for i in idx]), float(radius), _ptrs([clouds[i]._p for i in idx]),
+                                           _ints([len(clouds[i]) for i in idx]), float(radius), int(max_nn), None, _ptrs(nrm), None, _st())
         for k, i in enumerate(idx):
             if len(clouds[i]):
                 clouds[i]._n = nrm[k][:len(clouds[i])]
@@ -329,9 +320,8 @@ def transform(clouds, Ts):
         T_host = np.stack([np.asarray(Ts[i], dtype=np.float64).reshape(16) for i in live]).reshape(-1)
         for i in live:
             clouds[i]._epoch += 1
-        rc = _lib.lib().ape_transform_points_batch_f64(len(live), _ptrs([clouds[i]._p for i in live]), _ptrs([clouds[i]._n for i in live]),
-                                                       _ints([len(clouds[i]) for i in live]), _dbls(T_host), _st())
-        _lib.check(rc, "ape_transform_points_batch_f64")
+        _lib.call.ape_transform_points_batch_f64(len(live), _ptrs([clouds[i]._p for i in live]), _ptrs([clouds[i]._n for i in live]),
+                                                 _ints([len(clouds[i]) for i in live]), _dbls(T_host), _st())
     return clouds
 
 
@@ -343,10 +333,9 @@ def concat(a_list, b_list=None):
         na = [len(a_list[i]) for i in idx]
         nb_ = [len(b_list[i]) if b_list is not None else 0 for i in idx]
         bufs = [torch.empty(x + y, 3, dtype=_D, device=dev) for x, y in zip(na, nb_)]
-        rc = _lib.lib().ape_concat_points_batch_f64(len(idx), _ptrs([a_list[i]._p for i in idx]), _ints(na),
-                                                    _ptrs([b_list[i]._p for i in idx]) if b_list is not None else None,
-                                                    _ints(nb_) if b_list is not None else None, _ptrs(bufs), _st())
-        _lib.check(rc, "ape_concat_points_batch_f64")
+        _lib.call.ape_concat_points_batch_f64(len(idx), _ptrs([a_list[i]._p for i in idx]), _ints(na),
+                                              _ptrs([b_list[i]._p for i in idx]) if b_list is not None else None,
+                                              _ints(nb_) if b_list is not None else None, _ptrs(bufs), _st())
         out += [_cloud(b, dev) for b in bufs]
     return out
 
@@ -365,7 +354,6 @@ def icp_states(sources, targets, max_correspondence_distance, inits, kind, crite
     moved = transform(concat([sources[i] for i in live]), [Ts[i] for i in live])      # open3d works on a transformed copy
     tg = [targets[i] for i in live]
     grids = build_grids(tg, max_correspondence_distance)
-    L = _lib.lib()
     for idx in _chunks(live):
         dev = moved[idx[0]].device
         nb = len(idx)
@@ -384,12 +372,11 @@ def icp_states(sources, targets, max_correspondence_distance, inits, kind, crite
             ev0.record()
         while True:
             n_it = min(chunk, left)
-            rc = L.ape_icp_run_batch_f64(kind, nb, *_grid_args([grids[j] for j in idx]), float(max_correspondence_distance), _ptrs([moved[j]._p for j in idx]),
-                                         _ints(ns), _ptrs([tg[j]._p for j in idx]), _ptrs([tg[j]._n for j in idx]) if kind == 1 else None,
-                                         float(max_correspondence_distance), float(criteria.relative_fitness), float(criteria.relative_rmse),
-                                         int(criteria.max_iteration), n_it, first, _ptrs(corr), _ptrs(d2), _ptrs([sums[k] for k in range(nb)]),
-                                         _ptrs([state[k] for k in range(nb)]), _lib.dptr(ws), ws.numel(), _st())
-            _lib.check(rc, "ape_icp_run_batch_f64")
+            _lib.call.ape_icp_run_batch_f64(kind, nb, *_grid_args([grids[j] for j in idx]), float(max_correspondence_distance), _ptrs([moved[j]._p for j in idx]),
+                                            _ints(ns), _ptrs([tg[j]._p for j in idx]), _ptrs([tg[j]._n for j in idx]) if kind == 1 else None,
+                                            float(max_correspondence_distance), float(criteria.relative_fitness), float(criteria.relative_rmse),
+                                            int(criteria.max_iteration), n_it, first, _ptrs(corr), _ptrs(d2), _ptrs([sums[k] for k in range(nb)]),
+                                            _ptrs([state[k] for k in range(nb)]), _lib.dptr(ws), ws.numel(), _st())
             out = state.cpu().numpy()
             left -= n_it
             first = 0

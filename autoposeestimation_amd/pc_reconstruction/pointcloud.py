@@ -268,14 +268,12 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
     d2 = torch.empty(ns, dtype=_D, device=dev)
     sums = torch.empty(29, dtype=_D, device=dev)
     ws = torch.empty(512 * 29 * 8, dtype=torch.uint8, device=dev)
-    L = _lib.lib()
 
     def evaluate():
-        _lib.check(L.ape_grid_nn1_f64(*PointCloud._gargs(grid), _lib.dptr(pcd._p, _D), ns, float(max_correspondence_distance),
-                                      _lib.dptr(corr), _lib.dptr(d2), _st()), "ape_grid_nn1_f64")
-        _lib.check(L.ape_icp_sums_f64(estimation_method.kind, _lib.dptr(pcd._p, _D), _lib.dptr(target._p, _D), _lib.dptr(target._n),
-                                      _lib.dptr(corr), _lib.dptr(d2), ns, _lib.dptr(sums), _lib.dptr(ws), ws.numel(), _st()),
-                   "ape_icp_sums_f64")
+        _lib.call.ape_grid_nn1_f64(*PointCloud._gargs(grid), _lib.dptr(pcd._p, _D), ns, float(max_correspondence_distance),
+                                   _lib.dptr(corr), _lib.dptr(d2), _st())
+        _lib.call.ape_icp_sums_f64(estimation_method.kind, _lib.dptr(pcd._p, _D), _lib.dptr(target._p, _D), _lib.dptr(target._n),
+                                   _lib.dptr(corr), _lib.dptr(d2), ns, _lib.dptr(sums), _lib.dptr(ws), ws.numel(), _st())
         s = sums.cpu().numpy()
         n_corr = int(round(s[0]))
         fitness = n_corr / ns
@@ -327,8 +325,8 @@ def compute_fpfh_feature(pcd, search_param):
     out = torch.empty(n, 33, dtype=_D, device=pcd.device)
     L = _lib.lib()
     ws = torch.empty(L.ape_fpfh_workspace_bytes(n, max_nn), dtype=torch.uint8, device=pcd.device)
-    _lib.check(L.ape_fpfh_f64(*PointCloud._gargs(g), _lib.dptr(pcd._p, _D), _lib.dptr(pcd._n, _D), radius, max_nn, _lib.dptr(out),
-                              _lib.dptr(ws), ws.numel(), _st()), "ape_fpfh_f64")
+    _lib.call.ape_fpfh_f64(*PointCloud._gargs(g), _lib.dptr(pcd._p, _D), _lib.dptr(pcd._n, _D), radius, max_nn, _lib.dptr(out),
+                           _lib.dptr(ws), ws.numel(), _st())
     return Feature(out)
 
 
@@ -359,8 +357,8 @@ def feature_nn(source_feature, target_feature):
         return nn.fill_(-1)
     L = _lib.lib()
     ws = torch.empty(L.ape_feature_nn1_workspace_bytes(ns, nt), dtype=torch.uint8, device=dev)
-    _lib.check(L.ape_feature_nn1_f64(_lib.dptr(source_feature.t.contiguous(), _D), ns, _lib.dptr(target_feature.t.contiguous(), _D), nt,
-                                     _lib.dptr(nn), _lib.dptr(ws), ws.numel(), _st()), "ape_feature_nn1_f64")
+    _lib.call.ape_feature_nn1_f64(_lib.dptr(source_feature.t.contiguous(), _D), ns, _lib.dptr(target_feature.t.contiguous(), _D), nt,
+                                  _lib.dptr(nn), _lib.dptr(ws), ws.numel(), _st())
     return nn
 
 
@@ -417,9 +415,8 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
     it, k = 0, 0
     while it < max_it:                                  # bounded by max_iteration; the device list stops growing once full
         c = min(chunk, max_it - it)
-        _lib.check(L.ape_ransac_hypotheses_f64(src, ns, tgt, nt, _lib.dptr(nn), ransac_n, int(seed), edge_sim, dist_thr, it, c, max_val,
-                                               _lib.dptr(kept), _lib.dptr(n_kept), _lib.dptr(ws), ws.numel(), _st()),
-                   "ape_ransac_hypotheses_f64")
+        _lib.call.ape_ransac_hypotheses_f64(src, ns, tgt, nt, _lib.dptr(nn), ransac_n, int(seed), edge_sim, dist_thr, it, c, max_val,
+                                            _lib.dptr(kept), _lib.dptr(n_kept), _lib.dptr(ws), ws.numel(), _st())
         it += c
         k = int(n_kept.item())
         if k >= max_val:
@@ -427,8 +424,8 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
         chunk = min(chunk * 2, cap)
     grid = target._grid(max_dist)
     out = torch.empty(24, dtype=_D, device=dev)
-    _lib.check(L.ape_ransac_validate_f64(*PointCloud._gargs(grid), src, ns, tgt, nt, _lib.dptr(nn), ransac_n, int(seed), _lib.dptr(kept), k,
-                                         max_dist, _lib.dptr(out), None, _lib.dptr(ws), ws.numel(), _st()), "ape_ransac_validate_f64")
+    _lib.call.ape_ransac_validate_f64(*PointCloud._gargs(grid), src, ns, tgt, nt, _lib.dptr(nn), ransac_n, int(seed), _lib.dptr(kept), k,
+                                      max_dist, _lib.dptr(out), None, _lib.dptr(ws), ws.numel(), _st())
     r = out.cpu().numpy()
     res = RegistrationResult(r[:16].reshape(4, 4).copy(), float(r[16]), float(r[17]), int(round(r[18])))
     res.validated = kept[:k].cpu().numpy().astype(np.int64)

@@ -95,11 +95,10 @@ class FramePipeline:
         """objects: list of (frame, cls, rmin, rmax, cmin, cmax).  Returns (pose[n,7] f64 cuda, n_cand[n] i32 cuda,
         choose[n,N] i64 cuda) in the order of `objects`."""
         t_host = time.perf_counter()
-        prev, E.SPLITK_SMALL_M = E.SPLITK_SMALL_M, self.low_latency
         try:
-            return self._poses(rgb, depth, objmap, objects, meta, choose_override, seed)
+            with E.low_latency(self.low_latency):
+                return self._poses(rgb, depth, objmap, objects, meta, choose_override, seed)
         finally:
-            E.SPLITK_SMALL_M = prev
             self.host_poses_s += time.perf_counter() - t_host
 
     def _poses(self, rgb, depth, objmap, objects, meta, choose_override, seed):

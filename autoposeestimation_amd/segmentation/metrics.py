@@ -121,10 +121,9 @@ class ConfusionMatrix(Metric):
         b, h, w = pshape
         if b * h * w == 0:
             return
-        rc = _lib.lib().ape_confusion_add(ctypes.c_void_p(ps.data_ptr() if ps is not None else 0), pst, _lib.dptr(pl),
-                                          ctypes.c_void_p(ts.data_ptr() if ts is not None else 0), tst, _lib.dptr(tl), b, h, w, k,
-                                          _lib.dptr(self._dev[0]), _lib.dptr(self._dev[1]), _lib.stream_ptr())
-        _lib.check(rc, "ape_confusion_add")
+        _lib.call.ape_confusion_add(ctypes.c_void_p(ps.data_ptr() if ps is not None else 0), pst, _lib.dptr(pl),
+                                    ctypes.c_void_p(ts.data_ptr() if ts is not None else 0), tst, _lib.dptr(tl), b, h, w, k,
+                                    _lib.dptr(self._dev[0]), _lib.dptr(self._dev[1]), _lib.stream_ptr())
 
     def _fold(self):
         """device counts -> self.conf (one synchronisation)"""

@@ -118,10 +118,10 @@ int ape_conv_gemm_s32_per_image(const void* x_s32, const void* w_s32k, long w_im
                                 const ape_conv_params* params_host, void* stream);
 int ape_psp_fold_operands(const void* wf_s32k, const float* z1, const float* z2, const float* z3, const float* z6, void* w_out, void* x_s32,
                           int B, int h, int w, int ld, int Cin, int Cout, void* stream);
-/* Format-aware forms of three fp32 entry points, for the tensors that cross between fp32 and S32 kernels: ape_conv_gemm_bf16 with the
- * OUTPUT in either format (the stride-2 convs that feed the first S32 3x3 layer), ape_adaptive_avgpool_multi_nhwc_f32 with the INPUT
- * in either format (the PSP pools of the S32 layer-4 map), ape_upconv3x3_gather_f32 with the OUTPUT in either format (up_1's result
- * feeds up_2's S32 channel mixing).  Declared further down next to their fp32 forms' documentation. */
+/* Format-aware forms of three fp32 operations, for the tensors that cross between fp32 and S32 kernels: ape_conv_gemm_bf16 with the
+ * OUTPUT in either format (the stride-2 convs that feed the first S32 3x3 layer), the multi-size adaptive average pool with the INPUT
+ * in either format (ape_adaptive_avgpool_multi_nhwc_ld: the PSP pools of the S32 layer-4 map), ape_upconv3x3_gather_f32 with the OUTPUT
+ * in either format (ape_upconv3x3_gather_ex: up_1's result feeds up_2's S32 channel mixing). */
 int ape_conv_gemm_bf16_fmt(const float* x, const void* w_packed, const float* bias, const float* residual, void* y, int out_fmt,
                            const ape_conv_params* params_host, int nsplit, int variant, void* stream);
 /* The PSP module's stage convolutions (pspnet.py:15-18, 22: `stage(feats) for stage in self.stages` -- four bias-free 1x1 convolutions of the
@@ -137,17 +137,15 @@ int ape_conv_gemm_bf16_multi(int n, const float* const* x, const void* const* w_
 size_t ape_conv_gemm_splitk_workspace_bytes(const ape_conv_params* params);
 int ape_conv_gemm_bf16_splitk(const float* x, const void* w_packed, const float* bias, const float* residual, float* y,
                               const ape_conv_params* params, int nsplit, void* workspace, size_t workspace_bytes, void* stream);
-int ape_adaptive_avgpool_multi_nhwc_fmt(const void* x, int in_fmt, float* const* ys_host, const int* sizes_host, int nsizes, int B, int H, int W,
-                                        int C, void* workspace, size_t workspace_bytes, void* stream);
-/* ... of the first C channels of a map that holds ldx channels per pixel (the PSP module's feature map with the 64 spare channels of
- * ape_psp_fold_operands behind its 512: pspnet.py:15 pools the 512); outputs [B,s,s,C] fp32 */
+/* The multi-size adaptive average pool (documented with ape_adaptive_avgpool_multi_workspace_bytes below) of x in either activation
+ * format (APE_FMT_S32: C % 32 == 0 and ldx % 32 == 0), over the first C channels of a map that holds ldx >= C channels per pixel (the PSP
+ * module's feature map with the 64 spare channels of ape_psp_fold_operands behind its 512: pspnet.py:15 pools the 512); outputs
+ * [B,s,s,C] fp32 */
 int ape_adaptive_avgpool_multi_nhwc_ld(const void* x, int in_fmt, float* const* ys_host, const int* sizes_host, int nsizes, int B, int H, int W,
                                        int C, int ldx, void* workspace, size_t workspace_bytes, void* stream);
-int ape_upconv3x3_gather_fmt(const float* z, const float* bias, void* out, int out_fmt, int B, int h, int w, int C, int act, float alpha,
-                             void* stream);
-/* ... and with the interpolation arithmetic chosen: fma = 0 separately rounded products like ape_bilinear_nhwc_f32 (what the two entry
- * points above use), fma = 1 chained fused multiply-adds acc = fma(l1, v1, fma(l0, v0, acc)) -- the unfused twin of
- * ape_upconv3x3_fused_* called with fma = 1 */
+/* ape_upconv3x3_gather_f32 with the OUTPUT in either activation format (APE_FMT_S32: C % 32 == 0) and the interpolation arithmetic
+ * chosen: fma = 0 separately rounded products like ape_bilinear_nhwc_f32 (what ape_upconv3x3_gather_f32 uses), fma = 1 chained fused
+ * multiply-adds acc = fma(l1, v1, fma(l0, v0, acc)) -- the unfused twin of ape_upconv3x3_fused_* called with fma = 1 */
 int ape_upconv3x3_gather_ex(const float* z, const float* bias, void* out, int out_fmt, int B, int h, int w, int C, int act, float alpha,
                             int fma, void* stream);
 /* Channel counts that are multiples of 64 take a second kernel with the same arithmetic (bit-identical outputs): strips of `rows` output
@@ -215,13 +213,11 @@ int ape_conv3x3_halo_bf16(const float* x, const void* w_packed, const float* bia
 int ape_maxpool3x3s2_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, void* stream);
 /* nn.AdaptiveAvgPool2d((S,S))                DenseFusion/lib/pspnet.py:15.           y[B][S][S][C] */
 int ape_adaptive_avgpool_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, int S, void* stream);
-/* The PSP module's pools (pspnet.py:15: sizes 2, 3, 6 of one map) in ONE pass over the map: the bin edges of all sizes cut each axis
- * into at most 12 "atoms" (APE_EINVAL otherwise: use the per-size entry point); every atom is summed once into `workspace`
- * (ape_adaptive_avgpool_multi_workspace_bytes(B, C)), then each bin adds up its atoms.  ys_host / sizes_host: host arrays of nsizes
- * <= 4 device output pointers y_i[B][S_i][S_i][C] and sizes S_i <= 8. */
+/* The PSP module's pools (pspnet.py:15: sizes 2, 3, 6 of one map) in ONE pass over the map (ape_adaptive_avgpool_multi_nhwc_ld): the
+ * bin edges of all sizes cut each axis into at most 12 "atoms" (APE_EINVAL otherwise: use the per-size entry point); every atom is
+ * summed once into `workspace` (ape_adaptive_avgpool_multi_workspace_bytes(B, C)), then each bin adds up its atoms.  ys_host /
+ * sizes_host: host arrays of nsizes <= 4 device output pointers y_i[B][S_i][S_i][C] and sizes S_i <= 8. */
 size_t ape_adaptive_avgpool_multi_workspace_bytes(int B, int C);
-int ape_adaptive_avgpool_multi_nhwc_f32(const float* x, float* const* ys_host, const int* sizes_host, int nsizes, int B, int H, int W,
-                                        int C, void* workspace, size_t workspace_bytes, void* stream);
 /* F.upsample(size=(Ho,Wo), 'bilinear') / nn.Upsample(x2, align_corners=True)   pspnet.py:22,31.
  * Reads x[B][H][W][ldx] channels 0..C-1, writes y[B][Ho][Wo][ldy] channels yoff..yoff+C-1 (a slice of the PSP
  * concat buffer, pspnet.py:22-23); accumulate != 0 adds into y instead of overwriting. */
@@ -315,9 +311,7 @@ int ape_seg_head_f32(const float* feat, const float* w, const float* bias, int C
  * reference's per-class mask is (objmap == cls) * 255) and det[B][C][5] i32 = (valid, rmin, rmax, cmin, cmax).
  * Classes with <= min_pixels pixels are skipped (reference: 100). */
 size_t ape_seg_components_workspace_bytes(int B, int H, int W, int C);
-int ape_seg_components(const uint8_t* label, const float* score, uint8_t* objmap, int* det, int B, int H, int W,
-                       int C, int min_pixels, void* workspace, size_t workspace_bytes, void* stream);
-/* Same with the component score selectable: APE_SEG_SCORE_MEAN = mean probability (pipeline/utils.py:456-462),
+/* The component score is selectable: APE_SEG_SCORE_MEAN = mean probability (pipeline/utils.py:456-462),
  * APE_SEG_SCORE_SUM = summed probability, the rule of do_cca (background_subtraction/utils.py:199-222: label 0/1,
  * biggest = arg max_u sum(max-prob[labels == u]), first component wins ties). */
 #define APE_SEG_SCORE_MEAN 0
@@ -333,7 +327,7 @@ int ape_seg_components_scored(const uint8_t* label, const float* score, uint8_t*
 int ape_bgsub_features_f32(const uint8_t* f_rgb, const uint8_t* b_rgb, const uint16_t* f_depth, const uint16_t* b_depth,
                            const double* gate_min_max, const float* mean7_host, const float* std7_host, float* out,
                            uint8_t* diff_or_null, int B, int H, int W, void* stream);
-/* trust checks of the relabelling loop   label_generator/create_labels.py:166-196.  objmap from ape_seg_components
+/* trust checks of the relabelling loop   label_generator/create_labels.py:166-196.  objmap from ape_seg_components_scored
  * (min_pixels = 0), cls = target class; counts[B][6] u32 (zeroed by the caller) = (bs&pred, bs&!pred, depth&pred,
  * depth&!pred, centre&pred, centre&!pred) with the depth gate [min,max] per frame (:106-112) and the 30/50 px centre window. */
 int ape_label_trust_counts(const uint8_t* objmap, int cls, const uint8_t* bs_label_or_null, const uint16_t* depth,
