@@ -128,6 +128,14 @@ SIGNATURES = {
     "ape_ransac_workspace_bytes": [_I, _I, _I],
     "ape_ransac_hypotheses_f64": [_P, _I, _P, _I, _P, _I, _c.c_long, _D, _D, _I, _I, _I, _P, _P, _P, _c.c_size_t, _P],
     "ape_ransac_validate_f64": [_P, _P, _P, _P, _I, _D, _P, _I, _P, _I, _P, _I, _c.c_long, _P, _I, _D, _P, _P, _P, _c.c_size_t, _P],
+    # their batched forms: per-pair arguments as host arrays of pointers / sizes, the pair's index in a grid dimension
+    "ape_fpfh_batch_workspace_bytes": [_I, _P, _I],
+    "ape_fpfh_batch_f64": [_I, _P, _P, _P, _P, _P, _D, _P, _P, _D, _I, _P, _P, _c.c_size_t, _P],
+    "ape_feature_nn1_batch_workspace_bytes": [_I, _P, _P],
+    "ape_feature_nn1_batch_f64": [_I, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P],
+    "ape_ransac_batch_workspace_bytes": [_I, _P, _I, _I],
+    "ape_ransac_hypotheses_batch_f64": [_I, _P, _P, _P, _P, _P, _I, _P, _D, _D, _I, _I, _I, _P, _P, _P, _c.c_size_t, _P],
+    "ape_ransac_validate_batch_f64": [_I, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _D, _P, _P, _P, _c.c_size_t, _P],
     # segmentor training (csrc/segtrain.hip)
     "ape_bn_workspace_bytes": [_I],
     "ape_bn_train_fwd_f32": [_P] * 10 + [_c.c_long, _I, _F, _F, _I, _P, _c.c_size_t, _P],
@@ -183,6 +191,8 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
              "ape_packed_weights_bf16_elems": _c.c_long, "ape_pc_batch_workspace_bytes": _c.c_size_t,
              "ape_conv2d_wgrad_workspace_bytes": _c.c_size_t, "ape_conv_gemm_splitk_workspace_bytes": _c.c_size_t,
              "ape_fpfh_workspace_bytes": _c.c_size_t, "ape_feature_nn1_workspace_bytes": _c.c_size_t, "ape_ransac_workspace_bytes": _c.c_size_t,
+             "ape_fpfh_batch_workspace_bytes": _c.c_size_t, "ape_feature_nn1_batch_workspace_bytes": _c.c_size_t,
+             "ape_ransac_batch_workspace_bytes": _c.c_size_t,
              "ape_bn_workspace_bytes": _c.c_size_t, "ape_jaccard_workspace_bytes": _c.c_size_t,
              "ape_bgsub_train_workspace_bytes": _c.c_size_t}
 

@@ -12,6 +12,10 @@
 //                        the target's grid), fixed-order sums, then the winner by (fitness desc, rmse asc, iteration asc)
 // The neighbour lists of pass 1 are written out (12 B per entry) rather than recomputed in pass 2: the selection -- min(max_nn, candidates)
 // rounds of a 32-lane shuffle reduction over the candidate list -- is most of pass 1's time, and re-reading 1.2 KB per point is not.
+// Every kernel is written in the batched form of pointcloud.hip ("BATCHED forms"): a by-value table of up to kMaxBatch per-pair argument
+// records, the pair's index in a grid dimension, and a per-pair extent so that a block beyond its pair's extent exits.  A pair's blocks,
+// partial layouts and summation orders depend on that pair's sizes alone, so its result does not depend on its slot or its neighbours;
+// the one-pair entry points are nb = 1 callers of the same launch code.
 #include "common.h"
 #include "pc_grid.h"
 
@@ -25,6 +29,9 @@ constexpr int kBins = 33;
 constexpr int kMaxRansacN = 16;
 constexpr int kNNT = 128;                 // source features per block of feature_nn_kernel (one per thread)
 constexpr int kNNTile = 64;               // target features per LDS tile
+constexpr int kNNBlocks = 2048;           // blocks a feature_nn launch aims at (all pairs together)
+constexpr int kMaxBatch = 16;             // pairs / clouds per launch, as pointcloud.hip
+template <class T> struct Batch { T t[kMaxBatch]; };
 
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -77,10 +84,20 @@ __device__ __forceinline__ int bin11(double x)
 // FPFH pass 1: kG lanes per point (as normals_kernel in pointcloud.hip).  The in-radius candidates of the 27 cells go to the group's LDS
 // list; cnt = min(max_nn, candidates) rounds take the smallest (d^2, original index) after the last one taken.  Entry 0 (the point
 // itself) is skipped like open3d does; every further entry adds 100 / (cnt - 1) to three bins, summed in list order by the bin's lane.
-__global__ __launch_bounds__(kT) void fpfh_spfh_kernel(Grid g, const double* __restrict__ pts, const double* __restrict__ nrm, int n, double r2,
-                                                       int max_nn, int* __restrict__ nbr, double* __restrict__ nbr_d2, int* __restrict__ nbr_cnt,
-                                                       double* __restrict__ spfh)
+struct BFpfh { Grid g; const double* pts; const double* nrm; int* nbr; double* nbr_d2; int* nbr_cnt; double* spfh; double* out; int n, gx; };
+
+__global__ __launch_bounds__(kT) void fpfh_spfh_kernel(const Batch<BFpfh> bt, double r2, int max_nn)
 {
+    const BFpfh& a = bt.t[blockIdx.y];
+    if ((int)blockIdx.x >= a.gx) return;
+    const Grid& g = a.g;
+    const double* __restrict__ pts = a.pts;
+    const double* __restrict__ nrm = a.nrm;
+    int* __restrict__ nbr = a.nbr;
+    double* __restrict__ nbr_d2 = a.nbr_d2;
+    int* __restrict__ nbr_cnt = a.nbr_cnt;
+    double* __restrict__ spfh = a.spfh;
+    const int n = a.n;
     __shared__ double cand_d[kGroups][kFCand];
     __shared__ int cand_o[kGroups][kFCand];
     __shared__ int sel[kGroups][kFeatMaxNN];
@@ -154,9 +171,16 @@ __global__ __launch_bounds__(kT) void fpfh_spfh_kernel(Grid g, const double* __r
 
 // FPFH pass 2: lane b sums SPFH_k[b] / d^2_k over the list in order (d^2 = 0 skipped), each 11-bin block is scaled to 100, then SPFH_i is
 // added.  Points with at most one list entry get zeros.
-__global__ __launch_bounds__(kT) void fpfh_kernel(const int* __restrict__ nbr, const double* __restrict__ nbr_d2, const int* __restrict__ nbr_cnt,
-                                                  const double* __restrict__ spfh, int n, int max_nn, double* __restrict__ out)
+__global__ __launch_bounds__(kT) void fpfh_kernel(const Batch<BFpfh> bt, int max_nn)
 {
+    const BFpfh& a = bt.t[blockIdx.y];
+    if ((int)blockIdx.x >= a.gx) return;
+    const int* __restrict__ nbr = a.nbr;
+    const double* __restrict__ nbr_d2 = a.nbr_d2;
+    const int* __restrict__ nbr_cnt = a.nbr_cnt;
+    const double* __restrict__ spfh = a.spfh;
+    double* __restrict__ out = a.out;
+    const int n = a.n;
     __shared__ double F[kGroups][kBins];
     const int lane = threadIdx.x % kG, grp = threadIdx.x / kG;
     const int i = (blockIdx.x * kT + threadIdx.x) / kG;
@@ -187,11 +211,20 @@ __global__ __launch_bounds__(kT) void fpfh_kernel(const int* __restrict__ nbr, c
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// nearest feature: blockIdx.y takes target slice [y * slice, min(nt, (y + 1) * slice)); d = sum_j (a_j - b_j)^2 in j order; strict < in
-// ascending target order keeps the lowest index of a tie, and so does the slice-ordered merge
-__global__ __launch_bounds__(kNNT) void feature_nn_kernel(const double* __restrict__ src, int ns, const double* __restrict__ tgt, int nt, int slice,
-                                                          double* __restrict__ part_d, int* __restrict__ part_i)
+// nearest feature: blockIdx.z = pair, blockIdx.y takes target slice [y * slice, min(nt, (y + 1) * slice)); d = sum_j (a_j - b_j)^2 in j
+// order; strict < in ascending target order keeps the lowest index of a tie, and so does the slice-ordered merge -- the minimum and its
+// lowest index do not depend on where the slices are cut, so the slice count is free to follow the size of the whole launch
+struct BNN { const double* src; const double* tgt; double* part_d; int* part_i; int* nn; int ns, nt, slice, nslice, gx; };
+
+__global__ __launch_bounds__(kNNT) void feature_nn_kernel(const Batch<BNN> bt)
 {
+    const BNN& p = bt.t[blockIdx.z];
+    if ((int)blockIdx.x >= p.gx || (int)blockIdx.y >= p.nslice) return;
+    const double* __restrict__ src = p.src;
+    const double* __restrict__ tgt = p.tgt;
+    double* __restrict__ part_d = p.part_d;
+    int* __restrict__ part_i = p.part_i;
+    const int ns = p.ns, nt = p.nt, slice = p.slice;
     __shared__ double tile[kNNTile][kBins];
     const int s = blockIdx.x * kNNT + threadIdx.x;
     const bool valid = s < ns;
@@ -218,8 +251,13 @@ __global__ __launch_bounds__(kNNT) void feature_nn_kernel(const double* __restri
     if (valid) { part_d[(size_t)blockIdx.y * ns + s] = best; part_i[(size_t)blockIdx.y * ns + s] = bi; }
 }
 
-__global__ void feature_nn_merge_kernel(const double* __restrict__ part_d, const int* __restrict__ part_i, int ns, int nslice, int* __restrict__ nn)
+__global__ void feature_nn_merge_kernel(const Batch<BNN> bt)
 {
+    const BNN& p = bt.t[blockIdx.y];
+    const double* __restrict__ part_d = p.part_d;
+    const int* __restrict__ part_i = p.part_i;
+    int* __restrict__ nn = p.nn;
+    const int ns = p.ns, nslice = p.nslice;
     for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < ns; s += gridDim.x * blockDim.x) {
         double best = part_d[s];
         int bi = part_i[s];
@@ -299,11 +337,17 @@ __device__ bool ransac_hypothesis(const Hyp& h, int it, bool checks, double T[12
     return true;
 }
 
-// iterations [it0, it0 + n_it): block b writes its passing iterations in order to blist[b][0..bcount[b]); a no-op once n_kept is full
-__global__ __launch_bounds__(kT) void ransac_hyp_kernel(Hyp h, int it0, int n_it, const int* __restrict__ n_kept, int max_validation,
-                                                        int* __restrict__ blist, int* __restrict__ bcount)
+// iterations [it0, it0 + n_it) of pair blockIdx.y: block b writes its passing iterations in order to blist[b][0..bcount[b]); a no-op once
+// the pair's own n_kept word is full (the other pairs of the launch go on)
+struct BHyp { Hyp h; int* kept; int* n_kept; int* blist; int* bcount; };
+
+__global__ __launch_bounds__(kT) void ransac_hyp_kernel(const Batch<BHyp> bt, int it0, int n_it, int max_validation)
 {
-    if (*n_kept >= max_validation) return;
+    const BHyp& a = bt.t[blockIdx.y];
+    if (*a.n_kept >= max_validation) return;
+    const Hyp& h = a.h;
+    int* __restrict__ blist = a.blist;
+    int* __restrict__ bcount = a.bcount;
     __shared__ int wc[kT / 64];
     const int gid = blockIdx.x * kT + threadIdx.x;
     double T[12];
@@ -318,10 +362,14 @@ __global__ __launch_bounds__(kT) void ransac_hyp_kernel(Hyp h, int it0, int n_it
     if (threadIdx.x == 0) bcount[blockIdx.x] = tot;
 }
 
-// one block: appends the blocks' lists in block order to kept[*n_kept ..] up to max_validation entries
-__global__ __launch_bounds__(kT) void ransac_append_kernel(const int* __restrict__ blist, const int* __restrict__ bcount, int nb, int max_validation,
-                                                           int* __restrict__ kept, int* __restrict__ n_kept)
+// one block per pair: appends the blocks' lists in block order to kept[*n_kept ..] up to max_validation entries
+__global__ __launch_bounds__(kT) void ransac_append_kernel(const Batch<BHyp> bt, int nb, int max_validation)
 {
+    const BHyp& a = bt.t[blockIdx.y];
+    const int* __restrict__ blist = a.blist;
+    const int* __restrict__ bcount = a.bcount;
+    int* __restrict__ kept = a.kept;
+    int* __restrict__ n_kept = a.n_kept;
     const int base = *n_kept;
     if (base >= max_validation) return;
     __shared__ int pre[kT + 1];
@@ -347,26 +395,36 @@ __global__ __launch_bounds__(kT) void ransac_append_kernel(const int* __restrict
     if (threadIdx.x == 0) *n_kept = min(max_validation, base + pre[kT]);
 }
 
+struct BVal { Grid g; Hyp h; const int* kept; double* T12; double* part; double* fr; double* out; int nh, G; };
+
 // the transformation of every kept iteration (rows 0..2)
-__global__ void ransac_models_kernel(Hyp h, const int* __restrict__ kept, int nh, double* __restrict__ T12)
+__global__ void ransac_models_kernel(const Batch<BVal> bt)
 {
+    const BVal& a = bt.t[blockIdx.y];
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nh) return;
+    if (k >= a.nh) return;
     double T[12];
-    ransac_hypothesis(h, kept[k], false, T);
-    for (int e = 0; e < 12; ++e) T12[(size_t)k * 12 + e] = T[e];
+    ransac_hypothesis(a.h, a.kept[k], false, T);
+    for (int e = 0; e < 12; ++e) a.T12[(size_t)k * 12 + e] = T[e];
 }
 
-// blockIdx.y = hypothesis, blockIdx.x strides over the source (kGroups points per pass, kG lanes each, as nn1_group_kernel); the group's
-// lane 0 accumulates its points' count / sum d^2 in order, the block reduces its groups in order -> part[h][bx][2]
-__global__ __launch_bounds__(kT) void ransac_validate_kernel(Grid g, const double* __restrict__ src, int ns, const double* __restrict__ T12, double r2,
-                                                             double* __restrict__ part)
+// blockIdx.z = pair, blockIdx.y = hypothesis, blockIdx.x < G (the pair's own count) strides over the source (kGroups points per pass, kG
+// lanes each, as nn1_group_kernel); the group's lane 0 accumulates its points' count / sum d^2 in order, the block reduces its groups
+// in order -> part[h][bx][2]
+__global__ __launch_bounds__(kT) void ransac_validate_kernel(const Batch<BVal> bt, double r2)
 {
+    const BVal& a = bt.t[blockIdx.z];
+    const int G = a.G;
+    if ((int)blockIdx.x >= G || (int)blockIdx.y >= a.nh) return;
+    const Grid& g = a.g;
+    const double* __restrict__ src = a.h.src;
+    double* __restrict__ part = a.part;
+    const int ns = a.h.ns;
     __shared__ double sc[kGroups], sd[kGroups];
     const int lane = threadIdx.x % kG, grp = threadIdx.x / kG;
-    const double* T = T12 + (size_t)blockIdx.y * 12;
+    const double* T = a.T12 + (size_t)blockIdx.y * 12;
     double cnt = 0.0, sum = 0.0;
-    for (int base = blockIdx.x * kGroups; base < ns; base += gridDim.x * kGroups) {
+    for (int base = blockIdx.x * kGroups; base < ns; base += G * kGroups) {
         const int i = base + grp;
         if (i >= ns) continue;
         const double x = src[(size_t)i * 3], y = src[(size_t)i * 3 + 1], z = src[(size_t)i * 3 + 2];
@@ -387,17 +445,23 @@ __global__ __launch_bounds__(kT) void ransac_validate_kernel(Grid g, const doubl
     if (threadIdx.x == 0) {
         double c = 0.0, s = 0.0;
         for (int k = 0; k < kGroups; ++k) { c += sc[k]; s += sd[k]; }
-        part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2] = c;
-        part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 + 1] = s;
+        part[((size_t)blockIdx.y * G + blockIdx.x) * 2] = c;
+        part[((size_t)blockIdx.y * G + blockIdx.x) * 2 + 1] = s;
     }
 }
 
-// one block: fitness / rmse of every hypothesis (partials summed in block order), then the winner in iteration order, replaced only by a
+// one block per pair: fitness / rmse of every hypothesis (partials summed in block order), then the winner in iteration order, replaced only by a
 // strictly better one (open3d IsBetterRANSACThan) starting from (identity, 0, 0).  out: [0..15] T, [16] fitness, [17] rmse,
 // [18] correspondences, [19] winner's position in `kept` (-1: none), [20] its iteration index (-1: none)
-__global__ __launch_bounds__(kT) void ransac_select_kernel(const double* __restrict__ part, int G, int nh, int ns, const double* __restrict__ T12,
-                                                           const int* __restrict__ kept, double* __restrict__ fr, double* __restrict__ out)
+__global__ __launch_bounds__(kT) void ransac_select_kernel(const Batch<BVal> bt)
 {
+    const BVal& a = bt.t[blockIdx.y];
+    const double* __restrict__ part = a.part;
+    const double* __restrict__ T12 = a.T12;
+    const int* __restrict__ kept = a.kept;
+    double* __restrict__ fr = a.fr;
+    double* __restrict__ out = a.out;
+    const int G = a.G, nh = a.nh, ns = a.h.ns;
     for (int k = threadIdx.x; k < nh; k += kT) {
         double c = 0.0, s = 0.0;
         for (int b = 0; b < G; ++b) { c += part[((size_t)k * G + b) * 2]; s += part[((size_t)k * G + b) * 2 + 1]; }
@@ -424,74 +488,31 @@ int validate_blocks(int ns)
     return g < 1 ? 1 : (g > 64 ? 64 : g);
 }
 
-int nn_slices(int ns, int nt)
+// slices of one pair's target range when `live` pairs share the launch: the launch as a whole aims at kNNBlocks blocks
+int nn_slices(int ns, int nt, int live)
 {
     const int bx = ape::ceil_div(ns, kNNT);
     const int max_s = ape::ceil_div(nt, kNNTile);
-    int s = ape::ceil_div(2048, bx);
+    const int s = ape::ceil_div(ape::ceil_div(kNNBlocks, live < 1 ? 1 : live), bx);
     return s < 1 ? 1 : (s > max_s ? max_s : s);
 }
 
-}  // namespace
-
-#define GRID_ARGS const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n, double cell
-#define MAKE_GRID Grid g{sorted, (const u64*)keys, order, origin3, n, cell}
-
-extern "C" size_t ape_fpfh_workspace_bytes(int n, int max_nn)
+size_t fpfh_ws(int n, int max_nn)
 {
     if (n < 1) n = 1;
     if (max_nn < 1) max_nn = 1;
     return align_up((size_t)n * max_nn * 4) + align_up((size_t)n * max_nn * 8) + align_up((size_t)n * 4) + align_up((size_t)n * kBins * 8);
 }
 
-extern "C" int ape_fpfh_f64(GRID_ARGS, const double* pts, const double* normals, double radius, int max_nn, double* feature, void* ws,
-                            size_t ws_bytes, void* stream)
-{
-    if (!sorted || !keys || !order || !origin3 || !pts || !normals || !feature || !ws || n < 1 || !(radius > 0) || radius > cell ||
-        max_nn < 1 || max_nn > kFeatMaxNN)
-        return APE_EINVAL;
-    if (ws_bytes < ape_fpfh_workspace_bytes(n, max_nn)) return APE_EWORKSPACE;
-    MAKE_GRID;
-    char* p = (char*)ws;
-    int* nbr = (int*)p;          p += align_up((size_t)n * max_nn * 4);
-    double* nbr_d2 = (double*)p; p += align_up((size_t)n * max_nn * 8);
-    int* cnt = (int*)p;          p += align_up((size_t)n * 4);
-    double* spfh = (double*)p;
-    hipStream_t st = (hipStream_t)stream;
-    const int blocks = ape::ceil_div((long)n * kG, (long)kT);
-    hipLaunchKernelGGL(fpfh_spfh_kernel, dim3(blocks), dim3(kT), 0, st, g, pts, normals, n, radius * radius, max_nn, nbr, nbr_d2, cnt, spfh);
-    hipLaunchKernelGGL(fpfh_kernel, dim3(blocks), dim3(kT), 0, st, (const int*)nbr, (const double*)nbr_d2, (const int*)cnt, (const double*)spfh,
-                       n, max_nn, feature);
-    return ape::check_launch("ape_fpfh_f64");
-}
-
-extern "C" size_t ape_feature_nn1_workspace_bytes(int ns, int nt)
+size_t nn_ws(int ns, int nt, int live)
 {
     if (ns < 1) ns = 1;
     if (nt < 1) nt = 1;
-    const size_t s = (size_t)nn_slices(ns, nt);
+    const size_t s = (size_t)nn_slices(ns, nt, live);
     return align_up(s * ns * 8) + align_up(s * ns * 4);
 }
 
-extern "C" int ape_feature_nn1_f64(const double* src_feature, int ns, const double* tgt_feature, int nt, int* nn, void* ws, size_t ws_bytes,
-                                   void* stream)
-{
-    if (!src_feature || !tgt_feature || !nn || !ws || ns < 0 || nt < 1) return APE_EINVAL;
-    if (ns == 0) return APE_OK;
-    if (ws_bytes < ape_feature_nn1_workspace_bytes(ns, nt)) return APE_EWORKSPACE;
-    const int nslice0 = nn_slices(ns, nt);
-    const int slice = ape::ceil_div(ape::ceil_div(nt, nslice0), kNNTile) * kNNTile;
-    const int nslice = ape::ceil_div(nt, slice);
-    double* part_d = (double*)ws;
-    int* part_i = (int*)((char*)ws + align_up((size_t)nslice0 * ns * 8));
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(feature_nn_kernel, dim3(ape::ceil_div(ns, kNNT), nslice), dim3(kNNT), 0, st, src_feature, ns, tgt_feature, nt, slice, part_d, part_i);
-    hipLaunchKernelGGL(feature_nn_merge_kernel, dim3(ape::ceil_div(ns, kT) > 1024 ? 1024 : ape::ceil_div(ns, kT)), dim3(kT), 0, st,
-                       (const double*)part_d, (const int*)part_i, ns, nslice, nn);
-    return ape::check_launch("ape_feature_nn1_f64");
-}
-
-extern "C" size_t ape_ransac_workspace_bytes(int ns, int chunk, int max_validation)
+size_t ransac_ws(int ns, int chunk, int max_validation)
 {
     if (ns < 1) ns = 1;
     if (chunk < 1) chunk = 1;
@@ -501,6 +522,197 @@ extern "C" size_t ape_ransac_workspace_bytes(int ns, int chunk, int max_validati
            align_up((size_t)max_validation * validate_blocks(ns) * 2 * 8) + align_up((size_t)max_validation * 3 * 8);
 }
 
+int live_pairs(int nb, const int* ns, const int* nt)
+{
+    int live = 0;
+    for (int c = 0; c < nb; ++c) live += (ns[c] > 0 && nt[c] > 0) ? 1 : 0;
+    return live;
+}
+
+// ---- the launch code: nb records each, the one-pair entry points call it with nb = 1 ----------------------------------------------------
+// both FPFH passes of nb clouds (g[c].n points each, 0: skipped); workspace: the clouds' fpfh_ws regions one after the other
+int fpfh_launch(int nb, const Grid* g, const double* const* pts, const double* const* nrm, double radius, int max_nn, double* const* feature,
+                void* ws, size_t ws_bytes, hipStream_t st, const char* what)
+{
+    size_t need = 0;
+    for (int c = 0; c < nb; ++c) need += fpfh_ws(g[c].n, max_nn);
+    if (ws_bytes < need) return APE_EWORKSPACE;
+    Batch<BFpfh> b{};
+    char* p = (char*)ws;
+    int mg = 0;
+    for (int c = 0; c < nb; ++c) {
+        const int n = g[c].n;
+        const size_t m = (size_t)(n < 1 ? 1 : n);
+        int* nbr = (int*)p;          p += align_up(m * max_nn * 4);
+        double* nbr_d2 = (double*)p; p += align_up(m * max_nn * 8);
+        int* cnt = (int*)p;          p += align_up(m * 4);
+        double* spfh = (double*)p;   p += align_up(m * kBins * 8);
+        const int gx = n > 0 ? ape::ceil_div((long)n * kG, (long)kT) : 0;
+        b.t[c] = BFpfh{g[c], pts[c], nrm[c], nbr, nbr_d2, cnt, spfh, feature[c], n, gx};
+        mg = gx > mg ? gx : mg;
+    }
+    if (mg == 0) return APE_OK;
+    hipLaunchKernelGGL(fpfh_spfh_kernel, dim3(mg, nb), dim3(kT), 0, st, b, radius * radius, max_nn);
+    hipLaunchKernelGGL(fpfh_kernel, dim3(mg, nb), dim3(kT), 0, st, b, max_nn);
+    return ape::check_launch(what);
+}
+
+// nearest target feature for nb (source, target) feature pairs (a pair with ns or nt == 0 is skipped); workspace: the pairs' nn_ws regions
+int nn_launch(int nb, const double* const* src, const int* ns, const double* const* tgt, const int* nt, int* const* nn, void* ws, size_t ws_bytes,
+              hipStream_t st, const char* what)
+{
+    const int live = live_pairs(nb, ns, nt);
+    if (live == 0) return APE_OK;
+    size_t need = 0;
+    for (int c = 0; c < nb; ++c) need += (ns[c] > 0 && nt[c] > 0) ? nn_ws(ns[c], nt[c], live) : 0;
+    if (ws_bytes < need) return APE_EWORKSPACE;
+    Batch<BNN> b{};
+    char* p = (char*)ws;
+    int mgx = 0, mgy = 0, mgm = 0;
+    for (int c = 0; c < nb; ++c) {
+        if (ns[c] <= 0 || nt[c] <= 0) continue;              // the zeroed record: gx = nslice = ns = 0
+        const int nslice0 = nn_slices(ns[c], nt[c], live);
+        const int slice = ape::ceil_div(ape::ceil_div(nt[c], nslice0), kNNTile) * kNNTile;
+        const int nslice = ape::ceil_div(nt[c], slice);
+        double* part_d = (double*)p;
+        int* part_i = (int*)(p + align_up((size_t)nslice0 * ns[c] * 8));
+        p += nn_ws(ns[c], nt[c], live);
+        const int gx = ape::ceil_div(ns[c], kNNT);
+        const int gm = ape::ceil_div(ns[c], kT) > 1024 ? 1024 : ape::ceil_div(ns[c], kT);
+        b.t[c] = BNN{src[c], tgt[c], part_d, part_i, nn[c], ns[c], nt[c], slice, nslice, gx};
+        mgx = gx > mgx ? gx : mgx;
+        mgy = nslice > mgy ? nslice : mgy;
+        mgm = gm > mgm ? gm : mgm;
+    }
+    hipLaunchKernelGGL(feature_nn_kernel, dim3(mgx, mgy, nb), dim3(kNNT), 0, st, b);
+    hipLaunchKernelGGL(feature_nn_merge_kernel, dim3(mgm, nb), dim3(kT), 0, st, b);
+    return ape::check_launch(what);
+}
+
+// one chunk of iterations for nb pairs; kept[c] / n_kept[c] on the device; workspace: the pairs' ransac_ws(ns, n_it, max_validation) regions
+int hyp_launch(int nb, const Hyp* h, int it_begin, int n_it, int max_validation, int* const* kept, int* const* n_kept, void* ws, size_t ws_bytes,
+               hipStream_t st, const char* what)
+{
+    if (n_it == 0) return APE_OK;
+    size_t need = 0;
+    for (int c = 0; c < nb; ++c) need += ransac_ws(h[c].ns, n_it, max_validation);
+    if (ws_bytes < need) return APE_EWORKSPACE;
+    const int nblk = ape::ceil_div(n_it, kT);
+    Batch<BHyp> b{};
+    char* p = (char*)ws;
+    for (int c = 0; c < nb; ++c) {
+        b.t[c] = BHyp{h[c], kept[c], n_kept[c], (int*)p, (int*)(p + align_up((size_t)nblk * kT * 4))};
+        p += ransac_ws(h[c].ns, n_it, max_validation);
+    }
+    hipLaunchKernelGGL(ransac_hyp_kernel, dim3(nblk, nb), dim3(kT), 0, st, b, it_begin, n_it, max_validation);
+    hipLaunchKernelGGL(ransac_append_kernel, dim3(1, nb), dim3(kT), 0, st, b, nblk, max_validation);
+    return ape::check_launch(what);
+}
+
+// models, validation and selection of nb pairs (nk[c] kept iterations, host counts); workspace: the pairs' ransac_ws(ns, 1, max(nk, 1))
+// regions; fr[c] (may be NULL): the caller's [nk][3] array instead of the workspace's
+int validate_launch(int nb, const Grid* g, const Hyp* h, const int* const* kept, const int* nk, double max_dist, double* result, double* const* fr,
+                    void* ws, size_t ws_bytes, hipStream_t st, const char* what)
+{
+    size_t need = 0;
+    for (int c = 0; c < nb; ++c) need += ransac_ws(h[c].ns, 1, nk[c]);
+    if (ws_bytes < need) return APE_EWORKSPACE;
+    Batch<BVal> b{};
+    char* base = (char*)ws;
+    int mh = 0, mG = 0;
+    for (int c = 0; c < nb; ++c) {
+        const int mv = nk[c] < 1 ? 1 : nk[c];
+        const int G = validate_blocks(h[c].ns);
+        char* p = base + align_up((size_t)kT * 4) + align_up(4);
+        double* T12 = (double*)p;  p += align_up((size_t)mv * 12 * 8);
+        double* part = (double*)p; p += align_up((size_t)mv * G * 2 * 8);
+        b.t[c] = BVal{g[c], h[c], kept[c], T12, part, fr && fr[c] ? fr[c] : (double*)p, result + (size_t)c * 24, nk[c], G};
+        base += ransac_ws(h[c].ns, 1, nk[c]);
+        mh = nk[c] > mh ? nk[c] : mh;
+        mG = G > mG ? G : mG;
+    }
+    if (mh > 0) {
+        hipLaunchKernelGGL(ransac_models_kernel, dim3(ape::ceil_div(mh, 64), nb), dim3(64), 0, st, b);
+        hipLaunchKernelGGL(ransac_validate_kernel, dim3(mG, mh, nb), dim3(kT), 0, st, b, max_dist * max_dist);
+    }
+    hipLaunchKernelGGL(ransac_select_kernel, dim3(1, nb), dim3(kT), 0, st, b);
+    return ape::check_launch(what);
+}
+
+}  // namespace
+
+#define GRID_ARGS const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n, double cell
+#define MAKE_GRID Grid g{sorted, (const u64*)keys, order, origin3, n, cell}
+#define BGRID_ARGS const double* const* sorted, const unsigned long long* const* keys, const unsigned* const* order, const double* const* origin3, const int* gn, double cell
+#define BGRID(c) Grid{sorted[c], (const u64*)keys[c], order[c], origin3[c], gn[c], cell}
+#define APE_BATCH_CHECK(nb) if ((nb) < 1 || (nb) > kMaxBatch) return APE_EINVAL
+
+extern "C" size_t ape_fpfh_workspace_bytes(int n, int max_nn) { return fpfh_ws(n, max_nn); }
+
+extern "C" int ape_fpfh_f64(GRID_ARGS, const double* pts, const double* normals, double radius, int max_nn, double* feature, void* ws,
+                            size_t ws_bytes, void* stream)
+{
+    if (!sorted || !keys || !order || !origin3 || !pts || !normals || !feature || !ws || n < 1 || !(radius > 0) || radius > cell ||
+        max_nn < 1 || max_nn > kFeatMaxNN)
+        return APE_EINVAL;
+    MAKE_GRID;
+    return fpfh_launch(1, &g, &pts, &normals, radius, max_nn, &feature, ws, ws_bytes, (hipStream_t)stream, "ape_fpfh_f64");
+}
+
+extern "C" size_t ape_fpfh_batch_workspace_bytes(int nb, const int* n_host, int max_nn)
+{
+    size_t s = 0;
+    for (int c = 0; n_host && c < nb && c < kMaxBatch; ++c) s += fpfh_ws(n_host[c], max_nn);
+    return s;
+}
+
+extern "C" int ape_fpfh_batch_f64(int nb, BGRID_ARGS, const double* const* pts, const double* const* normals, double radius, int max_nn,
+                                  double* const* feature, void* ws, size_t ws_bytes, void* stream)
+{
+    APE_BATCH_CHECK(nb);
+    if (!sorted || !keys || !order || !origin3 || !gn || !pts || !normals || !feature || !ws || !(radius > 0) || radius > cell || max_nn < 1 ||
+        max_nn > kFeatMaxNN)
+        return APE_EINVAL;
+    Grid g[kMaxBatch];
+    for (int c = 0; c < nb; ++c) {
+        if (gn[c] < 0 || (gn[c] > 0 && (!sorted[c] || !keys[c] || !order[c] || !origin3[c] || !pts[c] || !normals[c] || !feature[c]))) return APE_EINVAL;
+        g[c] = BGRID(c);
+    }
+    return fpfh_launch(nb, g, pts, normals, radius, max_nn, feature, ws, ws_bytes, (hipStream_t)stream, "ape_fpfh_batch_f64");
+}
+
+extern "C" size_t ape_feature_nn1_workspace_bytes(int ns, int nt) { return nn_ws(ns, nt, 1); }
+
+extern "C" int ape_feature_nn1_f64(const double* src_feature, int ns, const double* tgt_feature, int nt, int* nn, void* ws, size_t ws_bytes,
+                                   void* stream)
+{
+    if (!src_feature || !tgt_feature || !nn || !ws || ns < 0 || nt < 1) return APE_EINVAL;
+    return nn_launch(1, &src_feature, &ns, &tgt_feature, &nt, &nn, ws, ws_bytes, (hipStream_t)stream, "ape_feature_nn1_f64");
+}
+
+extern "C" size_t ape_feature_nn1_batch_workspace_bytes(int nb, const int* ns_host, const int* nt_host)
+{
+    if (!ns_host || !nt_host || nb < 1 || nb > kMaxBatch) return 0;
+    const int live = live_pairs(nb, ns_host, nt_host);
+    size_t s = 0;
+    for (int c = 0; c < nb; ++c) s += (ns_host[c] > 0 && nt_host[c] > 0) ? nn_ws(ns_host[c], nt_host[c], live) : 0;
+    return s;
+}
+
+extern "C" int ape_feature_nn1_batch_f64(int nb, const double* const* src_feature, const int* ns, const double* const* tgt_feature, const int* nt,
+                                         int* const* nn, void* ws, size_t ws_bytes, void* stream)
+{
+    APE_BATCH_CHECK(nb);
+    if (!src_feature || !ns || !tgt_feature || !nt || !nn) return APE_EINVAL;
+    for (int c = 0; c < nb; ++c) {
+        if (ns[c] < 0 || nt[c] < 0) return APE_EINVAL;
+        if (ns[c] > 0 && nt[c] > 0 && (!src_feature[c] || !tgt_feature[c] || !nn[c] || !ws)) return APE_EINVAL;
+    }
+    return nn_launch(nb, src_feature, ns, tgt_feature, nt, nn, ws, ws_bytes, (hipStream_t)stream, "ape_feature_nn1_batch_f64");
+}
+
+extern "C" size_t ape_ransac_workspace_bytes(int ns, int chunk, int max_validation) { return ransac_ws(ns, chunk, max_validation); }
+
 extern "C" int ape_ransac_hypotheses_f64(const double* src, int ns, const double* tgt, int nt, const int* nn, int ransac_n, long seed,
                                          double edge_sim, double dist_thr, int it_begin, int n_it, int max_validation, int* kept, int* n_kept,
                                          void* ws, size_t ws_bytes, void* stream)
@@ -508,16 +720,36 @@ extern "C" int ape_ransac_hypotheses_f64(const double* src, int ns, const double
     if (!src || !tgt || !nn || !kept || !n_kept || !ws || ns < 1 || nt < 1 || ransac_n < 3 || ransac_n > kMaxRansacN || it_begin < 0 ||
         n_it < 0 || max_validation < 1)
         return APE_EINVAL;
-    if (n_it == 0) return APE_OK;
-    if (ws_bytes < ape_ransac_workspace_bytes(ns, n_it, max_validation)) return APE_EWORKSPACE;
-    const int nb = ape::ceil_div(n_it, kT);
-    int* blist = (int*)ws;
-    int* bcount = (int*)((char*)ws + align_up((size_t)nb * kT * 4));
     const Hyp h{src, ns, tgt, nt, nn, ransac_n, (u64)seed, edge_sim, dist_thr};
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(ransac_hyp_kernel, dim3(nb), dim3(kT), 0, st, h, it_begin, n_it, (const int*)n_kept, max_validation, blist, bcount);
-    hipLaunchKernelGGL(ransac_append_kernel, dim3(1), dim3(kT), 0, st, (const int*)blist, (const int*)bcount, nb, max_validation, kept, n_kept);
-    return ape::check_launch("ape_ransac_hypotheses_f64");
+    return hyp_launch(1, &h, it_begin, n_it, max_validation, &kept, &n_kept, ws, ws_bytes, (hipStream_t)stream, "ape_ransac_hypotheses_f64");
+}
+
+extern "C" size_t ape_ransac_batch_workspace_bytes(int nb, const int* ns_host, int chunk, int max_validation)
+{
+    size_t s = 0;
+    for (int c = 0; ns_host && c < nb && c < kMaxBatch; ++c) s += ransac_ws(ns_host[c], chunk, max_validation);
+    return s;
+}
+
+extern "C" int ape_ransac_hypotheses_batch_f64(int nb, const double* const* src, const int* ns, const double* const* tgt, const int* nt,
+                                               const int* const* nn, int ransac_n, const long* seed_host, double edge_sim, double dist_thr,
+                                               int it_begin, int n_it, int max_validation, int* kept, int* n_kept, void* ws, size_t ws_bytes,
+                                               void* stream)
+{
+    APE_BATCH_CHECK(nb);
+    if (!src || !ns || !tgt || !nt || !nn || !seed_host || !kept || !n_kept || !ws || ransac_n < 3 || ransac_n > kMaxRansacN || it_begin < 0 ||
+        n_it < 0 || max_validation < 1)
+        return APE_EINVAL;
+    Hyp h[kMaxBatch];
+    int* kp[kMaxBatch];
+    int* np[kMaxBatch];
+    for (int c = 0; c < nb; ++c) {
+        if (!src[c] || !tgt[c] || !nn[c] || ns[c] < 1 || nt[c] < 1) return APE_EINVAL;
+        h[c] = Hyp{src[c], ns[c], tgt[c], nt[c], nn[c], ransac_n, (u64)seed_host[c], edge_sim, dist_thr};
+        kp[c] = kept + (size_t)c * max_validation;
+        np[c] = n_kept + c;
+    }
+    return hyp_launch(nb, h, it_begin, n_it, max_validation, kp, np, ws, ws_bytes, (hipStream_t)stream, "ape_ransac_hypotheses_batch_f64");
 }
 
 extern "C" int ape_ransac_validate_f64(GRID_ARGS, const double* src, int ns, const double* tgt, int nt, const int* nn, int ransac_n,
@@ -527,20 +759,30 @@ extern "C" int ape_ransac_validate_f64(GRID_ARGS, const double* src, int ns, con
     if (!sorted || !keys || !order || !origin3 || !src || !tgt || !nn || !result || !ws || n < 1 || ns < 1 || nt != n || ransac_n < 3 ||
         ransac_n > kMaxRansacN || n_kept < 0 || n_kept > 65535 || (n_kept > 0 && !kept) || !(max_dist > 0) || max_dist > cell)
         return APE_EINVAL;
-    const int mv = n_kept < 1 ? 1 : n_kept;
-    if (ws_bytes < ape_ransac_workspace_bytes(ns, 1, mv)) return APE_EWORKSPACE;
-    char* p = (char*)ws + align_up((size_t)kT * 4) + align_up(4);
-    double* T12 = (double*)p;  p += align_up((size_t)mv * 12 * 8);
-    double* part = (double*)p; p += align_up((size_t)mv * validate_blocks(ns) * 2 * 8);
-    double* fr = fit_rmse ? fit_rmse : (double*)p;
     MAKE_GRID;
     const Hyp h{src, ns, tgt, nt, nn, ransac_n, (u64)seed, -1.0, -1.0};
-    hipStream_t st = (hipStream_t)stream;
-    const int G = validate_blocks(ns);
-    if (n_kept > 0) {
-        hipLaunchKernelGGL(ransac_models_kernel, dim3(ape::ceil_div(n_kept, 64)), dim3(64), 0, st, h, kept, n_kept, T12);
-        hipLaunchKernelGGL(ransac_validate_kernel, dim3(G, n_kept), dim3(kT), 0, st, g, src, ns, (const double*)T12, max_dist * max_dist, part);
+    return validate_launch(1, &g, &h, &kept, &n_kept, max_dist, result, &fit_rmse, ws, ws_bytes, (hipStream_t)stream, "ape_ransac_validate_f64");
+}
+
+extern "C" int ape_ransac_validate_batch_f64(int nb, BGRID_ARGS, const double* const* src, const int* ns, const double* const* tgt, const int* nt,
+                                             const int* const* nn, int ransac_n, const long* seed_host, const int* kept, int kept_stride,
+                                             const int* n_kept_host, double max_dist, double* result, double* const* fit_rmse, void* ws,
+                                             size_t ws_bytes, void* stream)
+{
+    APE_BATCH_CHECK(nb);
+    if (!sorted || !keys || !order || !origin3 || !gn || !src || !ns || !tgt || !nt || !nn || !seed_host || !kept || !n_kept_host || !result || !ws ||
+        ransac_n < 3 || ransac_n > kMaxRansacN || kept_stride < 1 || !(max_dist > 0) || max_dist > cell)
+        return APE_EINVAL;
+    Grid g[kMaxBatch];
+    Hyp h[kMaxBatch];
+    const int* kp[kMaxBatch];
+    for (int c = 0; c < nb; ++c) {
+        if (!sorted[c] || !keys[c] || !order[c] || !origin3[c] || !src[c] || !tgt[c] || !nn[c] || gn[c] < 1 || ns[c] < 1 || nt[c] != gn[c] ||
+            n_kept_host[c] < 0 || n_kept_host[c] > 65535 || n_kept_host[c] > kept_stride)
+            return APE_EINVAL;
+        g[c] = BGRID(c);
+        h[c] = Hyp{src[c], ns[c], tgt[c], nt[c], nn[c], ransac_n, (u64)seed_host[c], -1.0, -1.0};
+        kp[c] = kept + (size_t)c * kept_stride;
     }
-    hipLaunchKernelGGL(ransac_select_kernel, dim3(1), dim3(kT), 0, st, (const double*)part, G, n_kept, ns, (const double*)T12, kept, fr, result);
-    return ape::check_launch("ape_ransac_validate_f64");
+    return validate_launch(nb, g, h, kp, n_kept_host, max_dist, result, fit_rmse, ws, ws_bytes, (hipStream_t)stream, "ape_ransac_validate_batch_f64");
 }

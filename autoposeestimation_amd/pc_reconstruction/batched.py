@@ -10,6 +10,12 @@ implementation: the methods of `PointCloud` and `pointcloud.registration_icp` ca
 
     get_surface_batch(views, ...)          = [open3d_utils.get_surface(v) for v in views]              (reference open3d_utils.py:171-213)
     fuse_surfaces_batch(chains, ...)       = [open3d_utils.fuse_surfaces(c) for c in chains]           (create_pointcloud.py:288-312)
+
+The global registration that `global_regression=True` puts in front of every ICP (reference open3d_utils.py:19-49) advances in lock step
+too: `compute_fpfh_feature`, `feature_nn` and `registration_ransac` below take lists of clouds / pairs and drive the batched entry points
+of csrc/registration.hip (two FPFH launches for all clouds, one hypothesis chunk for every pair that is not yet full, one copy of all
+`n_kept` words per chunk, one validation for all pairs).  `pointcloud.registration_ransac_based_on_feature_matching` stays the one-pair
+reference of it (the same kernels launched with nb = 1); tests/test_gpu_registration_batch.py compares the two bit for bit.
 """
 import ctypes
 import math
@@ -406,6 +412,153 @@ def registration_icp(sources, targets, max_correspondence_distance, inits, kind,
             for i, st in enumerate(states)]
 
 
+# ---- global registration over lists of clouds / pairs (csrc/registration.hip, batched entry points) -----------------------------------------
+def _longs(values):
+    return (ctypes.c_long * len(values))(*[int(v) for v in values])
+
+
+def compute_fpfh_feature(clouds, radius, max_nn):
+    """[pointcloud.compute_fpfh_feature(c, KDTreeSearchParamHybrid(radius, max_nn))]: both passes of up to 16 clouds in two launches; the
+    clouds need normals; an empty cloud gives an empty Feature"""
+    radius, max_nn = float(radius), int(max_nn)
+    out = [None] * len(clouds)
+    live = []
+    for i, c in enumerate(clouds):
+        if len(c) == 0:
+            out[i] = PC.Feature(device=c.device)
+            continue
+        if not c.has_normals():
+            raise RuntimeError("compute_fpfh_feature requires normals (estimate_normals first)")
+        live.append(i)
+    sub = [clouds[i] for i in live]
+    grids = build_grids(sub, radius)
+    L = _lib.lib()
+    for idx in _chunks(sub):
+        dev = sub[idx[0]].device
+        ns = [len(sub[j]) for j in idx]
+        pts = [sub[j]._p for j in idx]
+        nrm = [sub[j]._n for j in idx]
+        for t in pts + nrm:
+            _lib.dptr(t, _D)                             # device, contiguous, float64
+        feats = [torch.empty(n, 33, dtype=_D, device=dev) for n in ns]
+        ws = torch.empty(L.ape_fpfh_batch_workspace_bytes(len(idx), _ints(ns), max_nn), dtype=torch.uint8, device=dev)
+        _lib.call.ape_fpfh_batch_f64(len(idx), *_grid_args([grids[j] for j in idx]), radius, _ptrs(pts), _ptrs(nrm), radius, max_nn, _ptrs(feats),
+                                     _lib.dptr(ws), ws.numel(), _st())
+        for k, j in enumerate(idx):
+            out[live[j]] = PC.Feature(feats[k])
+    return out
+
+
+def feature_nn(source_features, target_features):
+    """[pointcloud.feature_nn(s, t)]: the index of the nearest target feature of every source feature, int32 on the device; all -1 for a
+    pair without target features"""
+    n = len(source_features)
+    out = [None] * n
+    live = []
+    for i in range(n):
+        ns, nt = source_features[i].num(), target_features[i].num()
+        if ns == 0 or nt == 0:
+            out[i] = torch.empty(ns, dtype=torch.int32, device=source_features[i].t.device).fill_(-1)
+        else:
+            live.append(i)
+    L = _lib.lib()
+    for idx in _chunks(live):
+        sel = [live[j] for j in idx]
+        fs = [source_features[i].t.contiguous() for i in sel]
+        ft = [target_features[i].t.contiguous() for i in sel]
+        for t in fs + ft:
+            _lib.dptr(t, _D)
+        dev = fs[0].device
+        ns, nt = [int(t.shape[0]) for t in fs], [int(t.shape[0]) for t in ft]
+        nn = [torch.empty(x, dtype=torch.int32, device=dev) for x in ns]
+        ws = torch.empty(max(L.ape_feature_nn1_batch_workspace_bytes(len(sel), _ints(ns), _ints(nt)), 1), dtype=torch.uint8, device=dev)
+        _lib.call.ape_feature_nn1_batch_f64(len(sel), _ptrs(fs), _ints(ns), _ptrs(ft), _ints(nt), _ptrs(nn), _lib.dptr(ws), ws.numel(), _st())
+        for k, i in enumerate(sel):
+            out[i] = nn[k]
+    return out
+
+
+def registration_ransac(sources, targets, source_features, target_features, max_correspondence_distance, ransac_n, edge_similarity,
+                        distance_threshold, criteria, seeds):
+    """[pointcloud.registration_ransac_based_on_feature_matching(s, t, fs, ft, max_correspondence_distance, None, ransac_n, [edge-length
+    checker(edge_similarity), distance checker(distance_threshold)], criteria, seed)] for pairs advancing together (a threshold of None:
+    no such checker).  One launch pair draws a chunk of iterations for every pair that is not yet full -- a full pair's blocks read its
+    own device counter and return -- and one copy brings all `n_kept` words back; the loop ends when every pair is full or max_iteration
+    is reached.  The kept list of a pair is its first max_validation passing iterations in iteration order, whatever the schedule, so the
+    results (`validated` and `iterations` included) equal the one-pair call's bit for bit."""
+    n = len(sources)
+    edge_sim = -1.0 if edge_similarity is None else float(edge_similarity)
+    dist_thr = -1.0 if distance_threshold is None else float(distance_threshold)
+    ransac_n, max_dist = int(ransac_n), float(max_correspondence_distance)
+
+    def empty():
+        r = PC.RegistrationResult(np.eye(4), 0.0, 0.0, 0)
+        r.validated, r.iterations = np.zeros(0, np.int64), 0
+        return r
+
+    out = [empty() for _ in range(n)]
+    if ransac_n < 3 or max_dist <= 0.0:
+        return out
+    if ransac_n > 16:
+        raise ValueError("ransac_n > 16 is not supported")
+    for i in range(n):
+        if source_features[i].num() != len(sources[i]) or target_features[i].num() != len(targets[i]):
+            raise ValueError("features and clouds differ in size")
+    max_it, max_val = int(criteria.max_iteration), int(criteria.max_validation)
+    if max_val > 65535:
+        raise ValueError("max_validation > 65535 is not supported")
+    live = [i for i in range(n) if len(sources[i]) and len(targets[i])]
+    if not live or max_it <= 0 or max_val <= 0:
+        return out
+    nns = feature_nn([source_features[i] for i in live], [target_features[i] for i in live])
+    grids = build_grids([targets[i] for i in live], max_dist)
+    L = _lib.lib()
+    for idx in _chunks(live):
+        sel = [live[j] for j in idx]
+        nb = len(sel)
+        dev = sources[sel[0]].device
+        ns, nt = [len(sources[i]) for i in sel], [len(targets[i]) for i in sel]
+        src, tgt = [sources[i]._p for i in sel], [targets[i]._p for i in sel]
+        for t in src + tgt:
+            _lib.dptr(t, _D)
+        pair = (_ptrs(src), _ints(ns), _ptrs(tgt), _ints(nt), _ptrs([nns[j] for j in idx]), ransac_n, _longs([seeds[i] for i in sel]))
+        chunk, cap = min(PC._RANSAC_CHUNK[0], max_it), min(PC._RANSAC_CHUNK[1], max_it)
+        ws = torch.empty(L.ape_ransac_batch_workspace_bytes(nb, _ints(ns), max(chunk, cap), max_val), dtype=torch.uint8, device=dev)
+        kept = torch.empty(nb, max_val, dtype=torch.int32, device=dev)
+        n_kept = torch.zeros(nb, dtype=torch.int32, device=dev)
+        it = 0
+        while it < max_it:                               # bounded by max_iteration; a full pair's list stops growing on the device
+            c = min(chunk, max_it - it)
+            _lib.call.ape_ransac_hypotheses_batch_f64(nb, *pair, edge_sim, dist_thr, it, c, max_val, _lib.dptr(kept), _lib.dptr(n_kept),
+                                                      _lib.dptr(ws), ws.numel(), _st())
+            it += c
+            k = n_kept.cpu().numpy()                     # ONE copy of all pairs' counters per chunk
+            if (k >= max_val).all():
+                break
+            chunk = min(chunk * 2, cap)
+        res = torch.empty(nb, 24, dtype=_D, device=dev)
+        _lib.call.ape_ransac_validate_batch_f64(nb, *_grid_args([grids[j] for j in idx]), max_dist, *pair, _lib.dptr(kept), max_val, _ints(k),
+                                                max_dist, _lib.dptr(res), None, _lib.dptr(ws), ws.numel(), _st())
+        r_all, kept_all = res.cpu().numpy(), kept.cpu().numpy()
+        for m, i in enumerate(sel):
+            r, km = r_all[m], int(k[m])
+            o = PC.RegistrationResult(r[:16].reshape(4, 4).copy(), float(r[16]), float(r[17]), int(round(r[18])))
+            o.validated = kept_all[m, :km].astype(np.int64)
+            o.iterations = int(o.validated[-1]) + 1 if km >= max_val else it
+            out[i] = o
+    return out
+
+
+def execute_global_registration_batch(sources_down, targets_down, voxel_size):
+    """[open3d_utils.execute_global_registration(s, t, None, None, voxel_size)] (reference :28-49): FPFH (radius 5 * voxel, max_nn 100) of
+    all clouds, then RANSAC on the feature matches: distance 1.5 * voxel, ransac_n 4, edge length 0.9, 4 000 000 iterations / 500
+    validations, seed 0"""
+    n = len(sources_down)
+    feats = compute_fpfh_feature(list(sources_down) + list(targets_down), voxel_size * 5, 100)
+    thr = voxel_size * 1.5
+    return registration_ransac(sources_down, targets_down, feats[:n], feats[n:], thr, 4, 0.9, thr, PC.RANSACConvergenceCriteria(4000000, 500), [0] * n)
+
+
 # ---- the two stages of the label path, in lock step over chains -------------------------------------------------------------------------
 def get_surface_batch(views, intr, min_friends, min_dist, nb_neighbors, voxel_size, device="cuda"):
     """[open3d_utils.get_surface(label, depth, intr, robot2cam, ...)] for many views at once (reference open3d_utils.py:171-213)"""
@@ -418,13 +571,17 @@ def get_surface_batch(views, intr, min_friends, min_dist, nb_neighbors, voxel_si
     return remove_statistical_outlier(clouds, nb_neighbors, std_ratios, hint)
 
 
-def icp_regression_batch(targets, sources, voxel_size, threshold, icp_point2point=True, icp_point2plane=True):
-    """[open3d_utils.icp_regression(t, s, ...)[2]] (reference :63-122): down-sample + normals of both clouds, p2p then p2plane ICP"""
+def icp_regression_batch(targets, sources, voxel_size, threshold, icp_point2point=True, icp_point2plane=True, global_regression=False):
+    """[open3d_utils.icp_regression(t, s, ...)[2]] (reference :63-122): down-sample + normals of both clouds, p2p then p2plane ICP;
+    global_regression: the RANSAC transformations of execute_global_registration_batch are the initial guesses of the ICP stages, or the
+    result when both are off"""
     n = len(targets)
     tg = estimate_normals(voxel_down_sample(targets, voxel_size), voxel_size * 2, 30)        # preprocess_point_cloud(target.clone(), voxel)
     sr = estimate_normals(voxel_down_sample(sources, voxel_size), voxel_size * 2, 30)
     criteria = PC.ICPConvergenceCriteria(relative_fitness=1e-2, relative_rmse=1e-2, max_iteration=100)
     Ts = [np.identity(4) for _ in range(n)]
+    if global_regression:
+        Ts = [r.transformation for r in execute_global_registration_batch(sr, tg, voxel_size)]
     if icp_point2point:
         Ts = registration_icp(sr, tg, threshold, Ts, 0, criteria)
     if icp_point2plane:
@@ -432,7 +589,8 @@ def icp_regression_batch(targets, sources, voxel_size, threshold, icp_point2poin
     return Ts
 
 
-def fuse_surfaces_batch(chains, voxel_size=2, threshold=10, voxel_size_out=None, icp_point2point=True, icp_point2plane=False):
+def fuse_surfaces_batch(chains, voxel_size=2, threshold=10, voxel_size_out=None, icp_point2point=True, icp_point2plane=False,
+                        global_regression=False):
     """[open3d_utils.fuse_surfaces(surfaces, ...)] for several chains in lock step: step v registers every chain's v-th surface to that chain's
     accumulating cloud (create_pointcloud.py:288-312).  Empty surfaces are skipped, a chain's first surface starts its cloud -- as in the
     one-chain loop.  -> [(cloud or None, [T per surface])]"""
@@ -455,7 +613,7 @@ def fuse_surfaces_batch(chains, voxel_size=2, threshold=10, voxel_size_out=None,
         if not work:
             continue
         srcs = [chains[ci][v] for ci in work]
-        Ts = icp_regression_batch([acc[ci] for ci in work], srcs, voxel_size, threshold, icp_point2point, icp_point2plane)
+        Ts = icp_regression_batch([acc[ci] for ci in work], srcs, voxel_size, threshold, icp_point2point, icp_point2plane, global_regression)
         moved = transform(concat(srcs), Ts)                                               # source.clone().transform(T)
         merged = voxel_down_sample(concat(moved, [acc[ci] for ci in work]), voxel_size)   # cat([source, acc]) -> voxel_down_sample
         for k, ci in enumerate(work):

@@ -214,12 +214,12 @@ def fuse_chains(chains, intr, voxel_size=2, threshold=10, min_friends=20, min_di
     of all chains is spread over the ranks, one padded all-gather, then every rank runs the sequential fusion of the chains it owns
     (chain i -> rank i % world) -- the chains' ICP sequences proceed in parallel on different GPUs.
     Returns {chain index: (cloud, [T per view])} for this rank's chains; each is bit-identical to the single-rank fuse_views of it.
-    global_regression=True runs FPFH + RANSAC before every registration (icp_regression) and takes the sequential per-chain route:
-    the batched lock-step form is ICP only."""
+    global_regression=True runs FPFH + RANSAC before every registration (icp_regression); the lock-step form advances it for all chains
+    at once too (batched.execute_global_registration_batch), with the same clouds and transformations bit for bit."""
     from autoposeestimation_amd import sharding
     make_set, fuse = _chain_workers(intr, voxel_size, threshold, min_friends, min_dist, nb_neighbors, voxel_size_out, icp_point2point,
                                     icp_point2plane, global_regression)
-    if not USE_BATCHED or global_regression:
+    if not USE_BATCHED:
         return sharding.sharded_chains([list(v) for v in chains], make_set, fuse, dist, load=_load_view)
     # lock-step batched form (pc_reconstruction/batched.py): one host thread, one launch per step for all of this rank's views / chains
     from autoposeestimation_amd.pc_reconstruction import batched as B
@@ -239,7 +239,7 @@ def fuse_chains(chains, intr, voxel_size=2, threshold=10, min_friends=20, min_di
                 row.append(c)
             clouds.append(row)
         return B.fuse_surfaces_batch(clouds, voxel_size=voxel_size, threshold=threshold, voxel_size_out=voxel_size_out,
-                                     icp_point2point=icp_point2point, icp_point2plane=icp_point2plane)
+                                     icp_point2point=icp_point2point, icp_point2plane=icp_point2plane, global_regression=global_regression)
 
     return sharding.sharded_chains([list(v) for v in chains], make_set, fuse, dist, load=_load_view, make_sets=make_sets, fuse_many=fuse_many)
 

@@ -458,6 +458,37 @@ int ape_ransac_validate_f64(const double* sorted, const unsigned long long* keys
                             double cell, const double* src, int ns, const double* tgt, int nt, const int* nn, int ransac_n,
                             long seed, const int* kept, int n_kept, double max_dist, double* result, double* fit_rmse,
                             void* ws, size_t ws_bytes, void* stream);
+/* The four calls above for nb = 1..16 clouds / pairs per launch (APE_EINVAL otherwise): the kernels take a by-value table of per-pair
+ * records and the pair's index in a grid dimension, the one-pair calls above are their nb = 1 callers.  Per-pair arguments are HOST arrays
+ * [nb] of device pointers / sizes (as the `*_batch_f64` point-cloud calls); a pair's result is bit-identical to the one-pair call of it
+ * and does not depend on its slot or its neighbours.  Workspaces: the pairs' one-pair regions one after the other.
+ * FPFH of nb clouds in two launches; a cloud with gn[c] == 0 is skipped. */
+size_t ape_fpfh_batch_workspace_bytes(int nb, const int* n_host, int max_nn);
+int ape_fpfh_batch_f64(int nb, const double* const* sorted, const unsigned long long* const* keys, const unsigned* const* order,
+                       const double* const* origin3, const int* gn, double cell, const double* const* pts, const double* const* normals,
+                       double radius, int max_nn, double* const* feature, void* ws, size_t ws_bytes, void* stream);
+/* Nearest target feature for nb (source, target) feature pairs in two launches; a pair with ns[c] == 0 or nt[c] == 0 is skipped (its nn
+ * is not written).  The target range of a pair is cut into slices so that the whole launch has about 2048 blocks. */
+size_t ape_feature_nn1_batch_workspace_bytes(int nb, const int* ns_host, const int* nt_host);
+int ape_feature_nn1_batch_f64(int nb, const double* const* src_feature, const int* ns, const double* const* tgt_feature, const int* nt,
+                              int* const* nn, void* ws, size_t ws_bytes, void* stream);
+/* Workspace of the two batched RANSAC calls below (ns_host[nb] source sizes). */
+size_t ape_ransac_batch_workspace_bytes(int nb, const int* ns_host, int chunk, int max_validation);
+/* Iterations [it_begin, it_begin + n_it) for every pair whose list is not yet full: pair c draws with seed_host[c] and appends to
+ * kept[c * max_validation ..] / n_kept[c] (device, n_kept zeroed by the caller before the first chunk); a pair whose n_kept[c] has
+ * reached max_validation turns its blocks into no-ops by reading that word.  ns[c], nt[c] >= 1.  Two launches. */
+int ape_ransac_hypotheses_batch_f64(int nb, const double* const* src, const int* ns, const double* const* tgt, const int* nt,
+                                    const int* const* nn, int ransac_n, const long* seed_host, double edge_sim, double dist_thr,
+                                    int it_begin, int n_it, int max_validation, int* kept, int* n_kept, void* ws, size_t ws_bytes,
+                                    void* stream);
+/* Models, validation and selection of all pairs in three launches: pair c validates kept[c * kept_stride .. + n_kept_host[c]) against
+ * its target's grid (gn[c] == nt[c]); result[nb][24] laid out as ape_ransac_validate_f64's; fit_rmse: NULL or [nb] pointers (NULL or
+ * [n_kept_host[c]][3]). */
+int ape_ransac_validate_batch_f64(int nb, const double* const* sorted, const unsigned long long* const* keys, const unsigned* const* order,
+                                  const double* const* origin3, const int* gn, double cell, const double* const* src, const int* ns,
+                                  const double* const* tgt, const int* nt, const int* const* nn, int ransac_n, const long* seed_host,
+                                  const int* kept, int kept_stride, const int* n_kept_host, double max_dist, double* result,
+                                  double* const* fit_rmse, void* ws, size_t ws_bytes, void* stream);
 
 /* ape_conv3x3_halo_bf16 for a 64-channel layer (the segmentor's up_3, pspnet.py:51) with ape_seg_head_f32 fused into its
  * epilogue: the [B][H][W][64] activation is never written, label[B][H][W] u8 / score[B][H][W] f32 are (bit-identical to the

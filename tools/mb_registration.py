@@ -10,6 +10,14 @@ ellipsoid (scaled to hold the count), voxelised at 5 mm, subsampled to exactly N
     python tools/mb_registration.py --stats F.csv --shapes S.json
                                                   -> per kernel of that run's kernel_stats.csv: calls, average us, and the fraction of its
                                                      HBM / FP64 bound for the shapes the trace-only run wrote to S.json (no GPU needed)
+    python tools/mb_registration.py --batch N [--sizes 2000,8000] [--reps 12] [--out F.json (default profiles/r13_registration_batch.json)]
+                                                  -> N pairs per size (make_pair seeds 0..N-1) registered once as N one-pair
+                                                     icp_regression(global_regression=True) calls and once as ONE
+                                                     batched.icp_regression_batch(global_regression=True) call: same process, the two
+                                                     routes alternating, HIP events around each, median of --reps repeats after a warm-up;
+                                                     both times, their ratio and whether the transformations agree bit for bit
+    python tools/mb_registration.py --batch N --trace-only --route one|batch [--sizes 2000]
+                                                  -> three rounds of one route: the program for rocprofv3 --kernel-trace --stats
 Bounds: 6.3 TB/s HBM (what the copy benchmark reaches on this box) and 78.6 TFLOP/s FP64 vector -- the figure of AMD's
 public MI355X product page; MI355X_MICROARCH.md gives no FP64 peak.  Operation counts are FP64 arithmetic of the work the algorithm
 needs (selection compares and the SVD sweeps excluded, see the formulas), bytes the unavoidable HBM traffic (inputs once, outputs once)."""
@@ -163,6 +171,55 @@ def run(trace_only=False, shapes_out=None):
         json.dump(shapes, open(shapes_out, "w"), indent=1)
 
 
+def run_batch(nb, sizes, reps, out_path=None, trace_route=None):
+    """N one-pair calls against one lock-step call on the same N pairs (see the module docstring)"""
+    import torch
+    from autoposeestimation_amd.pc_reconstruction import batched as B
+    from autoposeestimation_amd.pc_reconstruction import open3d_utils as U
+    from autoposeestimation_amd.pc_reconstruction import pointcloud as PC
+    torch.cuda.set_device(0)
+    rows = []
+    for n in sizes:
+        clouds = []
+        for k in range(nb):
+            src, tgt, _ = make_pair(n, seed=k)
+            clouds.append((PC.PointCloud(src), PC.PointCloud(tgt)))
+
+        def one():
+            return [U.icp_regression(t, s, voxel_size=VOXEL, threshold=10, global_regression=True)[2] for s, t in clouds]
+
+        def lock():
+            return B.icp_regression_batch([t for _, t in clouds], [s for s, _ in clouds], VOXEL, 10, global_regression=True)
+
+        if trace_route:
+            for _ in range(3):
+                (one if trace_route == "one" else lock)()
+            torch.cuda.synchronize()
+            continue
+        same = all(np.array_equal(a, b) for a, b in zip(one(), lock()))      # also the first warm-up round of both routes
+        one()
+        lock()
+        torch.cuda.synchronize()
+        times = {"one": [], "lock": []}
+        for _ in range(reps):
+            for name, fn in (("one", one), ("lock", lock)):                  # alternating: drift of the box hits both alike
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[name].append(e0.elapsed_time(e1))
+        t_one, t_lock = float(np.median(times["one"])), float(np.median(times["lock"]))
+        rows.append({"n": n, "pairs": nb, "repeats": reps, "one_pair_calls_ms": round(t_one, 3), "batched_call_ms": round(t_lock, 3),
+                     "ratio_one_over_batched": round(t_one / t_lock, 3), "one_pair_ms_min_max": [round(min(times["one"]), 3), round(max(times["one"]), 3)],
+                     "batched_ms_min_max": [round(min(times["lock"]), 3), round(max(times["lock"]), 3)], "bit_identical": bool(same)})
+        print(json.dumps(rows[-1]), flush=True)
+    if out_path and rows:
+        json.dump({"what": "N one-pair icp_regression(global_regression=True) calls against one icp_regression_batch(global_regression=True) "
+                           "call on the same pairs; HIP events, medians, the routes alternating in one process (tools/mb_registration.py --batch)",
+                   "rows": rows}, open(out_path, "w"), indent=1)
+
+
 def stats(csv_path, shapes_path):
     """kernel_stats.csv of the --trace-only run -> per kernel calls, avg us and bound fractions per round over the three sizes (the
     trace-only run makes 4 rounds of the fpfh kernels per size and 3 of the others; the shapes are summed over the sizes)"""
@@ -188,7 +245,13 @@ def stats(csv_path, shapes_path):
 
 
 if __name__ == "__main__":
-    if "--stats" in sys.argv:
+    arg = lambda name, default=None: sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default  # noqa: E731
+    if "--batch" in sys.argv:
+        trace = "--trace-only" in sys.argv
+        run_batch(int(arg("--batch")), [int(x) for x in arg("--sizes", "2000" if trace else "2000,8000").split(",")], int(arg("--reps", 12)),
+                  out_path=arg("--out", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r13_registration_batch.json")),
+                  trace_route=arg("--route", "batch") if trace else None)
+    elif "--stats" in sys.argv:
         stats(sys.argv[sys.argv.index("--stats") + 1], sys.argv[sys.argv.index("--shapes") + 1])
     else:
         out = sys.argv[sys.argv.index("--shapes") + 1] if "--shapes" in sys.argv else None
