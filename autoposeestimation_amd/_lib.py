@@ -150,6 +150,14 @@ SIGNATURES = {
     "ape_sgd_step_multi_f32": [_I, _P, _F, _F, _F, _F, _I, _P],
     "ape_bgsub_train_workspace_bytes": [_I],
     "ape_bgsub_train_samples": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P],
+    # segmentor training samples (csrc/seg_train.hip): the extents of segmentation/utils.py:450-462 and ImageEnhance.Contrast's mean,
+    # then dataset.py:98-112 with the transforms of utils.py:25-66 and CropAndZoom :361-487; the 'test' mode sample
+    "ape_seg_train_workspace_bytes": [_I, _I],
+    "ape_seg_train_extents_offset": [_I],
+    "ape_seg_train_tables_offset": [_I],
+    "ape_seg_train_stats": [_P, _I, _I, _I, _P, _c.c_size_t, _P],
+    "ape_seg_train_samples": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _c.c_size_t, _P],
+    "ape_seg_plain_samples": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
 }
 
 
@@ -186,6 +194,13 @@ class BgsubTrainJob(_c.Structure):
                 ("op_shift", (_c.c_int32 * 4) * 2), ("reserved", _c.c_int32)]
 
 
+class SegTrainJob(_c.Structure):
+    """Mirror of `ape_seg_train_job` (include/ape_hip.h)."""
+    _fields_ = [("rgb", _c.c_void_p), ("label", _c.c_void_p), ("fa", _c.c_int32 * 6), ("rot_mode", _c.c_int32), ("n_ops", _c.c_int32),
+                ("op_code", _c.c_int32 * 4), ("op_factor", _c.c_float * 4), ("op_shift", _c.c_int32 * 4), ("crop_x", _c.c_int32),
+                ("crop_y", _c.c_int32), ("crop_side", _c.c_int32), ("class_id", _c.c_int32)]
+
+
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_SIGMOID = 0, 1, 2, 3
 _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspace_bytes": _c.c_size_t, "ape_seg_components_workspace_bytes": _c.c_size_t,
              "ape_packed_weights_bf16_elems": _c.c_long, "ape_pc_batch_workspace_bytes": _c.c_size_t,
@@ -194,12 +209,13 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
              "ape_fpfh_batch_workspace_bytes": _c.c_size_t, "ape_feature_nn1_batch_workspace_bytes": _c.c_size_t,
              "ape_ransac_batch_workspace_bytes": _c.c_size_t,
              "ape_bn_workspace_bytes": _c.c_size_t, "ape_jaccard_workspace_bytes": _c.c_size_t,
-             "ape_bgsub_train_workspace_bytes": _c.c_size_t}
+             "ape_bgsub_train_workspace_bytes": _c.c_size_t, "ape_seg_train_workspace_bytes": _c.c_size_t,
+             "ape_seg_train_extents_offset": _c.c_size_t, "ape_seg_train_tables_offset": _c.c_size_t}
 
 _lib = None
 
 
-ABI_VERSION = 6      # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 7      # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

@@ -1,0 +1,112 @@
+"""`segmentation_training(training_config, segmentation_config)`: the reference's "Train Segmentation" entry (segmentation/__init__.py:27-244)
+without its figures: per epoch the training loss and IoU and the validation loss and IoU, the best-validation-mIoU checkpoint
+`<root>/segmentation/trained_models/<dataset_name>/<name>_<encoder>.ckpt` (where get_default_model reads it) and the JSON log
+`<root>/segmentation/logs/<dataset_name>/<name>_<encoder>.json`.  Batches come from `SegmentationDataset.batch` (built on the device,
+segmentation/augment.py), in `torch.randperm` order when `shuffle` is set; the step is segmentation/train.py's.  One process drives one
+GPU (no DataParallel)."""
+import json
+import os
+
+IMAGENET_MEAN, IMAGENET_STD = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
+FULL_12_MEAN, FULL_12_STD = [0.7423757, 0.74199075, 0.7420199], [0.1662702, 0.16652738, 0.16721568]
+
+
+class _Batches:
+    """an epoch's batches from `dataset.batch`: a new `torch.randperm` order per pass when `shuffle` is set"""
+
+    def __init__(self, dataset, batch_size, shuffle):
+        self.dataset, self.batch_size, self.shuffle = dataset, int(batch_size), bool(shuffle)
+
+    def __len__(self):
+        return (len(self.dataset) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        import torch
+        n = len(self.dataset)
+        order = torch.randperm(n).tolist() if self.shuffle else list(range(n))
+        for i in range(0, n, self.batch_size):
+            yield self.dataset.batch(order[i:i + self.batch_size])
+
+
+def _statistics_for(training_config, segmentation_config):
+    """reference :41-51: ImageNet's for an ImageNet encoder, the recorded ones of 'full_12_classes', else computed from the frames"""
+    if segmentation_config["encoder_weights"] == "imagenet":
+        print("use imagenet mean and std")
+        return IMAGENET_MEAN, IMAGENET_STD
+    if training_config["dataset_name"] == "full_12_classes":
+        print("use full_12_classes mean and std")
+        return FULL_12_MEAN, FULL_12_STD
+    return None, None
+
+
+def segmentation_training(training_config, segmentation_config, root=None, crop=None):
+    """`root` holds the reference's tree (data_generation/, label_generator/, segmentation/; default: this package's directory); `crop`
+    may replace the training set's CropAndZoom (small test trees).  What matches the reference is what can be observed: the printed
+    lines, the checkpoint's keys and path, the log's keys and path.  -> the log dict."""
+    import numpy as np
+    import torch
+
+    from autoposeestimation_amd.segmentation import train as T
+    from autoposeestimation_amd.segmentation.dataset import SegmentationDataset
+    from autoposeestimation_amd.segmentation.metrics import IoU
+    from autoposeestimation_amd.segmentation.utils import get_model
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("segmentation_training runs on the GPU only (no CPU fallback in this build)")
+    root = root or os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    ds_name = training_config["dataset_name"]
+    print("create paths")
+    save_path = os.path.join(root, "segmentation", "trained_models", ds_name)
+    logs_path = os.path.join(root, "segmentation", "logs", ds_name)
+    os.makedirs(save_path, exist_ok=True)
+    os.makedirs(logs_path, exist_ok=True)
+    mean, std = _statistics_for(training_config, segmentation_config)
+    print("create datasets")
+    train_set = SegmentationDataset(ds_name, "train", mean=mean, std=std, root=root, crop=crop)
+    valid_set = SegmentationDataset(ds_name, "test", mean=train_set.mean, std=train_set.std, root=root)
+    print("create model")
+    model_config = dict(segmentation_config, classes=train_set.n_classes)           # the caller's dict is left alone
+    name = model_config.pop("name")
+    stem = "{}_{}".format(name, model_config["encoder_name"])
+    model = get_model(name, model_config).cuda()
+    print("create optimizer, dataloader and metric")
+    adam = training_config.get("optimizer") == "Adam"                              # anything else is SGD with Nesterov momentum (:88-100)
+    print("use {} optimizer: lr = {}".format("Adam" if adam else "SGD", training_config["lr"]))
+    optimizer = T.make_optimizer(model, dict(training_config, optimizer="Adam" if adam else "SGD"))
+    bs, shuffle = training_config["batch_size"], training_config["shuffle"]
+    train_batches, valid_batches = _Batches(train_set, bs, shuffle), _Batches(valid_set, bs, shuffle)
+    print("class names: {}".format(train_set.classes))
+    print("n classes: {}".format(train_set.n_classes))
+    print("n train batches: {}".format(len(train_batches)))
+    print("n valid batches: {}".format(len(valid_batches)))
+    metric = IoU(num_classes=train_set.n_classes)
+    # per epoch: loss, mIoU and per-class IoU of either pass
+    hist = {"train": {"loss": [], "miou": [], "iou": []}, "valid": {"loss": [], "miou": [], "iou": []}}
+    best = {"iou": 0, "epoch": 0}
+    logs = {}
+    print("start training")
+    for epoch in range(training_config["epochs"]):
+        print("_" * 50)
+        print("Epoch {}/{}".format(epoch, training_config["epochs"] - 1))
+        for mode, run in (("train", lambda: T.train_epoch(model, optimizer, train_batches, metric)),
+                          ("valid", lambda: T.evaluate(model, valid_batches, metric))):
+            loss, iou, miou = run()
+            h = hist[mode]
+            h["loss"].append(float(loss))
+            h["miou"].append(float(miou))
+            h["iou"].append(iou)
+            print("{} Loss: {}".format(mode, h["loss"][-1]))
+            print("{} mIoU: {}".format(mode, miou))
+            print("{} per class mIOU: {}".format(mode, np.round(np.mean(np.array(h["iou"]), axis=0), 3)))       # mean over the epochs so far
+        if hist["valid"]["miou"][-1] > best["iou"]:
+            best = {"iou": hist["valid"]["miou"][-1], "epoch": epoch}
+            torch.save(T.checkpoint(model, epoch, best["iou"], hist["train"]["miou"], hist["train"]["loss"], hist["valid"]["miou"],
+                                    hist["valid"]["loss"], training_config, name, model_config), os.path.join(save_path, stem + ".ckpt"))
+        print("best iou: {}".format(best["iou"]))
+        print("best_epoch: {}".format(best["epoch"]))
+        logs = {"best_iou_score": best["iou"], "best_iou_score_epoch": best["epoch"],
+                "train_iou_scores": hist["train"]["miou"], "train_losses": hist["train"]["loss"],
+                "valid_iou_scores": hist["valid"]["miou"], "valid_losses": hist["valid"]["loss"]}
+        with open(os.path.join(logs_path, stem + ".json"), "w") as f:      # rewritten every epoch: a run that is stopped leaves its log
+            json.dump(logs, f)
+    return logs

@@ -4,9 +4,9 @@ DenseFusion/tools/train.py: `train_step`, `train_epoch`, `evaluate`, `checkpoint
 The model is `get_model('Unet' | 'PsPNet', cfg)` on one GPU; its train-mode forward builds the training graph on the tape
 (autoposeestimation_amd/autograd.py), `jaccard_loss` / `IoU` are the package's device kernels, the optimizer is autograd.Adam / SGD or a
 torch.optim one (`make_optimizer` restates the reference's choice, segmentation/__init__.py:96-101).  One process drives one GPU: the
-reference wraps the model in nn.DataParallel when several are visible (segmentation/__init__.py:68-82); that is not restated.  The
-reference's SegmentationDataset (torchvision augmentations) is not either: any iterable of (img [B,C,H,W] f32, label [B,H,W] i64)
-batches will do.
+reference wraps the model in nn.DataParallel when several are visible (segmentation/__init__.py:68-82); that is not restated.  Any
+iterable of (img [B,C,H,W] f32, label [B,H,W] i64) batches will do; `segmentation_training` (segmentation/__init__.py) feeds them from
+SegmentationDataset.batch (segmentation/dataset.py), which builds them on the device.
 """
 import numpy as np
 import torch

@@ -10,9 +10,17 @@ encoder) with smp's state-dict keys, so the reference's `Unet_resnet34.ckpt` fil
 
 The training loss and metric (jaccard_loss, Metric, ConfusionMatrix, IoU) live in segmentation/metrics.py and are re-exported here under
 the reference's names; in train mode both segmentors' forward() builds a training graph on the tape (segmentation/train.py drives them).
-The reference's transforms and animate* stay outside the package.
+
+The reference's transforms (:12-66, CropAndZoom :361-487) are at the end of this file under their names: callable on `[PIL image, PIL
+label]` through Pillow -- the host path -- and each with a `params(...)` that draws from the reference's generators in the reference's
+order and returns plain numbers, which the device builder (segmentation/augment.py, csrc/seg_train.hip) takes instead.  animate* stay
+outside the package.
 """
+import random
+
+import numpy as np
 import torch
+from PIL import Image
 
 from autoposeestimation_amd import engine as E
 from autoposeestimation_amd.DenseFusion.lib.network import PSPNet, _need_cuda, _pspnet_train
@@ -118,3 +126,153 @@ def get_model(name, segmentation_config):
     model = nets[name]
     model = model(**segmentation_config)
     return model
+
+
+# ---- the transforms of the training samples (reference :12-66, :361-487) -------------------------------------------------------------
+from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented.dataset import ColorJitterPIL  # noqa: E402
+
+
+class HFlipDefault:
+    def __init__(self):
+        self.p = 0.5
+
+    def params(self):
+        return bool(np.random.rand() <= self.p)
+
+    def __call__(self, data, flip=None):
+        img, label = data
+        if self.params() if flip is None else flip:
+            img = img.transpose(Image.Transpose.FLIP_LEFT_RIGHT)
+            label = label.transpose(Image.Transpose.FLIP_LEFT_RIGHT)
+        return [img, label]
+
+
+class rotate:
+    def __init__(self):
+        self.range = [-180, 180]
+
+    def params(self):
+        return random.uniform(self.range[0], self.range[1])
+
+    def __call__(self, data, angle=None):
+        image, label = data
+        if angle is None:
+            angle = self.params()
+        return image.rotate(angle), label.rotate(angle)          # transforms.functional.rotate's defaults: nearest, no expand, zero fill
+
+
+class colorJitter:
+    def __init__(self):
+        self.ColorJitter = ColorJitterPIL(brightness=0.2, contrast=0.2, saturation=0.2, hue=0.05)
+
+    def params(self):
+        return self.ColorJitter.params()
+
+    def __call__(self, data, ops=None):
+        img, label = data
+        img = ColorJitterPIL.apply(img, self.params() if ops is None else ops)
+        return [img, label]
+
+
+class normalize:
+    def __init__(self, mean, std):
+        self.mean = torch.as_tensor([float(m) for m in mean], dtype=torch.float32).view(-1, 1, 1)
+        self.std = torch.as_tensor([float(s) for s in std], dtype=torch.float32).view(-1, 1, 1)
+        if (self.std == 0).any():
+            raise ValueError("std evaluated to zero")
+
+    def params(self):
+        return [float(m) for m in self.mean.view(-1)], [float(s) for s in self.std.view(-1)]
+
+    def __call__(self, data):
+        img, label = data
+        return [(img - self.mean) / self.std, label]
+
+
+class toTensor:
+    """ToTensor of the frame (HWC u8 -> CHW f32 / 255); the label becomes an i64 tensor of its values"""
+
+    def params(self):
+        return 255.0
+
+    def __call__(self, data):
+        img, label = data
+        a = np.asarray(img, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[:, :, None]
+        img = torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1))).to(torch.float32).div(255)
+        return [img, torch.from_numpy(np.asarray(label).astype(np.int64))]
+
+
+def _square(centre, side):
+    """rows and columns of the square of `side` around `centre`: the half side is truncated, so an odd side loses a pixel"""
+    half = int(side / 2)
+    return [centre[0] - half, centre[0] + half, centre[1] - half, centre[1] + half]
+
+
+def _shift_inside(box, height, width):
+    """slide the box back when it sticks out at the top / left, else at the bottom / right; a box larger than the frame still sticks out"""
+    top, bottom, left, right = box
+    dr = top if top < 0 else max(bottom - height, 0)
+    dc = left if left < 0 else max(right - width, 0)
+    return [top - dr, bottom - dr, left - dc, right - dc]
+
+
+class CropAndZoom:
+    """The label-driven random crop of reference :361-487, restated.  A square of a random side in [min_l, max_l) is centred on the
+    object (the label's pixels == 255).  When the object's extent is not about square (height / width outside [0.8, 1.2]) the centre is
+    first moved to a random place along the longer axis.  A square taller than the frame is replaced by one of height - 2; the square is
+    then slid inside the frame, cropped and resized to output_size (Pillow's default BICUBIC for the image, NEAREST for the label).
+
+    Three properties of the reference's arithmetic are kept because the boxes depend on them: the "taller than the frame" test and the
+    height - 2 replacement use the frame's HEIGHT for the columns too; every half (of a side, of an extent) is truncated with int(); an
+    about-square object is slid, along the columns, only on the too-tall route.  The reference also builds a box of 1.1 times the
+    object first, but only its centre survives the zoom, and that is the object's, so it is not built here."""
+
+    def __init__(self, output_size=480, max_zoom=2):
+        self.output_size, self.max_zoom = output_size, max_zoom
+        self.max_l = output_size
+        self.min_l = int(float(output_size) / max_zoom)
+        self.to_small, self.to_big = 0.8, 1.2
+
+    def draw_zoom(self):
+        """the side, before truncation: the one draw from `random`; it does not depend on the label"""
+        return random.uniform(self.min_l, self.max_l)
+
+    def box(self, extreme_points, size, zoom=None):
+        """extreme_points = (first row, last row, first column, last column) of the object, size = (height, width) of the frame ->
+        [top, bottom, left, right] as Python ints.  Draws the zoom unless it is given, then at most one `np.random.randint(0, n)` with
+        n the object's extent along the axis it slides on."""
+        height, width = int(size[0]), int(size[1])
+        r0, r1, c0, c1 = [int(v) for v in extreme_points]
+        extent = [r1 - r0, c1 - c0]
+        centre = [r0 + int(extent[0] / 2), c0 + int(extent[1] / 2)]
+        ratio = (float(extent[0]) / float(self.output_size)) / (float(extent[1]) / float(self.output_size))
+        side = 2 * int(int(self.draw_zoom() if zoom is None else zoom) / 2)
+        if self.to_small <= ratio <= self.to_big:
+            axis = 1 if side > height else None
+        else:
+            axis = 1 if extent[1] > extent[0] else 0
+        if axis is not None:
+            centre[axis] = int(centre[axis] - extent[axis] / 2) + int(np.random.randint(0, extent[axis]))
+        return _shift_inside(_square(centre, side if side <= height else height - 2), height, width)
+
+    def params(self, extreme_points, size, zoom=None):
+        """-> the box in Image.crop's order: (left, upper, right, lower)"""
+        top, bottom, left, right = self.box(extreme_points, size, zoom)
+        return (left, top, right, bottom)
+
+    def get_extreme_points(self, label, name=None):
+        rows, cols = np.where(np.asarray(label) == 255)
+        if rows.size == 0:
+            raise ValueError("the label of sample %s has no pixel equal to 255: CropAndZoom has no object to crop around" %
+                             ("<unnamed>" if name is None else name))
+        return [int(rows.min()), int(rows.max()), int(cols.min()), int(cols.max())]
+
+    def __call__(self, data, box=None, name=None):
+        image, label = data
+        if box is None:
+            lab = np.array(label)
+            box = self.params(self.get_extreme_points(lab, name), lab.shape[:2])
+        out = (self.output_size, self.output_size)
+        return [image.crop(box=list(box)).resize(size=out), label.crop(box=list(box)).resize(size=out, resample=Image.NEAREST)]

@@ -685,6 +685,48 @@ size_t ape_bgsub_train_workspace_bytes(int B);
 int ape_bgsub_train_samples(const ape_bgsub_train_job* jobs_host, int B, int H, int W, const float* mean7_host, const float* std7_host,
                             float* x8, long long* label, uint8_t* u8_or_null, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Segmentor training samples (csrc/seg_train.hip; reference segmentation/dataset.py:88-112 with the transforms of
+ * segmentation/utils.py:25-66 and CropAndZoom :361-487) -------------------------------------------------------------------------------
+ * One job per sample: DEVICE pointers to the resident frame and its label and what the host drew.  Order, as the reference composes it:
+ * colour jitter of the full frame (op lists as in ape_bgsub_train_job, one image) -> Image.rotate of image and label (rot_mode / fa as
+ * there; both are 8-bit, so both walk `fa`) -> crop of the square crop_side x crop_side box at (crop_x, crop_y) of the rotated frame (zero
+ * outside it, like Image.crop) -> resize to S x S, Pillow's BICUBIC for the image and NEAREST for the label -> ToTensor, Normalize; label
+ * pixels != 0 become class_id. */
+typedef struct ape_seg_train_job {
+    const uint8_t* rgb;        /* [H][W][3] */
+    const uint8_t* label;      /* [H][W] */
+    int fa[6];
+    int rot_mode;
+    int n_ops;
+    int op_code[4];
+    float op_factor[4];
+    int op_shift[4];
+    int crop_x, crop_y, crop_side;
+    int class_id;
+} ape_seg_train_job;
+/* The workspace of a batch: [B][64] u64 luma partial sums | [B][64][5] i32 extent partials at ape_seg_train_extents_offset(B) | the
+ * resize tables [B][14 * S] i32 at ape_seg_train_tables_offset(B).  One per stream; not shared by batches in flight at once. */
+size_t ape_seg_train_workspace_bytes(int B, int S);
+size_t ape_seg_train_extents_offset(int B);
+size_t ape_seg_train_tables_offset(int B);
+/* Launch A (replaces the host's `np.where(label == 255)` of segmentation/utils.py:450-462 and ImageStat of ImageEnhance.Contrast): per
+ * sample 64 workgroups, each writing ONE partial of the integer L sum of the un-rotated frame as it is when its contrast op runs, and one
+ * (min row, max row, min column, max column, count) of the ROTATED label's pixels == 255 (INT_MAX, -1, INT_MAX, -1, 0 when it saw none).
+ * The caller reads the extent partials back, combines them (min / max / sum: exact whatever the schedule), draws the crop boxes and fills
+ * crop_* before launch B.  crop_* and class_id are not read here. */
+int ape_seg_train_stats(const ape_seg_train_job* jobs_host, int B, int H, int W, void* ws, size_t ws_bytes, void* stream);
+/* Launch B: img[B][3][S][S] f32 (16-byte aligned), label[B][S][S] i64.  The tables of sample b, built by the caller in double as
+ * Pillow's Resample.c / ImagingScaleAffine do and copied into the workspace: hmin[S], hk[S][5], vmin[S], vk[S][5] (first source index and
+ * the five 2^22 fixed-point BICUBIC weights of every output column / row; unused weights 0), nx[S], ny[S] (NEAREST source column / row).
+ * A pass is clip8((2^21 + sum pixel * k) >> 22), horizontal first, its u8 result feeding the vertical one.  Enlargement only:
+ * crop_side > S is APE_EINVAL. */
+int ape_seg_train_samples(const ape_seg_train_job* jobs_host, int B, int H, int W, int S, const float* mean3_host, const float* std3_host,
+                          float* img, long long* label, void* ws, size_t ws_bytes, void* stream);
+/* The un-augmented sample of mode 'test' (segmentation/dataset.py:98-112 without the augmentations): img[B][3][H][W] f32 = (rgb / 255 -
+ * mean) / std, label[B][H][W] i64 = class_id where the label is != 0.  Only rgb, label and class_id of a job are read. */
+int ape_seg_plain_samples(const ape_seg_train_job* jobs_host, int B, int H, int W, const float* mean3_host, const float* std3_host, float* img,
+                          long long* label, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

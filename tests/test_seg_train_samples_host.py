@@ -1,0 +1,174 @@
+"""Host side of the segmentor's training samples (no GPU): segmentation/utils.py's transforms against tests/golden/seg_train.npz (made by
+running the reference's CropAndZoom and rotate), the resize tables of segmentation/augment.py against the installed Pillow, and
+SegmentationDataset's list handling, class ids and statistics.  Every comparison is exact."""
+import random
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+import seg_train_reference as R
+
+G = R.golden()
+NAMES = [str(n) for n in G["names"]]
+
+
+def _extremes(label):
+    pos = np.where(label == 255)
+    return [pos[0].min(), pos[0].max(), pos[1].min(), pos[1].max()]
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_box_and_params_reproduce_the_golden_box(name):
+    label, seed = G["%s_label" % name], int(G["%s_seed" % name])
+    want = [int(v) for v in G["%s_box" % name]]                 # as handed to Image.crop: left, upper, right, lower
+    cz = R.crop_and_zoom(G, name)
+    random.seed(seed)
+    np.random.seed(seed)
+    assert list(cz.params(_extremes(label), label.shape)) == want
+    random.seed(seed)
+    np.random.seed(seed)
+    bbox = cz.box(_extremes(label), label.shape)                # [up, down, left, right]
+    assert [bbox[2], bbox[0], bbox[3], bbox[1]] == want and all(isinstance(v, int) for v in bbox)
+    # the zoom drawn ahead of the label (the device path's order) gives the same box and leaves both generators where they were
+    random.seed(seed)
+    np.random.seed(seed)
+    zoom = cz.draw_zoom()
+    assert list(cz.params(_extremes(label), label.shape, zoom=zoom)) == want
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_call_reproduces_the_golden_outputs(name):
+    seed = int(G["%s_seed" % name])
+    cz = R.crop_and_zoom(G, name)
+    random.seed(seed)
+    np.random.seed(seed)
+    img, lab = cz([Image.fromarray(G["rgb"], "RGB"), Image.fromarray(G["%s_label" % name], "L")])
+    assert np.array_equal(np.array(img), G["%s_img_out" % name]) and np.array_equal(np.array(lab), G["%s_label_out" % name])
+
+
+def test_rotate_reproduces_the_golden_result():
+    from autoposeestimation_amd.segmentation.utils import rotate
+    random.seed(int(G["rotate_seed"]))
+    rot = rotate()
+    img, lab = rot([Image.fromarray(G["rgb"], "RGB"), Image.fromarray(G["rotate_label"], "L")])
+    assert np.array_equal(np.array(img), G["rotate_img_out"]) and np.array_equal(np.array(lab), G["rotate_label_out"])
+    random.seed(int(G["rotate_seed"]))
+    assert rot.params() == float(G["rotate_angle"])
+
+
+def test_jitter_params_are_the_reference_draws():
+    from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented.dataset import ColorJitterPIL
+    from autoposeestimation_amd.segmentation.utils import colorJitter
+    random.seed(3)
+    want = ColorJitterPIL(0.2, 0.2, 0.2, 0.05).params()
+    random.seed(3)
+    assert colorJitter().params() == want and len(want) == 4
+
+
+def _resize_with_tables(a, out):
+    """what the kernel does with the tables, in numpy: horizontal pass to u8, then vertical"""
+    from autoposeestimation_amd.segmentation import augment as A
+    n = a.shape[0]
+    xmin, k = A.bicubic_table(n, out)
+    idx = np.minimum(xmin[:, None] + np.arange(A.TAPS)[None], n - 1)          # taps past the crop carry weight 0
+    a = a.astype(np.int64)
+    hh = np.clip(((1 << 21) + (a[:, idx, :] * k[None, :, :, None]).sum(2)) >> 22, 0, 255)
+    return np.clip(((1 << 21) + (hh[idx, :, :] * k[:, :, None, None]).sum(1)) >> 22, 0, 255).astype(np.uint8)
+
+
+@pytest.mark.parametrize("n,out", [(24, 48), (31, 48), (46, 48), (47, 48), (48, 48), (1, 48), (2, 40), (20, 40), (38, 40),
+                                   (240, 480), (333, 480), (478, 480), (479, 480)])
+def test_tables_equal_pillow_resize(n, out):
+    from autoposeestimation_amd.segmentation import augment as A
+    rng = np.random.default_rng(n * 1000 + out)
+    a = rng.integers(0, 256, (n, n, 3), dtype=np.uint8)
+    assert np.array_equal(_resize_with_tables(a, out), np.array(Image.fromarray(a, "RGB").resize((out, out))))
+    lab = (rng.integers(0, 2, (n, n)) * 255).astype(np.uint8)
+    near = A.nearest_table(n, out)
+    assert np.array_equal(lab[near][:, near], np.array(Image.fromarray(lab, "L").resize((out, out), resample=Image.NEAREST)))
+    xmin, k = A.bicubic_table(n, out)
+    assert k.shape == (out, 5) and int(xmin.min()) >= 0 and int((xmin[-1] - xmin[0])) <= n
+    assert int(np.diff(xmin).min()) >= 0 and int((xmin[31:] - xmin[:-31]).max(initial=0)) <= 32          # a 32-wide tile's patch: <= 37 wide
+
+
+def test_tables_refuse_a_reduction():
+    from autoposeestimation_amd.segmentation import augment as A
+    with pytest.raises(ValueError, match="enlargement"):
+        A.bicubic_table(49, 48)
+
+
+def _tree(tmp_path):
+    rng = np.random.default_rng(1)
+    entries = ["bluedude/run1/000001", "greendude_extra/run1/000004", "xx_bluedude_greendude/000002"]
+    items = [(e,) + R.synthetic_sample(rng, 24, 40) for e in entries]
+    R.write_tree(str(tmp_path), "two", items, items[:1], ["greendude", "bluedude"])
+    return items
+
+
+def test_dataset_class_ids_and_lists(tmp_path):
+    from autoposeestimation_amd.segmentation.dataset import SegmentationDataset
+    items = _tree(tmp_path)
+    ds = SegmentationDataset("two", "train", mean=R.MEAN, std=R.STD, root=str(tmp_path))
+    assert ds.classes == ["greendude", "bluedude"] and ds.n_classes == 3 and len(ds) == 3
+    assert ds.labels == [2, 1, 1]                     # the first class NAME contained in the entry, 1-based (the third holds both)
+    assert ds.dirs == [e for e, _, _ in items]
+    test = SegmentationDataset("two", "test", mean=R.MEAN, std=R.STD, root=str(tmp_path))
+    img, lab = test[0]                                # mode 'test': the full frame, ToTensor + Normalize
+    assert np.array_equal(img.numpy(), R.normalise(items[0][1])) and lab.dtype == torch.int64
+    assert np.array_equal(lab.numpy(), np.where(items[0][2] != 0, 2, 0))
+    with pytest.raises(NotImplementedError):
+        SegmentationDataset("two", "train", mean=R.MEAN, std=R.STD, root=str(tmp_path), plot=True)
+
+
+def test_dataset_unknown_class_raises(tmp_path):
+    from autoposeestimation_amd.segmentation.dataset import SegmentationDataset
+    rng = np.random.default_rng(2)
+    R.write_tree(str(tmp_path), "one", [("reddude/000001",) + R.synthetic_sample(rng, 24, 40)], [], ["bluedude"])
+    with pytest.raises(ValueError):
+        SegmentationDataset("one", "train", mean=R.MEAN, std=R.STD, root=str(tmp_path))
+
+
+def test_dataset_statistics_are_column_indexed(tmp_path):
+    from autoposeestimation_amd.segmentation.dataset import SegmentationDataset
+    items = _tree(tmp_path)
+    ds = SegmentationDataset("two", "train", root=str(tmp_path))
+    x = [torch.from_numpy(np.ascontiguousarray(rgb.transpose(2, 0, 1))).float().div(255) for _, rgb, _ in items]
+    want_mean = np.mean([[x_[:, :, i].mean().numpy() for i in range(3)] for x_ in x], axis=0)          # COLUMN i of the width
+    want_std = np.mean([[x_[:, :, i].std().numpy() for i in range(3)] for x_ in x], axis=0)            # unbiased
+    assert np.array_equal(np.array(ds.mean), want_mean) and np.array_equal(np.array(ds.std), want_std)
+    per_channel = np.mean([[x_[i].mean().numpy() for i in range(3)] for x_ in x], axis=0)
+    assert not np.array_equal(np.array(ds.mean), per_channel)
+
+
+def test_host_sample_is_seeded_and_shaped(tmp_path):
+    from autoposeestimation_amd.segmentation.dataset import SegmentationDataset
+    from autoposeestimation_amd.segmentation.utils import CropAndZoom
+    items = _tree(tmp_path)
+    ds = SegmentationDataset("two", "train", mean=R.MEAN, std=R.STD, root=str(tmp_path), crop=CropAndZoom(output_size=24))
+    random.seed(5)
+    np.random.seed(5)
+    params = ds.draw()
+    random.seed(5)
+    np.random.seed(5)
+    img, lab = ds[1]
+    assert tuple(img.shape) == (3, 24, 24) and img.dtype == torch.float32 and tuple(lab.shape) == (24, 24) and lab.dtype == torch.int64
+    assert set(np.unique(lab.numpy())) <= {0, 1}
+    np.random.seed(5)
+    img2, lab2 = ds.sample_host(1, params)            # the same draws handed over as parameters
+    assert torch.equal(img, img2) and torch.equal(lab, lab2)
+    assert items[1][0] == ds.dirs[1]
+
+
+def test_empty_label_raises(tmp_path):
+    from autoposeestimation_amd.segmentation.dataset import SegmentationDataset
+    from autoposeestimation_amd.segmentation.utils import CropAndZoom
+    rng = np.random.default_rng(3)
+    rgb, label = R.synthetic_sample(rng, 24, 40)
+    R.write_tree(str(tmp_path), "one", [("bluedude/000007", rgb, np.where(label == 255, 254, 0).astype(np.uint8))], [], ["bluedude"])
+    ds = SegmentationDataset("one", "train", mean=R.MEAN, std=R.STD, root=str(tmp_path), crop=CropAndZoom(output_size=24))
+    with pytest.raises(ValueError, match="bluedude/000007"):
+        ds[0]
+    with pytest.raises(ValueError, match="no pixel equal to 255"):
+        CropAndZoom()([Image.fromarray(rgb, "RGB"), Image.fromarray(np.zeros_like(label), "L")])
