@@ -158,6 +158,16 @@ SIGNATURES = {
     "ape_seg_train_stats": [_P, _I, _I, _I, _P, _c.c_size_t, _P],
     "ape_seg_train_samples": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _c.c_size_t, _P],
     "ape_seg_plain_samples": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
+    # DenseFusion training samples (csrc/pose_train.hip): DenseFusion/datasets/myDatasetAugmented/dataset.py:158-326
+    "ape_pose_train_extents_offset": [_I],
+    "ape_pose_train_rows_offset": [_I],
+    "ape_pose_train_tables_offset": [_I, _I],
+    "ape_pose_train_sel_offset": [_I, _I],
+    "ape_pose_train_workspace_bytes": [_I, _I, _I],
+    "ape_pose_train_image_offset": [_I],
+    "ape_pose_train_sample_bytes": [_I, _I, _I],
+    "ape_pose_train_stats": [_P, _I, _I, _I, _P, _c.c_size_t, _P],
+    "ape_pose_train_samples": [_P, _I, _I, _I, _I, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P],
 }
 
 
@@ -201,6 +211,16 @@ class SegTrainJob(_c.Structure):
                 ("crop_y", _c.c_int32), ("crop_side", _c.c_int32), ("class_id", _c.c_int32)]
 
 
+class PoseTrainJob(_c.Structure):
+    """Mirror of `ape_pose_train_job` (include/ape_hip.h)."""
+    _fields_ = [("rgb", _c.c_void_p), ("depth", _c.c_void_p), ("label", _c.c_void_p), ("a", _c.c_double * 6), ("add_t", _c.c_double * 3),
+                ("out_off", _c.c_longlong), ("fa", _c.c_int32 * 6), ("rot_mode", _c.c_int32), ("n_ops", _c.c_int32),
+                ("op_code", _c.c_int32 * 4), ("op_factor", _c.c_float * 4), ("op_shift", _c.c_int32 * 4), ("rmin", _c.c_int32),
+                ("rmax", _c.c_int32), ("cmin", _c.c_int32), ("cmax", _c.c_int32), ("ppx", _c.c_float), ("ppy", _c.c_float),
+                ("fx", _c.c_float), ("fy", _c.c_float), ("depth_scale", _c.c_float), ("to_meter", _c.c_int32), ("add_noise", _c.c_int32),
+                ("reserved", _c.c_int32)]
+
+
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_SIGMOID = 0, 1, 2, 3
 _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspace_bytes": _c.c_size_t, "ape_seg_components_workspace_bytes": _c.c_size_t,
              "ape_packed_weights_bf16_elems": _c.c_long, "ape_pc_batch_workspace_bytes": _c.c_size_t,
@@ -210,12 +230,16 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
              "ape_ransac_batch_workspace_bytes": _c.c_size_t,
              "ape_bn_workspace_bytes": _c.c_size_t, "ape_jaccard_workspace_bytes": _c.c_size_t,
              "ape_bgsub_train_workspace_bytes": _c.c_size_t, "ape_seg_train_workspace_bytes": _c.c_size_t,
-             "ape_seg_train_extents_offset": _c.c_size_t, "ape_seg_train_tables_offset": _c.c_size_t}
+             "ape_seg_train_extents_offset": _c.c_size_t, "ape_seg_train_tables_offset": _c.c_size_t,
+             "ape_pose_train_extents_offset": _c.c_size_t, "ape_pose_train_rows_offset": _c.c_size_t,
+             "ape_pose_train_tables_offset": _c.c_size_t, "ape_pose_train_sel_offset": _c.c_size_t,
+             "ape_pose_train_workspace_bytes": _c.c_size_t, "ape_pose_train_image_offset": _c.c_size_t,
+             "ape_pose_train_sample_bytes": _c.c_size_t}
 
 _lib = None
 
 
-ABI_VERSION = 7      # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 8      # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

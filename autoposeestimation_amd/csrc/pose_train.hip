@@ -1,0 +1,273 @@
+// Training samples of DenseFusion, built on the device from resident frames (reference DenseFusion/datasets/myDatasetAugmented/
+// dataset.py:158-326).  The reference does this in Pillow and numpy on the host, per sample: colour jitter of the full frame, Image.rotate
+// of colour, label and depth, get_bbox of the label, the `choose` compaction of the valid pixels inside the box with a drawn subset, the
+// back-projection of the chosen pixels and the normalised crop.  Here a batch is two launches with one small read-back between them:
+//   pose_stats_kernel    over the full frames, one wave per row: the integer L sum that ImageEnhance.Contrast needs, the extents of the
+//                        ROTATED label's pixels == 255 (one partial of each per workgroup) and, per row, the number of valid pixels
+//                        (rotated label == 255 and rotated depth != 0), written by the wave that walked the row.  Plain stores, combined in
+//                        index order: exact whatever the schedule.
+//   pose_samples_kernel  workgroups 0..kImgBlocks-1 of a sample write the normalised crop, the others one chosen point per wave: the row
+//                        by a binary search of the row prefix, the column by a ballot / popcount walk of that one row.
+// Whole-row counts are in-crop counts: every labelled pixel lies inside get_bbox's crop.  With the tight extents [r0, r1) the rounded side
+// s' is an even number >= s = r1 - r0 (a multiple of 40), the centre is c = floor((r0 + r1) / 2) >= (r0 + r1 - 1) / 2, so
+// c - s'/2 <= (r0 + r1)/2 - s/2 = r0 and c + s'/2 >= r1 - 1/2, an integer, hence >= r1; a shift back inside the frame moves the box over
+// [0, s') or (480 - s', 480], which still covers [r0, r1) because s' <= 480 (640 for the columns) -- tests/test_pose_samples_host.py
+// checks this over random extents.
+// The host only draws and does get_bbox's arithmetic; `target` / `model_points` depend on no pixel and stay with numpy's float64 there.
+// The per-pixel arithmetic is pose_px.h / seg_px.h / bgsub_px.h (also compiled for the host, tools/check_pose_px.py).
+#include <limits.h>
+
+#include "common.h"
+#include "pose_px.h"
+
+namespace {
+
+constexpr int kT = 256, kWaves = kT / 64;
+constexpr int kJobs = 16;            // jobs per launch: 16 * 232 B of kernel arguments (limit 4 KB)
+constexpr int kBlocks = 64;          // partials per sample
+constexpr int kImgBlocks = 96;       // workgroups per sample that write the crop (at most 480 * 640 pixels: <= 12.5 per thread)
+
+struct PoseBatch {
+    ape_pose_train_job j[kJobs];
+    float mean[3], stdv[3];
+};
+
+size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// grid (kBlocks, nb)
+__global__ __launch_bounds__(kT) void pose_stats_kernel(PoseBatch bt, int job0, int H, int W, unsigned long long* __restrict__ luma,
+                                                        int* __restrict__ ext, int* __restrict__ rows)
+{
+    __shared__ unsigned long long red_s[kWaves];
+    __shared__ int red_e[kWaves][4];
+    const ape_pose_train_job& j = bt.j[blockIdx.y];
+    const int kc = seg_contrast_at(j);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long s = 0;
+    int rmin = INT_MAX, rmax = -1, cmin = INT_MAX, cmax = -1;
+    int* row_out = rows + (long)(job0 + blockIdx.y) * H;
+    for (int y = blockIdx.x * kWaves + wave; y < H; y += gridDim.x * kWaves) {          // a row belongs to one wave
+        int cnt = 0;
+        for (int x = lane; x < W; x += 64) {
+            if (kc >= 0) {                           // uniform per workgroup
+                int r, g, b;
+                seg_jittered_rgb(j, W, x, y, kc, 0, r, g, b);
+                s += (unsigned long long)pil_luma(r, g, b);
+            }
+            if (pose_label_at(j, H, W, x, y) == 255) {
+                rmin = y < rmin ? y : rmin; rmax = y > rmax ? y : rmax;
+                cmin = x < cmin ? x : cmin; cmax = x > cmax ? x : cmax;
+                cnt += pose_depth_at(j, H, W, x, y) != 0;
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
+        if (lane == 0) row_out[y] = cnt;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_down(s, o, 64);
+        const int a = __shfl_down(rmin, o, 64), b = __shfl_down(rmax, o, 64), c = __shfl_down(cmin, o, 64), d = __shfl_down(cmax, o, 64);
+        rmin = a < rmin ? a : rmin; rmax = b > rmax ? b : rmax;
+        cmin = c < cmin ? c : cmin; cmax = d > cmax ? d : cmax;
+    }
+    if (lane == 0) {
+        red_s[wave] = s;
+        red_e[wave][0] = rmin; red_e[wave][1] = rmax; red_e[wave][2] = cmin; red_e[wave][3] = cmax;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tot = 0;
+        int e[4] = {INT_MAX, -1, INT_MAX, -1};
+        for (int w = 0; w < kWaves; ++w) {
+            tot += red_s[w];
+            e[0] = red_e[w][0] < e[0] ? red_e[w][0] : e[0]; e[1] = red_e[w][1] > e[1] ? red_e[w][1] : e[1];
+            e[2] = red_e[w][2] < e[2] ? red_e[w][2] : e[2]; e[3] = red_e[w][3] > e[3] ? red_e[w][3] : e[3];
+        }
+        const long p = (long)(job0 + blockIdx.y) * kBlocks + blockIdx.x;
+        luma[p] = tot;
+        for (int i = 0; i < 4; ++i) ext[p * 4 + i] = e[i];
+    }
+}
+
+// grid (kImgBlocks + ceil(N / kWaves), nb).  `prefix` and `sel` come from the caller through device memory, where the entry point cannot
+// look at them: the row found is always inside the frame, every frame read is bounds-checked on its coordinates (pose_px.h), and a rank
+// without a pixel writes zeros.
+__global__ __launch_bounds__(kT) void pose_samples_kernel(PoseBatch bt, int job0, int H, int W, int N, const unsigned long long* __restrict__ luma,
+                                                          const int* __restrict__ prefix, const int* __restrict__ sel, unsigned char* __restrict__ out,
+                                                          long img_off)
+{
+    __shared__ int s_mean;
+    const ape_pose_train_job& j = bt.j[blockIdx.y];
+    const int s = job0 + blockIdx.y;
+    const int Wc = j.cmax - j.cmin, Hc = j.rmax - j.rmin;
+    unsigned char* base = out + j.out_off;
+    if (blockIdx.x < kImgBlocks) {                   // the normalised crop (:307-313), planar
+        if (threadIdx.x == 0) {
+            int m = 0;
+            if (seg_contrast_at(j) >= 0) {
+                unsigned long long tot = 0;
+                const unsigned long long* p = luma + (long)s * kBlocks;
+                for (int i = 0; i < kBlocks; ++i) tot += p[i];
+                m = bgsub_mean_of_sum(tot, H, W);
+            }
+            s_mean = m;
+        }
+        __syncthreads();
+        const int mean = s_mean;
+        const long plane = (long)Hc * Wc;
+        float* img = (float*)(base + img_off);
+        for (long i = (long)blockIdx.x * kT + threadIdx.x; i < plane; i += (long)kImgBlocks * kT) {
+            const int r = (int)(i / Wc), c = (int)(i % Wc);
+            int cr, cg, cb;
+            pose_rgb_at(j, H, W, j.cmin + c, j.rmin + r, mean, cr, cg, cb);
+            img[i] = ((float)cr - bt.mean[0]) / bt.stdv[0];
+            img[plane + i] = ((float)cg - bt.mean[1]) / bt.stdv[1];
+            img[2 * plane + i] = ((float)cb - bt.mean[2]) / bt.stdv[2];
+        }
+        return;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pt = (blockIdx.x - kImgBlocks) * kWaves + wave;       // one chosen point per wave
+    if (pt >= N) return;
+    const int* pf = prefix + (long)s * H;
+    const int rank = sel[(long)s * N + pt];
+    const int y = pose_row_of_rank(pf, H, rank);
+    int rem = rank - pf[y];                          // the pixel's rank inside its row; wave-uniform like everything up to here
+    bool found = false;
+    for (int x0 = 0; x0 < W && !found; x0 += 64) {
+        const int x = x0 + lane;
+        const bool v = x < W && pose_valid(j, H, W, x, y);
+        const unsigned long long m = __ballot(v);
+        const int c = __popcll(m);
+        if (rem >= 0 && rem < c) {
+            found = true;
+            if (v && __popcll(m & ((1ull << lane) - 1ull)) == rem) {       // exactly one lane
+                long long* choose = (long long*)base;
+                float* p = (float*)(base + 8L * N) + 3L * pt;
+                float q[3];
+                pose_point(j, x, y, pose_depth_at(j, H, W, x, y), q);
+                choose[pt] = (long long)(y - j.rmin) * Wc + (x - j.cmin);
+                p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
+            }
+        }
+        rem -= c;
+    }
+    if (!found && lane == 0) {
+        long long* choose = (long long*)base;
+        float* p = (float*)(base + 8L * N) + 3L * pt;
+        choose[pt] = 0;
+        p[0] = p[1] = p[2] = 0.f;
+    }
+}
+
+bool frame_ok(int B, int H, int W) { return B >= 0 && H >= 1 && W >= 1 && H <= 32767 && W <= 32767; }
+
+bool job_ok(const ape_pose_train_job& j, int H, int W)
+{
+    if (!j.rgb || !j.depth || !j.label) return false;
+    if (j.rot_mode < APE_ROT_NONE || j.rot_mode > APE_ROT_270) return false;
+    if ((j.rot_mode == APE_ROT_90 || j.rot_mode == APE_ROT_270) && H != W) return false;
+    if (j.rot_mode == APE_ROT_AFFINE)
+        for (int i = 0; i < 6; ++i)
+            if (!(j.a[i] == j.a[i])) return false;                                        // NaN
+    if (j.n_ops < 0 || j.n_ops > 4) return false;
+    int contrasts = 0;
+    for (int k = 0; k < j.n_ops; ++k) {
+        const int c = j.op_code[k];
+        if (c < APE_JIT_BRIGHTNESS || c > APE_JIT_HUE) return false;
+        if (c == APE_JIT_HUE && (j.op_shift[k] < 0 || j.op_shift[k] > 255)) return false;
+        if (c != APE_JIT_HUE && !(j.op_factor[k] == j.op_factor[k])) return false;       // NaN
+        contrasts += c == APE_JIT_CONTRAST;
+    }
+    return contrasts <= 1;               // a second one would need the sum of an image that depends on the first sum
+}
+
+// get_bbox's crops: sides from border_list inside a 480 x 640 frame
+bool crop_ok(const ape_pose_train_job& j, int H, int W)
+{
+    const int hc = j.rmax - j.rmin, wc = j.cmax - j.cmin;
+    if (j.rmin < 0 || j.cmin < 0 || j.rmax > H || j.cmax > W) return false;
+    return hc >= 40 && hc <= 480 && wc >= 40 && wc <= 640 && hc % 40 == 0 && wc % 40 == 0;
+}
+
+}  // namespace
+
+extern "C" size_t ape_pose_train_extents_offset(int B) { return B < 1 ? 0 : (size_t)B * kBlocks * sizeof(unsigned long long); }
+
+extern "C" size_t ape_pose_train_rows_offset(int B)
+{
+    return B < 1 ? 0 : ape_pose_train_extents_offset(B) + (size_t)B * kBlocks * 4 * sizeof(int);         // a multiple of 16
+}
+
+extern "C" size_t ape_pose_train_tables_offset(int B, int H)
+{
+    return B < 1 || H < 1 ? 0 : ape_pose_train_rows_offset(B) + up16((size_t)B * H * sizeof(int));
+}
+
+extern "C" size_t ape_pose_train_sel_offset(int B, int H)
+{
+    return B < 1 || H < 1 ? 0 : ape_pose_train_tables_offset(B, H) + (size_t)B * H * sizeof(int);
+}
+
+extern "C" size_t ape_pose_train_workspace_bytes(int B, int H, int N)
+{
+    return B < 1 || H < 1 || N < 1 ? 0 : up16(ape_pose_train_sel_offset(B, H) + (size_t)B * N * sizeof(int));
+}
+
+extern "C" size_t ape_pose_train_image_offset(int N) { return N < 1 ? 0 : up16((size_t)N * 20); }
+
+extern "C" size_t ape_pose_train_sample_bytes(int N, int Hc, int Wc)
+{
+    return N < 1 || Hc < 1 || Wc < 1 ? 0 : up16(ape_pose_train_image_offset(N) + (size_t)3 * Hc * Wc * sizeof(float));
+}
+
+extern "C" int ape_pose_train_stats(const ape_pose_train_job* jobs, int B, int H, int W, void* ws, size_t ws_bytes, void* stream)
+{
+    static_assert(sizeof(ape_pose_train_job) == 232, "ape_pose_train_job layout (mirrored by _lib.PoseTrainJob)");
+    static_assert(sizeof(PoseBatch) <= 3900, "kernel arguments");
+    if (!frame_ok(B, H, W)) return APE_EINVAL;
+    if (B == 0) return APE_OK;
+    if (!jobs || !ws || ((uintptr_t)ws & 15)) return APE_EINVAL;
+    if (ws_bytes < ape_pose_train_tables_offset(B, H)) return APE_EWORKSPACE;
+    for (int i = 0; i < B; ++i)
+        if (!job_ok(jobs[i], H, W)) return APE_EINVAL;
+    PoseBatch bt = {};
+    for (int i0 = 0; i0 < B; i0 += kJobs) {
+        const int nb = B - i0 < kJobs ? B - i0 : kJobs;
+        for (int i = 0; i < nb; ++i) bt.j[i] = jobs[i0 + i];
+        hipLaunchKernelGGL(pose_stats_kernel, dim3(kBlocks, nb), dim3(kT), 0, (hipStream_t)stream, bt, i0, H, W, (unsigned long long*)ws,
+                           (int*)((char*)ws + ape_pose_train_extents_offset(B)), (int*)((char*)ws + ape_pose_train_rows_offset(B)));
+    }
+    return ape::check_launch("ape_pose_train_stats");
+}
+
+extern "C" int ape_pose_train_samples(const ape_pose_train_job* jobs, int B, int H, int W, int N, const float* mean3_host, const float* std3_host,
+                                      void* out, size_t out_bytes, void* ws, size_t ws_bytes, void* stream)
+{
+    PoseBatch bt = {};
+    if (!frame_ok(B, H, W) || N < 1 || N > (1 << 24) || !mean3_host || !std3_host) return APE_EINVAL;
+    for (int c = 0; c < 3; ++c) {
+        if (!(std3_host[c] != 0.f) || !(mean3_host[c] == mean3_host[c])) return APE_EINVAL;
+        bt.mean[c] = mean3_host[c];
+        bt.stdv[c] = std3_host[c];
+    }
+    if (B == 0) return APE_OK;
+    if (!jobs || !out || !ws || ((uintptr_t)out & 15) || ((uintptr_t)ws & 15)) return APE_EINVAL;
+    if (ws_bytes < ape_pose_train_workspace_bytes(B, H, N)) return APE_EWORKSPACE;
+    for (int i = 0; i < B; ++i) {
+        const ape_pose_train_job& j = jobs[i];
+        if (!job_ok(j, H, W) || !crop_ok(j, H, W)) return APE_EINVAL;
+        if (j.out_off < 0 || (j.out_off & 15)) return APE_EINVAL;
+        const size_t need = ape_pose_train_sample_bytes(N, j.rmax - j.rmin, j.cmax - j.cmin);
+        if ((size_t)j.out_off > out_bytes || out_bytes - (size_t)j.out_off < need) return APE_EINVAL;
+    }
+    const int blocks = kImgBlocks + ape::ceil_div(N, kWaves);
+    const char* w = (const char*)ws;
+    for (int i0 = 0; i0 < B; i0 += kJobs) {
+        const int nb = B - i0 < kJobs ? B - i0 : kJobs;
+        for (int i = 0; i < nb; ++i) bt.j[i] = jobs[i0 + i];
+        hipLaunchKernelGGL(pose_samples_kernel, dim3(blocks, nb), dim3(kT), 0, (hipStream_t)stream, bt, i0, H, W, N, (const unsigned long long*)ws,
+                           (const int*)(w + ape_pose_train_tables_offset(B, H)), (const int*)(w + ape_pose_train_sel_offset(B, H)),
+                           (unsigned char*)out, (long)ape_pose_train_image_offset(N));
+    }
+    return ape::check_launch("ape_pose_train_samples");
+}

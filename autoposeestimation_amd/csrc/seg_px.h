@@ -6,8 +6,11 @@
 
 constexpr int kSegResampleBits = 22;          // Resample.c PRECISION_BITS for 8-bit images: 32 - 8 - 2
 
+// The first three functions read only the fields that ape_seg_train_job and ape_pose_train_job (pose_px.h) name alike -- rgb, fa, rot_mode,
+// n_ops, op_* -- and take either.
 // (x, y) of the rotated frame -> source pixel; false = outside the frame (Pillow leaves its zero fill).  Image and label are both 8-bit.
-APE_PX bool seg_rot_src(const ape_seg_train_job& j, int H, int W, int x, int y, int& xs, int& ys)
+template <class Job>
+APE_PX bool seg_rot_src(const Job& j, int H, int W, int x, int y, int& xs, int& ys)
 {
     switch (j.rot_mode) {
         case APE_ROT_NONE: xs = x; ys = y; return true;
@@ -21,7 +24,8 @@ APE_PX bool seg_rot_src(const ape_seg_train_job& j, int H, int W, int x, int y, 
 }
 
 // index of the contrast op, or -1
-APE_PX int seg_contrast_at(const ape_seg_train_job& j)
+template <class Job>
+APE_PX int seg_contrast_at(const Job& j)
 {
     for (int k = 0; k < j.n_ops; ++k)
         if (j.op_code[k] == APE_JIT_CONTRAST) return k;
@@ -29,7 +33,8 @@ APE_PX int seg_contrast_at(const ape_seg_train_job& j)
 }
 
 // pixel (xs, ys) of the UN-rotated frame after the first n_ops colour ops
-APE_PX void seg_jittered_rgb(const ape_seg_train_job& j, int W, int xs, int ys, int n_ops, int mean, int& r, int& g, int& b)
+template <class Job>
+APE_PX void seg_jittered_rgb(const Job& j, int W, int xs, int ys, int n_ops, int mean, int& r, int& g, int& b)
 {
     const uint8_t* px = j.rgb + ((long)ys * W + xs) * 3;
     r = px[0]; g = px[1]; b = px[2];

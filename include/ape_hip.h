@@ -727,6 +727,60 @@ int ape_seg_train_samples(const ape_seg_train_job* jobs_host, int B, int H, int 
 int ape_seg_plain_samples(const ape_seg_train_job* jobs_host, int B, int H, int W, const float* mean3_host, const float* std3_host, float* img,
                           long long* label, void* stream);
 
+/* ---- DenseFusion training samples (csrc/pose_train.hip; reference DenseFusion/datasets/myDatasetAugmented/dataset.py:158-326) ---------
+ * One job per sample: DEVICE pointers to the resident colour frame, 16-bit depth and label, and what the host drew.  Order, as the
+ * reference composes it (:204-214): colour jitter of the full frame (op list as in ape_seg_train_job) -> Image.rotate of colour, label and
+ * depth (rot_mode / a / fa as in ape_bgsub_train_job: the 8-bit images walk `fa`, the depth reads `a` in double at the pixel centre) ->
+ * the get_bbox crop [rmin, rmax) x [cmin, cmax) of the rotated frame -> `choose`, the back-projected cloud and the normalised crop.
+ * The crop, the intrinsics (as C floats: numpy computes the cloud in float32), depth_scale, to_meter, add_noise / add_t (the translation
+ * noise, double: numpy adds it in float64 and rounds once) and out_off (byte offset of the sample in the output block, a multiple of 16)
+ * are read by launch B only. */
+typedef struct ape_pose_train_job {
+    const uint8_t* rgb;        /* [H][W][3] */
+    const uint16_t* depth;     /* [H][W] */
+    const uint8_t* label;      /* [H][W] */
+    double a[6];
+    double add_t[3];
+    long long out_off;
+    int fa[6];
+    int rot_mode;
+    int n_ops;
+    int op_code[4];
+    float op_factor[4];
+    int op_shift[4];
+    int rmin, rmax, cmin, cmax;
+    float ppx, ppy, fx, fy, depth_scale;
+    int to_meter, add_noise;
+    int reserved;
+} ape_pose_train_job;
+/* The workspace of a batch: [B][64] u64 luma partial sums | at ape_pose_train_extents_offset(B): [B][64][4] i32 extent partials, then
+ * [B][H] i32 row counts (one read-back covers both) | at ape_pose_train_tables_offset(B, H): [B][H] i32 exclusive row prefix, then
+ * [B][N] i32 `sel` (one upload covers both).  One per stream; not shared by batches in flight at once. */
+size_t ape_pose_train_extents_offset(int B);
+size_t ape_pose_train_rows_offset(int B);
+size_t ape_pose_train_tables_offset(int B, int H);
+size_t ape_pose_train_sel_offset(int B, int H);
+size_t ape_pose_train_workspace_bytes(int B, int H, int N);
+/* bytes of one sample in the output block: choose[N] i64 | points[N][3] f32 | (at ape_pose_train_image_offset(N), a multiple of 16)
+ * img[3][Hc][Wc] f32; the total is rounded up to a multiple of 16 */
+size_t ape_pose_train_image_offset(int N);
+size_t ape_pose_train_sample_bytes(int N, int Hc, int Wc);
+/* Launch A over the full frames: per sample 64 workgroups, each writing ONE partial of the integer L sum of the un-rotated frame as it is
+ * when its contrast op runs and one (min row, max row, min column, max column) of the ROTATED label's pixels == 255 (INT_MAX, -1, INT_MAX,
+ * -1 when it saw none); and rows[b][y] = the number of VALID pixels of row y (rotated label == 255 and rotated depth != 0), each row
+ * written once by the one wave that walked it.  No atomics, nothing to zero.  The crop and what follows it in a job are not read. */
+int ape_pose_train_stats(const ape_pose_train_job* jobs_host, int B, int H, int W, void* ws, size_t ws_bytes, void* stream);
+/* Launch B.  The caller has read extents and row counts back, set the crops (every labelled pixel lies inside get_bbox's crop, so the row
+ * counts are in-crop counts), and copied into the workspace the exclusive prefix of every sample's row counts and sel[B][N]: the RANKS,
+ * among the valid pixels in row-major order, that `choose` keeps.  Per sample, at out + out_off: choose[j] = the flat index inside the crop
+ * of the valid pixel of rank sel[j] (row by the prefix, column by a ballot walk of that row; 0 and a zero point when no such pixel
+ * exists), points[j] = its back-projection in float32 without fused multiply-adds (+ add_t in double, rounded once, when add_noise),
+ * img = ((float)v - mean[c]) / std[c] of the jittered, rotated frame inside the crop, planar (mean3 / std3: HOST pointers).
+ * A crop outside the frame, outside 40..480 x 40..640 or not a multiple of 40, a sample that does not fit out_bytes, out or out_off not
+ * 16-byte aligned: APE_EINVAL, nothing launched. */
+int ape_pose_train_samples(const ape_pose_train_job* jobs_host, int B, int H, int W, int N, const float* mean3_host, const float* std3_host,
+                           void* out, size_t out_bytes, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,211 @@
+"""Host check of autoposeestimation_amd/csrc/pose_px.h against PoseDataset.sample_host (Pillow and numpy; no GPU).
+
+The header holds the per-pixel arithmetic of DenseFusion's training-sample kernels (csrc/pose_train.hip) in plain C++.  This tool compiles
+it with the host compiler (-ffp-contract=off, as csrc/Makefile) behind plain loops that do, pixel by pixel and without waves, what the two
+launches do -- L sum, extents of the rotated label and valid pixels per row; then, with the host's get_bbox arithmetic, row prefixes and
+ranks in between, `choose`, the back-projected cloud and the normalised crop -- and compares whole samples, exactly, with `sample_host`
+over a synthetic data-set tree.  It is a stand-alone program: `--sanitize` builds the host code with -fsanitize=address,undefined into an
+executable of its own (never into this interpreter) and runs it over the same jobs.
+Usage: python tools/check_pose_px.py [--quick] [--sanitize]"""
+import ctypes
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+_SRC = r"""
+#include <limits.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <vector>
+#include "pose_px.h"
+extern "C" void stats(const ape_pose_train_job* j, int H, int W, int* ext, int* rows, unsigned long long* lsum) {
+    const int kc = seg_contrast_at(*j);
+    unsigned long long s = 0;
+    int e[4] = {INT_MAX, -1, INT_MAX, -1};
+    for (int y = 0; y < H; ++y) {
+        int cnt = 0;
+        for (int x = 0; x < W; ++x) {
+            if (kc >= 0) { int r, g, b; seg_jittered_rgb(*j, W, x, y, kc, 0, r, g, b); s += pil_luma(r, g, b); }
+            if (pose_label_at(*j, H, W, x, y) == 255) {
+                e[0] = y < e[0] ? y : e[0]; e[1] = y > e[1] ? y : e[1]; e[2] = x < e[2] ? x : e[2]; e[3] = x > e[3] ? x : e[3];
+                cnt += pose_depth_at(*j, H, W, x, y) != 0;
+            }
+        }
+        rows[y] = cnt;
+    }
+    for (int i = 0; i < 4; ++i) ext[i] = e[i];
+    *lsum = s;
+}
+extern "C" void samples(const ape_pose_train_job* j, int H, int W, int N, unsigned long long lsum, const int* prefix, const int* sel,
+                        const float* mean3, const float* std3, long long* choose, float* points, float* img) {
+    const int mean = seg_contrast_at(*j) >= 0 ? bgsub_mean_of_sum(lsum, H, W) : 0;
+    const int Hc = j->rmax - j->rmin, Wc = j->cmax - j->cmin;
+    const long plane = (long)Hc * Wc;
+    for (long i = 0; i < plane; ++i) {
+        int c[3];
+        pose_rgb_at(*j, H, W, j->cmin + (int)(i % Wc), j->rmin + (int)(i / Wc), mean, c[0], c[1], c[2]);
+        for (int k = 0; k < 3; ++k) img[k * plane + i] = ((float)c[k] - mean3[k]) / std3[k];
+    }
+    for (int pt = 0; pt < N; ++pt) {
+        const int y = pose_row_of_rank(prefix, H, sel[pt]);
+        int rem = sel[pt] - prefix[y];
+        choose[pt] = 0; points[3 * pt] = points[3 * pt + 1] = points[3 * pt + 2] = 0.f;
+        for (int x = 0; x < W; ++x) {
+            if (!pose_valid(*j, H, W, x, y)) continue;
+            if (rem-- == 0) {
+                choose[pt] = (long long)(y - j->rmin) * Wc + (x - j->cmin);
+                pose_point(*j, x, y, pose_depth_at(*j, H, W, x, y), points + 3 * pt);
+                break;
+            }
+        }
+    }
+}
+#ifdef POSE_PX_MAIN
+// stand-alone form for the sanitizer build: jobs from a file written by tools/check_pose_px.py --sanitize, results to stdout as a checksum
+static void rd(FILE* f, void* p, size_t n) { if (fread(p, 1, n, f) != n) { fprintf(stderr, "short read\n"); exit(2); } }
+int main(int argc, char** argv) {
+    if (argc < 2) return 2;
+    FILE* f = fopen(argv[1], "rb");
+    if (!f) return 2;
+    int hdr[4];
+    rd(f, hdr, sizeof hdr);
+    const int n_jobs = hdr[0], H = hdr[1], W = hdr[2], N = hdr[3];
+    const float mean3[3] = {0.485f, 0.456f, 0.406f}, std3[3] = {0.229f, 0.224f, 0.225f};
+    unsigned long long sum = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        ape_pose_train_job j;
+        rd(f, &j, sizeof j);
+        std::vector<uint8_t> rgb((size_t)H * W * 3), label((size_t)H * W);
+        std::vector<uint16_t> depth((size_t)H * W);
+        std::vector<int> prefix(H), sel(N), rows(H);
+        rd(f, rgb.data(), rgb.size()); rd(f, depth.data(), depth.size() * 2); rd(f, label.data(), label.size());
+        rd(f, prefix.data(), (size_t)H * 4); rd(f, sel.data(), (size_t)N * 4);
+        j.rgb = rgb.data(); j.depth = depth.data(); j.label = label.data();
+        int ext[4];
+        unsigned long long lsum;
+        stats(&j, H, W, ext, rows.data(), &lsum);
+        const size_t plane = (size_t)(j.rmax - j.rmin) * (j.cmax - j.cmin);
+        std::vector<long long> choose(N);
+        std::vector<float> points((size_t)N * 3), img(plane * 3);
+        samples(&j, H, W, N, lsum, prefix.data(), sel.data(), mean3, std3, choose.data(), points.data(), img.data());
+        for (int k = 0; k < N; ++k) sum += (unsigned long long)choose[k];
+        for (int k = 0; k < 4; ++k) sum += (unsigned long long)ext[k];
+    }
+    fclose(f);
+    printf("jobs %d checksum %llu\n", n_jobs, sum);
+    return 0;
+}
+#endif
+"""
+_INC = os.path.join(REPO, "autoposeestimation_amd", "csrc")
+
+
+def build():
+    d = tempfile.mkdtemp(prefix="pose_px_")
+    with open(os.path.join(d, "px.cpp"), "w") as f:
+        f.write(_SRC)
+    so = os.path.join(d, "libpx.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I", _INC, os.path.join(d, "px.cpp"), "-o", so])
+    return ctypes.CDLL(so)
+
+
+def _p(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def host_sample(lib, ds, rgb, depth, label, params, cam, name="?", record=None, select=None):
+    """the header's passes over one sample on the host, with the package's own arithmetic in between (augment.py) -> (points[N,3] f32,
+    choose[N] i64, img[3,Hc,Wc] f32, box); select(count) draws the subset when there are more valid pixels than points (it is stored in
+    `params`, as PoseDataset.batch stores it)"""
+    from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented import augment as G
+    from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented.dataset import _MEAN, _STD, bbox_from_extents
+    rgb, depth, label = np.ascontiguousarray(rgb), np.ascontiguousarray(depth), np.ascontiguousarray(label)
+    h, w = label.shape
+    n = ds.num_pt
+    job = G.make_job(params, h, w, rgb.ctypes.data, depth.ctypes.data, label.ctypes.data, cam[0], cam[1], ds.to_meter, ds.add_noise)
+    ext, rows, lsum = np.zeros(4, np.int32), np.zeros(h, np.int32), ctypes.c_ulonglong(0)
+    lib.stats(ctypes.byref(job), h, w, _p(ext), _p(rows), ctypes.byref(lsum))
+    if ext[1] < 0:
+        raise ValueError("sample %s: no label pixel" % name)
+    box = bbox_from_extents(*ext)
+    count = int(rows.sum())
+    if count > n and params.get("subset") is None:
+        params["subset"] = select(count)
+    sel = np.ascontiguousarray(G.selection(count, n, params.get("subset")))
+    prefix = np.ascontiguousarray(G.row_prefix(rows))
+    G.set_crop(job, box)
+    hc, wc = box[1] - box[0], box[3] - box[2]
+    choose, points, img = np.zeros(n, np.int64), np.zeros((n, 3), np.float32), np.zeros((3, hc, wc), np.float32)
+    mean, std = np.ascontiguousarray(_MEAN), np.ascontiguousarray(_STD)
+    lib.samples(ctypes.byref(job), h, w, n, lsum, _p(prefix), _p(sel), _p(mean), _p(std), _p(choose), _p(points), _p(img))
+    if record is not None:
+        record.append(bytes(job) + rgb.tobytes() + depth.tobytes() + label.tobytes() + prefix.tobytes() + sel.tobytes())
+    return points, choose, img, box
+
+
+def _cases(quick):
+    ops = [("brightness", 1.13), ("contrast", 0.87), ("saturation", 1.08), ("hue", -0.031)]
+    angles = [None, 180.0, 33.3, -120.5, 0.0, -180.0, 1e-3, 45.0, 90.0, 271.7]
+    lists = [ops, ops[::-1], [], [ops[1]], [ops[0], ops[3]]]
+    out = []
+    for t in range(6 if quick else 30):
+        out.append(dict(angle=angles[t % len(angles)], ops=lists[t % len(lists)], noise=t % 3 != 2, to_meter=t % 4 != 3, n=[500, 1000, 60000][t % 3]))
+    return out
+
+
+def run(quick=True, sanitize=False, verbose=True):
+    """-> the number of samples compared (every one exact, or AssertionError)"""
+    from PIL import Image
+    from autoposeestimation_amd import synthetic as S
+    from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented.dataset import PoseDataset
+    lib = build()
+    lib.samples.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong] + [ctypes.c_void_p] * 7
+    root = tempfile.mkdtemp(prefix="pose_px_tree_")
+    S.pose_dataset_tree(root)
+    rng = np.random.default_rng(11)
+    done, record, n_rec = 0, [], None
+    for t, c in enumerate(_cases(quick)):
+        ds = PoseDataset("train", c["n"], c["noise"], 0.03, False, "synth", root, to_meter=c["to_meter"], p_extra_data=0.0, seed=t)
+        i = t % len(ds)
+        rel, lmode, _ = ds._entry(i)
+        rgb, depth, label = (np.array(x) for x in ds._open(rel, lmode))
+        image_meta, meta = ds._metas(rel)
+        obj = ds.class_id_names.index(meta["cls_name"])
+        params = {"entry": (rel, lmode), "ops": c["ops"], "angle": c["angle"], "add_t": list(rng.uniform(-0.03, 0.03, 3)),
+                  "dellist": sorted(rng.choice(len(ds.cld[obj]), len(ds.cld[obj]) - ds.num_pt_mesh, replace=False).tolist())}
+        rec = record if sanitize and c["n"] == (n_rec or c["n"]) else None
+        if rec is not None:
+            n_rec = c["n"]
+        points, choose, img, box = host_sample(lib, ds, rgb, depth, label, params, (image_meta["intr"], image_meta["depth_scale"]), rel, rec,
+                                               select=lambda count: np.sort(rng.choice(count, c["n"], replace=False)))
+        want = ds.sample_host(i, params)
+        for got, wv, name in zip((points, choose[None], img), want[:3], ("points", "choose", "img")):
+            bad = int((got != wv.numpy()).sum()) if got.shape == tuple(wv.shape) else -1
+            assert bad == 0, "%s differs in %d places: sample %s case %r box %r" % (name, bad, rel, c, box)
+        done += 1
+    if verbose:
+        print("samples: %d exact against sample_host (Pillow %s, numpy %s)" % (done, Image.__version__, np.__version__))
+    if sanitize:
+        d = tempfile.mkdtemp(prefix="pose_px_san_")
+        with open(os.path.join(d, "px.cpp"), "w") as f:
+            f.write(_SRC)
+        exe, jobs = os.path.join(d, "px_san"), os.path.join(d, "jobs.bin")
+        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                               "-DPOSE_PX_MAIN", "-I", _INC, os.path.join(d, "px.cpp"), "-o", exe])
+        with open(jobs, "wb") as f:
+            f.write(np.array([len(record), 480, 640, n_rec], np.int32).tobytes())
+            for r in record:
+                f.write(r)
+        print(subprocess.check_output([exe, jobs]).decode().strip(), "(address + undefined-behaviour sanitizers: clean)")
+    return done
+
+
+if __name__ == "__main__":
+    run(quick="--quick" in sys.argv, sanitize="--sanitize" in sys.argv)
