@@ -15,34 +15,16 @@ import numpy as np
 import torch
 
 from autoposeestimation_amd import _lib
-from autoposeestimation_amd.background_subtraction.augment import MAX_OPS, _OP_CODES, rotation
+from autoposeestimation_amd import sample_jobs as J
 from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented.dataset import bbox_from_extents
-
-PARTIALS = 64                # extent / sum partials per sample (csrc/pose_train.hip kBlocks)
 
 
 def make_job(params, h, w, rgb, depth, label, intr, depth_scale, to_meter, add_noise):
     """one `ape_pose_train_job` without its crop and output offset; the frames are addresses (device pointers for the kernels)"""
     job = _lib.PoseTrainJob()
     job.rgb, job.depth, job.label = rgb, depth, label
-    mode, a, fa = rotation(params.get("angle") if add_noise else None, h, w)
-    job.rot_mode = mode
-    for i in range(6):
-        job.a[i], job.fa[i] = a[i], fa[i]
-    ops = list(params.get("ops") or []) if add_noise else []
-    if len(ops) > MAX_OPS:
-        raise ValueError("at most %d colour ops, got %d" % (MAX_OPS, len(ops)))
-    if sum(1 for name, _ in ops if name == "contrast") > 1:
-        raise ValueError("at most one contrast op (its mean is taken over the whole image in a pass of its own)")
-    job.n_ops = len(ops)
-    for k, (name, f) in enumerate(ops):
-        if name not in _OP_CODES:
-            raise ValueError("unknown colour op %r" % (name,))
-        job.op_code[k] = _OP_CODES[name]
-        if name == "hue":
-            job.op_shift[k] = int(f * 255) & 0xFF              # adjust_hue's uint8 shift
-        else:
-            job.op_factor[k] = float(f)                        # Image.blend takes a C float
+    J.fill_rotation(job.rot, params.get("angle") if add_noise else None, h, w)
+    J.fill_jitter(job.jit, params.get("ops") if add_noise else None)
     # numpy computes the cloud in float32: the Python floats of the meta file enter as float32 scalars
     job.ppx, job.ppy, job.fx, job.fy = float(intr["ppx"]), float(intr["ppy"]), float(intr["fx"]), float(intr["fy"])
     job.depth_scale = float(depth_scale)
@@ -55,12 +37,6 @@ def make_job(params, h, w, rgb, depth, label, intr, depth_scale, to_meter, add_n
 
 def set_crop(job, box):
     job.rmin, job.rmax, job.cmin, job.cmax = [int(v) for v in box]
-
-
-def combine_extents(partials):
-    """[B, PARTIALS, 4] partials of ape_pose_train_stats -> [B, 4] (min row, max row, min column, max column)"""
-    p = np.asarray(partials).reshape(-1, PARTIALS, 4)
-    return np.stack([p[:, :, 0].min(1), p[:, :, 1].max(1), p[:, :, 2].min(1), p[:, :, 3].max(1)], 1)
 
 
 def selection(count, n, subset=None):
@@ -82,31 +58,6 @@ def row_prefix(rows):
     return (np.cumsum(rows, axis=-1) - rows).astype(np.int32)
 
 
-def _frame(t, dtype, shape, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise _lib.ApeError("%s must be a device tensor (the sample builder has no CPU path)" % what)
-    if t.dtype != dtype:
-        raise TypeError("%s must be %s, got %s" % (what, dtype, t.dtype))
-    if tuple(t.shape) != shape:
-        raise ValueError("%s must be %s, got %s" % (what, shape, tuple(t.shape)))
-    if not t.is_contiguous():
-        raise ValueError("%s must be contiguous" % what)
-    return t.data_ptr()
-
-
-_ws = {}          # (device, stream) -> workspace, kept for the life of the process like segmentation/augment.py's: one entry per stream
-                  # that ever built a batch (the driver uses one), ~10 KB per sample of the largest batch seen there
-
-
-def _workspace(dev, nbytes):
-    key = (str(dev), _lib.stream_ptr().value)
-    ws = _ws.get(key)
-    if ws is None or ws.numel() < nbytes:                      # one per stream: it carries a batch's sums and tables between its launches
-        ws = torch.empty(max(nbytes, 64 * 1024), dtype=torch.uint8, device=dev)
-        _ws[key] = ws
-    return ws
-
-
 def build_samples(samples, params, cams, num_pt, to_meter, add_noise, mean, std, select, names=None):
     """samples: per sample (rgb[H,W,3] u8, depth[H,W] u16, label[H,W] u8) device tensors (views into a resident set; nothing is copied);
     params: one parameter dict per sample; cams: per sample (intr dict, depth_scale); select(k, count): called once per sample, in sample
@@ -124,15 +75,15 @@ def build_samples(samples, params, cams, num_pt, to_meter, add_noise, mean, std,
     name = lambda i: i if names is None else names[i]  # noqa: E731
     jobs = (_lib.PoseTrainJob * b)()
     for i, ((rgb, depth, label), p, (intr, scale)) in enumerate(zip(samples, params, cams)):
-        jobs[i] = make_job(p, h, w, _frame(rgb, torch.uint8, (h, w, 3), "frame"), _frame(depth, torch.uint16, (h, w), "depth"),
-                           _frame(label, torch.uint8, (h, w), "label"), intr, scale, to_meter, add_noise)
+        jobs[i] = make_job(p, h, w, J.frame(rgb, torch.uint8, (h, w, 3), "frame"), J.frame(depth, torch.uint16, (h, w), "depth"),
+                           J.frame(label, torch.uint8, (h, w), "label"), intr, scale, to_meter, add_noise)
     L = _lib.lib()
-    ws = _workspace(dev, L.ape_pose_train_workspace_bytes(b, h, n))
+    ws = J.workspace("pose", dev, L.ape_pose_train_workspace_bytes(b, h, n))
     jp = ctypes.cast(jobs, ctypes.c_void_p)
     _lib.call.ape_pose_train_stats(jp, b, h, w, _lib.dptr(ws), ws.numel(), _lib.stream_ptr())
     e0, r0, t0 = L.ape_pose_train_extents_offset(b), L.ape_pose_train_rows_offset(b), L.ape_pose_train_tables_offset(b, h)
     back = ws[e0:t0].cpu().numpy()                               # the one read-back of the batch
-    ext = combine_extents(back[:r0 - e0].view(np.int32))
+    ext = J.combine_extents(back[:r0 - e0].view(np.int32), 4)
     rows = back[r0 - e0:r0 - e0 + b * h * 4].view(np.int32).reshape(b, h)
     tab = np.empty(b * h + b * n, np.int32)
     tab[:b * h] = row_prefix(rows).reshape(-1)
@@ -140,7 +91,7 @@ def build_samples(samples, params, cams, num_pt, to_meter, add_noise, mean, std,
     for i in range(b):
         if ext[i, 1] < 0:
             raise ValueError("sample %s: the label has no pixel equal to 255%s: get_bbox has no object to crop around"
-                             % (name(i), " after its rotation" if jobs[i].rot_mode else ""))
+                             % (name(i), " after its rotation" if jobs[i].rot.mode else ""))
         box = bbox_from_extents(*ext[i])
         count = int(rows[i].sum())               # whole rows: every labelled pixel lies inside the crop (csrc/pose_train.hip)
         if count == 0:
@@ -152,10 +103,8 @@ def build_samples(samples, params, cams, num_pt, to_meter, add_noise, mean, std,
         total += L.ape_pose_train_sample_bytes(n, box[1] - box[0], box[3] - box[2])
     ws[t0:t0 + tab.nbytes].view(torch.int32).copy_(torch.from_numpy(tab))        # the one upload: row prefixes and ranks
     block = torch.empty(total, dtype=torch.uint8, device=dev)
-    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
-    sd = (ctypes.c_float * 3)(*[float(v) for v in std])
-    _lib.call.ape_pose_train_samples(jp, b, h, w, n, ctypes.cast(m, ctypes.c_void_p), ctypes.cast(sd, ctypes.c_void_p), _lib.dptr(block),
-                                     block.numel(), _lib.dptr(ws), ws.numel(), _lib.stream_ptr())
+    m, sd = J.norm(mean, std, 3)
+    _lib.call.ape_pose_train_samples(jp, b, h, w, n, m, sd, _lib.dptr(block), block.numel(), _lib.dptr(ws), ws.numel(), _lib.stream_ptr())
     img_off = L.ape_pose_train_image_offset(n)
     views = []
     for i, o in enumerate(offsets):

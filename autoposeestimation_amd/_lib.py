@@ -196,29 +196,34 @@ class ConvParams(_c.Structure):
                [("alpha", _c.c_float), ("bias_bstride", _c.c_int32), ("ldr", _c.c_int32), ("roff", _c.c_int32), ("ups", _c.c_int32)]
 
 
+class AugRotation(_c.Structure):
+    """Mirror of `ape_aug_rotation` (include/ape_hip.h)."""
+    _fields_ = [("a", _c.c_double * 6), ("fa", _c.c_int32 * 6), ("mode", _c.c_int32), ("reserved", _c.c_int32)]
+
+
+class AugJitter(_c.Structure):
+    """Mirror of `ape_aug_jitter` (include/ape_hip.h)."""
+    _fields_ = [("n_ops", _c.c_int32), ("code", _c.c_int32 * 4), ("factor", _c.c_float * 4), ("shift", _c.c_int32 * 4)]
+
+
 class BgsubTrainJob(_c.Structure):
     """Mirror of `ape_bgsub_train_job` (include/ape_hip.h)."""
     _fields_ = [("f_rgb", _c.c_void_p), ("b_rgb", _c.c_void_p), ("f_depth", _c.c_void_p), ("b_depth", _c.c_void_p), ("label", _c.c_void_p),
-                ("a", _c.c_double * 6), ("fa", _c.c_int32 * 6), ("rot_mode", _c.c_int32), ("hflip", _c.c_int32), ("vflip", _c.c_int32),
-                ("n_ops", _c.c_int32 * 2), ("op_code", (_c.c_int32 * 4) * 2), ("op_factor", (_c.c_float * 4) * 2),
-                ("op_shift", (_c.c_int32 * 4) * 2), ("reserved", _c.c_int32)]
+                ("rot", AugRotation), ("jit", AugJitter * 2), ("hflip", _c.c_int32), ("vflip", _c.c_int32)]
 
 
 class SegTrainJob(_c.Structure):
     """Mirror of `ape_seg_train_job` (include/ape_hip.h)."""
-    _fields_ = [("rgb", _c.c_void_p), ("label", _c.c_void_p), ("fa", _c.c_int32 * 6), ("rot_mode", _c.c_int32), ("n_ops", _c.c_int32),
-                ("op_code", _c.c_int32 * 4), ("op_factor", _c.c_float * 4), ("op_shift", _c.c_int32 * 4), ("crop_x", _c.c_int32),
+    _fields_ = [("rgb", _c.c_void_p), ("label", _c.c_void_p), ("rot", AugRotation), ("jit", AugJitter), ("crop_x", _c.c_int32),
                 ("crop_y", _c.c_int32), ("crop_side", _c.c_int32), ("class_id", _c.c_int32)]
 
 
 class PoseTrainJob(_c.Structure):
     """Mirror of `ape_pose_train_job` (include/ape_hip.h)."""
-    _fields_ = [("rgb", _c.c_void_p), ("depth", _c.c_void_p), ("label", _c.c_void_p), ("a", _c.c_double * 6), ("add_t", _c.c_double * 3),
-                ("out_off", _c.c_longlong), ("fa", _c.c_int32 * 6), ("rot_mode", _c.c_int32), ("n_ops", _c.c_int32),
-                ("op_code", _c.c_int32 * 4), ("op_factor", _c.c_float * 4), ("op_shift", _c.c_int32 * 4), ("rmin", _c.c_int32),
-                ("rmax", _c.c_int32), ("cmin", _c.c_int32), ("cmax", _c.c_int32), ("ppx", _c.c_float), ("ppy", _c.c_float),
-                ("fx", _c.c_float), ("fy", _c.c_float), ("depth_scale", _c.c_float), ("to_meter", _c.c_int32), ("add_noise", _c.c_int32),
-                ("reserved", _c.c_int32)]
+    _fields_ = [("rgb", _c.c_void_p), ("depth", _c.c_void_p), ("label", _c.c_void_p), ("rot", AugRotation), ("add_t", _c.c_double * 3),
+                ("out_off", _c.c_longlong), ("jit", AugJitter), ("rmin", _c.c_int32), ("rmax", _c.c_int32), ("cmin", _c.c_int32),
+                ("cmax", _c.c_int32), ("ppx", _c.c_float), ("ppy", _c.c_float), ("fx", _c.c_float), ("fy", _c.c_float),
+                ("depth_scale", _c.c_float), ("to_meter", _c.c_int32), ("add_noise", _c.c_int32)]
 
 
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_SIGMOID = 0, 1, 2, 3
@@ -239,7 +244,7 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
 _lib = None
 
 
-ABI_VERSION = 8      # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 9      # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

@@ -1,173 +1,36 @@
-// Per-pixel arithmetic of the background-subtraction feature kernels (segpost.hip: inference, bgsub_train.hip: training samples),
-// written as Pillow's C does it so the results agree with Pillow bit for bit.  Plain C++ without device intrinsics: the same text
-// compiles for the host (tools/check_bgsub_px.py builds it with the host compiler and compares it with the installed Pillow over whole
-// value ranges) and for the device.  Everything relies on -ffp-contract=off (csrc/Makefile): no multiply-add is fused.
+// The two-image pixel of the background-subtraction training samples (bgsub_train.hip), on top of aug_px.h: plain C++, so
+// tools/check_bgsub_px.py compiles the same text for the host and compares whole samples with the installed Pillow.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/ape_hip.h"
-
-#if defined(__HIPCC__)
-#define APE_PX __host__ __device__ __forceinline__
-#else
-#define APE_PX static inline
-#endif
-
-// Pillow's rgb2hsv_row (Convert.c, follows colorsys.py): float divisions, the hue wrap and the * 255.0 in double, truncation.
-// Pinned bit for bit against PIL over all 2^24 colours (tools/gen_golden_bgsub.py).
-APE_PX void pil_hsv(int r, int g, int b, int& uh, int& us, int& uv)
-{
-    const int gb_max = g > b ? g : b, gb_min = g < b ? g : b;
-    const int maxc = r > gb_max ? r : gb_max, minc = r < gb_min ? r : gb_min;
-    uv = maxc;
-    if (minc == maxc) { uh = 0; us = 0; return; }
-    const float cr = (float)(maxc - minc);
-    const float s = cr / (float)maxc;
-    const float rc = (float)(maxc - r) / cr, gc = (float)(maxc - g) / cr, bc = (float)(maxc - b) / cr;
-    float h;
-    if (r == maxc) h = bc - gc;
-    else if (g == maxc) h = (float)(2.0 + (double)rc - (double)bc);
-    else h = (float)(4.0 + (double)gc - (double)rc);
-    const double hw = (double)h / 6.0 + 1.0;
-    h = (float)(hw - floor(hw));                    // fmod(., 1.0) of a positive double: exact
-    const int ih = (int)((double)h * 255.0), is = (int)((double)s * 255.0);
-    uh = ih < 0 ? 0 : (ih > 255 ? 255 : ih);
-    us = is < 0 ? 0 : (is > 255 ? 255 : is);
-}
-
-APE_PX int pil_clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
-// Pillow's hsv2rgb (Convert.c): the sector and the remainder in double, `fs * f` in float, round() half away from zero.
-APE_PX void pil_hsv2rgb(int h, int s, int v, int& r, int& g, int& b)
-{
-    if (s == 0) { r = g = b = v; return; }
-    const double h6 = (double)(float)h * 6.0 / 255.0;
-    const int i = (int)floor(h6);
-    const float f = (float)(h6 - (double)(float)i);
-    const float fs = (float)((double)(float)s / 255.0);
-    const double fv = (double)(float)v;
-    const int p = pil_clip8((int)round(fv * (1.0 - (double)fs)));
-    const int q = pil_clip8((int)round(fv * (1.0 - (double)(fs * f))));
-    const int t = pil_clip8((int)round(fv * (1.0 - (double)fs * (1.0 - (double)f))));
-    switch (i % 6) {
-        case 0: r = v; g = t; b = p; break;
-        case 1: r = q; g = v; b = p; break;
-        case 2: r = p; g = v; b = t; break;
-        case 3: r = p; g = q; b = v; break;
-        case 4: r = t; g = p; b = v; break;
-        default: r = v; g = p; b = q; break;
-    }
-}
-
-// Pillow's rgb2l (Convert.c, L24 with rounding): ITU-R 601-2 luma in 16.16
-APE_PX int pil_luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
-
-// ImagingBlend (Blend.c) of one band value: degenerate + alpha * (image - degenerate) in C float, truncated; clipped when alpha is
-// outside [0, 1]; alpha 0 / 1 return an input untouched
-APE_PX int pil_blend(int deg, int img, float alpha)
-{
-    if (alpha == 0.0f) return deg;
-    if (alpha == 1.0f) return img;
-    const float prod = alpha * (float)(img - deg);
-    const float t = (float)deg + prod;
-    if (alpha >= 0.0f && alpha <= 1.0f) return (int)t & 255;
-    return t <= 0.0f ? 0 : (t >= 255.0f ? 255 : (int)t);
-}
-
-// one colour op of the jitter on one pixel; `mean` is the rounded mean of L over the whole image (contrast only), `shift` the u8 hue shift
-APE_PX void pil_jitter_op(int code, float factor, int shift, int mean, int& r, int& g, int& b)
-{
-    if (code == APE_JIT_BRIGHTNESS) {
-        r = pil_blend(0, r, factor); g = pil_blend(0, g, factor); b = pil_blend(0, b, factor);
-    } else if (code == APE_JIT_CONTRAST) {
-        r = pil_blend(mean, r, factor); g = pil_blend(mean, g, factor); b = pil_blend(mean, b, factor);
-    } else if (code == APE_JIT_SATURATION) {
-        const int l = pil_luma(r, g, b);
-        r = pil_blend(l, r, factor); g = pil_blend(l, g, factor); b = pil_blend(l, b, factor);
-    } else if (code == APE_JIT_HUE) {
-        int h, s, v;
-        pil_hsv(r, g, b, h, s, v);
-        pil_hsv2rgb((h + shift) & 255, s, v, r, g, b);
-    }
-}
-
-// Source pixel of Pillow's affine nearest-neighbour walk.  8-bit images (Geometry.c affine_fixed): 16.16 fixed point, the start of a row
-// and the step along it accumulate in 32-bit integers (wrapping), so pixel (x, y) reads (fa[2] + y*fa[1] + x*fa[0]) >> 16.
-APE_PX void pil_affine_fixed(const int* fa, int x, int y, int& xin, int& yin)
-{
-    const unsigned int xx = (unsigned int)fa[2] + (unsigned int)y * (unsigned int)fa[1] + (unsigned int)x * (unsigned int)fa[0];
-    const unsigned int yy = (unsigned int)fa[5] + (unsigned int)y * (unsigned int)fa[4] + (unsigned int)x * (unsigned int)fa[3];
-    xin = (int)xx >> 16;
-    yin = (int)yy >> 16;
-}
-
-// 16-bit images (`I;16`, Geometry.c ImagingGenericTransform + affine_transform + nearest_filter16): double precision at the pixel
-// centre, COORD() truncates and sends negatives to -1
-APE_PX void pil_affine_double(const double* a, int x, int y, int& xin, int& yin)
-{
-    const double xc = (double)x + 0.5, yc = (double)y + 0.5;
-    const double xo = a[0] * xc + a[1] * yc + a[2];
-    const double yo = a[3] * xc + a[4] * yc + a[5];
-    xin = xo < 0.0 ? -1 : (xo >= 2147483647.0 ? 2147483647 : (int)xo);
-    yin = yo < 0.0 ? -1 : (yo >= 2147483647.0 ? 2147483647 : (int)yo);
-}
-
-// ---- one training sample (ape_bgsub_train_samples), pixel by pixel --------------------------------------------------------------------
-// (x, y) of the rotated image -> source pixel; false = outside the frame (Pillow leaves its zero fill).  wide = the 16-bit route.
-APE_PX bool bgsub_rot_src(const ape_bgsub_train_job& j, int H, int W, int x, int y, bool wide, int& xs, int& ys)
-{
-    switch (j.rot_mode) {
-        case APE_ROT_NONE: xs = x; ys = y; return true;
-        case APE_ROT_180: xs = W - 1 - x; ys = H - 1 - y; return true;
-        case APE_ROT_90: xs = W - 1 - y; ys = x; return true;            // Image.Transpose.ROTATE_90 (counter-clockwise), W == H
-        case APE_ROT_270: xs = y; ys = H - 1 - x; return true;
-        default: break;
-    }
-    if (wide) pil_affine_double(j.a, x, y, xs, ys);
-    else pil_affine_fixed(j.fa, x, y, xs, ys);
-    return xs >= 0 && xs < W && ys >= 0 && ys < H;
-}
-
-// index of the contrast op in image `im`'s list, or -1
-APE_PX int bgsub_contrast_at(const ape_bgsub_train_job& j, int im)
-{
-    for (int k = 0; k < j.n_ops[im]; ++k)
-        if (j.op_code[im][k] == APE_JIT_CONTRAST) return k;
-    return -1;
-}
+#include "aug_px.h"
 
 // RGB of image `im` (0 foreground, 1 background) at (x, y) of the rotated image after its first n_ops colour ops
 APE_PX void bgsub_jittered_rgb(const ape_bgsub_train_job& j, int im, int H, int W, int x, int y, int n_ops, int mean, int& r, int& g, int& b)
 {
     int xs, ys;
     r = g = b = 0;
-    if (bgsub_rot_src(j, H, W, x, y, false, xs, ys)) {
+    if (aug_rot_src(j.rot, H, W, x, y, false, xs, ys)) {
         const uint8_t* px = (im ? j.b_rgb : j.f_rgb) + ((long)ys * W + xs) * 3;
         r = px[0]; g = px[1]; b = px[2];
     }
-    for (int k = 0; k < n_ops; ++k) pil_jitter_op(j.op_code[im][k], j.op_factor[im][k], j.op_shift[im][k], mean, r, g, b);
+    aug_jitter(j.jit[im], n_ops, mean, r, g, b);
 }
-
-// ImageEnhance.Contrast's `int(ImageStat.Stat(L).mean[0] + 0.5)` from the integer sum of L
-APE_PX int bgsub_mean_of_sum(unsigned long long sum, int H, int W) { return (int)((double)sum / (double)((long)H * W) + 0.5); }
 
 // output pixel (xo, yo): ch[7] = the uint8 difference channels, returns the label bit
 APE_PX int bgsub_train_pixel(const ape_bgsub_train_job& j, int H, int W, int xo, int yo, int mean_f, int mean_b, int* ch)
 {
     const int x = j.hflip ? W - 1 - xo : xo, y = j.vflip ? H - 1 - yo : yo;      // the flips come last: undo them first
     int fr, fg, fb, br, bg, bb, fh, fs, fv, bh, bs, bv;
-    bgsub_jittered_rgb(j, 0, H, W, x, y, j.n_ops[0], mean_f, fr, fg, fb);
-    bgsub_jittered_rgb(j, 1, H, W, x, y, j.n_ops[1], mean_b, br, bg, bb);
+    bgsub_jittered_rgb(j, 0, H, W, x, y, j.jit[0].n_ops, mean_f, fr, fg, fb);
+    bgsub_jittered_rgb(j, 1, H, W, x, y, j.jit[1].n_ops, mean_b, br, bg, bb);
     pil_hsv(fr, fg, fb, fh, fs, fv);
     pil_hsv(br, bg, bb, bh, bs, bv);
     int xs, ys, lab = 0;
     double fd = 0.0, bd = 0.0;
-    if (bgsub_rot_src(j, H, W, x, y, true, xs, ys)) {
+    if (aug_rot_src(j.rot, H, W, x, y, true, xs, ys)) {
         fd = (double)j.f_depth[(long)ys * W + xs];
         bd = (double)j.b_depth[(long)ys * W + xs];
     }
-    if (bgsub_rot_src(j, H, W, x, y, false, xs, ys)) lab = j.label[(long)ys * W + xs] != 0;
+    if (aug_rot_src(j.rot, H, W, x, y, false, xs, ys)) lab = j.label[(long)ys * W + xs] != 0;
     if (bd == 0.0) fd = 0.0;             // utils.py:549-550, sequential: the second test sees the updated f_depth
     if (fd == 0.0) bd = 0.0;
     ch[0] = fr > br ? fr - br : br - fr;

@@ -5,37 +5,34 @@
 //   bgsub_luma_sum_kernel   ImageEnhance.Contrast blends towards the mean of L over the WHOLE image as it is when the op runs (after the
 //                           rotation's black corners and the colour ops before it): replay those per pixel and sum L in integers
 //   bgsub_train_kernel      rotate -> jitter -> flips -> HSV -> differences -> normalise, one thread per output pixel
-// The per-pixel arithmetic is bgsub_px.h (Pillow's own C restated; also compiled for the host and checked against the installed Pillow
-// there).  Bandwidth- and latency-bound: ~3.4 MB gathered twice and ~12 MB written per 480 x 640 sample.
+// The per-pixel arithmetic is bgsub_px.h on aug_px.h (Pillow's own C restated; also compiled for the host and checked against the
+// installed Pillow there); batch, reduction and job checks are sample_batch.h, shared with the other two sample builders.
+// Bandwidth- and latency-bound: ~3.4 MB gathered twice and ~12 MB written per 480 x 640 sample.
 //
 // Thread map: a workgroup is a 32 x 8 tile of OUTPUT pixels, x fastest.  Stores are then full lines (a wave covers two rows of 32 pixels:
 // 2 x 1 KB of x8 as float4 pairs, 2 x 256 B of labels), and the rotated gathers of a tile stay inside a compact patch of the source
 // (at most ~34 x 34 pixels at 45 degrees) instead of a 256-pixel slanted line that touches a new cache line every few pixels.
 //
 // Sums: each workgroup of the first pass writes ONE partial sum of its own (plain store, fixed grid-stride order inside), the second
-// pass adds the kLumaBlocks partials of its sample in index order: integer, so exact and bit-reproducible whatever the schedule, and the
+// pass adds the kBlocks partials of its sample in index order: integer, so exact and bit-reproducible whatever the schedule, and the
 // workspace never needs zeroing -- the batch is two launches with nothing between them.
-#include "common.h"
+#include "sample_batch.h"
 #include "bgsub_px.h"
 
 namespace {
 
+using namespace ape;
+
 constexpr int kTileW = 32, kTileH = 8, kT = kTileW * kTileH;
-constexpr int kJobs = 16;            // jobs per launch: 16 * 232 B of kernel arguments (limit 4 KB)
-constexpr int kLumaBlocks = 64;      // partial sums per (sample, image)
+using TrainBatch = SampleBatch<ape_bgsub_train_job, 7>;
 
-struct TrainBatch {
-    ape_bgsub_train_job j[kJobs];
-    float mean[7], stdv[7];
-};
-
-// grid (kLumaBlocks, 2 * nb): image = blockIdx.y & 1 of job blockIdx.y >> 1; partial[(job0 + job) * 2 + image][kLumaBlocks]
+// grid (kBlocks, 2 * nb): image = blockIdx.y & 1 of job blockIdx.y >> 1; partial[(job0 + job) * 2 + image][kBlocks]
 __global__ __launch_bounds__(kT) void bgsub_luma_sum_kernel(TrainBatch bt, int job0, int H, int W, unsigned long long* __restrict__ partial)
 {
     __shared__ unsigned long long red[kT / 64];
     const ape_bgsub_train_job& j = bt.j[blockIdx.y >> 1];
     const int im = blockIdx.y & 1;
-    const int kc = bgsub_contrast_at(j, im);
+    const int kc = aug_contrast_at(j.jit[im]);
     unsigned long long s = 0;
     if (kc >= 0) {                                   // uniform per workgroup
         const int tiles_x = (W + kTileW - 1) / kTileW, tiles = tiles_x * ((H + kTileH - 1) / kTileH);
@@ -49,14 +46,9 @@ __global__ __launch_bounds__(kT) void bgsub_luma_sum_kernel(TrainBatch bt, int j
             }
         }
     }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    park(part<Sum>(s, red));
     __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long tot = 0;
-        for (int w = 0; w < kT / 64; ++w) tot += red[w];
-        partial[((long)(job0 + (blockIdx.y >> 1)) * 2 + im) * kLumaBlocks + blockIdx.x] = tot;
-    }
+    if (threadIdx.x == 0) partial[((long)(job0 + (blockIdx.y >> 1)) * 2 + im) * kBlocks + blockIdx.x] = total<kT / 64, Sum>(red);
 }
 
 // grid (tiles_x, tiles_y, nb)
@@ -66,16 +58,7 @@ __global__ __launch_bounds__(kT) void bgsub_train_kernel(TrainBatch bt, int job0
     __shared__ int means[2];
     const ape_bgsub_train_job& j = bt.j[blockIdx.z];
     const int s = job0 + blockIdx.z;
-    if (threadIdx.x < 2) {
-        int m = 0;
-        if (bgsub_contrast_at(j, threadIdx.x) >= 0) {
-            unsigned long long tot = 0;
-            const unsigned long long* p = partial + ((long)s * 2 + threadIdx.x) * kLumaBlocks;
-            for (int i = 0; i < kLumaBlocks; ++i) tot += p[i];
-            m = bgsub_mean_of_sum(tot, H, W);
-        }
-        means[threadIdx.x] = m;
-    }
+    if (threadIdx.x < 2) means[threadIdx.x] = mean_from_partials(j.jit[threadIdx.x], partial + ((long)s * 2 + threadIdx.x) * kBlocks, H, W);
     __syncthreads();
     const int xo = blockIdx.x * kTileW + threadIdx.x % kTileW, yo = blockIdx.y * kTileH + threadIdx.x / kTileW;
     if (xo >= W || yo >= H) return;
@@ -97,63 +80,40 @@ __global__ __launch_bounds__(kT) void bgsub_train_kernel(TrainBatch bt, int job0
 bool job_ok(const ape_bgsub_train_job& j, int H, int W)
 {
     if (!j.f_rgb || !j.b_rgb || !j.f_depth || !j.b_depth || !j.label) return false;
-    if (j.rot_mode < APE_ROT_NONE || j.rot_mode > APE_ROT_270) return false;
-    if ((j.rot_mode == APE_ROT_90 || j.rot_mode == APE_ROT_270) && H != W) return false;
-    for (int im = 0; im < 2; ++im) {
-        if (j.n_ops[im] < 0 || j.n_ops[im] > 4) return false;
-        int contrasts = 0;
-        for (int k = 0; k < j.n_ops[im]; ++k) {
-            const int c = j.op_code[im][k];
-            if (c < APE_JIT_BRIGHTNESS || c > APE_JIT_HUE) return false;
-            if (c == APE_JIT_HUE && (j.op_shift[im][k] < 0 || j.op_shift[im][k] > 255)) return false;
-            if (c != APE_JIT_HUE && !(j.op_factor[im][k] == j.op_factor[im][k])) return false;       // NaN
-            contrasts += c == APE_JIT_CONTRAST;
-        }
-        if (contrasts > 1) return false;             // a second one would need the sum of an image that depends on the first sum
-    }
-    return true;
+    return rotation_ok(j.rot, H, W) && jitter_ok(j.jit[0]) && jitter_ok(j.jit[1]);
 }
 
 }  // namespace
 
 extern "C" size_t ape_bgsub_train_workspace_bytes(int B)
 {
-    return B < 1 ? 0 : (size_t)B * 2 * kLumaBlocks * sizeof(unsigned long long);
+    return B < 1 ? 0 : (size_t)B * 2 * kBlocks * sizeof(unsigned long long);
 }
 
 extern "C" int ape_bgsub_train_samples(const ape_bgsub_train_job* jobs, int B, int H, int W, const float* mean7_host, const float* std7_host,
                                        float* x8, long long* label, uint8_t* u8_or_null, void* ws, size_t ws_bytes, void* stream)
 {
-    static_assert(sizeof(TrainBatch) <= 3900, "kernel arguments");
-    if (B < 0 || H < 1 || W < 1 || H > 32767 || W > 32767 || !mean7_host || !std7_host) return APE_EINVAL;
+    if (!frame_ok(B, H, W) || !mean7_host || !std7_host) return APE_EINVAL;
     if (B == 0) return APE_OK;
-    if (!jobs || !x8 || !label || !ws || ((uintptr_t)x8 & 15)) return APE_EINVAL;
+    if (!jobs || !x8 || !label || !ws || ((uintptr_t)x8 & 15) || ((uintptr_t)ws & 15)) return APE_EINVAL;
     if (ws_bytes < ape_bgsub_train_workspace_bytes(B)) return APE_EWORKSPACE;
-    for (int c = 0; c < 7; ++c)
-        if (!(std7_host[c] != 0.f)) return APE_EINVAL;
+    TrainBatch bt;
+    if (!norm_ok(mean7_host, std7_host, bt)) return APE_EINVAL;
     bool any_contrast = false;
     for (int i = 0; i < B; ++i) {
         if (!job_ok(jobs[i], H, W)) return APE_EINVAL;
-        any_contrast = any_contrast || bgsub_contrast_at(jobs[i], 0) >= 0 || bgsub_contrast_at(jobs[i], 1) >= 0;
+        any_contrast = any_contrast || aug_contrast_at(jobs[i].jit[0]) >= 0 || aug_contrast_at(jobs[i].jit[1]) >= 0;
     }
-    const dim3 tiles(ape::ceil_div(W, kTileW), ape::ceil_div(H, kTileH));
-    TrainBatch bt;
-    for (int c = 0; c < 7; ++c) {
-        bt.mean[c] = mean7_host[c];
-        bt.stdv[c] = std7_host[c];
-    }
+    const dim3 tiles(ceil_div(W, kTileW), ceil_div(H, kTileH));
+    const hipStream_t st = (hipStream_t)stream;
     // the first pass of every chunk, then the second: two launches for B <= kJobs
-    for (int pass = any_contrast ? 0 : 1; pass < 2; ++pass) {
-        for (int i0 = 0; i0 < B; i0 += kJobs) {
-            const int nb = B - i0 < kJobs ? B - i0 : kJobs;
-            for (int i = 0; i < nb; ++i) bt.j[i] = jobs[i0 + i];
-            if (pass == 0)
-                hipLaunchKernelGGL(bgsub_luma_sum_kernel, dim3(kLumaBlocks, 2 * nb), dim3(kT), 0, (hipStream_t)stream, bt, i0, H, W,
-                                   (unsigned long long*)ws);
-            else
-                hipLaunchKernelGGL(bgsub_train_kernel, dim3(tiles.x, tiles.y, nb), dim3(kT), 0, (hipStream_t)stream, bt, i0, H, W,
-                                   (const unsigned long long*)ws, (float4*)x8, label, u8_or_null);
-        }
-    }
-    return ape::check_launch("ape_bgsub_train_samples");
+    if (any_contrast)
+        for_each_chunk(bt, jobs, B, [&](const TrainBatch& b, int i0, int nb) {
+            hipLaunchKernelGGL(bgsub_luma_sum_kernel, dim3(kBlocks, 2 * nb), dim3(kT), 0, st, b, i0, H, W, (unsigned long long*)ws);
+        });
+    for_each_chunk(bt, jobs, B, [&](const TrainBatch& b, int i0, int nb) {
+        hipLaunchKernelGGL(bgsub_train_kernel, dim3(tiles.x, tiles.y, nb), dim3(kT), 0, st, b, i0, H, W, (const unsigned long long*)ws,
+                           (float4*)x8, label, u8_or_null);
+    });
+    return check_launch("ape_bgsub_train_samples");
 }

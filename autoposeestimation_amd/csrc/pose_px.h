@@ -1,23 +1,21 @@
-// Per-pixel arithmetic of DenseFusion's training-sample kernels (pose_train.hip), on top of seg_px.h / bgsub_px.h: plain C++, so
+// Per-pixel arithmetic of DenseFusion's training-sample kernels (pose_train.hip), on top of aug_px.h: plain C++, so
 // tools/check_pose_px.py compiles the same text for the host and compares whole samples with PoseDataset.sample_host.
 // Order of the reference (DenseFusion/datasets/myDatasetAugmented/dataset.py:204-214): colour jitter of the full frame -> Image.rotate of
 // colour, label and depth -> get_bbox crop -> choose / cloud / normalised crop.  Everything relies on -ffp-contract=off.
 #pragma once
-#include "seg_px.h"
+#include "aug_px.h"
 
 // (x, y) of the rotated frame -> source pixel of the 16-bit depth: Pillow's double-precision walk when the rotation is the affine one
 APE_PX bool pose_rot_src_depth(const ape_pose_train_job& j, int H, int W, int x, int y, int& xs, int& ys)
 {
-    if (j.rot_mode != APE_ROT_AFFINE) return seg_rot_src(j, H, W, x, y, xs, ys);
-    pil_affine_double(j.a, x, y, xs, ys);
-    return xs >= 0 && xs < W && ys >= 0 && ys < H;
+    return aug_rot_src(j.rot, H, W, x, y, true, xs, ys);
 }
 
 // the rotated label / depth at (x, y); zero where the rotation reads outside the frame
 APE_PX int pose_label_at(const ape_pose_train_job& j, int H, int W, int x, int y)
 {
     int xs, ys;
-    return seg_rot_src(j, H, W, x, y, xs, ys) ? j.label[(long)ys * W + xs] : 0;
+    return aug_rot_src(j.rot, H, W, x, y, false, xs, ys) ? j.label[(long)ys * W + xs] : 0;
 }
 
 APE_PX int pose_depth_at(const ape_pose_train_job& j, int H, int W, int x, int y)
@@ -37,7 +35,7 @@ APE_PX void pose_rgb_at(const ape_pose_train_job& j, int H, int W, int x, int y,
 {
     int xs, ys;
     r = g = b = 0;
-    if (seg_rot_src(j, H, W, x, y, xs, ys)) seg_jittered_rgb(j, W, xs, ys, j.n_ops, mean, r, g, b);
+    if (aug_rot_src(j.rot, H, W, x, y, false, xs, ys)) aug_jittered_rgb(j.rgb, j.jit, W, xs, ys, j.jit.n_ops, mean, r, g, b);
 }
 
 // the back-projection of pixel (column x, row y) with depth d as numpy computes it in float32 (:260-278): `depth * depth_scale` (`* 1000`

@@ -14,23 +14,19 @@
 // [0, s') or (480 - s', 480], which still covers [r0, r1) because s' <= 480 (640 for the columns) -- tests/test_pose_samples_host.py
 // checks this over random extents.
 // The host only draws and does get_bbox's arithmetic; `target` / `model_points` depend on no pixel and stay with numpy's float64 there.
-// The per-pixel arithmetic is pose_px.h / seg_px.h / bgsub_px.h (also compiled for the host, tools/check_pose_px.py).
-#include <limits.h>
-
-#include "common.h"
+// The per-pixel arithmetic is pose_px.h / aug_px.h (also compiled for the host, tools/check_pose_px.py); batch, reduction and job checks
+// are sample_batch.h, shared with the other two sample builders.
+#include "sample_batch.h"
 #include "pose_px.h"
 
 namespace {
 
+using namespace ape;
+
 constexpr int kT = 256, kWaves = kT / 64;
-constexpr int kJobs = 16;            // jobs per launch: 16 * 232 B of kernel arguments (limit 4 KB)
-constexpr int kBlocks = 64;          // partials per sample
 constexpr int kImgBlocks = 96;       // workgroups per sample that write the crop (at most 480 * 640 pixels: <= 12.5 per thread)
 
-struct PoseBatch {
-    ape_pose_train_job j[kJobs];
-    float mean[3], stdv[3];
-};
+using PoseBatch = SampleBatch<ape_pose_train_job, 3>;
 
 size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
@@ -41,50 +37,33 @@ __global__ __launch_bounds__(kT) void pose_stats_kernel(PoseBatch bt, int job0, 
     __shared__ unsigned long long red_s[kWaves];
     __shared__ int red_e[kWaves][4];
     const ape_pose_train_job& j = bt.j[blockIdx.y];
-    const int kc = seg_contrast_at(j);
+    const int kc = aug_contrast_at(j.jit);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     unsigned long long s = 0;
-    int rmin = INT_MAX, rmax = -1, cmin = INT_MAX, cmax = -1;
+    Extent e;
     int* row_out = rows + (long)(job0 + blockIdx.y) * H;
     for (int y = blockIdx.x * kWaves + wave; y < H; y += gridDim.x * kWaves) {          // a row belongs to one wave
         int cnt = 0;
         for (int x = lane; x < W; x += 64) {
             if (kc >= 0) {                           // uniform per workgroup
                 int r, g, b;
-                seg_jittered_rgb(j, W, x, y, kc, 0, r, g, b);
+                aug_jittered_rgb(j.rgb, j.jit, W, x, y, kc, 0, r, g, b);
                 s += (unsigned long long)pil_luma(r, g, b);
             }
             if (pose_label_at(j, H, W, x, y) == 255) {
-                rmin = y < rmin ? y : rmin; rmax = y > rmax ? y : rmax;
-                cmin = x < cmin ? x : cmin; cmax = x > cmax ? x : cmax;
+                e.add(x, y);
                 cnt += pose_depth_at(j, H, W, x, y) != 0;
             }
         }
         for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
         if (lane == 0) row_out[y] = cnt;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_down(s, o, 64);
-        const int a = __shfl_down(rmin, o, 64), b = __shfl_down(rmax, o, 64), c = __shfl_down(cmin, o, 64), d = __shfl_down(cmax, o, 64);
-        rmin = a < rmin ? a : rmin; rmax = b > rmax ? b : rmax;
-        cmin = c < cmin ? c : cmin; cmax = d > cmax ? d : cmax;
-    }
-    if (lane == 0) {
-        red_s[wave] = s;
-        red_e[wave][0] = rmin; red_e[wave][1] = rmax; red_e[wave][2] = cmin; red_e[wave][3] = cmax;
-    }
+    park(part<Sum>(s, red_s), part(e, red_e));
     __syncthreads();
     if (threadIdx.x == 0) {
-        unsigned long long tot = 0;
-        int e[4] = {INT_MAX, -1, INT_MAX, -1};
-        for (int w = 0; w < kWaves; ++w) {
-            tot += red_s[w];
-            e[0] = red_e[w][0] < e[0] ? red_e[w][0] : e[0]; e[1] = red_e[w][1] > e[1] ? red_e[w][1] : e[1];
-            e[2] = red_e[w][2] < e[2] ? red_e[w][2] : e[2]; e[3] = red_e[w][3] > e[3] ? red_e[w][3] : e[3];
-        }
         const long p = (long)(job0 + blockIdx.y) * kBlocks + blockIdx.x;
-        luma[p] = tot;
-        for (int i = 0; i < 4; ++i) ext[p * 4 + i] = e[i];
+        luma[p] = total<kWaves, Sum>(red_s);
+        total<kWaves>(red_e, ext + p * 4);
     }
 }
 
@@ -101,16 +80,7 @@ __global__ __launch_bounds__(kT) void pose_samples_kernel(PoseBatch bt, int job0
     const int Wc = j.cmax - j.cmin, Hc = j.rmax - j.rmin;
     unsigned char* base = out + j.out_off;
     if (blockIdx.x < kImgBlocks) {                   // the normalised crop (:307-313), planar
-        if (threadIdx.x == 0) {
-            int m = 0;
-            if (seg_contrast_at(j) >= 0) {
-                unsigned long long tot = 0;
-                const unsigned long long* p = luma + (long)s * kBlocks;
-                for (int i = 0; i < kBlocks; ++i) tot += p[i];
-                m = bgsub_mean_of_sum(tot, H, W);
-            }
-            s_mean = m;
-        }
+        if (threadIdx.x == 0) s_mean = mean_from_partials(j.jit, luma + (long)s * kBlocks, H, W);
         __syncthreads();
         const int mean = s_mean;
         const long plane = (long)Hc * Wc;
@@ -159,26 +129,13 @@ __global__ __launch_bounds__(kT) void pose_samples_kernel(PoseBatch bt, int job0
     }
 }
 
-bool frame_ok(int B, int H, int W) { return B >= 0 && H >= 1 && W >= 1 && H <= 32767 && W <= 32767; }
-
 bool job_ok(const ape_pose_train_job& j, int H, int W)
 {
     if (!j.rgb || !j.depth || !j.label) return false;
-    if (j.rot_mode < APE_ROT_NONE || j.rot_mode > APE_ROT_270) return false;
-    if ((j.rot_mode == APE_ROT_90 || j.rot_mode == APE_ROT_270) && H != W) return false;
-    if (j.rot_mode == APE_ROT_AFFINE)
+    if (j.rot.mode == APE_ROT_AFFINE)
         for (int i = 0; i < 6; ++i)
-            if (!(j.a[i] == j.a[i])) return false;                                        // NaN
-    if (j.n_ops < 0 || j.n_ops > 4) return false;
-    int contrasts = 0;
-    for (int k = 0; k < j.n_ops; ++k) {
-        const int c = j.op_code[k];
-        if (c < APE_JIT_BRIGHTNESS || c > APE_JIT_HUE) return false;
-        if (c == APE_JIT_HUE && (j.op_shift[k] < 0 || j.op_shift[k] > 255)) return false;
-        if (c != APE_JIT_HUE && !(j.op_factor[k] == j.op_factor[k])) return false;       // NaN
-        contrasts += c == APE_JIT_CONTRAST;
-    }
-    return contrasts <= 1;               // a second one would need the sum of an image that depends on the first sum
+            if (!(j.rot.a[i] == j.rot.a[i])) return false;                                // NaN: the depth's walk casts it to int
+    return rotation_ok(j.rot, H, W) && jitter_ok(j.jit);
 }
 
 // get_bbox's crops: sides from border_list inside a 480 x 640 frame
@@ -222,8 +179,6 @@ extern "C" size_t ape_pose_train_sample_bytes(int N, int Hc, int Wc)
 
 extern "C" int ape_pose_train_stats(const ape_pose_train_job* jobs, int B, int H, int W, void* ws, size_t ws_bytes, void* stream)
 {
-    static_assert(sizeof(ape_pose_train_job) == 232, "ape_pose_train_job layout (mirrored by _lib.PoseTrainJob)");
-    static_assert(sizeof(PoseBatch) <= 3900, "kernel arguments");
     if (!frame_ok(B, H, W)) return APE_EINVAL;
     if (B == 0) return APE_OK;
     if (!jobs || !ws || ((uintptr_t)ws & 15)) return APE_EINVAL;
@@ -231,25 +186,18 @@ extern "C" int ape_pose_train_stats(const ape_pose_train_job* jobs, int B, int H
     for (int i = 0; i < B; ++i)
         if (!job_ok(jobs[i], H, W)) return APE_EINVAL;
     PoseBatch bt = {};
-    for (int i0 = 0; i0 < B; i0 += kJobs) {
-        const int nb = B - i0 < kJobs ? B - i0 : kJobs;
-        for (int i = 0; i < nb; ++i) bt.j[i] = jobs[i0 + i];
-        hipLaunchKernelGGL(pose_stats_kernel, dim3(kBlocks, nb), dim3(kT), 0, (hipStream_t)stream, bt, i0, H, W, (unsigned long long*)ws,
+    for_each_chunk(bt, jobs, B, [&](const PoseBatch& b, int i0, int nb) {
+        hipLaunchKernelGGL(pose_stats_kernel, dim3(kBlocks, nb), dim3(kT), 0, (hipStream_t)stream, b, i0, H, W, (unsigned long long*)ws,
                            (int*)((char*)ws + ape_pose_train_extents_offset(B)), (int*)((char*)ws + ape_pose_train_rows_offset(B)));
-    }
-    return ape::check_launch("ape_pose_train_stats");
+    });
+    return check_launch("ape_pose_train_stats");
 }
 
 extern "C" int ape_pose_train_samples(const ape_pose_train_job* jobs, int B, int H, int W, int N, const float* mean3_host, const float* std3_host,
                                       void* out, size_t out_bytes, void* ws, size_t ws_bytes, void* stream)
 {
     PoseBatch bt = {};
-    if (!frame_ok(B, H, W) || N < 1 || N > (1 << 24) || !mean3_host || !std3_host) return APE_EINVAL;
-    for (int c = 0; c < 3; ++c) {
-        if (!(std3_host[c] != 0.f) || !(mean3_host[c] == mean3_host[c])) return APE_EINVAL;
-        bt.mean[c] = mean3_host[c];
-        bt.stdv[c] = std3_host[c];
-    }
+    if (!frame_ok(B, H, W) || N < 1 || N > (1 << 24) || !norm_ok(mean3_host, std3_host, bt)) return APE_EINVAL;
     if (B == 0) return APE_OK;
     if (!jobs || !out || !ws || ((uintptr_t)out & 15) || ((uintptr_t)ws & 15)) return APE_EINVAL;
     if (ws_bytes < ape_pose_train_workspace_bytes(B, H, N)) return APE_EWORKSPACE;
@@ -260,14 +208,12 @@ extern "C" int ape_pose_train_samples(const ape_pose_train_job* jobs, int B, int
         const size_t need = ape_pose_train_sample_bytes(N, j.rmax - j.rmin, j.cmax - j.cmin);
         if ((size_t)j.out_off > out_bytes || out_bytes - (size_t)j.out_off < need) return APE_EINVAL;
     }
-    const int blocks = kImgBlocks + ape::ceil_div(N, kWaves);
+    const int blocks = kImgBlocks + ceil_div(N, kWaves);
     const char* w = (const char*)ws;
-    for (int i0 = 0; i0 < B; i0 += kJobs) {
-        const int nb = B - i0 < kJobs ? B - i0 : kJobs;
-        for (int i = 0; i < nb; ++i) bt.j[i] = jobs[i0 + i];
-        hipLaunchKernelGGL(pose_samples_kernel, dim3(blocks, nb), dim3(kT), 0, (hipStream_t)stream, bt, i0, H, W, N, (const unsigned long long*)ws,
+    for_each_chunk(bt, jobs, B, [&](const PoseBatch& b, int i0, int nb) {
+        hipLaunchKernelGGL(pose_samples_kernel, dim3(blocks, nb), dim3(kT), 0, (hipStream_t)stream, b, i0, H, W, N, (const unsigned long long*)ws,
                            (const int*)(w + ape_pose_train_tables_offset(B, H)), (const int*)(w + ape_pose_train_sel_offset(B, H)),
                            (unsigned char*)out, (long)ape_pose_train_image_offset(N));
-    }
-    return ape::check_launch("ape_pose_train_samples");
+    });
+    return check_launch("ape_pose_train_samples");
 }

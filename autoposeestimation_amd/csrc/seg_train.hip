@@ -13,36 +13,33 @@
 //                      gathered through the NEAREST index tables.
 // The host only draws: the crop box needs the extents (the upper bound of np.random.randint depends on them), hence the read-back; the
 // resize tables (2 x S x 5 weights and starts, 2 x S nearest indices per sample) are built there in double, as Pillow builds them, and the
-// kernels do integer work only.  The per-pixel arithmetic is seg_px.h / bgsub_px.h (also compiled for the host, tools/check_seg_px.py).
-#include <limits.h>
-
-#include "common.h"
+// kernels do integer work only.  The per-pixel arithmetic is seg_px.h / aug_px.h (also compiled for the host, tools/check_seg_px.py);
+// batch, reduction and job checks are sample_batch.h, shared with the other two sample builders.
+#include "sample_batch.h"
 #include "seg_px.h"
 
 namespace {
 
+using namespace ape;
+
 constexpr int kTileW = 32, kTileH = 8, kT = kTileW * kTileH;
-constexpr int kJobs = 16;            // jobs per launch: 16 * 112 B of kernel arguments (limit 4 KB)
-constexpr int kBlocks = 64;          // partials per sample
 constexpr int kOT = 32;              // output tile side of the second launch
 constexpr int kPatch = 40;           // patch side in LDS: (kOT - 1) * scale + 1 starts and 5 taps <= 37 for scale <= 1
 constexpr int kTabInts = 14;         // table ints per output pixel side: hmin 1, hk 5, vmin 1, vk 5, nx 1, ny 1
 
-struct SegBatch {
-    ape_seg_train_job j[kJobs];
-    float mean[3], stdv[3];
-};
+using SegBatch = SampleBatch<ape_seg_train_job, 3>;
 
 // grid (kBlocks, nb)
 __global__ __launch_bounds__(kT) void seg_stats_kernel(SegBatch bt, int job0, int H, int W, unsigned long long* __restrict__ luma,
                                                        int* __restrict__ ext)
 {
     __shared__ unsigned long long red_s[kT / 64];
-    __shared__ int red_e[kT / 64][5];
+    __shared__ int red_e[kT / 64][4], red_c[kT / 64];
     const ape_seg_train_job& j = bt.j[blockIdx.y];
-    const int kc = seg_contrast_at(j);
+    const int kc = aug_contrast_at(j.jit);
     unsigned long long s = 0;
-    int rmin = INT_MAX, rmax = -1, cmin = INT_MAX, cmax = -1, cnt = 0;
+    Extent e;
+    int cnt = 0;
     const int tiles_x = (W + kTileW - 1) / kTileW, tiles = tiles_x * ((H + kTileH - 1) / kTileH);
     const int tx = threadIdx.x % kTileW, ty = threadIdx.x / kTileW;
     for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
@@ -50,42 +47,23 @@ __global__ __launch_bounds__(kT) void seg_stats_kernel(SegBatch bt, int job0, in
         if (x < W && y < H) {
             if (kc >= 0) {                           // uniform per workgroup
                 int r, g, b;
-                seg_jittered_rgb(j, W, x, y, kc, 0, r, g, b);
+                aug_jittered_rgb(j.rgb, j.jit, W, x, y, kc, 0, r, g, b);
                 s += (unsigned long long)pil_luma(r, g, b);
             }
             int xs, ys;
-            if (seg_rot_src(j, H, W, x, y, xs, ys) && j.label[(long)ys * W + xs] == 255) {
-                rmin = y < rmin ? y : rmin; rmax = y > rmax ? y : rmax;
-                cmin = x < cmin ? x : cmin; cmax = x > cmax ? x : cmax;
+            if (aug_rot_src(j.rot, H, W, x, y, false, xs, ys) && j.label[(long)ys * W + xs] == 255) {
+                e.add(x, y);
                 ++cnt;
             }
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_down(s, o, 64);
-        const int a = __shfl_down(rmin, o, 64), b = __shfl_down(rmax, o, 64), c = __shfl_down(cmin, o, 64), d = __shfl_down(cmax, o, 64);
-        rmin = a < rmin ? a : rmin; rmax = b > rmax ? b : rmax;
-        cmin = c < cmin ? c : cmin; cmax = d > cmax ? d : cmax;
-        cnt += __shfl_down(cnt, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        const int w = threadIdx.x >> 6;
-        red_s[w] = s;
-        red_e[w][0] = rmin; red_e[w][1] = rmax; red_e[w][2] = cmin; red_e[w][3] = cmax; red_e[w][4] = cnt;
-    }
+    park(part<Sum>(s, red_s), part(e, red_e), part<Sum>(cnt, red_c));
     __syncthreads();
     if (threadIdx.x == 0) {
-        unsigned long long tot = 0;
-        int e[5] = {INT_MAX, -1, INT_MAX, -1, 0};
-        for (int w = 0; w < kT / 64; ++w) {
-            tot += red_s[w];
-            e[0] = red_e[w][0] < e[0] ? red_e[w][0] : e[0]; e[1] = red_e[w][1] > e[1] ? red_e[w][1] : e[1];
-            e[2] = red_e[w][2] < e[2] ? red_e[w][2] : e[2]; e[3] = red_e[w][3] > e[3] ? red_e[w][3] : e[3];
-            e[4] += red_e[w][4];
-        }
         const long p = (long)(job0 + blockIdx.y) * kBlocks + blockIdx.x;
-        luma[p] = tot;
-        for (int i = 0; i < 5; ++i) ext[p * 5 + i] = e[i];
+        luma[p] = total<kT / 64, Sum>(red_s);
+        total<kT / 64>(red_e, ext + p * 5);
+        ext[p * 5 + 4] = total<kT / 64, Sum>(red_c);
     }
 }
 
@@ -114,14 +92,7 @@ __global__ __launch_bounds__(kT) void seg_train_kernel(SegBatch bt, int job0, in
         s_min[ax][t] = base[oc];
         for (int k = 0; k < 5; ++k) s_k[ax][t][k] = base[S + oc * 5 + k];
     } else if (tid == 2 * kOT) {
-        int m = 0;
-        if (seg_contrast_at(j) >= 0) {
-            unsigned long long tot = 0;
-            const unsigned long long* p = luma + (long)s * kBlocks;
-            for (int i = 0; i < kBlocks; ++i) tot += p[i];
-            m = bgsub_mean_of_sum(tot, H, W);
-        }
-        s_mean = m;
+        s_mean = mean_from_partials(j.jit, luma + (long)s * kBlocks, H, W);
     }
     __syncthreads();
     const int px0 = s_min[0][0], py0 = s_min[1][0];
@@ -194,35 +165,7 @@ __global__ __launch_bounds__(kT) void seg_plain_kernel(SegBatch bt, int job0, in
     label[(long)s * plane + o] = j.label[o] ? j.class_id : 0;
 }
 
-bool frame_ok(int B, int H, int W) { return B >= 0 && H >= 1 && W >= 1 && H <= 32767 && W <= 32767; }
-
-bool job_ok(const ape_seg_train_job& j, int H, int W)
-{
-    if (!j.rgb || !j.label) return false;
-    if (j.rot_mode < APE_ROT_NONE || j.rot_mode > APE_ROT_270) return false;
-    if ((j.rot_mode == APE_ROT_90 || j.rot_mode == APE_ROT_270) && H != W) return false;
-    if (j.n_ops < 0 || j.n_ops > 4) return false;
-    int contrasts = 0;
-    for (int k = 0; k < j.n_ops; ++k) {
-        const int c = j.op_code[k];
-        if (c < APE_JIT_BRIGHTNESS || c > APE_JIT_HUE) return false;
-        if (c == APE_JIT_HUE && (j.op_shift[k] < 0 || j.op_shift[k] > 255)) return false;
-        if (c != APE_JIT_HUE && !(j.op_factor[k] == j.op_factor[k])) return false;       // NaN
-        contrasts += c == APE_JIT_CONTRAST;
-    }
-    return contrasts <= 1;               // a second one would need the sum of an image that depends on the first sum
-}
-
-bool norm_ok(const float* mean, const float* stdv, SegBatch& bt)
-{
-    if (!mean || !stdv) return false;
-    for (int c = 0; c < 3; ++c) {
-        if (!(stdv[c] != 0.f) || !(mean[c] == mean[c])) return false;
-        bt.mean[c] = mean[c];
-        bt.stdv[c] = stdv[c];
-    }
-    return true;
-}
+bool job_ok(const ape_seg_train_job& j, int H, int W) { return j.rgb && j.label && rotation_ok(j.rot, H, W) && jitter_ok(j.jit); }
 
 }  // namespace
 
@@ -240,7 +183,6 @@ extern "C" size_t ape_seg_train_workspace_bytes(int B, int S)
 
 extern "C" int ape_seg_train_stats(const ape_seg_train_job* jobs, int B, int H, int W, void* ws, size_t ws_bytes, void* stream)
 {
-    static_assert(sizeof(SegBatch) <= 3900, "kernel arguments");
     if (!frame_ok(B, H, W)) return APE_EINVAL;
     if (B == 0) return APE_OK;
     if (!jobs || !ws || ((uintptr_t)ws & 15)) return APE_EINVAL;
@@ -248,13 +190,11 @@ extern "C" int ape_seg_train_stats(const ape_seg_train_job* jobs, int B, int H, 
     for (int i = 0; i < B; ++i)
         if (!job_ok(jobs[i], H, W)) return APE_EINVAL;
     SegBatch bt = {};
-    for (int i0 = 0; i0 < B; i0 += kJobs) {
-        const int nb = B - i0 < kJobs ? B - i0 : kJobs;
-        for (int i = 0; i < nb; ++i) bt.j[i] = jobs[i0 + i];
-        hipLaunchKernelGGL(seg_stats_kernel, dim3(kBlocks, nb), dim3(kT), 0, (hipStream_t)stream, bt, i0, H, W, (unsigned long long*)ws,
+    for_each_chunk(bt, jobs, B, [&](const SegBatch& b, int i0, int nb) {
+        hipLaunchKernelGGL(seg_stats_kernel, dim3(kBlocks, nb), dim3(kT), 0, (hipStream_t)stream, b, i0, H, W, (unsigned long long*)ws,
                            (int*)((char*)ws + ape_seg_train_extents_offset(B)));
-    }
-    return ape::check_launch("ape_seg_train_stats");
+    });
+    return check_launch("ape_seg_train_stats");
 }
 
 extern "C" int ape_seg_train_samples(const ape_seg_train_job* jobs, int B, int H, int W, int S, const float* mean3_host, const float* std3_host,
@@ -274,14 +214,12 @@ extern "C" int ape_seg_train_samples(const ape_seg_train_job* jobs, int B, int H
         if (j.crop_x < -32768 || j.crop_x > 32767 || j.crop_y < -32768 || j.crop_y > 32767) return APE_EINVAL;
         if (j.class_id < 0) return APE_EINVAL;
     }
-    const int tiles = ape::ceil_div(S, kOT);
-    for (int i0 = 0; i0 < B; i0 += kJobs) {
-        const int nb = B - i0 < kJobs ? B - i0 : kJobs;
-        for (int i = 0; i < nb; ++i) bt.j[i] = jobs[i0 + i];
-        hipLaunchKernelGGL(seg_train_kernel, dim3(tiles, tiles, nb), dim3(kT), 0, (hipStream_t)stream, bt, i0, H, W, S,
+    const int tiles = ceil_div(S, kOT);
+    for_each_chunk(bt, jobs, B, [&](const SegBatch& b, int i0, int nb) {
+        hipLaunchKernelGGL(seg_train_kernel, dim3(tiles, tiles, nb), dim3(kT), 0, (hipStream_t)stream, b, i0, H, W, S,
                            (const unsigned long long*)ws, (const int*)((const char*)ws + ape_seg_train_tables_offset(B)), img, label);
-    }
-    return ape::check_launch("ape_seg_train_samples");
+    });
+    return check_launch("ape_seg_train_samples");
 }
 
 extern "C" int ape_seg_plain_samples(const ape_seg_train_job* jobs, int B, int H, int W, const float* mean3_host, const float* std3_host,
@@ -293,11 +231,9 @@ extern "C" int ape_seg_plain_samples(const ape_seg_train_job* jobs, int B, int H
     if (!jobs || !img || !label || ((uintptr_t)img & 3) || ((uintptr_t)label & 7)) return APE_EINVAL;
     for (int i = 0; i < B; ++i)
         if (!jobs[i].rgb || !jobs[i].label || jobs[i].class_id < 0) return APE_EINVAL;
-    const dim3 tiles(ape::ceil_div(W, kTileW), ape::ceil_div(H, kTileH));
-    for (int i0 = 0; i0 < B; i0 += kJobs) {
-        const int nb = B - i0 < kJobs ? B - i0 : kJobs;
-        for (int i = 0; i < nb; ++i) bt.j[i] = jobs[i0 + i];
-        hipLaunchKernelGGL(seg_plain_kernel, dim3(tiles.x, tiles.y, nb), dim3(kT), 0, (hipStream_t)stream, bt, i0, H, W, img, label);
-    }
-    return ape::check_launch("ape_seg_plain_samples");
+    const dim3 tiles(ceil_div(W, kTileW), ceil_div(H, kTileH));
+    for_each_chunk(bt, jobs, B, [&](const SegBatch& b, int i0, int nb) {
+        hipLaunchKernelGGL(seg_plain_kernel, dim3(tiles.x, tiles.y, nb), dim3(kT), 0, (hipStream_t)stream, b, i0, H, W, img, label);
+    });
+    return check_launch("ape_seg_plain_samples");
 }

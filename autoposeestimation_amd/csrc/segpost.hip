@@ -23,7 +23,7 @@
 //   crop_normalize u8 RGB -> NHWC4 f32 (x[/255] - mean) / std
 #include "common.h"
 #include "seg_head.h"
-#include "bgsub_px.h"
+#include "aug_px.h"
 
 namespace {
 
@@ -420,7 +420,7 @@ struct BgsubArgs {
     float mean[7], stdv[7];
 };
 
-// pil_hsv: Pillow's rgb2hsv_row, bgsub_px.h (shared with the training-sample builder, bgsub_train.hip)
+// pil_hsv: Pillow's rgb2hsv_row, aug_px.h (shared with the training-sample builders)
 __global__ void bgsub_features_kernel(const uint8_t* __restrict__ f_rgb, const uint8_t* __restrict__ b_rgb,
                                       const uint16_t* __restrict__ f_depth, const uint16_t* __restrict__ b_depth,
                                       const double* __restrict__ gate /*[B][2] min,max*/, BgsubArgs a, float4* __restrict__ out,

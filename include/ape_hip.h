@@ -20,6 +20,9 @@
 
 #ifdef __cplusplus
 extern "C" {
+#define APE_STATIC_ASSERT static_assert
+#else
+#define APE_STATIC_ASSERT _Static_assert
 #endif
 
 #define APE_OK 0
@@ -648,34 +651,48 @@ typedef struct ape_sgd_job {
 int ape_sgd_step_multi_f32(int n, const ape_sgd_job* jobs_host, float lr, float momentum, float dampening, float weight_decay, int nesterov,
                            void* stream);
 
+/* ---- What the three training-sample builders below share: a rotation and an ordered list of colour ops, as the host drew them --------
+ * ape_aug_rotation.  mode: APE_ROT_NONE, APE_ROT_180, APE_ROT_90 / APE_ROT_270 (Pillow's transposes, square frames only) or
+ * APE_ROT_AFFINE = Pillow's Image.rotate through its AFFINE nearest-neighbour transform with zero fill: `a` is the inverse matrix
+ * Image.rotate hands the transform (output pixel -> source position), read in double precision at the pixel centre by 16-bit images (the
+ * depth), and `fa` its 16.16 fixed-point form FLOOR(v * 65536 + 0.5) of (a0, a1, a2 + a0/2 + a1/2, a3, a4, a5 + a3/2 + a4/2) that the
+ * 8-bit images (RGB, label) walk.
+ * ape_aug_jitter.  The first n_ops (<= 4) entries are ops APE_JIT_* in the order they run: brightness / contrast / saturation blend
+ * towards black / the rounded mean of L over the whole image as it is at that point / L by `factor` (C float, truncated, clipped outside
+ * [0, 1]); hue adds `shift` (0..255) to H of Pillow's HSV, wrapping.  At most one contrast per list. */
+enum { APE_ROT_NONE = 0, APE_ROT_180 = 1, APE_ROT_AFFINE = 2, APE_ROT_90 = 3, APE_ROT_270 = 4 };
+enum { APE_JIT_END = 0, APE_JIT_BRIGHTNESS = 1, APE_JIT_CONTRAST = 2, APE_JIT_SATURATION = 3, APE_JIT_HUE = 4 };
+typedef struct ape_aug_rotation {
+    double a[6];
+    int fa[6];
+    int mode;
+    int reserved;
+} ape_aug_rotation;
+typedef struct ape_aug_jitter {
+    int n_ops;
+    int code[4];
+    float factor[4];
+    int shift[4];
+} ape_aug_jitter;
+APE_STATIC_ASSERT(sizeof(ape_aug_rotation) == 80, "ape_aug_rotation layout (mirrored by _lib.AugRotation)");
+APE_STATIC_ASSERT(sizeof(ape_aug_jitter) == 52, "ape_aug_jitter layout (mirrored by _lib.AugJitter)");
+
 /* ---- Background-subtraction training samples (csrc/bgsub_train.hip; reference background_subtraction/utils.py:414-646 load_subtraction +
  * augment, dataset.py:60-86) ---------------------------------------------------------------------------------------------------------
  * One job per sample of the batch: DEVICE pointers to the raw frames (any frames of a resident set: a batch is a table of pointers, not a
- * copy) and the augmentation the host drew.  Order per image: rotate -> colour jitter (RGB only) -> h-flip -> v-flip.
- * rot_mode: APE_ROT_NONE, APE_ROT_180, APE_ROT_90 / APE_ROT_270 (Pillow's transposes, square frames only) or APE_ROT_AFFINE = Pillow's
- * Image.rotate through its AFFINE nearest-neighbour transform with zero fill: `a` is the inverse matrix Image.rotate hands the transform
- * (output pixel -> source position), read in double precision at the pixel centre for the 16-bit depth, and `fa` its 16.16 fixed-point
- * form FLOOR(v * 65536 + 0.5) of (a0, a1, a2 + a0/2 + a1/2, a3, a4, a5 + a3/2 + a4/2) that the 8-bit images (RGB, label) walk.
- * Colour ops: image 0 = foreground, 1 = background, each with its own ordered list of up to four ops APE_JIT_*: brightness / contrast /
- * saturation blend towards black / the rounded mean of L over the whole image as it is at that point / L by `op_factor` (C float,
- * truncated, clipped outside [0, 1]); hue adds `op_shift` (0..255) to H of Pillow's HSV, wrapping.  At most one contrast per list. */
-enum { APE_ROT_NONE = 0, APE_ROT_180 = 1, APE_ROT_AFFINE = 2, APE_ROT_90 = 3, APE_ROT_270 = 4 };
-enum { APE_JIT_END = 0, APE_JIT_BRIGHTNESS = 1, APE_JIT_CONTRAST = 2, APE_JIT_SATURATION = 3, APE_JIT_HUE = 4 };
+ * copy) and the augmentation the host drew.  Order per image: rotate (the RGB and the label walk `fa`, the depths read `a`) -> colour
+ * jitter (RGB only; jit[0] = foreground, jit[1] = background) -> h-flip -> v-flip. */
 typedef struct ape_bgsub_train_job {
     const uint8_t* f_rgb;      /* [H][W][3] */
     const uint8_t* b_rgb;
     const uint16_t* f_depth;   /* [H][W] */
     const uint16_t* b_depth;
     const uint8_t* label;      /* [H][W] */
-    double a[6];
-    int fa[6];
-    int rot_mode, hflip, vflip;
-    int n_ops[2];
-    int op_code[2][4];
-    float op_factor[2][4];
-    int op_shift[2][4];
-    int reserved;
+    ape_aug_rotation rot;
+    ape_aug_jitter jit[2];
+    int hflip, vflip;
 } ape_bgsub_train_job;
+APE_STATIC_ASSERT(sizeof(ape_bgsub_train_job) == 232, "ape_bgsub_train_job layout (mirrored by _lib.BgsubTrainJob)");
 /* x8[B][H][W][8] f32 NHWC: |f - b| of RGB (3), of Pillow's HSV (3) and of the depth after `f_depth[b_depth == 0] = 0` then
  * `b_depth[f_depth == 0] = 0` (no distance gate), each cast to uint8 as numpy does (the depth difference wraps mod 256), / 255, then
  * (x - mean7) / std7 (HOST pointers); channel 7 = 0.  label[B][H][W] i64 in {0, 1} (non-zero -> 1).  u8_or_null[B][H][W][7] receives the
@@ -688,22 +705,18 @@ int ape_bgsub_train_samples(const ape_bgsub_train_job* jobs_host, int B, int H, 
 /* ---- Segmentor training samples (csrc/seg_train.hip; reference segmentation/dataset.py:88-112 with the transforms of
  * segmentation/utils.py:25-66 and CropAndZoom :361-487) -------------------------------------------------------------------------------
  * One job per sample: DEVICE pointers to the resident frame and its label and what the host drew.  Order, as the reference composes it:
- * colour jitter of the full frame (op lists as in ape_bgsub_train_job, one image) -> Image.rotate of image and label (rot_mode / fa as
- * there; both are 8-bit, so both walk `fa`) -> crop of the square crop_side x crop_side box at (crop_x, crop_y) of the rotated frame (zero
+ * colour jitter of the full frame -> Image.rotate of image and label (both are 8-bit, so both walk `fa`; `a` is not read) -> crop of the square crop_side x crop_side box at (crop_x, crop_y) of the rotated frame (zero
  * outside it, like Image.crop) -> resize to S x S, Pillow's BICUBIC for the image and NEAREST for the label -> ToTensor, Normalize; label
  * pixels != 0 become class_id. */
 typedef struct ape_seg_train_job {
     const uint8_t* rgb;        /* [H][W][3] */
     const uint8_t* label;      /* [H][W] */
-    int fa[6];
-    int rot_mode;
-    int n_ops;
-    int op_code[4];
-    float op_factor[4];
-    int op_shift[4];
+    ape_aug_rotation rot;
+    ape_aug_jitter jit;
     int crop_x, crop_y, crop_side;
     int class_id;
 } ape_seg_train_job;
+APE_STATIC_ASSERT(sizeof(ape_seg_train_job) == 168, "ape_seg_train_job layout (mirrored by _lib.SegTrainJob)");
 /* The workspace of a batch: [B][64] u64 luma partial sums | [B][64][5] i32 extent partials at ape_seg_train_extents_offset(B) | the
  * resize tables [B][14 * S] i32 at ape_seg_train_tables_offset(B).  One per stream; not shared by batches in flight at once. */
 size_t ape_seg_train_workspace_bytes(int B, int S);
@@ -729,8 +742,8 @@ int ape_seg_plain_samples(const ape_seg_train_job* jobs_host, int B, int H, int 
 
 /* ---- DenseFusion training samples (csrc/pose_train.hip; reference DenseFusion/datasets/myDatasetAugmented/dataset.py:158-326) ---------
  * One job per sample: DEVICE pointers to the resident colour frame, 16-bit depth and label, and what the host drew.  Order, as the
- * reference composes it (:204-214): colour jitter of the full frame (op list as in ape_seg_train_job) -> Image.rotate of colour, label and
- * depth (rot_mode / a / fa as in ape_bgsub_train_job: the 8-bit images walk `fa`, the depth reads `a` in double at the pixel centre) ->
+ * reference composes it (:204-214): colour jitter of the full frame -> Image.rotate of colour, label and depth (the 8-bit images walk `fa`,
+ * the depth reads `a`) ->
  * the get_bbox crop [rmin, rmax) x [cmin, cmax) of the rotated frame -> `choose`, the back-projected cloud and the normalised crop.
  * The crop, the intrinsics (as C floats: numpy computes the cloud in float32), depth_scale, to_meter, add_noise / add_t (the translation
  * noise, double: numpy adds it in float64 and rounds once) and out_off (byte offset of the sample in the output block, a multiple of 16)
@@ -739,20 +752,15 @@ typedef struct ape_pose_train_job {
     const uint8_t* rgb;        /* [H][W][3] */
     const uint16_t* depth;     /* [H][W] */
     const uint8_t* label;      /* [H][W] */
-    double a[6];
+    ape_aug_rotation rot;
     double add_t[3];
     long long out_off;
-    int fa[6];
-    int rot_mode;
-    int n_ops;
-    int op_code[4];
-    float op_factor[4];
-    int op_shift[4];
+    ape_aug_jitter jit;
     int rmin, rmax, cmin, cmax;
     float ppx, ppy, fx, fy, depth_scale;
     int to_meter, add_noise;
-    int reserved;
 } ape_pose_train_job;
+APE_STATIC_ASSERT(sizeof(ape_pose_train_job) == 232, "ape_pose_train_job layout (mirrored by _lib.PoseTrainJob)");
 /* The workspace of a batch: [B][64] u64 luma partial sums | at ape_pose_train_extents_offset(B): [B][64][4] i32 extent partials, then
  * [B][H] i32 row counts (one read-back covers both) | at ape_pose_train_tables_offset(B, H): [B][H] i32 exclusive row prefix, then
  * [B][N] i32 `sel` (one upload covers both).  One per stream; not shared by batches in flight at once. */

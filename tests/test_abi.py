@@ -3,6 +3,7 @@ and the ctypes table mirrors the header (no compute calls without a GPU)."""
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -61,9 +62,35 @@ def test_ctypes_table_matches_header():
         assert same(want, rt), "%s return type: header %r vs ctypes %s" % (name, m.group(1).strip(), rt.__name__)
 
 
+MIRRORS = {"ape_aug_rotation": "AugRotation", "ape_aug_jitter": "AugJitter", "ape_bgsub_train_job": "BgsubTrainJob",
+           "ape_seg_train_job": "SegTrainJob", "ape_pose_train_job": "PoseTrainJob", "ape_adam_job": "AdamJob", "ape_sgd_job": "SgdJob",
+           "ape_pack_job": "PackJob", "ape_conv_params": "ConvParams"}
+
+
+def test_ctypes_mirrors_have_the_c_layout(tmp_path):
+    """every ctypes.Structure of _lib.py against the struct it mirrors: a host program generated from the `_fields_` prints sizeof and
+    every offsetof as the C compiler sees include/ape_hip.h -- a field renamed, dropped, reordered or resized on one side fails here"""
+    from autoposeestimation_amd import _lib
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "ape_hip.h"', "int main() {"]
+    want = []
+    for c_name, py_name in MIRRORS.items():
+        cls = getattr(_lib, py_name)
+        names = [fld[0] for fld in cls._fields_]
+        lines.append('    printf("%s %%zu%s\\n", sizeof(%s)%s);' % (c_name, " %zu" * len(names), c_name,
+                                                                "".join(", offsetof(%s, %s)" % (c_name, n) for n in names)))
+        want.append("%s %d%s" % (c_name, ctypes.sizeof(cls), "".join(" %d" % getattr(cls, n).offset for n in names)))
+    lines += ["    return 0;", "}"]
+    (tmp_path / "layout.cpp").write_text("\n".join(lines) + "\n")
+    exe = str(tmp_path / "layout")
+    subprocess.check_call(["g++", "-I", os.path.join(REPO, "include"), str(tmp_path / "layout.cpp"), "-o", exe])
+    assert subprocess.check_output([exe]).decode().split("\n")[:-1] == want
+    mirrored = {n for n, c in vars(_lib).items() if isinstance(c, type) and issubclass(c, ctypes.Structure)}
+    assert mirrored == set(MIRRORS.values())                       # a new mirror joins the table above
+
+
 def test_abi_version_callable_without_gpu():
     from autoposeestimation_amd import _lib
-    assert _lib.lib().ape_abi_version() >= 1
+    assert _lib.lib().ape_abi_version() == _lib.ABI_VERSION
 
 
 def test_product_path_never_imports_oracle():

@@ -1,6 +1,7 @@
 """tests/bgsub_train_reference.py (the CPU restatement of the training-sample builder on Pillow + numpy) against
 tests/golden/bgsub_train.npz, which tools/gen_golden_bgsub_train.py made by running the reference's load_subtraction,
 SegmentationDataset.__getitem__ and IoU_cca.  Everything is compared exactly.  No GPU."""
+import importlib.util
 import os
 import random
 
@@ -91,6 +92,15 @@ def test_cca_confusion_counts_equal_reference(tag, k):
     conf = np.bincount((_cca_host(pred) + k * target).reshape(-1), minlength=k * k).reshape(k, k)
     assert np.array_equal(conf, GOLDEN["cca_%s_conf" % tag])
     assert int(GOLDEN["cca_%s_conf" % tag].sum()) == target.size
+
+
+def test_header_on_the_host_equals_pillow():
+    """csrc/bgsub_px.h on csrc/aug_px.h through tools/check_bgsub_px.py's loops: Pillow's conversions and blends over a seventeenth of
+    the value range, whole samples at every rotation mode, exact"""
+    spec = importlib.util.spec_from_file_location("check_bgsub_px", os.path.join(REPO, "tools", "check_bgsub_px.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    assert mod.main(quick=True) == 102
 
 
 def test_job_table_refuses_what_the_kernel_cannot_take():

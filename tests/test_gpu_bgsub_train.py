@@ -1,6 +1,7 @@
 """The training-sample builder (csrc/bgsub_train.hip), SegmentationDataset, IoU_cca and the training driver of the background-subtraction
 segmentor on the GPU, against tests/golden/bgsub_train.npz (made by running the reference) and tests/bgsub_train_reference.py (Pillow).
 Every comparison of samples is exact: u8 channels, the fp32 tensor and the labels with np.array_equal, no pixel excused."""
+import ctypes
 import json
 import os
 import random
@@ -168,6 +169,28 @@ def test_refusals(ds_tree, tmp_path):
         G.build_samples([(f[0].float(),) + f[1:]], [plain], [0.0] * 7, [1.0] * 7)
     with pytest.raises(ValueError, match="at most 4"):                              # more than four colour ops
         G.build_samples([f], [{"angle": None, "ops_f": [("brightness", 0.9)] * 5}], [0.0] * 7, [1.0] * 7)
+    # the entry point itself: a NaN mean and a workspace that is not 16-byte aligned are APE_EINVAL, as in the other two builders
+    from autoposeestimation_amd import _lib
+    L = _lib.lib()
+    h, w = frames[4].shape
+    jobs = (_lib.BgsubTrainJob * 1)(G.make_job({"angle": None, "ops_f": [("contrast", 0.9)]}, h, w, *[t.data_ptr() for t in f]))
+    need = L.ape_bgsub_train_workspace_bytes(1)
+    ws = torch.full((need + 16,), 9, dtype=torch.uint8, device=DEV)
+    x8 = torch.full((h * w * 8,), 7.0, dtype=torch.float32, device=DEV)
+    lab = torch.full((h * w,), 7, dtype=torch.int64, device=DEV)
+    zeros, ones = (ctypes.c_float * 7)(*[0.0] * 7), (ctypes.c_float * 7)(*[1.0] * 7)
+    nan_mean = (ctypes.c_float * 7)(*[0.0, 0.0, 0.0, float("nan"), 0.0, 0.0, 0.0])
+
+    def run(mean, ws_ptr):
+        return L.ape_bgsub_train_samples(ctypes.cast(jobs, ctypes.c_void_p), 1, h, w, mean, ones, _lib.dptr(x8), _lib.dptr(lab), None, ws_ptr,
+                                         need, _lib.stream_ptr())
+
+    EINVAL = -1                                                                     # include/ape_hip.h
+    assert run(nan_mean, _lib.dptr(ws)) == EINVAL                                   # NaN mean
+    assert run(zeros, ctypes.c_void_p(ws.data_ptr() + 8)) == EINVAL                 # misaligned workspace
+    torch.cuda.synchronize()
+    assert float(x8.min()) == 7.0 and float(x8.max()) == 7.0 and int(lab.min()) == 7 and int(lab.max()) == 7      # nothing ran
+    assert int(ws.min()) == 9 and int(ws.max()) == 9
     root = str(tmp_path)
     _write_tree(root, "c", [frames])
     Image.fromarray(np.stack([frames[4]] * 3, -1), "RGB").save(os.path.join(root, "c", "groundtruth", "img000000.mask.0.png"))

@@ -323,7 +323,7 @@ def test_argument_checks_return_errors_without_launching():
     assert stats(job(rgb_ptr=0), need) == EINVAL
     assert stats(job(), L.ape_pose_train_tables_offset(1, h) - 1) == EWORKSPACE
     bad = job()
-    bad.n_ops, bad.op_code[0] = 1, 9
+    bad.jit.n_ops, bad.jit.code[0] = 1, 9
     assert stats(bad, need) == EINVAL and run(bad) == EINVAL
     torch.cuda.synchronize()
     assert int(out.min()) == 7 and int(out.max()) == 7 and int(ws.min()) == 9 and int(ws.max()) == 9            # nothing ran

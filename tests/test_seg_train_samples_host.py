@@ -1,6 +1,8 @@
 """Host side of the segmentor's training samples (no GPU): segmentation/utils.py's transforms against tests/golden/seg_train.npz (made by
 running the reference's CropAndZoom and rotate), the resize tables of segmentation/augment.py against the installed Pillow, and
 SegmentationDataset's list handling, class ids and statistics.  Every comparison is exact."""
+import importlib.util
+import os
 import random
 
 import numpy as np
@@ -9,9 +11,18 @@ import torch
 from PIL import Image
 
 import seg_train_reference as R
+from conftest import REPO
 
 G = R.golden()
 NAMES = [str(n) for n in G["names"]]
+
+
+def test_header_on_the_host_equals_pillow():
+    """csrc/seg_px.h on csrc/aug_px.h through tools/check_seg_px.py's loops: whole samples, every rotation mode, exact"""
+    spec = importlib.util.spec_from_file_location("check_seg_px", os.path.join(REPO, "tools", "check_seg_px.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    assert mod.main(quick=True) == 102
 
 
 def _extremes(label):

@@ -2,21 +2,21 @@
 
 The header holds the per-pixel arithmetic of the training-sample kernels (csrc/bgsub_train.hip) in plain C++.  This tool compiles the same
 text with the host compiler (-ffp-contract=off, as csrc/Makefile) behind three small loops and compares, exactly:
-  * pil_hsv2rgb with Image.convert('HSV' -> 'RGB') over all 2^24 HSV triples, pil_luma with convert('L') over all 2^24 colours;
+  * (aug_px.h, which the header stands on) pil_hsv2rgb with Image.convert('HSV' -> 'RGB') over all 2^24 HSV triples, pil_luma with convert('L') over all 2^24 colours;
   * pil_blend with Image.blend over every (degenerate, image) byte pair for a set of factors inside and outside [0, 1];
   * whole samples (both passes of the builder, every rotation mode, flips, jitters) with tests/bgsub_train_reference.py, which is Pillow.
 Usage: python tools/check_bgsub_px.py [--quick]
 """
 import ctypes
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 from PIL import Image
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.append(os.path.dirname(os.path.abspath(__file__)))
+from px_host import REPO, build, p as _p  # noqa: E402
+
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
@@ -30,11 +30,11 @@ extern "C" void blend_all(const uint8_t* d, const uint8_t* im, uint8_t* out, lon
 extern "C" void sample(const ape_bgsub_train_job* j, int H, int W, uint8_t* u8, long long* label) {
     int means[2] = {0, 0};
     for (int im = 0; im < 2; ++im) {
-        const int kc = bgsub_contrast_at(*j, im);
+        const int kc = aug_contrast_at(j->jit[im]);
         if (kc < 0) continue;
         unsigned long long s = 0;
         for (int y = 0; y < H; ++y) for (int x = 0; x < W; ++x) { int r, g, b; bgsub_jittered_rgb(*j, im, H, W, x, y, kc, 0, r, g, b); s += pil_luma(r, g, b); }
-        means[im] = bgsub_mean_of_sum(s, H, W);
+        means[im] = aug_mean_of_sum(s, H, W);
     }
     for (int y = 0; y < H; ++y) for (int x = 0; x < W; ++x) {
         int ch[7];
@@ -43,20 +43,6 @@ extern "C" void sample(const ape_bgsub_train_job* j, int H, int W, uint8_t* u8, 
     }
 }
 """
-
-
-def build():
-    d = tempfile.mkdtemp(prefix="bgsub_px_")
-    with open(os.path.join(d, "px.cpp"), "w") as f:
-        f.write(_SRC)
-    so = os.path.join(d, "libpx.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(REPO, "autoposeestimation_amd", "csrc"),
-                           os.path.join(d, "px.cpp"), "-o", so])
-    return ctypes.CDLL(so)
-
-
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 def host_sample(lib, frames, params):
@@ -71,9 +57,9 @@ def host_sample(lib, frames, params):
     return u8, lab
 
 
-def main():
-    quick = "--quick" in sys.argv
-    lib = build()
+def main(quick=False):
+    """-> the number of samples compared (every one exact, or AssertionError)"""
+    lib = build(_SRC)
     lib.blend_all.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_long, ctypes.c_float]
     v = np.arange(1 << 24, dtype=np.uint32)
     tri = np.ascontiguousarray(np.stack([(v >> 16) & 255, (v >> 8) & 255, v & 255], -1).astype(np.uint8))
@@ -120,7 +106,8 @@ def main():
                 assert bad == 0, "%s differs in %d places: %dx%d params %r" % (name, bad, h, w, params)
             n += 1
     print("samples: %d exact against the Pillow restatement" % n)
+    return n
 
 
 if __name__ == "__main__":
-    main()
+    main("--quick" in sys.argv)

@@ -8,14 +8,14 @@ Usage: python tools/check_seg_px.py [--quick]"""
 import ctypes
 import os
 import random
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 from PIL import Image
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.append(os.path.dirname(os.path.abspath(__file__)))
+from px_host import REPO, build, p as _p  # noqa: E402
+
 sys.path.insert(0, REPO)
 
 _SRC = r"""
@@ -23,19 +23,19 @@ _SRC = r"""
 #include <vector>
 #include "seg_px.h"
 extern "C" void sample(const ape_seg_train_job* j, int H, int W, int S, const int* tab, uint8_t* img, uint8_t* label, int* ext) {
-    const int kc = seg_contrast_at(*j);
+    const int kc = aug_contrast_at(j->jit);
     unsigned long long s = 0;
     int e[5] = {INT_MAX, -1, INT_MAX, -1, 0};
     for (int y = 0; y < H; ++y) for (int x = 0; x < W; ++x) {
-        if (kc >= 0) { int r, g, b; seg_jittered_rgb(*j, W, x, y, kc, 0, r, g, b); s += pil_luma(r, g, b); }
+        if (kc >= 0) { int r, g, b; aug_jittered_rgb(j->rgb, j->jit, W, x, y, kc, 0, r, g, b); s += pil_luma(r, g, b); }
         int xs, ys;
-        if (seg_rot_src(*j, H, W, x, y, xs, ys) && j->label[(long)ys * W + xs] == 255) {
+        if (aug_rot_src(j->rot, H, W, x, y, false, xs, ys) && j->label[(long)ys * W + xs] == 255) {
             e[0] = y < e[0] ? y : e[0]; e[1] = y > e[1] ? y : e[1]; e[2] = x < e[2] ? x : e[2]; e[3] = x > e[3] ? x : e[3]; ++e[4];
         }
     }
     for (int i = 0; i < 5; ++i) ext[i] = e[i];
     if (!img) return;
-    const int mean = kc >= 0 ? bgsub_mean_of_sum(s, H, W) : 0, n = j->crop_side;
+    const int mean = kc >= 0 ? aug_mean_of_sum(s, H, W) : 0, n = j->crop_side;
     const int *hmin = tab, *hk = tab + S, *vmin = tab + 6 * S, *vk = tab + 7 * S, *nx = tab + 12 * S, *ny = tab + 13 * S;
     std::vector<uint8_t> crop((size_t)n * n * 3), hh((size_t)n * S * 3);
     for (int r = 0; r < n; ++r) for (int c = 0; c < n; ++c) {
@@ -57,20 +57,6 @@ extern "C" void sample(const ape_seg_train_job* j, int H, int W, int S, const in
     }
 }
 """
-
-
-def build():
-    d = tempfile.mkdtemp(prefix="seg_px_")
-    with open(os.path.join(d, "px.cpp"), "w") as f:
-        f.write(_SRC)
-    so = os.path.join(d, "libpx.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(REPO, "autoposeestimation_amd", "csrc"),
-                           os.path.join(d, "px.cpp"), "-o", so])
-    return ctypes.CDLL(so)
-
-
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 def host_sample(lib, rgb, label, params, crop):
@@ -99,10 +85,10 @@ def pillow_sample(rgb, label, params, crop):
     return np.array(img), np.array(lab)
 
 
-def main():
+def main(quick=False):
+    """-> the number of samples compared (every one exact, or AssertionError)"""
     from autoposeestimation_amd.segmentation import utils as U
-    quick = "--quick" in sys.argv
-    lib = build()
+    lib = build(_SRC)
     rng = np.random.default_rng(5)
     n = 0
     for (h, w, s) in ((48, 64, 48), (40, 56, 40), (40, 40, 40)) + (() if quick else ((480, 640, 480),)):
@@ -134,7 +120,8 @@ def main():
                 assert bad == 0, "%s differs in %d places: %dx%d params %r box %r" % (name, bad, h, w, params, box)
             n += 1
     print("samples: %d exact against Pillow %s" % (n, Image.__version__))
+    return n
 
 
 if __name__ == "__main__":
-    main()
+    main("--quick" in sys.argv)
