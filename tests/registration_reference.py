@@ -113,7 +113,9 @@ def fpfh(pts, normals, radius, max_nn):
 
 
 def feature_nn(fs, ft, chunk=512):
-    """nearest target feature of every source feature: d = sum_j (a_j - b_j)^2 in j order, ties -> lowest index"""
+    """nearest target feature of every source feature: d = sum_j (a_j - b_j)^2 in j order, ties -> lowest index.  A non-finite distance
+    (a NaN or an infinity in either row, or an overflowing sum) never wins; a source row without any finite distance gets -1, and no RANSAC
+    iteration that draws such a row is kept (ransac_hypotheses)."""
     fs, ft = np.asarray(fs, dtype=np.float64), np.asarray(ft, dtype=np.float64)
     out = np.empty(len(fs), np.int64)
     for a in range(0, len(fs), chunk):
@@ -122,7 +124,9 @@ def feature_nn(fs, ft, chunk=512):
         for j in range(fs.shape[1]):
             e = blk[:, j, None] - ft[None, :, j]
             d += e * e
-        out[a:a + chunk] = np.argmin(d, 1)          # first minimum = lowest index
+        d = np.where(np.isfinite(d), d, np.inf)
+        best = np.argmin(d, 1)                      # first minimum = lowest index
+        out[a:a + chunk] = np.where(np.isfinite(d[np.arange(len(blk)), best]), best, -1)
     return out
 
 
@@ -148,14 +152,16 @@ def _apply(T, p):
 
 
 def ransac_hypotheses(src, tgt, nn, ransac_n, seed, edge_sim, dist_thr, max_iteration, max_validation, chunk=1 << 16):
-    """the first max_validation iteration indices that pass the checkers, in iteration order (edge_sim / dist_thr < 0: no checker)"""
-    src, tgt = np.asarray(src, dtype=np.float64), np.asarray(tgt, dtype=np.float64)
+    """the first max_validation iteration indices that pass the checkers, in iteration order (edge_sim / dist_thr < 0: no checker); an
+    iteration that draws a source row without a match (nn < 0 or >= len(tgt)) is refused before any checker"""
+    src, tgt, nn = np.asarray(src, dtype=np.float64), np.asarray(tgt, dtype=np.float64), np.asarray(nn, dtype=np.int64)
     kept = []
     for a in range(0, max_iteration, chunk):
         its = np.arange(a, min(max_iteration, a + chunk))
         s = sample_indices(seed, its, ransac_n, len(src))
         t = nn[s]
-        ok = np.ones(len(its), bool)
+        ok = ((t >= 0) & (t < len(tgt))).all(1)
+        t = np.where(ok[:, None], t, 0)
         if edge_sim >= 0:
             for i in range(ransac_n):
                 for j in range(i + 1, ransac_n):

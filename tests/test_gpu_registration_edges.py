@@ -1,0 +1,319 @@
+"""GPU checks of the global-registration kernels (csrc/registration.hip) at their edge shapes, against the numpy restatement
+(tests/registration_reference.py) on the inputs of tests/registration_edge_cases.py -- whose guards and path-reached claims
+tests/test_registration_host.py proves on the CPU.  Tolerances are the project's own for these kernels: FPFH atol 1e-9; nn, kept lists,
+fitness and correspondence counts exact; rmse 1e-12 relative; transformations atol 1e-9.
+
+Sizes: the clouds have at most 343 points and the feature sets at most 4 097 rows, except the two clusters of 256 and 257 points, which
+share one cloud (513 points), and the 700-point pair of the validation stride loop."""
+import numpy as np
+import pytest
+import torch
+
+import registration_edge_cases as EC
+import registration_reference as R
+
+pytestmark = pytest.mark.gpu
+_D = torch.float64
+
+
+def _mods():
+    from autoposeestimation_amd import _lib
+    from autoposeestimation_amd.pc_reconstruction import batched as B
+    from autoposeestimation_amd.pc_reconstruction import pointcloud as PC
+    return _lib, B, PC
+
+
+def _dev(a, dtype=_D):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device="cuda", dtype=dtype).contiguous()
+
+
+def _cloud(pts, normals=None):
+    _, _, PC = _mods()
+    pc = PC.PointCloud(pts)
+    if normals is not None:
+        pc._n = _dev(normals)                                # injected, not estimated
+    return pc
+
+
+def _feature(a):
+    _, _, PC = _mods()
+    return PC.Feature(_dev(a))
+
+
+# ---- FPFH -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(EC.fpfh_cases()))
+def test_fpfh_matches_restatement(name):
+    _, _, PC = _mods()
+    c = EC.fpfh_cases()[name]
+    pc = _cloud(c["pts"], c["normals"])
+    for max_nn in c["max_nns"]:
+        got = PC.compute_fpfh_feature(pc, PC.KDTreeSearchParamHybrid(radius=c["radius"], max_nn=max_nn)).t.cpu().numpy()
+        want = EC.fpfh_expected(name, max_nn)
+        assert got.shape == want.shape
+        np.testing.assert_allclose(got, want, rtol=0, atol=1e-9, err_msg="%s max_nn=%d" % (name, max_nn))
+        if max_nn == 1:
+            assert np.all(got == 0)
+    if c["zero_only"]:                                       # vn == 0: zero features, bins 5, 16 and 27
+        assert all(np.flatnonzero(row).tolist() == [5, 16, 27] for row in got)
+
+
+def test_fpfh_in_one_list_equals_each_cloud_alone():
+    _, B, PC = _mods()
+    cases = EC.fpfh_cases()
+    names = EC.fpfh_batch_list()
+    clouds = [PC.PointCloud() if n is None else _cloud(cases[n]["pts"], cases[n]["normals"]) for n in names]
+    assert len(clouds) > 16 and len(clouds[0]) == 0
+    got = B.compute_fpfh_feature(clouds, EC.BATCH_RADIUS, EC.BATCH_MAX_NN)
+    assert len(got) == len(clouds) and got[0].num() == 0
+    for n, c, f in zip(names, clouds, got):
+        want = PC.compute_fpfh_feature(c, PC.KDTreeSearchParamHybrid(radius=EC.BATCH_RADIUS, max_nn=EC.BATCH_MAX_NN))
+        assert f.t.shape == (len(c), 33) and torch.equal(f.t, want.t), n
+    k = names.index("lattice9_r2.5")
+    np.testing.assert_allclose(got[k].t.cpu().numpy(), EC.fpfh_expected("lattice9_r2.5", EC.BATCH_MAX_NN), rtol=0, atol=1e-9)
+
+
+# ---- matching -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ns,nt", EC.MATCH_SHAPES)
+def test_matching_matches_restatement(ns, nt):
+    _, _, PC = _mods()
+    fs, ft, planted = EC.matching_case(ns, nt)
+    nn = PC.feature_nn(_feature(fs), _feature(ft)).cpu().numpy()
+    assert nn.shape == (ns,) and np.array_equal(nn, R.feature_nn(fs, ft))
+    for r, low in planted.items():
+        assert nn[r] == low                                  # the lowest of the exact copies, through tile and slice borders
+
+
+def test_matching_ties_in_a_sixteen_pair_launch():
+    """16 live pairs shrink a pair's slice count, so its slices are two tiles long: row 64 is a tile border inside a slice, row 128 a
+    slice border"""
+    _, B, _ = _mods()
+    fs, ft, planted = EC.matching_case(257, 4097)
+    a, b = _feature(fs), _feature(ft)
+    small = EC.matching_case(129, 65)
+    got = B.feature_nn([a] * 15 + [_feature(small[0])], [b] * 15 + [_feature(small[1])])
+    want = R.feature_nn(fs, ft)
+    assert want[0] == 63 and want[64] == 127 and planted[0] == 63 and planted[64] == 127
+    for nn in got[:15]:
+        assert np.array_equal(nn.cpu().numpy(), want)
+    assert np.array_equal(got[15].cpu().numpy(), R.feature_nn(small[0], small[1]))
+
+
+def test_matching_non_finite_rows_and_ransac_over_them():
+    """a non-finite distance never wins; a source row without a finite distance gets -1 and no iteration that draws it is kept"""
+    _, _, PC = _mods()
+    c = EC.nan_case()
+    nn_t = PC.feature_nn(_feature(c["fs"]), _feature(c["ft"]))
+    nn = nn_t.cpu().numpy()
+    want = R.feature_nn(c["fs"], c["ft"])
+    assert np.array_equal(nn, want)
+    assert all(nn[r] == -1 for r in c["no_match"]) and (np.delete(nn, c["no_match"]) >= 0).all()
+    assert not set(nn.tolist()) & set(c["nan_targets"]) and nn[4] == 1
+    kept = _hypotheses(c["src"], c["tgt"], nn, 3, 5, -1.0, -1.0, [(0, 2000)], 2000)
+    assert np.array_equal(kept, R.ransac_hypotheses(c["src"], c["tgt"], want, 3, 5, -1.0, -1.0, 2000, 2000))
+    drew = np.isin(R.sample_indices(5, kept, 3, 130), c["no_match"])
+    assert len(kept) < 2000 and not drew.any()
+
+
+# ---- hypothesis lists -----------------------------------------------------------------------------------------------------------------
+def _hypotheses(src, tgt, nn, ransac_n, seed, edge, dist, calls, max_val):
+    """ape_ransac_hypotheses_f64 for every (it_begin, n_it) of `calls` onto one kept list -> the kept iterations (host); the entries
+    behind the count must be untouched"""
+    _lib, _, _ = _mods()
+    L = _lib.lib()
+    s, t, n = _dev(src), _dev(tgt), _dev(nn, torch.int32)
+    ns, nt = len(src), len(tgt)
+    kept = torch.full((max_val,), -7, dtype=torch.int32, device="cuda")
+    n_kept = torch.zeros(1, dtype=torch.int32, device="cuda")
+    for it0, n_it in calls:
+        ws = torch.empty(L.ape_ransac_workspace_bytes(ns, n_it, max_val), dtype=torch.uint8, device="cuda")
+        _lib.call.ape_ransac_hypotheses_f64(_lib.dptr(s, _D), ns, _lib.dptr(t, _D), nt, _lib.dptr(n), ransac_n, int(seed), float(edge),
+                                            float(dist), it0, n_it, max_val, _lib.dptr(kept), _lib.dptr(n_kept), _lib.dptr(ws), ws.numel(),
+                                            _lib.stream_ptr())
+    k = int(n_kept.item())
+    out = kept.cpu().numpy()
+    assert 0 <= k <= max_val and np.all(out[k:] == -7)
+    return out[:k].astype(np.int64)
+
+
+@pytest.mark.parametrize("ransac_n", [3, 4, 5, 16])
+def test_hypothesis_lists_match_restatement(ransac_n):
+    p = EC.ransac_pair()
+    for it0 in (0, 12345):
+        for edge, dist in EC.CHECKERS:
+            want = EC.hypotheses_in_range(p, ransac_n, 7, edge, dist, it0, 1000)     # shorter calls keep its prefixes
+            for n_it in (1, 255, 257, 1000):
+                got = _hypotheses(p["src"], p["tgt"], p["nn"], ransac_n, 7, edge, dist, [(it0, n_it)], 1000)
+                assert np.array_equal(got, want[want < it0 + n_it]), (ransac_n, edge, dist, it0, n_it)
+            if edge < 0 and dist < 0:
+                assert np.array_equal(want, np.arange(it0, it0 + 1000))
+            elif ransac_n <= 4:
+                assert 0 < len(want) < 1000
+
+
+def test_hypothesis_list_of_more_than_256_blocks():
+    p = EC.ransac_pair()
+    n_it = 65836                                             # 258 blocks: the append kernel's threads take two blocks each
+    want = R.ransac_hypotheses(p["src"], p["tgt"], p["nn"], 3, 7, EC.EDGE, EC.DIST, n_it, n_it)
+    got = _hypotheses(p["src"], p["tgt"], p["nn"], 3, 7, EC.EDGE, EC.DIST, [(0, n_it)], n_it)
+    assert len(want) > 1000 and want[-1] >= 65536 and np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("max_val", [100, 257, 300])
+def test_all_pass_compaction_and_cut(max_val):
+    p = EC.ransac_pair()
+    for rn in (3, 16):
+        got = _hypotheses(p["src"], p["tgt"], p["nn"], rn, 7, -1.0, -1.0, [(0, 1000)], max_val)
+        assert np.array_equal(got, np.arange(max_val))
+    got = _hypotheses(p["src"], p["tgt"], p["nn"], 4, 7, -1.0, -1.0, [(500, 1000)], max_val)
+    assert np.array_equal(got, np.arange(500, 500 + max_val))
+
+
+def test_append_onto_a_partly_filled_list():
+    p = EC.ransac_pair()
+    first = EC.hypotheses_in_range(p, 3, 7, EC.EDGE, EC.DIST, 0, 600)
+    second = EC.hypotheses_in_range(p, 3, 7, EC.EDGE, EC.DIST, 600, 600)
+    assert len(first) > 4 and len(second) > 4
+    max_val = len(first) + len(second) // 2                  # the cut falls inside the second call
+    got = _hypotheses(p["src"], p["tgt"], p["nn"], 3, 7, EC.EDGE, EC.DIST, [(0, 600), (600, 600), (1200, 600)], max_val)
+    assert np.array_equal(got, np.r_[first, second][:max_val])
+    got = _hypotheses(p["src"], p["tgt"], p["nn"], 3, 7, EC.EDGE, EC.DIST, [(0, 600), (600, 600)], 10000)
+    assert np.array_equal(got, np.r_[first, second])
+
+
+def test_wrapper_keeps_the_first_17000_of_20000_over_two_chunks():
+    _, _, PC = _mods()
+    p = EC.ransac_pair(50, 3)
+    assert PC._RANSAC_CHUNK[0] < 17000                       # the list spans the first two chunks
+    r = PC.registration_ransac_based_on_feature_matching(_cloud(p["src"]), _cloud(p["tgt"]), _feature(p["fs"]), _feature(p["ft"]), EC.MAX_DIST, None, 4,
+                                                         [], PC.RANSACConvergenceCriteria(20000, 17000), seed=2)
+    assert np.array_equal(r.validated, np.arange(17000)) and r.iterations == 17000
+    T = r.transformation
+    f, rm, c = R.evaluate(p["src"], p["tgt"], T, EC.MAX_DIST)
+    assert EC.validation_margin(p["src"], p["tgt"], T, EC.MAX_DIST) >= EC.MARGIN
+    assert (r.fitness, r.correspondence_count) == (f, c) and abs(r.inlier_rmse - rm) <= 1e-12 * rm
+
+
+@pytest.mark.parametrize("ns", [1, 2, 3])
+def test_tiny_cloud_hypothesis_lists(ns):
+    p = EC.tiny_pair(ns)
+    for rn in (3, 4):
+        for edge, dist in EC.CHECKERS:
+            got = _hypotheses(p["src"], p["tgt"], p["nn"], rn, 9, edge, dist, [(0, 500)], 500)
+            assert np.array_equal(got, EC.hypotheses_in_range(p, rn, 9, edge, dist, 0, 500)), (ns, rn, edge, dist)
+
+
+# ---- validation and winner -------------------------------------------------------------------------------------------------------------
+def _validate(src, tgt, nn, ransac_n, seed, kept, max_dist):
+    """ape_ransac_validate_f64 on a given kept list -> (out[24], fit_rmse [k, 3]) on the host"""
+    _lib, _, PC = _mods()
+    L = _lib.lib()
+    s, n = _dev(src), _dev(nn, torch.int32)
+    target = _cloud(tgt)
+    grid = target._grid(float(max_dist))
+    k = len(kept)
+    kt = _dev(np.asarray(kept, np.int32) if k else np.zeros(1, np.int32), torch.int32)
+    out = torch.full((24,), -7.0, dtype=_D, device="cuda")
+    fr = torch.full((max(k, 1), 3), -7.0, dtype=_D, device="cuda")
+    ws = torch.empty(L.ape_ransac_workspace_bytes(len(src), 1, max(k, 1)), dtype=torch.uint8, device="cuda")
+    _lib.call.ape_ransac_validate_f64(*PC.PointCloud._gargs(grid), _lib.dptr(s, _D), len(src), _lib.dptr(target._p, _D), len(tgt), _lib.dptr(n), ransac_n,
+                                      int(seed), _lib.dptr(kt), k, float(max_dist), _lib.dptr(out), _lib.dptr(fr), _lib.dptr(ws), ws.numel(),
+                                      _lib.stream_ptr())
+    return out.cpu().numpy(), fr.cpu().numpy()[:k]
+
+
+def _checkers(PC, edge, dist):
+    return ([PC.CorrespondenceCheckerBasedOnEdgeLength(edge)] if edge >= 0 else []) + ([PC.CorrespondenceCheckerBasedOnDistance(dist)] if dist >= 0 else [])
+
+
+def _is_rotation(T):
+    Rm = T[:3, :3]
+    np.testing.assert_allclose(Rm @ Rm.T, np.eye(3), rtol=0, atol=1e-12)
+    assert abs(np.linalg.det(Rm) - 1.0) <= 1e-12 and np.array_equal(T[3], [0, 0, 0, 1])
+
+
+@pytest.mark.parametrize("name", [r[0] for r in EC.WINNER_RUNS])
+def test_winner_matches_restatement(name):
+    """the whole run through the device kernels: kept list, every hypothesis' (fitness, rmse, count), the winner and its iteration"""
+    _, _, PC = _mods()
+    w = EC.winner_run(name)
+    p, want, rn, seed, max_dist = w["pair"], w["want"], w["ransac_n"], w["seed"], w["max_dist"]
+    kept = _hypotheses(p["src"], p["tgt"], p["nn"], rn, seed, w["edge"], w["dist"], [(0, w["max_it"])], w["max_val"])
+    assert len(kept) > 0 and np.array_equal(kept, want["kept"])
+    out, fr = _validate(p["src"], p["tgt"], p["nn"], rn, seed, kept, max_dist)
+    T = out[:16].reshape(4, 4)
+    assert out[16] == want["fitness"] and out[18] == want["count"]
+    assert abs(out[17] - want["rmse"]) <= 1e-12 * want["rmse"]
+    assert out[19] == want["position"] and out[20] == want["winner"]
+    if want["winner"] < 0:                                   # nothing beats the identity
+        assert np.array_equal(T, np.eye(4)) and out[16] == 0.0 and out[17] == 0.0
+    else:
+        assert EC.well_posed(w["sigma"])
+        np.testing.assert_allclose(T, want["T"], rtol=0, atol=1e-9)
+        _is_rotation(T)
+    # every kept hypothesis, not the winner alone
+    sig = EC.hypothesis_report(p["src"], p["tgt"], p["nn"], rn, seed, kept)["sigma"]
+    Ts = EC.kept_transforms(p["src"], p["tgt"], p["nn"], rn, seed, kept)
+    for k in np.flatnonzero(EC.well_posed(sig)):
+        f, rm, c = R.evaluate(p["src"], p["tgt"], Ts[k], max_dist)
+        assert fr[k, 0] == f and fr[k, 2] == c and abs(fr[k, 1] - rm) <= 1e-12 * rm, (name, k)
+    if "fs" in p:                                            # the same through the wrapper, which matches the features itself
+        r = PC.registration_ransac_based_on_feature_matching(_cloud(p["src"]), _cloud(p["tgt"]), _feature(p["fs"]), _feature(p["ft"]), max_dist, None,
+                                                             rn, _checkers(PC, w["edge"], w["dist"]),
+                                                             PC.RANSACConvergenceCriteria(w["max_it"], w["max_val"]), seed=seed)
+        assert np.array_equal(r.validated, want["kept"]) and np.array_equal(r.transformation, T)
+        assert (r.fitness, r.inlier_rmse, r.correspondence_count) == (out[16], out[17], out[18])
+
+
+@pytest.mark.parametrize("ns", [1, 8, 9, 700])
+def test_validation_of_the_devices_own_transformation(ns):
+    """whatever rotation the SVD completed a rank-deficient covariance with: a proper rotation, and (fitness, rmse, count) are those of
+    the returned T.  ns = 1, 8, 9: around one block of 8 groups; 700: the stride loop over 64 blocks"""
+    p = EC.ransac_pair(ns, 40 + ns)
+    kept = _hypotheses(p["src"], p["tgt"], p["nn"], 3, 17, -1.0, -1.0, [(0, 300)], 50)
+    assert np.array_equal(kept, np.arange(50))
+    out, fr = _validate(p["src"], p["tgt"], p["nn"], 3, 17, kept, EC.MAX_DIST)
+    T = out[:16].reshape(4, 4)
+    assert out[19] >= 0 and out[20] == kept[int(out[19])]
+    _is_rotation(T)
+    assert EC.validation_margin(p["src"], p["tgt"], T, EC.MAX_DIST) >= EC.MARGIN       # a guard on the input T, not on the result
+    f, rm, c = R.evaluate(p["src"], p["tgt"], T, EC.MAX_DIST)
+    assert out[16] == f and out[18] == c and abs(out[17] - rm) <= 1e-12 * rm
+    assert np.array_equal(fr[int(out[19])], out[16:19])
+    # the winner rule over the device's own per-hypothesis figures: first strictly better one in list order
+    best = (0.0, 0.0, -1)
+    for k in range(len(kept)):
+        if fr[k, 0] > best[0] or (fr[k, 0] == best[0] and fr[k, 1] < best[1]):
+            best = (fr[k, 0], fr[k, 1], k)
+    assert out[19] == best[2]
+    if ns == 1:                                              # one point: every hypothesis is the same, position 0 stands
+        assert out[19] == 0 and out[16] == 1.0 and out[18] == 1 and np.all(fr == fr[0])
+        # (the rotation need not be the identity: (p + p + p) / 3 may differ from p in its last bit, and that rounding residue is a rank-1
+        # covariance with a direction of its own; exact_pair() has the exactly-zero covariance, on integer coordinates)
+
+
+@pytest.mark.parametrize("ns", [1, 2, 3])
+def test_tiny_cloud_winner_is_a_rotation_and_evaluates_to_itself(ns):
+    p = EC.tiny_pair(ns)
+    for rn in (3, 4):
+        kept = _hypotheses(p["src"], p["tgt"], p["nn"], rn, 9, -1.0, -1.0, [(0, 64)], 64)
+        out, _ = _validate(p["src"], p["tgt"], p["nn"], rn, 9, kept, 2.0)
+        T = out[:16].reshape(4, 4)
+        _is_rotation(T)
+        assert EC.validation_margin(p["src"], p["tgt"], T, 2.0) >= EC.MARGIN
+        f, rm, c = R.evaluate(p["src"], p["tgt"], T, 2.0)
+        assert out[16] == f and out[18] == c and abs(out[17] - rm) <= 1e-12 * max(rm, 1e-300)
+
+
+def test_point_exactly_at_max_dist_is_not_counted():
+    _, _, PC = _mods()
+    p = EC.exact_pair()
+    want = EC.ransac_from_nn(p["src"], p["tgt"], p["nn"], p["max_dist"], 3, 21, EC.EDGE, -1.0, 64, 64)
+    kept = _hypotheses(p["src"], p["tgt"], p["nn"], 3, 21, EC.EDGE, -1.0, [(0, 64)], 64)
+    assert np.array_equal(kept, want["kept"])
+    out, fr = _validate(p["src"], p["tgt"], p["nn"], 3, 21, kept, p["max_dist"])
+    assert np.array_equal(out[:16].reshape(4, 4), want["T"])
+    assert (out[16], out[17], out[18]) == (0.5, 0.0, 1.0)
+    assert out[19] == 0 and out[20] == kept[0]               # equal (fitness, rmse) all along: the lowest iteration stands
+    assert np.all(fr == [0.5, 0.0, 1.0])
+    out, _ = _validate(p["src"], p["tgt"], p["nn"], 3, 21, kept, float(np.nextafter(p["max_dist"], 6.0)))
+    assert (out[16], out[18]) == (1.0, 2.0)                  # one ulp more and it is
