@@ -1,0 +1,138 @@
+"""Device builder of the LineMOD samples (csrc/linemod.hip) and the host arithmetic between its launches.
+
+The reference builds a sample in Pillow, numpy and OpenCV on the host (dataset.py:90-195).  Here the host only DRAWS (PoseDataset.batch)
+and does get_bbox's integer arithmetic; a batch over frames that already live on the device is
+`largest_boxes` (mode 'eval' only: `ape_linemod_boxes`, eight small launches, and a read-back of 16 bytes per frame) -> `count`
+(`ape_linemod_rows`: the valid pixels of every crop row and the L sums of the contrast ops; a read-back of 2 KB per sample) -> one upload
+of the row prefixes and the ranks to keep -> `samples` (`ape_linemod_samples`).
+
+A parameter set is a dict: ops (the ordered `(name, factor)` list of `ColorJitterPIL.params()`; [] = none), add_t (3 floats)."""
+import ctypes
+
+import numpy as np
+import torch
+
+from autoposeestimation_amd import _lib
+from autoposeestimation_amd import sample_jobs as J
+from autoposeestimation_amd.DenseFusion.datasets.linemod.dataset import get_bbox
+from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented.augment import row_prefix, selection  # noqa: F401 (selection: re-exported)
+
+_c = ctypes
+
+
+class LinemodJob(_c.Structure):
+    """Mirror of `ape_linemod_job` (include/ape_hip.h); tests/test_linemod_host.py compares the layout with the C compiler's."""
+    _fields_ = [("rgb", _c.c_void_p), ("depth", _c.c_void_p), ("label", _c.c_void_p), ("add_t", _c.c_double * 3), ("out_off", _c.c_longlong),
+                ("jit", _lib.AugJitter), ("rmin", _c.c_int32), ("rmax", _c.c_int32), ("cmin", _c.c_int32), ("cmax", _c.c_int32),
+                ("label_bands", _c.c_int32), ("add_noise", _c.c_int32), ("skip", _c.c_int32), ("reserved", _c.c_int32),
+                ("cam_cx", _c.c_float), ("cam_cy", _c.c_float), ("cam_fx", _c.c_float), ("cam_fy", _c.c_float), ("cam_scale", _c.c_float)]
+
+
+def largest_boxes(labels):
+    """labels: one-band [H,W] u8 device tensors -> i32 [B,4] on the device: `mask_to_bbox(label == 255)` of every frame, `[x, y, w, h]`"""
+    if not labels:
+        raise ValueError("empty batch")
+    h, w = labels[0].shape
+    dev, b = labels[0].device, len(labels)
+    ptrs = (_c.c_void_p * b)(*[J.frame(t, torch.uint8, (h, w), "label") for t in labels])
+    L = _lib.lib()
+    ws = J.workspace("linemod_box", dev, L.ape_linemod_box_workspace_bytes(b, h, w))
+    boxes = torch.empty((b, 4), dtype=torch.int32, device=dev)
+    _lib.call.ape_linemod_boxes(_c.cast(ptrs, _c.c_void_p), b, h, w, _lib.dptr(boxes), _lib.dptr(ws), ws.numel(), _lib.stream_ptr())
+    return boxes
+
+
+class Counted:
+    """a batch between `count` and `samples`: the jobs with their crops, the frames they point into, and the in-crop row counts"""
+
+    def __init__(self, jobs, frames, h, w, num, ws, rows, boxes):
+        self.jobs, self.frames, self.h, self.w, self.num, self.ws, self.rows, self.boxes = jobs, frames, h, w, num, ws, rows, boxes
+        self.counts = rows.sum(axis=1)
+
+
+def count(frames, params, boxes, eval_mode, add_noise, cam, num, names=None):
+    """frames: per sample (rgb[H,W,3] u8, depth[H,W] u16, label u8 [H,W] or [H,W,bands]) device tensors (views into a resident set;
+    nothing is copied); params: one dict per sample; boxes: per sample the `[x, y, w, h]` the crop is cut around (`obj_bb`), or None in
+    eval_mode, where the device finds the largest contour of every label; cam: (cx, cy, fx, fy); num: points per sample -> Counted"""
+    if not frames:
+        raise ValueError("empty batch")
+    if len(frames) != len(params) or len(frames) != len(boxes):
+        raise ValueError("%d samples, %d parameter sets, %d boxes" % (len(frames), len(params), len(boxes)))
+    h, w = frames[0][0].shape[:2]
+    dev, b = frames[0][0].device, len(frames)
+    name = lambda i: i if names is None else names[i]  # noqa: E731
+    boxes = list(boxes)
+    if eval_mode and any(bx is None for bx in boxes):
+        got = largest_boxes([f[2] for f in frames]).cpu().numpy()            # read-back: 16 bytes per frame
+        boxes = [got[i].tolist() if bx is None else bx for i, bx in enumerate(boxes)]
+    jobs = (LinemodJob * b)()
+    for i, ((rgb, depth, label), p) in enumerate(zip(frames, params)):
+        job = jobs[i]
+        bands = 1 if label.dim() == 2 else int(label.shape[2])
+        job.rgb = J.frame(rgb, torch.uint8, (h, w, 3), "frame")
+        job.depth = J.frame(depth, torch.uint16, (h, w), "depth")
+        job.label = J.frame(label, torch.uint8, (h, w) if label.dim() == 2 else (h, w, bands), "label")
+        job.label_bands, job.add_noise = bands, int(bool(add_noise))
+        J.fill_jitter(job.jit, p.get("ops") if add_noise else None)
+        job.cam_cx, job.cam_cy, job.cam_fx, job.cam_fy = [float(v) for v in cam]      # numpy computes the cloud in float32
+        job.cam_scale = 1.0
+        if add_noise:
+            for k in range(3):
+                job.add_t[k] = float(p["add_t"][k])
+        rmin, rmax, cmin, cmax = [int(v) for v in get_bbox([int(v) for v in boxes[i]])]
+        hc, wc = rmax - rmin, cmax - cmin
+        if rmin < 0 or cmin < 0 or rmax > h or cmax > w or hc < 40 or wc < 40 or hc % 40 or wc % 40:
+            raise ValueError("sample %s: get_bbox(%s) gives the crop rows %d:%d, columns %d:%d, which is no crop of border_list sides "
+                             "inside the frame" % (name(i), list(boxes[i]), rmin, rmax, cmin, cmax))
+        job.rmin, job.rmax, job.cmin, job.cmax = rmin, rmax, cmin, cmax
+    L = _lib.lib()
+    ws = J.workspace("linemod", dev, L.ape_linemod_workspace_bytes(b, h, int(num)))   # carries the L sums to `samples`
+    _lib.call.ape_linemod_rows(_c.cast(jobs, _c.c_void_p), b, h, w, _lib.dptr(ws), ws.numel(), _lib.stream_ptr())
+    r0 = L.ape_linemod_rows_offset(b)
+    rows = ws[r0:r0 + b * h * 4].cpu().numpy().view(np.int32).reshape(b, h)   # read-back: the in-crop counts per row
+    return Counted(jobs, frames, h, w, int(num), ws, rows, boxes)
+
+
+def samples(st, sels, mean, std):
+    """st: `count`'s result; sels: per sample the i32[num] ranks to keep (`selection`), or None for a sample that is not built (no valid
+    pixel) -> per sample (cloud[1,N,3] f32, choose[1,1,N] i64, img[1,3,Hc,Wc] f32) views into ONE packed block, or None"""
+    b, h, w, n, jobs, ws = len(st.jobs), st.h, st.w, st.num, st.jobs, st.ws
+    if len(sels) != b:
+        raise ValueError("%d samples but %d selections" % (b, len(sels)))
+    L = _lib.lib()
+    tab = np.zeros(b * h + b * n, np.int32)
+    tab[:b * h] = row_prefix(st.rows).reshape(-1)
+    offsets, total = [], 0
+    for i, sel in enumerate(sels):
+        jobs[i].skip = int(sel is None)
+        jobs[i].out_off = 0
+        offsets.append(None)
+        if sel is None:
+            continue
+        sel = np.asarray(sel, np.int32).reshape(-1)
+        if sel.size != n or sel.min() < 0 or sel.max() >= st.counts[i]:
+            raise ValueError("sample %d: the selection must be %d ranks below its %d valid pixels" % (i, n, st.counts[i]))
+        tab[b * h + i * n:b * h + (i + 1) * n] = sel
+        jobs[i].out_off = total
+        offsets[i] = total
+        total += L.ape_pose_train_sample_bytes(n, jobs[i].rmax - jobs[i].rmin, jobs[i].cmax - jobs[i].cmin)
+    if total == 0:
+        return [None] * b
+    t0 = L.ape_linemod_tables_offset(b, h)
+    ws[t0:t0 + tab.nbytes].view(torch.int32).copy_(torch.from_numpy(tab))        # the one upload: row prefixes and ranks
+    block = torch.empty(total, dtype=torch.uint8, device=ws.device)
+    m, sd = J.norm(mean, std, 3)
+    _lib.call.ape_linemod_samples(_c.cast(jobs, _c.c_void_p), b, h, w, n, m, sd, _lib.dptr(block), block.numel(), _lib.dptr(ws), ws.numel(),
+                                  _lib.stream_ptr())
+    img_off = L.ape_pose_train_image_offset(n)
+    views = []
+    for i, o in enumerate(offsets):
+        if o is None:
+            views.append(None)
+            continue
+        hc, wc = jobs[i].rmax - jobs[i].rmin, jobs[i].cmax - jobs[i].cmin
+        choose = block[o:o + 8 * n].view(torch.int64).view(1, 1, n)
+        points = block[o + 8 * n:o + 20 * n].view(torch.float32).view(1, n, 3)
+        img = block[o + img_off:o + img_off + 12 * hc * wc].view(torch.float32).view(1, 3, hc, wc)
+        views.append((points, choose, img))
+    return views

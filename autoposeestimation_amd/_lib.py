@@ -168,6 +168,16 @@ SIGNATURES = {
     "ape_pose_train_sample_bytes": [_I, _I, _I],
     "ape_pose_train_stats": [_P, _I, _I, _I, _P, _c.c_size_t, _P],
     "ape_pose_train_samples": [_P, _I, _I, _I, _I, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P],
+    # LineMOD samples (csrc/linemod.hip): DenseFusion/datasets/linemod/dataset.py:90-195; the job struct `ape_linemod_job` is mirrored next
+    # to its one user, DenseFusion/datasets/linemod/augment.py
+    "ape_linemod_box_workspace_bytes": [_I, _I, _I],
+    "ape_linemod_boxes": [_P, _I, _I, _I, _P, _P, _c.c_size_t, _P],
+    "ape_linemod_rows_offset": [_I],
+    "ape_linemod_tables_offset": [_I, _I],
+    "ape_linemod_sel_offset": [_I, _I],
+    "ape_linemod_workspace_bytes": [_I, _I, _I],
+    "ape_linemod_rows": [_P, _I, _I, _I, _P, _c.c_size_t, _P],
+    "ape_linemod_samples": [_P, _I, _I, _I, _I, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P],
 }
 
 
@@ -239,12 +249,14 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
              "ape_pose_train_extents_offset": _c.c_size_t, "ape_pose_train_rows_offset": _c.c_size_t,
              "ape_pose_train_tables_offset": _c.c_size_t, "ape_pose_train_sel_offset": _c.c_size_t,
              "ape_pose_train_workspace_bytes": _c.c_size_t, "ape_pose_train_image_offset": _c.c_size_t,
-             "ape_pose_train_sample_bytes": _c.c_size_t}
+             "ape_pose_train_sample_bytes": _c.c_size_t,
+             "ape_linemod_box_workspace_bytes": _c.c_size_t, "ape_linemod_rows_offset": _c.c_size_t,
+             "ape_linemod_tables_offset": _c.c_size_t, "ape_linemod_sel_offset": _c.c_size_t, "ape_linemod_workspace_bytes": _c.c_size_t}
 
 _lib = None
 
 
-ABI_VERSION = 9      # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 10     # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

@@ -401,3 +401,107 @@ def pose_dataset_tree(root, data_set_name="synth", n_view=5, n_extra=3, seed=3):
         with open(os.path.join(ds, name), "w") as f:
             f.write("".join(x + "\n" for x in items))
     return classes, train, test, extra
+
+
+# ---- a LineMOD-shaped tree (DenseFusion/datasets/linemod/dataset.py:24-88) ----------------------------------------------------------------
+LINEMOD_OBJECTS = [1, 2, 4, 5, 6, 8, 9, 10, 11, 12, 13, 14, 15]
+# lines of test.txt per object.  The reference's keep-every-tenth counter runs on across the objects and is incremented before the
+# end-of-file check, so an end of file that does not fall on a multiple of ten is read again until one does: mode 'test' keeps the tenth
+# line of the objects that have one -- here objects 2, 5, 11 (symmetric) and 13
+LINEMOD_TEST_LINES = [1, 10, 2, 10, 1, 1, 2, 1, 10, 1, 10, 1, 2]
+
+
+# The objects whose 'eval' samples are counted: the segnet_results labels of the others are empty (lost detections).  These are the objects
+# whose confidence head, with the seeded weights posenet_state_dict(13, 0), answers a far point with a maximum at least 1e-2 above the
+# second confidence; the heads of the others saturate (object 2: every confidence within 2e-5 of 1.0) or answer it with their minimum, so
+# that no frame gives their arg-max a margin.  Object 11 is one of the symmetric pair.
+LINEMOD_EVAL_OBJECTS = (1, 5, 6, 9, 11)
+
+
+def linemod_tree(root, seed=0):
+    """A small LineMOD_preprocessed tree: for each of the 13 objects `data/%02d/{rgb,depth,mask}/%04d.png` (480 x 640; the mask with three
+    bands), `gt.yml` (object 2 with two records per frame, the first of another object), `train.txt`, `test.txt`, `models/obj_%02d.ply`
+    (more than 500 vertices, mm) and `segnet_results/%02d_label/%04d_label.png` (one band; for LINEMOD_EVAL_OBJECTS it differs from the mask: most of
+    the object cut off, a hole, an extra blob, a region of another value, one far depth value; for the other objects it is empty = a lost
+    detection), and `models/models_info.yml` with
+    diameters chosen so that random networks pass the ADD threshold for some objects and fail it for others.  `obj_bb` is the mask's
+    box moved and resized by a few pixels, so mask pixels fall outside the crop.  Deterministic in `seed`.
+    Shared by tools/gen_golden_linemod.py (which runs the REFERENCE's PoseDataset on it) and the LineMOD tests.
+    -> {object id: [frame names of test.txt]}"""
+    import os
+    from PIL import Image
+    rng = np.random.default_rng([77, int(seed)])
+    h, w = 480, 640
+    yy, xx = np.mgrid[0:h, 0:w]
+    os.makedirs(os.path.join(root, "models"), exist_ok=True)
+    frames_of, info = {}, []
+    for oi, obj in enumerate(LINEMOD_OBJECTS):
+        d = os.path.join(root, "data", "%02d" % obj)
+        seg = os.path.join(root, "segnet_results", "%02d_label" % obj)
+        for sub in ("rgb", "depth", "mask"):
+            os.makedirs(os.path.join(d, sub), exist_ok=True)
+        os.makedirs(seg, exist_ok=True)
+        n_vtx = 520 + 7 * oi
+        vtx = (rng.uniform(-1, 1, (n_vtx, 3)) * [40.0 + 3 * oi, 30.0, 25.0 + oi]).round(4)
+        with open(os.path.join(root, "models", "obj_%02d.ply" % obj), "w") as f:
+            f.write("ply\nformat ascii 1.0\ncomment synthetic\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                    "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
+                    "element face 0\nproperty list uchar int vertex_indices\nend_header\n" % n_vtx)
+            for v in vtx:
+                f.write("%.4f %.4f %.4f 0.0 0.0 1.0 %d %d %d\n" % (v[0], v[1], v[2], 200, 100, 50))
+        info.append("%d: {diameter: %.8f, min_x: 0.0, min_y: 0.0, min_z: 0.0, size_x: 1.0, size_y: 1.0, size_z: 1.0}\n"
+                    % (obj, 40000.0 if oi % 2 == 0 else 90.0 + oi))
+        names, gt = [], []
+        for k in range(LINEMOD_TEST_LINES[oi]):
+            fid = 3 * k + oi                                     # frame ids with gaps, like the real lists
+            name = "%04d" % fid
+            names.append(name)
+            hh, ww = int(rng.integers(24, 130)), int(rng.integers(30, 170))
+            r0, c0 = int(rng.integers(5, h - hh - 5)), int(rng.integers(5, w - ww - 5))
+            inside = (((yy - r0 - hh / 2) / (hh / 2)) ** 2 + ((xx - c0 - ww / 2) / (ww / 2)) ** 2) < 1
+            rgb = (rng.integers(0, 60, (h, w, 3)) + 90).astype(np.uint8)
+            rgb[inside] = (CLASS_COLOURS[oi % len(CLASS_COLOURS)] * 0.8).astype(np.uint8) + rng.integers(0, 40, (int(inside.sum()), 3)).astype(np.uint8)
+            depth = np.full((h, w), 1100, np.uint16) + (xx // 40).astype(np.uint16)
+            depth[inside] = (900 + 25 * np.sin(xx[inside] / 17.0) + 15 * np.cos(yy[inside] / 13.0)).astype(np.uint16)
+            depth[rng.random((h, w)) < 0.03] = 0
+            Image.fromarray(rgb).save(os.path.join(d, "rgb", name + ".png"), compress_level=1)
+            Image.fromarray(depth).save(os.path.join(d, "depth", name + ".png"), compress_level=1)
+            mask = np.repeat((inside.astype(np.uint8) * 255)[:, :, None], 3, axis=2)
+            Image.fromarray(mask).save(os.path.join(d, "mask", name + ".png"))
+            lab = np.zeros((h, w), np.uint8)
+            if obj in LINEMOD_EVAL_OBJECTS:
+                # the segmentation result: a 16 x 24 window of the object (the rest cut off) with a hole -- between 250 and 500 valid
+                # pixels, so `choose` keeps every one of them and its wrap pad repeats only the first
+                wr, wc = r0 + hh // 2 - 8, c0 + ww // 2 - 12
+                lab[wr:wr + 16, wc:wc + 24] = inside[wr:wr + 16, wc:wc + 24] * 255
+                lab[wr + 7:wr + 9, wc + 11:wc + 13] = 0                                       # a hole
+                br, bc = (r0 + hh + 40) % (h - 12), (c0 + ww + 60) % (w - 12)
+                lab[br:br + 6, bc:bc + 9] = 255                                               # an extra blob, far from the object
+                lab[5:9, 5:30] = 128                                                          # another value: not the object
+                # and one far point, the last of the window in raster order: the confidence head answers it with a maximum that stands
+                # clear of the second (tests/test_linemod_host.py::test_eval_fixture_guard)
+                lab[wr + 15, wc + 23] = 255
+                depth[wr + 15, wc + 23] = 63000
+                Image.fromarray(depth).save(os.path.join(d, "depth", name + ".png"), compress_level=1)
+            Image.fromarray(lab).save(os.path.join(seg, name + "_label.png"))
+            R = rigid(rng.uniform(-1, 1), rng.uniform(-1, 1), rng.uniform(-3, 3), (0, 0, 0))[:3, :3]
+            z = 900.0
+            t = [float((c0 + ww / 2 - 325.2611) * z / 572.4114), float((r0 + hh / 2 - 242.04899) * z / 573.57043), z]
+            bb = [c0 + int(rng.integers(-6, 7)), r0 + int(rng.integers(-6, 7)), ww + int(rng.integers(-8, 9)), hh + int(rng.integers(-8, 9))]
+            recs = [(obj, R, t, bb)]
+            if obj == 2:                                         # several objects are annotated in object 2's frames; its own is not first
+                recs.insert(0, (5, rigid(0.3, -0.2, 1.0, (0, 0, 0))[:3, :3], [10.0, -20.0, 1000.0], [30, 40, 50, 60]))
+            gt.append("%d:\n" % fid + "".join(
+                "- cam_R_m2c: [%s]\n  cam_t_m2c: [%s]\n  obj_bb: [%s]\n  obj_id: %d\n"
+                % (", ".join("%.8f" % v for v in Rm.flatten()), ", ".join("%.8f" % v for v in tm), ", ".join("%d" % v for v in b4), oid)
+                for oid, Rm, tm, b4 in recs))
+        with open(os.path.join(d, "gt.yml"), "w") as f:
+            f.write("".join(gt))
+        with open(os.path.join(d, "test.txt"), "w") as f:
+            f.write("".join(n + "\n" for n in names))
+        with open(os.path.join(d, "train.txt"), "w") as f:
+            f.write("".join(n + "\n" for n in names[:2]))
+        frames_of[obj] = names
+    with open(os.path.join(root, "models", "models_info.yml"), "w") as f:
+        f.write("".join(info))
+    return frames_of

@@ -789,6 +789,52 @@ int ape_pose_train_stats(const ape_pose_train_job* jobs_host, int B, int H, int 
 int ape_pose_train_samples(const ape_pose_train_job* jobs_host, int B, int H, int W, int N, const float* mean3_host, const float* std3_host,
                            void* out, size_t out_bytes, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- LineMOD samples (csrc/linemod.hip; reference DenseFusion/datasets/linemod/dataset.py:90-195) -------------------------------------
+ * One job per sample: DEVICE pointers to the resident colour frame, 16-bit depth and label ([H][W][label_bands] u8; band 0 decides, as
+ * `masked_equal(label, [255, 255, 255])[:, :, 0]` does) and what the host drew.  There is no rotation.  The crop [rmin, rmax) x [cmin, cmax)
+ * comes from the host's get_bbox over `obj_bb` or over the largest-contour box below, so label pixels may lie OUTSIDE it: only pixels
+ * inside the crop are counted and chosen.  cam_*: the camera constants as C floats (numpy computes the cloud in float32):
+ * z = depth / cam_scale, x = (col - cam_cx) * z / cam_fx, y = (row - cam_cy) * z / cam_fy, then each / 1000.0f; add_t (double) is added in
+ * float64 and rounded once when add_noise.  skip != 0: the sample has no valid pixel; launch C writes nothing for it. */
+typedef struct ape_linemod_job {
+    const uint8_t* rgb;        /* [H][W][3] */
+    const uint16_t* depth;     /* [H][W] */
+    const uint8_t* label;      /* [H][W][label_bands] */
+    double add_t[3];
+    long long out_off;
+    ape_aug_jitter jit;
+    int rmin, rmax, cmin, cmax;
+    int label_bands, add_noise, skip, reserved;
+    float cam_cx, cam_cy, cam_fx, cam_fy, cam_scale;
+} ape_linemod_job;
+APE_STATIC_ASSERT(sizeof(ape_linemod_job) == 160, "ape_linemod_job layout (mirrored by linemod/augment.py LinemodJob)");
+/* Largest-contour box of `mask_to_bbox` (dataset.py:216-230 with cv2.findContours / boundingRect restated): per frame the 8-connected
+ * components of label == 255 (labels_host: HOST array of B DEVICE pointers to one-band [H][W] u8 labels), per component its extents,
+ * boxes[b] = (x, y, w, h) of the component with the largest w * h, ties to the component whose first pixel comes first in raster order,
+ * zeros when the frame has none.  Integer min / max / compare only: identical whatever the schedule.  B * H * W < 2^31. */
+size_t ape_linemod_box_workspace_bytes(int B, int H, int W);
+int ape_linemod_boxes(const void* const* labels_host, int B, int H, int W, int* boxes, void* ws, size_t ws_bytes, void* stream);
+/* The workspace of a batch of samples: [B][64] u64 luma partial sums | at ape_linemod_rows_offset(B): [B][H] i32 row counts (the one
+ * read-back) | at ape_linemod_tables_offset(B, H): [B][H] i32 exclusive row prefix, then at ape_linemod_sel_offset(B, H): [B][N] i32 `sel`
+ * (one upload covers both).  One per stream; not shared by batches in flight at once.  A sample's bytes in the output block are those of
+ * ape_pose_train_image_offset / ape_pose_train_sample_bytes: choose[N] i64 | points[N][3] f32 | img[3][Hc][Wc] f32. */
+size_t ape_linemod_rows_offset(int B);
+size_t ape_linemod_tables_offset(int B, int H);
+size_t ape_linemod_sel_offset(int B, int H);
+size_t ape_linemod_workspace_bytes(int B, int H, int N);
+/* Launch B: rows[b][y] = the number of pixels of row y inside [cmin, cmax) with label band 0 == 255 and depth != 0 for rmin <= y < rmax,
+ * 0 for the other rows, each row written once by the wave that walked it; and per workgroup one partial of the integer L sum of the whole
+ * frame as it is when its contrast op runs.  A crop outside the frame, outside 40..480 x 40..640 or not a multiple of 40, label_bands
+ * outside 1..4, a workspace that is misaligned or too short (in all three entry points): APE_EINVAL, nothing launched. */
+int ape_linemod_rows(const ape_linemod_job* jobs_host, int B, int H, int W, void* ws, size_t ws_bytes, void* stream);
+/* Launch C, after the caller copied the exclusive row prefixes and sel[B][N] (the RANKS, among the valid in-crop pixels in row-major
+ * order, that `choose` keeps) into the workspace.  Per sample without `skip`, at out + out_off: choose[j] = the flat in-crop index of the
+ * valid pixel of rank sel[j] (0 and a zero point when there is none), points[j] its cloud point, img = ((float)v - mean[c]) / std[c] of
+ * the jittered frame inside the crop, planar.  The refusals of launch B, and a sample that does not fit out_bytes, out or out_off not
+ * 16-byte aligned: APE_EINVAL, nothing launched. */
+int ape_linemod_samples(const ape_linemod_job* jobs_host, int B, int H, int W, int N, const float* mean3_host, const float* std3_host,
+                        void* out, size_t out_bytes, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
