@@ -101,7 +101,25 @@ def surface_points(views, intr_default, device="cuda"):
     return out
 
 
+_KEY_CELLS = 1 << 21          # cell coordinates per axis of the packed 3 x 21-bit key
+_VOXEL_UNCHECKED = 1.0        # clouds here are millimetres from a 16-bit depth sensor (extent < 2^20): a voxel >= 1 cannot reach 2^21 cells
+
+
+def check_voxel_range(lo, hi, voxel_size):
+    """ValueError when a cloud with bounds lo / hi needs 2^21 or more voxels along an axis: the kernel clamps cell coordinates to the 21-bit
+    key fields, which would MERGE distant voxels (open3d keeps them apart).  The search grids clamp too and stay as they are: a clamped
+    search cell only holds more candidates, every distance is still tested."""
+    ext = float(np.max(np.asarray(hi, dtype=np.float64) - np.asarray(lo, dtype=np.float64)))
+    if not ext / float(voxel_size) < _KEY_CELLS:
+        raise ValueError("voxel_size %g is too small for a cloud of extent %g: %d or more voxels along an axis" % (voxel_size, ext, _KEY_CELLS))
+
+
 def voxel_down_sample(clouds, voxel_size):
+    if 0 < float(voxel_size) < _VOXEL_UNCHECKED:         # one bounds read, only where the key range can be exceeded
+        for c in clouds:
+            if len(c):
+                lo, hi = torch.aminmax(c._p, dim=0)
+                check_voxel_range(lo.cpu().numpy(), hi.cpu().numpy(), voxel_size)
     out = [None] * len(clouds)
     for idx in _chunks(clouds):
         ns = [len(clouds[i]) for i in idx]
@@ -225,6 +243,16 @@ def moments(clouds):
     return out
 
 
+def _inverse_or_nan(cov):
+    """cov^-1; all NaN for a singular or non-finite covariance (one point, an exactly coplanar cloud) -- what Eigen's inverse leaves the
+    reference with: non-finite distances for THAT cloud, not an exception that takes the other clouds of the batch with it"""
+    try:
+        inv = np.linalg.inv(cov) if np.isfinite(cov).all() else None
+    except np.linalg.LinAlgError:
+        inv = None
+    return inv if inv is not None and np.isfinite(inv).all() else np.full((3, 3), np.nan)
+
+
 def mahalanobis(clouds):
     """sqrt((p - mean)^T cov^-1 (p - mean)) of every point, per cloud, as host arrays"""
     mom = moments(clouds)
@@ -236,7 +264,7 @@ def mahalanobis(clouds):
         for k, i in enumerate(idx):
             if ns[k]:
                 mean, cov = mom[i]
-                mc[k] = np.concatenate([mean, np.linalg.inv(cov).reshape(9)])
+                mc[k] = np.concatenate([mean, _inverse_or_nan(cov).reshape(9)])
         total = sum(ns)
         if total == 0:
             continue
