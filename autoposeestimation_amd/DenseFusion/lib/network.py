@@ -454,6 +454,8 @@ class PoseNet(_HipModule):
         b1 = torch.cat([sd[f"conv1_{h}.bias"] for h in "rtc"], 0)
         pl.l1_point = E.Conv(w1[:, :384], None, act=E.ACT_RELU, **kw)           # per-point part
         pl.l1_global = E.Conv(w1[:, 384:], b1, act=E.ACT_NONE, **kw)            # per-crop bias from ap_x
+        pl.l1_c = E.Conv(w1[1280:, :384], None, act=E.ACT_RELU, **kw)           # forward_pose: the c rows of l1_point on every point,
+        pl.l1_rt = E.Conv(w1[:1280, :384], None, act=E.ACT_RELU, **kw)          # its r | t rows on the selected points
         pl.l2 = [E.Conv(sd[f"conv2_{h}.weight"], sd[f"conv2_{h}.bias"], act=E.ACT_RELU, **kw) for h in "rtc"]
         pl.l3 = [E.Conv(sd[f"conv3_{h}.weight"], sd[f"conv3_{h}.bias"], act=E.ACT_RELU, **kw) for h in "rtc"]
         pl.l4 = [t.detach().to(dev, torch.float32).reshape(t.shape[0], -1).contiguous()
@@ -463,6 +465,55 @@ class PoseNet(_HipModule):
     def forward_batch(self, img4, points4, choose, obj, taps=None):
         """img4[B,Hc,Wc,4] f32 (normalised RGB + 0), points4[B,N,4], choose[B,N] i64, obj[B] i64
         -> heads[B,N,8] (qw,qx,qy,qz,tx,ty,tz,c), emb[B,N,32]"""
+        pl, pf, ap, emb, gb = self._trunk(img4, points4, choose, obj, taps)
+        b, n = points4.shape[:2]
+        h3 = torch.empty(b, n, 1, 384, dtype=torch.float32, device=img4.device)
+        if pl.feat.pf_s32 is not None:                                          # pre-split route (see _FeatPlan): h1, h2 stay split
+            h1 = pl.l1_point(pl.feat.pf_s32, bias=gb, bias_bstride=1920, out_fmt=E.FMT_S32)
+            h2 = E.S32(torch.empty(b, n, 1, 768, dtype=torch.float32, device=img4.device))
+            for i in range(3):
+                pl.l2[i](h1, out=h2, xoff=640 * i, yoff=256 * i, out_fmt=E.FMT_S32)
+                pl.l3[i](h2, out=h3, xoff=256 * i, yoff=128 * i)
+        else:
+            h1 = pl.l1_point(pf, bias=gb, bias_bstride=1920)                    # [B,N,1,1920]
+            h2 = torch.empty(b, n, 1, 768, dtype=torch.float32, device=img4.device)
+            for i in range(3):
+                pl.l2[i](h1, out=h2, xoff=640 * i, yoff=256 * i)
+                pl.l3[i](h2, out=h3, xoff=256 * i, yoff=128 * i)
+        heads = E.head_select(h3.view(b * n, 384), 0, 128, 256, *pl.l4, obj, b, n, 128)
+        if taps is not None:
+            taps["pf"], taps["ap"], taps["emb"] = pf, ap, emb
+        return heads, emb
+
+    def forward_pose(self, img4, points4, choose, obj, want_new_points=True):
+        """The estimator when only the pose is wanted (tools/utils.py:7-18 reads r and t at the arg-max of the confidence alone): inputs as
+        forward_batch -> pose[B,7] f64, which[B] i32, new_points4[B,N,4] | None, emb[B,N,32], bit for bit what
+        E.pose_select(forward_batch(..)[0], points4) gives.  The confidence head (a third of the heads' matrix work) runs on all B*N rows, the
+        r / t heads on the B selected rows.  No host synchronisation: capturable into a graph."""
+        pl, pf, ap, emb, gb = self._trunk(img4, points4, choose, obj, None)
+        b, n = points4.shape[:2]
+        dev = img4.device
+        gbf = gb.view(-1)                                                       # (a layer's columns of gb: a 1-D tail of it, row stride 1920)
+        # c chain on every row, on the route forward_batch takes: an output element of these layers depends on its own input row, its own
+        # weight row and the K order only, so the slices give the values of the merged layer
+        h3c = torch.empty(b, n, 1, 128, dtype=torch.float32, device=dev)
+        if pl.feat.pf_s32 is not None:
+            h1c = pl.l1_c(pl.feat.pf_s32, bias=gbf[1280:], bias_bstride=1920, out_fmt=E.FMT_S32)
+            pl.l3[2](pl.l2[2](h1c, out_fmt=E.FMT_S32), out=h3c)
+        else:
+            h1c = pl.l1_c(pf, bias=gbf[1280:], bias_bstride=1920)               # [B,N,1,640]
+            pl.l3[2](pl.l2[2](h1c), out=h3c)
+        which, _, pf_row = E.head_conf_argmax(h3c.view(b * n, 128), 0, pl.l4[4], pl.l4[5], obj, b, n, 128, pf=pf.view(b * n, 384))
+        # r | t chain on the B selected rows (one "pixel" per crop, so crop b still takes row b of gb)
+        h1rt = pl.l1_rt(pf_row.view(b, 1, 1, 384), bias=gbf, bias_bstride=1920)  # [B,1,1,1280]
+        h3rt = torch.empty(b, 1, 1, 256, dtype=torch.float32, device=dev)
+        for i in range(2):
+            pl.l3[i](pl.l2[i](h1rt, xoff=640 * i), out=h3rt, yoff=128 * i)
+        pose, newp = E.pose_from_row(h3rt.view(b, 256), 0, 128, *pl.l4[:4], obj, which, points4, 128, want_new_points)
+        return pose, which, newp, emb
+
+    def _trunk(self, img4, points4, choose, obj, taps):
+        """everything before the heads: -> plan, pf[B,N,1,384], ap[B,1024], emb[B,N,32], gb[B,1920] (the per-crop bias of the heads' first layer)"""
         pl = self.plan()
         for t, name in ((img4, "img"), (points4, "points"), (choose, "choose"), (obj, "obj")):      # (img4: the normalised crops or engine.U8Frames)
             _need_cuda(t, name)
@@ -481,23 +532,7 @@ class PoseNet(_HipModule):
         emb = E.log_softmax_rows(pl.cnn.final(g.view(b, n, 1, 64)).view(b, n, 32))
         pf, ap = pl.feat(points4, emb)
         gb = pl.l1_global(ap.view(b, 1, 1, 1024)).view(b, 1920)            # W[:, 384:] . ap_x + b
-        h3 = torch.empty(b, n, 1, 384, dtype=torch.float32, device=img4.device)
-        if pl.feat.pf_s32 is not None:                                          # pre-split route (see _FeatPlan): h1, h2 stay split
-            h1 = pl.l1_point(pl.feat.pf_s32, bias=gb, bias_bstride=1920, out_fmt=E.FMT_S32)
-            h2 = E.S32(torch.empty(b, n, 1, 768, dtype=torch.float32, device=img4.device))
-            for i in range(3):
-                pl.l2[i](h1, out=h2, xoff=640 * i, yoff=256 * i, out_fmt=E.FMT_S32)
-                pl.l3[i](h2, out=h3, xoff=256 * i, yoff=128 * i)
-        else:
-            h1 = pl.l1_point(pf, bias=gb, bias_bstride=1920)                    # [B,N,1,1920]
-            h2 = torch.empty(b, n, 1, 768, dtype=torch.float32, device=img4.device)
-            for i in range(3):
-                pl.l2[i](h1, out=h2, xoff=640 * i, yoff=256 * i)
-                pl.l3[i](h2, out=h3, xoff=256 * i, yoff=128 * i)
-        heads = E.head_select(h3.view(b * n, 384), 0, 128, 256, *pl.l4, obj, b, n, 128)
-        if taps is not None:
-            taps["pf"], taps["ap"], taps["emb"] = pf, ap, emb
-        return heads, emb
+        return pl, pf, ap, emb, gb
 
     def forward(self, img, x, choose, obj):
         """Reference signature (network.py:95): img[1,3,Hc,Wc], x[1,N,3], choose[1,1,N] i64, obj[1,1] i64 ->

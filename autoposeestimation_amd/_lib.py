@@ -67,6 +67,8 @@ SIGNATURES = {
     "ape_pad3to4_f32": [_P, _P, _c.c_long, _P],
     "ape_head_select_f32": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "ape_pose_select_f32": [_P, _P, _P, _P, _P, _I, _I, _P],
+    "ape_head_conf_argmax_f32": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P],
+    "ape_pose_from_row_f32": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "ape_pose_compose_f64": [_P, _P, _I, _P, _I, _I, _P],
     "ape_pose_recentre_f32": [_P, _P, _P, _I, _I, _P],
     "ape_adds_dis_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
@@ -256,7 +258,7 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
 _lib = None
 
 
-ABI_VERSION = 10     # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 11    # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

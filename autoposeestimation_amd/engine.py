@@ -867,6 +867,30 @@ def pose_select(heads, points4, want_new_points=True):
     return pose, which, newp
 
 
+def head_conf_argmax(h3c, off_c, wc, bc, obj, b, n, k, pf=None):
+    """h3c[B*n, ldh] (the confidence head's input at off_c), pf[B*n, ld] | None -> which[B] i32 (first maximum of sigmoid(c) over the crop's
+    rows), conf[B], pf_row[B, ld] | None (pf at the selected rows)"""
+    which = torch.empty(b, dtype=torch.int32, device=h3c.device)
+    conf = torch.empty(b, dtype=torch.float32, device=h3c.device)
+    row = None if pf is None else torch.empty(b, pf.shape[-1], dtype=torch.float32, device=h3c.device)
+    _lib.call.ape_head_conf_argmax_f32(_lib.dptr(h3c, torch.float32), h3c.shape[-1], off_c, _lib.dptr(wc), _lib.dptr(bc),
+                                       _lib.dptr(obj, torch.int64), _lib.dptr(which), _lib.dptr(conf), _lib.dptr(pf, torch.float32),
+                                       0 if pf is None else pf.shape[-1], _lib.dptr(row), b, n, k, _st())
+    return which, conf, row
+
+
+def pose_from_row(h3rt, off_r, off_t, wr, br, wt, bt, obj, which, points4, k, want_new_points=True):
+    """h3rt[B, ldh] (the r / t heads' inputs of each crop's selected row), which[B] i32, points4[B,n,4]
+    -> pose[B,7] f64, new_points4[B,n,4] | None: what pose_select gives from the full heads"""
+    b, n, _ = points4.shape
+    pose = torch.empty(b, 7, dtype=torch.float64, device=h3rt.device)
+    newp = torch.empty(b, n, 4, dtype=torch.float32, device=h3rt.device) if want_new_points else None
+    _lib.call.ape_pose_from_row_f32(_lib.dptr(h3rt, torch.float32), h3rt.shape[-1], off_r, off_t, _lib.dptr(wr), _lib.dptr(br),
+                                    _lib.dptr(wt), _lib.dptr(bt), _lib.dptr(obj, torch.int64), _lib.dptr(which, torch.int32),
+                                    _lib.dptr(points4, torch.float32), _lib.dptr(pose), _lib.dptr(newp), b, n, k, _st())
+    return pose, newp
+
+
 def pose_compose(pose, ref_r, ref_t):
     """in-place: pose[B,7] f64 <- pose o (ref_r[B,>=4], ref_t[B,>=3]) ; ref_* are (possibly strided) row views"""
     b = pose.shape[0]

@@ -173,14 +173,13 @@ class FramePipeline:
         pts4 = E.backproject(depth, objs, choose, meta["intr"], meta["depth_scale"])
         img4 = E.U8Frames(rgb, rects, hc, wc, div255=False)
         obj_idx = (objs[:, 1].to(torch.int64) - 1).contiguous()         # class_names.index(cls) (pipeline/utils.py:561)
-        heads, emb = self.estimator.forward_batch(img4, pts4, choose, obj_idx)
+        # (forward_pose: r and t are read at the most confident point alone, so their heads run on that row only)
+        pose, _, newp, emb = self.estimator.forward_pose(img4, pts4, choose, obj_idx, want_new_points=self.refine_mode == "live_compat")
         if self.refine_mode == "live_compat":
-            pose, _, newp = E.pose_select(heads, pts4)
             for _ in range(self.iterations):
                 out = self.refiner.forward_batch(newp, emb, obj_idx)
             E.pose_compose(pose, out[:, 0:4], out[:, 4:7])
         else:
-            pose, _, _ = E.pose_select(heads, pts4, want_new_points=False)
             for _ in range(self.iterations):
                 out = self.refiner.forward_batch(E.pose_recentre(pts4, pose), emb, obj_idx)
                 E.pose_compose(pose, out[:, 0:4], out[:, 4:7])

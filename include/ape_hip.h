@@ -263,7 +263,21 @@ int ape_head_select_f32(const float* h, int ldh, int off_r, int off_t, int off_c
  * which[B] (arg-max confidence, may be NULL), new_points4[B][n][4] (may be NULL). */
 int ape_pose_select_f32(const float* heads, const float* points4, double* pose, int* which, float* new_points4,
                         int B, int n, void* stream);
-/* my_refined_prediction                      DenseFusion/tools/utils.py:20-40 (+ transformations.py:1254-1278,1320-1363).
+/* The two above for a caller that wants the pose only (my_estimator_prediction reads r and t at ONE row per crop): the confidence head on
+ * every row, the r / t heads on the selected row.  Same arithmetic and the same first-maximum rule as ape_head_select_f32 followed by
+ * ape_pose_select_f32, bit for bit.
+ * ape_head_conf_argmax_f32: h3c[B*n][ldh] holds the K-wide input of the confidence head at channel offset off_c (16-byte aligned base,
+ * ldh, off_c and K multiples of 4, K <= 1024) -> which[B] (arg-max of sigmoid(c) over the crop's n rows), conf[B] (that value), and, when
+ * pf != NULL, pf_row_out[B][ld_pf] = pf[b*n + which[b]][0..ld_pf).
+ * ape_pose_from_row_f32: h3rt_row[B][ldh] holds the K-wide inputs of the r and t heads of each crop's selected row at off_r / off_t;
+ * which[B] as written above -> pose[B][7] f64 and new_points4[B][n][4] (may be NULL) as ape_pose_select_f32 writes them. */
+int ape_head_conf_argmax_f32(const float* h3c, int ldh, int off_c, const float* wc, const float* bc, const int64_t* obj,
+                             int* which_out, float* conf_out, const float* pf, int ld_pf, float* pf_row_out, int B, int n, int K,
+                             void* stream);
+int ape_pose_from_row_f32(const float* h3rt_row, int ldh, int off_r, int off_t, const float* wr, const float* br, const float* wt,
+                          const float* bt, const int64_t* obj, const int* which, const float* points4, double* pose,
+                          float* new_points4, int B, int n, int K, void* stream);
+/* my_refined_prediction                     DenseFusion/tools/utils.py:20-40 (+ transformations.py:1254-1278,1320-1363).
  * pose[B][7] f64 is updated in place with the refiner residual ref_r[B][ldr>=4], ref_t[B][ldt>=3] (f32). */
 int ape_pose_compose_f64(double* pose, const float* ref_r, int ldr, const float* ref_t, int ldt, int B, void* stream);
 /* cloud re-centring of the iterative loop    DenseFusion/tools/eval_ycb.py:205-210. */
