@@ -1,0 +1,341 @@
+"""Device builder of the YCB-Video samples (csrc/ycb.hip) and the host arithmetic between its launches.
+
+The reference builds a sample in Pillow and numpy on the host (dataset.py:97-232).  Here the host only DRAWS and does get_bbox's integer
+arithmetic; a batch over frames that already live on the device is
+`overlap` (`ape_ycb_overlap`: per (frame, front candidate) the joint histogram of label class, front class and depth != 0; a read-back of
+3.9 KB per pair) -> the front decisions, the object draws -> `rows` (`ape_ycb_rows`: the valid pixels and the member extent of every row,
+the L sums of the contrast ops; a read-back of 5.6 KB per sample) -> get_bbox, the draws that wait for the crop -> one upload of the row
+prefixes, the ranks to keep and the float64 noise of the synthetic samples -> `samples` (`ape_ycb_samples`).
+Every index a kernel uses that comes from a read-back is range-checked here before the launch."""
+import ctypes
+
+import numpy as np
+import torch
+
+from autoposeestimation_amd import _lib
+from autoposeestimation_amd import sample_jobs as J
+from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented.augment import row_prefix, selection, upload_targets
+from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented.dataset import _MEAN, _STD
+from autoposeestimation_amd.DenseFusion.datasets.ycb.dataset import NUM_CLASSES, bbox_from_extents
+
+_c = ctypes
+BINS = (NUM_CLASSES + 1, NUM_CLASSES + 1, 2)
+NOISE_GUESS = 24 * 160 * 160          # workspace bytes set aside per synthetic sample before its crop is known
+
+
+class YcbJitter(_c.Structure):
+    """Mirror of `ape_ycb_jitter` (include/ape_hip.h)"""
+    _fields_ = [("code", _c.c_uint8 * 4), ("shift", _c.c_uint8 * 4), ("factor", _c.c_float * 4)]
+
+
+class YcbJob(_c.Structure):
+    """Mirror of `ape_ycb_job` (include/ape_hip.h); tests/test_ycb_host.py compares the layout with the C compiler's."""
+    _fields_ = [("rgb", _c.c_void_p), ("depth", _c.c_void_p), ("label", _c.c_void_p), ("back_rgb", _c.c_void_p), ("front_rgb", _c.c_void_p),
+                ("front_label", _c.c_void_p), ("add_t", _c.c_double * 3), ("out_off", _c.c_longlong), ("noise_off", _c.c_longlong),
+                ("jit", YcbJitter * 3), ("rmin", _c.c_int32), ("rmax", _c.c_int32), ("cmin", _c.c_int32), ("cmax", _c.c_int32),
+                ("win_r0", _c.c_int32), ("win_r1", _c.c_int32), ("win_c0", _c.c_int32), ("win_c1", _c.c_int32), ("obj", _c.c_int32),
+                ("front_a", _c.c_int32), ("front_b", _c.c_int32), ("add_noise", _c.c_int32), ("skip", _c.c_int32), ("reserved", _c.c_int32),
+                ("cam_cx", _c.c_float), ("cam_cy", _c.c_float), ("cam_fx", _c.c_float), ("cam_fy", _c.c_float), ("cam_scale", _c.c_float),
+                ("reserved_f", _c.c_float)]
+
+
+class YcbPair(_c.Structure):
+    """Mirror of `ape_ycb_pair` (include/ape_hip.h)"""
+    _fields_ = [("label", _c.c_void_p), ("front_label", _c.c_void_p), ("depth", _c.c_void_p)]
+
+
+def fill_jitter(dst, ops, what=""):
+    """the ordered `(name, factor)` list of `ColorJitterPIL.params()` into a `YcbJitter`, through the checks of `sample_jobs.fill_jitter`"""
+    tmp = _lib.AugJitter()
+    J.fill_jitter(tmp, ops, what)
+    for k in range(4):
+        live = k < tmp.n_ops
+        dst.code[k] = tmp.code[k] if live else 0
+        dst.shift[k] = tmp.shift[k] if live else 0
+        dst.factor[k] = tmp.factor[k] if live else 0.0
+
+
+def overlap(pairs, h, w):
+    """pairs: (label[H,W] u8, front label[H,W] u8 or None, depth[H,W] u16) device tensors -> u32 [P,22,22,2] on the HOST (the read-back):
+    table[p, a, f, d] = the pixels of pair p with label a, front label f (0 without a front) and d = (depth != 0)"""
+    if not pairs:
+        return np.zeros((0,) + BINS, np.uint32)
+    dev = pairs[0][0].device
+    arr = (YcbPair * len(pairs))()
+    for i, (label, front, depth) in enumerate(pairs):
+        arr[i].label = J.frame(label, torch.uint8, (h, w), "label")
+        arr[i].front_label = None if front is None else J.frame(front, torch.uint8, (h, w), "front label")
+        arr[i].depth = J.frame(depth, torch.uint16, (h, w), "depth")
+    table = torch.empty((len(pairs),) + BINS, dtype=torch.int32, device=dev)
+    _lib.call.ape_ycb_overlap(_c.cast(arr, _c.c_void_p), len(pairs), h, w, _lib.dptr(table), _lib.stream_ptr())
+    return table.cpu().numpy().view(np.uint32)
+
+
+def _addr(t, dtype, shape, what):
+    """the address of a resident frame after `sample_jobs.frame`'s checks; an int is an address already (tools/check_ycb_px.py: host arrays)"""
+    return t if isinstance(t, int) else J.frame(t, dtype, shape, what)
+
+
+def make_job(frame, h, w, obj, cam, cam_scale, ops=None, front=None, back=None, add_t=None, window=None):
+    """frame: (rgb, depth, label) device tensors; obj: the class the sample is about; cam: (cx, cy, fx, fy); front: None or (rgb, label,
+    [class, class], ops) of the occluding frame; back: None or (rgb, ops); add_t: None or 3 floats; window: (r0, r1, c0, c1) that
+    `rows` counts in, the whole frame when None -> YcbJob (crop, noise_off and out_off are set later)"""
+    job = YcbJob()
+    job.rgb = _addr(frame[0], torch.uint8, (h, w, 3), "frame")
+    job.depth = _addr(frame[1], torch.uint16, (h, w), "depth")
+    job.label = _addr(frame[2], torch.uint8, (h, w), "label")
+    fill_jitter(job.jit[0], ops)
+    if back is not None:
+        job.back_rgb = _addr(back[0], torch.uint8, (h, w, 3), "background")
+        fill_jitter(job.jit[1], back[1], " of the background")
+    if front is not None:
+        job.front_rgb = _addr(front[0], torch.uint8, (h, w, 3), "front")
+        job.front_label = _addr(front[1], torch.uint8, (h, w), "front label")
+        job.front_a, job.front_b = [int(v) for v in front[2]]
+        fill_jitter(job.jit[2], front[3], " of the front")
+    if not 1 <= int(obj) <= NUM_CLASSES:
+        raise ValueError("class %r outside 1..%d" % (obj, NUM_CLASSES))
+    job.obj = int(obj)
+    job.cam_cx, job.cam_cy, job.cam_fx, job.cam_fy = [float(v) for v in cam]          # numpy computes the cloud in float32
+    job.cam_scale = float(cam_scale)
+    job.noise_off = -1
+    if add_t is not None:
+        job.add_noise = 1
+        for k in range(3):
+            job.add_t[k] = float(add_t[k])
+    job.win_r0, job.win_r1, job.win_c0, job.win_c1 = (0, h, 0, w) if window is None else [int(v) for v in window]
+    return job
+
+
+def rows(jobs, h, w, num, dev, n_noisy=0):
+    """launches `ape_ycb_rows` -> (workspace, i32 [B,H,3] on the HOST: per row the valid pixels inside the job's window, the first and the
+    last member column).  The workspace carries the L sums to `samples`."""
+    b = len(jobs)
+    L = _lib.lib()
+    ws = J.workspace("ycb", dev, L.ape_ycb_noise_offset(b, h, int(num)) + n_noisy * NOISE_GUESS)
+    _lib.call.ape_ycb_rows(_c.cast(jobs, _c.c_void_p), b, h, w, _lib.dptr(ws), ws.numel(), _lib.stream_ptr())
+    r0 = L.ape_ycb_rows_offset(b)
+    return ws, ws[r0:r0 + b * h * 12].cpu().numpy().view(np.int32).reshape(b, h, 3)
+
+
+def member_extents(row, h, w):
+    """one sample's [H,3] read-back -> (first row, last row, first column, last column) of the members, or None without one; values that
+    no frame of this size can give are refused"""
+    has = row[:, 2] >= 0
+    if not has.any():
+        return None
+    ys = np.flatnonzero(has)
+    c0, c1 = int(row[has, 1].min()), int(row[has, 2].max())
+    if not (0 <= c0 <= c1 < w) or (row[:, 0] < 0).any() or (row[:, 0] > w).any():
+        raise _lib.ApeError("ape_ycb_rows returned extents outside the frame")
+    return int(ys[0]), int(ys[-1]), c0, c1
+
+
+def samples(jobs, ws, counts_rows, sels, noises, h, w, num, mean=_MEAN, std=_STD):
+    """jobs with their crops set; counts_rows: i32 [B,H] the valid pixels of every crop row (0 outside the crop); sels: per sample the
+    i32[num] ranks to keep (`selection`), or None for a sample that is not built; noises: per sample None or f64 [3,Hc,Wc] -> per sample
+    (cloud[1,N,3] f32, choose[1,1,N] i64, img[1,3,Hc,Wc] f32) views into ONE packed block, or None"""
+    b, n = len(jobs), int(num)
+    L = _lib.lib()
+    t0, n0 = L.ape_ycb_tables_offset(b, h), L.ape_ycb_noise_offset(b, h, n)
+    offsets, total, noise_at, noise_end = [], 0, [], n0
+    counts = counts_rows.sum(axis=1)
+    for i, sel in enumerate(sels):
+        jobs[i].skip, jobs[i].out_off, jobs[i].noise_off = int(sel is None), 0, -1
+        offsets.append(None)
+        noise_at.append(None)
+        if sel is None:
+            continue
+        hc, wc = jobs[i].rmax - jobs[i].rmin, jobs[i].cmax - jobs[i].cmin
+        if noises[i] is not None:
+            if noises[i].shape != (3, hc, wc) or noises[i].dtype != np.float64:
+                raise ValueError("sample %d: the noise must be float64 %s, got %s %s" % (i, (3, hc, wc), noises[i].dtype, noises[i].shape))
+            jobs[i].noise_off = noise_end
+            noise_at[i] = noise_end
+            noise_end += 24 * hc * wc
+        jobs[i].out_off = total
+        offsets[i] = total
+        total += L.ape_pose_train_sample_bytes(n, hc, wc)
+    if total == 0:
+        return [None] * b
+    buf = np.zeros(noise_end - t0, np.uint8)                     # the one upload: row prefixes, ranks, noise
+    tab = buf[:(b * h + b * n) * 4].view(np.int32)
+    tab[:b * h] = row_prefix(counts_rows).reshape(-1)
+    for i, sel in enumerate(sels):
+        if sel is None:
+            continue
+        sel = np.asarray(sel, np.int32).reshape(-1)
+        if sel.size != n or sel.min() < 0 or sel.max() >= counts[i]:
+            raise ValueError("sample %d: the selection must be %d ranks below its %d valid pixels" % (i, n, counts[i]))
+        tab[b * h + i * n:b * h + (i + 1) * n] = sel
+        if noise_at[i] is not None:
+            buf[noise_at[i] - t0:noise_at[i] - t0 + noises[i].nbytes] = np.ascontiguousarray(noises[i]).view(np.uint8).reshape(-1)
+    if ws.numel() < noise_end:                                   # larger crops than set aside: a larger workspace that keeps the L sums
+        old, ws = ws, J.workspace("ycb", ws.device, noise_end)
+        ws[:t0].copy_(old[:t0])
+    ws[t0:noise_end].copy_(torch.from_numpy(buf))
+    block = torch.empty(total, dtype=torch.uint8, device=ws.device)
+    m, sd = J.norm(mean, std, 3)
+    _lib.call.ape_ycb_samples(_c.cast(jobs, _c.c_void_p), b, h, w, n, m, sd, _lib.dptr(block), block.numel(), _lib.dptr(ws), ws.numel(),
+                              _lib.stream_ptr())
+    img_off = L.ape_pose_train_image_offset(n)
+    views = []
+    for i, o in enumerate(offsets):
+        if o is None:
+            views.append(None)
+            continue
+        hc, wc = jobs[i].rmax - jobs[i].rmin, jobs[i].cmax - jobs[i].cmin
+        choose = block[o:o + 8 * n].view(torch.int64).view(1, 1, n)
+        points = block[o + 8 * n:o + 20 * n].view(torch.float32).view(1, n, 3)
+        img = block[o + img_off:o + img_off + 12 * hc * wc].view(torch.float32).view(1, 3, hc, wc)
+        views.append((points, choose, img))
+    return views
+
+
+def left_labelled(tab, two):
+    """`len((label * mask_front).nonzero()[0])` (:133-134) from one pair's table: the labelled pixels the two front classes do not cover"""
+    keep = np.ones(BINS[1], bool)
+    keep[list(two)] = False
+    return int(tab[1:, keep, :].sum())
+
+
+def valid_of(tab, cls, two=None):
+    """the valid pixels class `cls` keeps, from one pair's table; two: the front classes that occlude, or None"""
+    keep = np.ones(BINS[1], bool)
+    if two is not None:
+        keep[list(two)] = False
+    return int(tab[int(cls), keep, 1].sum())
+
+
+def build(ds, indices, params):
+    """`PoseDataset.batch` for one run of samples -> (samples, parameter dicts); the draws are made where `sample_host` makes them"""
+    h, w, n, dev = 480, 640, int(ds.num_pt), ds.device
+    given = params is not None
+    b = len(indices)
+    lines = [ds.list[i] for i in indices]
+    frames = [ds._resident(x) for x in lines]
+    metas = [ds._meta(x) for x in lines]
+    ps = [dict(params[k]) if given else {} for k in range(b)]
+    draws = [None if given else ds._draws(i) for i in indices]
+    # ---- the front candidates of every sample, drawn ahead; one table per (frame, candidate frame) -----------------------------------------
+    cands, pairs, pair_at = [], [], []
+    for k in range(b):
+        p, d, cs = ps[k], draws[k], []
+        if ds.add_noise:
+            if "front" in p:
+                if p["front"] is not None:
+                    cs.append((p["front"], None))
+            elif d is None:
+                raise ValueError("batch: parameter 'front' of sample %d is missing" % k)
+            else:
+                for _ in range(5):
+                    seed = d.choice(ds.syn)
+                    ops = ds._jitter_ops(d)
+                    front_label = ds._resident(seed)[3][1:]      # drops the smallest value present, whatever it is
+                    if len(front_label) < ds.front_num:
+                        cs.append((None, d.state()))             # skipped, after drawing its seed and its jitter
+                        continue
+                    cs.append(((seed, ops, [int(c) for c in d.pick(front_label, ds.front_num)]), d.state()))
+        at = {}
+        for seed in [c[0][0] for c in cs if c[0] is not None] or [None]:
+            if seed not in at:
+                at[seed] = len(pairs)
+                pairs.append((frames[k][2], None if seed is None else ds._resident(seed)[2], frames[k][1]))
+        cands.append(cs)
+        pair_at.append(at)
+    table = overlap(pairs, h, w)                                 # read-back 1
+    # ---- the decisions the table allows; the draws up to the crop ---------------------------------------------------------------------------
+    jobs = (YcbJob * b)()
+    objs = []
+    for k in range(b):
+        p, d, line, frame, meta = ps[k], draws[k], lines[k], frames[k], metas[k]
+        front = None
+        for cand, state in cands[k]:
+            if cand is not None and (given or left_labelled(table[pair_at[k][cand[0]]], cand[2]) > 1000):
+                front = cand
+                if state is not None:
+                    d.restore(state)                             # the generator as the accepted candidate left it
+                break
+        if ds.add_noise:
+            p["front"] = front
+        # (without a front any table of the frame serves: the counts below then sum over every front class)
+        tab = table[pair_at[k][front[0]] if front is not None else next(iter(pair_at[k].values()))]
+        two = None if front is None else front[2]
+        cls = meta["cls_indexes"].flatten().astype(np.int32)
+        counts = [valid_of(tab, o, two) if 1 <= o <= NUM_CLASSES else 0 for o in cls]
+        if "obj" not in p:
+            if d is None:
+                raise ValueError("batch: parameter 'obj' of sample %d is missing" % k)
+            p["obj"] = ds._draw_obj(d, line, counts)
+        idx = int(p["obj"])
+        if not 0 <= idx < len(cls) or counts[idx] < 1:
+            raise ValueError("sample %s: object %d of its %d has no valid pixel" % (line, idx, len(cls)))
+        if ds.add_noise and "ops" not in p:
+            if d is None:
+                raise ValueError("batch: parameter 'ops' of sample %d is missing" % k)
+            p["ops"] = ds._jitter_ops(d)
+        back = None
+        if ds.is_syn(line):
+            if "back" not in p:
+                if d is None:
+                    raise ValueError("batch: parameter 'back' of sample %d is missing" % k)
+                seed = d.choice(ds.real)
+                p["back"] = (seed, ds._jitter_ops(d))
+            back = (ds._resident(p["back"][0])[0], p["back"][1])
+        fr = None if front is None else ds._resident(front[0])
+        jobs[k] = make_job(frame, h, w, cls[idx], ds._cam(line), meta["factor_depth"][0][0], p.get("ops") if ds.add_noise else None,
+                           None if fr is None else (fr[0], fr[2], front[2], front[1]), back)
+        objs.append((idx, int(cls[idx]), counts[idx]))
+    ws, back_rows = rows(jobs, h, w, n, dev, sum(ds.is_syn(x) for x in lines))       # read-back 2
+    # ---- get_bbox and the draws that wait for the crop --------------------------------------------------------------------------------------
+    sels, noises, host = [], [], []
+    for k in range(b):
+        p, d, line, (idx, cls, want) = ps[k], draws[k], lines[k], objs[k]
+        ext = member_extents(back_rows[k], h, w)
+        count = int(back_rows[k, :, 0].sum())
+        if ext is None or count != want:
+            raise _lib.ApeError("sample %s: ape_ycb_rows counts %d valid pixels of class %d where ape_ycb_overlap counted %d"
+                                % (line, count, cls, want))
+        # The crop always contains the label mask: get_bbox raises each side to the next entry of border_list (an even number, not below
+        # the extent), keeps the centre int((first + last + 1) / 2) -- so first >= centre - side / 2 and last < centre + side / 2 -- and
+        # then only shifts the box.  So the whole-row counts ARE the in-crop counts, and rows outside the crop count nothing.
+        rmin, rmax, cmin, cmax = bbox_from_extents(*ext)
+        if not (0 <= rmin <= ext[0] and ext[1] < rmax <= h and 0 <= cmin <= ext[2] and ext[3] < cmax <= w):
+            raise _lib.ApeError("sample %s: the crop %d:%d, %d:%d does not hold the mask" % (line, rmin, rmax, cmin, cmax))
+        jobs[k].rmin, jobs[k].rmax, jobs[k].cmin, jobs[k].cmax = rmin, rmax, cmin, cmax
+        noise = None
+        if ds.is_syn(line):
+            if "noise" not in p:
+                if d is None:
+                    raise ValueError("batch: parameter 'noise' of sample %d is missing" % k)
+                p["noise"] = d.normal((3, rmax - rmin, cmax - cmin))
+            noise = np.asarray(p["noise"], dtype=np.float64)
+        noises.append(noise)
+        if "add_t" not in p:
+            if d is None:
+                if ds.add_noise:
+                    raise ValueError("batch: parameter 'add_t' of sample %d is missing" % k)
+            else:
+                p["add_t"] = [d.uniform(-ds.noise_trans, ds.noise_trans) for _ in range(3)]
+        if ds.add_noise:
+            jobs[k].add_noise = 1
+            for a in range(3):
+                jobs[k].add_t[a] = float(p["add_t"][a])
+        if count > n and "subset" not in p:
+            if d is None:
+                raise ValueError("batch: sample %d has %d valid pixels, more than num_pt = %d, and its parameters give no 'subset'" % (k, count, n))
+            c_mask = np.zeros(count, dtype=int)
+            c_mask[:n] = 1
+            d.shuffle_array(c_mask)
+            p["subset"] = c_mask.nonzero()[0]
+        if "dellist" not in p:
+            if d is None:
+                raise ValueError("batch: parameter 'dellist' of sample %d is missing" % k)
+            p["dellist"] = ds._draw_dellist(d, cls)
+        sels.append(selection(count, n, p.get("subset")))
+        add_t = np.array(p["add_t"], dtype=np.float64) if ds.add_noise else None
+        target, model_points = ds._targets(metas[k], idx, cls, add_t, p["dellist"])
+        host.append((target, model_points, cls - 1))
+    views = samples(jobs, ws, np.ascontiguousarray(back_rows[:, :, 0]), sels, noises, h, w, n)
+    up = upload_targets(host, dev)                               # target, model points and idx: numpy's float64 on the host, one upload
+    return [views[k] + up[k] for k in range(b)], ps

@@ -1,0 +1,391 @@
+"""Drop-in for DenseFusion/datasets/ycb/dataset.py: `PoseDataset` (`__init__` :19-95, `__getitem__` :97-232), `get_bbox` (:251-289) and
+`border_list` over a YCB_Video_Dataset tree (`data/%04d/%06d-{color,depth,label}.png` with `-meta.mat`, `data_syn/...`,
+`models/<class>/points.xyz`) and the three lists of `dataset_config_dir` (`train_data_list.txt`, `test_data_list.txt`, `classes.txt`; the
+package ships no copy of them).
+
+The sample tuple is the reference's: (cloud[N,3] f32, choose[1,N] i64, img[3,Hc,Wc] f32, target[M,3] f32, model_points[M,3] f32,
+idx[1] i64).  Two paths to a sample, as in the sibling linemod/dataset.py: `ds[i]` / `ds.sample_host(i, params)` is the reference's, through
+Pillow and numpy on the host; `ds.batch(indices)` keeps the decoded frames on the GPU and builds the same samples there (augment.py,
+csrc/ycb.hip), shaped as `DataLoader(batch_size=1)` delivers them.
+
+Random draws.  The reference draws from the GLOBAL `random` / `numpy.random` states, per sample in this order: with add_noise, per front
+candidate (at most five) `random.choice(syn)`, the jitter, then `random.sample(front_label, 2)` unless the candidate has fewer than two
+classes; `np.random.randint(0, len(obj))` until an object has more than 50 valid pixels; the jitter of the frame (add_noise); for a
+`data_syn` frame `random.choice(real)` and the jitter of that background (ALWAYS, also without add_noise), then `np.random.normal` for the
+pixel noise; three `random.uniform` (always); `np.random.shuffle(c_mask)` (only above num_pt); `random.sample(dellist, ...)`.  With
+`reference_rng=True` this class makes exactly those calls in exactly that order.  By default every sample draws from its own
+`numpy.random.Generator` seeded by `(seed, index)`.
+
+Where the reference loops forever -- no object of the frame keeps more than 50 valid pixels -- this class raises `ValueError` naming the
+frame.  `-meta.mat` is read with `scipy.io.loadmat`, imported on first use."""
+import os
+import random
+
+import numpy as np
+import torch
+from PIL import Image
+
+# `get_bbox` (:251-289: sides up to the next entry of border_list, the centre kept, the box pushed back inside 480 x 640 -- LineMOD's clamps to
+# 479 / 639 are not in it), `border_list`, `img_width` and `img_length` are those of the sibling data set: the two files of the reference
+# hold the same text.  tests/test_ycb_host.py pins them to values recorded from THIS reference file.
+from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented.dataset import (ColorJitterPIL, _GlobalDraws, _SeededDraws, _MEAN, _STD,  # noqa: F401
+                                                                                    bbox_from_extents, border_list, get_bbox, img_length, img_width)
+
+NUM_CLASSES = 21
+
+
+class _Global(_GlobalDraws):
+    """the reference's generators, with the draws only this data set makes"""
+    choice = staticmethod(random.choice)
+    pick = staticmethod(random.sample)
+    state = staticmethod(random.getstate)              # the front candidates draw from `random` alone
+    restore = staticmethod(random.setstate)
+
+    @staticmethod
+    def randint(n):
+        return int(np.random.randint(0, n))
+
+    @staticmethod
+    def normal(shape):
+        return np.random.normal(loc=0.0, scale=7.0, size=shape)
+
+
+class _Seeded(_SeededDraws):
+    def choice(self, seq):
+        return seq[int(self.g.integers(len(seq)))]
+
+    def pick(self, seq, k):
+        return [seq[int(i)] for i in self.g.choice(len(seq), size=k, replace=False)]
+
+    def randint(self, n):
+        return int(self.g.integers(n))
+
+    def normal(self, shape):
+        return self.g.normal(0.0, 7.0, shape)
+
+    def state(self):
+        return self.g.bit_generator.state
+
+    def restore(self, s):
+        self.g.bit_generator.state = s
+
+
+class PoseDataset(torch.utils.data.Dataset):
+    def __init__(self, mode, num_pt, add_noise, root, noise_trans, refine, dataset_config_dir="datasets/ycb/dataset_config",
+                 reference_rng=False, trancolor=None, seed=0, device="cuda:0"):
+        if mode not in ("train", "test"):
+            raise ValueError("mode must be 'train' or 'test'")
+        self.mode = mode
+        self.path = os.path.join(dataset_config_dir, "train_data_list.txt" if mode == "train" else "test_data_list.txt")
+        self.num_pt = num_pt
+        self.root = root
+        self.add_noise = add_noise
+        self.noise_trans = noise_trans
+        self.list, self.real, self.syn = [], [], []
+        with open(self.path) as input_file:
+            while 1:
+                input_line = input_file.readline()
+                if not input_line:
+                    break
+                if input_line[-1:] == "\n":
+                    input_line = input_line[:-1]
+                if input_line[:5] == "data/":
+                    self.real.append(input_line)
+                else:
+                    self.syn.append(input_line)
+                self.list.append(input_line)
+        self.length = len(self.list)
+        self.len_real = len(self.real)
+        self.len_syn = len(self.syn)
+        self.cld = {}
+        class_id = 1
+        with open(os.path.join(dataset_config_dir, "classes.txt")) as class_file:
+            while 1:
+                class_input = class_file.readline()
+                if not class_input:
+                    break
+                pts = []
+                with open("{0}/models/{1}/points.xyz".format(self.root, class_input[:-1])) as input_file:
+                    while 1:
+                        input_line = input_file.readline()
+                        if not input_line:
+                            break
+                        input_line = input_line[:-1].split(" ")
+                        pts.append([float(input_line[0]), float(input_line[1]), float(input_line[2])])
+                self.cld[class_id] = np.array(pts)
+                class_id += 1
+        self.cam_cx_1 = 312.9869
+        self.cam_cy_1 = 241.3109
+        self.cam_fx_1 = 1066.778
+        self.cam_fy_1 = 1067.487
+        self.cam_cx_2 = 323.7872
+        self.cam_cy_2 = 279.6921
+        self.cam_fx_2 = 1077.836
+        self.cam_fy_2 = 1078.189
+        self.trancolor = trancolor if trancolor is not None else ColorJitterPIL(0.2, 0.2, 0.2, 0.05)
+        self.noise_img_loc = 0.0
+        self.noise_img_scale = 7.0
+        self.minimum_num_pt = 50
+        self.symmetry_obj_idx = [12, 15, 18, 19, 20]
+        self.num_pt_mesh_small = 500
+        self.num_pt_mesh_large = 2600
+        self.refine = refine
+        self.front_num = 2
+        self.reference_rng, self.seed = reference_rng, seed
+        self.device = torch.device(device)
+        self._res, self._metas = {}, {}
+
+    def __len__(self):
+        return self.length
+
+    def get_sym_list(self):
+        return self.symmetry_obj_idx
+
+    def get_num_points_mesh(self):
+        if self.refine:
+            return self.num_pt_mesh_large
+        else:
+            return self.num_pt_mesh_small
+
+    # ---- what depends on no pixel ---------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def is_syn(line):
+        return line[:8] == "data_syn"
+
+    def _cam(self, line):
+        """:103-112: camera 2 took the videos from number 60 on"""
+        if not self.is_syn(line) and int(line[5:9]) >= 60:
+            return self.cam_cx_2, self.cam_cy_2, self.cam_fx_2, self.cam_fy_2
+        return self.cam_cx_1, self.cam_cy_1, self.cam_fx_1, self.cam_fy_1
+
+    def _meta(self, line):
+        m = self._metas.get(line)
+        if m is None:
+            import scipy.io as scio                              # the package's only use of scipy
+            m = scio.loadmat("{0}/{1}-meta.mat".format(self.root, line))
+            m = {"cls_indexes": m["cls_indexes"], "poses": m["poses"], "factor_depth": m["factor_depth"]}
+            self._metas[line] = m
+        return m
+
+    def _open(self, line, what):
+        return Image.open("{0}/{1}-{2}.png".format(self.root, line, what))
+
+    def _draws(self, index):
+        return _Global if self.reference_rng else _Seeded(self.seed, index)
+
+    def _jitter(self, img, ops, d):
+        """the colour jitter of one image -> (image, the ops used; None for a bare callable, which draws what it draws)"""
+        if ops is None:
+            if not hasattr(self.trancolor, "params"):
+                return self.trancolor(img), None
+            if d is None:
+                raise ValueError("sample_host: the ops of a jitter are missing")
+            ops = self.trancolor.params(d.uniform, d.shuffle_list)
+        return ColorJitterPIL.apply(img, ops), ops
+
+    def _jitter_ops(self, d):
+        return self.trancolor.params(d.uniform, d.shuffle_list)
+
+    def _draw_dellist(self, d, cls):
+        n, keep = len(self.cld[cls]), self.get_num_points_mesh()
+        if n < keep:                                             # the reference's random.sample(dellist, negative) raises the same
+            raise ValueError("model of class %d has %d points, fewer than the %d model points of a sample" % (cls, n, keep))
+        return d.sample(n, n - keep)
+
+    def _targets(self, meta, idx, cls, add_t, dellist):
+        """:173-174, :204-220: numpy's float64 throughout, cast once -> (target f32[M,3], model_points f32[M,3])"""
+        target_r = meta["poses"][:, :, idx][:, 0:3]
+        target_t = np.array([meta["poses"][:, :, idx][:, 3:4].flatten()])
+        model_points = np.delete(self.cld[cls], dellist, axis=0)
+        target = np.dot(model_points, target_r.T)
+        if self.add_noise:
+            target = np.add(target, target_t + add_t)
+        else:
+            target = np.add(target, target_t)
+        return target.astype(np.float32), model_points.astype(np.float32)
+
+    def _draw_obj(self, d, line, counts):
+        """:141-147: draw among the frame's objects until one has more than 50 valid pixels (`counts`, per object of cls_indexes)"""
+        if not any(c > self.minimum_num_pt for c in counts):
+            raise ValueError("frame %s: none of its %d objects keeps more than %d valid pixels (the reference draws forever here)"
+                             % (line, len(counts), self.minimum_num_pt))
+        while 1:
+            idx = d.randint(len(counts))
+            if counts[idx] > self.minimum_num_pt:
+                return idx
+
+    # ---- host path ------------------------------------------------------------------------------------------------------------------------
+    def __getitem__(self, index):
+        """draw, then `sample_host`: every parameter is drawn from the sample's generator at the place where the reference draws it"""
+        return self.sample_host(index, None, _draws=self._draws(index))
+
+    def sample_host(self, index, params, _draws=None):
+        """The sample through Pillow and numpy on the host, with injected parameters: a dict with
+        `front`   None, or (seed entry, ops, [class, class]): the accepted front candidate (read only with add_noise);
+        `obj`     the position in the frame's `cls_indexes` of the object the sample is about;
+        `ops`     the ordered `(name, factor)` list of the frame's jitter (read only with add_noise);
+        `back`    (seed entry, ops): the real background of a `data_syn` frame;
+        `noise`   f64 [3, Hc, Wc]: the pixel noise of a `data_syn` frame;
+        `add_t`   3 floats (enters the sample only with add_noise);
+        `subset`  the sorted ranks, among the valid pixels of the crop, that `choose` keeps (read only above num_pt);
+        `dellist` the model points dropped.
+        `ds.batch(..., return_params=True)` returns such dicts.  Raises ValueError, naming the frame, when no object of the frame has more
+        than 50 valid pixels: the reference loops forever there."""
+        p = dict(params or {})
+        d = _draws
+
+        def need(key, draw):
+            if key not in p:
+                if d is None:
+                    raise ValueError("sample_host: parameter %r is missing" % (key,))
+                p[key] = draw()
+            return p[key]
+
+        line = self.list[index]
+        img = self._open(line, "color")
+        depth = np.array(self._open(line, "depth"))
+        label = np.array(self._open(line, "label"))
+        meta = self._meta(line)
+        cam_cx, cam_cy, cam_fx, cam_fy = self._cam(line)
+        mask_back = label == 0                                   # before the front occlusion changes the label (:114)
+        add_front, mask_front, front = False, None, None
+        if self.add_noise:
+            if "front" in p:
+                if p["front"] is not None:
+                    seed, ops, classes = p["front"]
+                    front = np.transpose(np.array(self._jitter(self._open(seed, "color").convert("RGB"), ops, None)[0]), (2, 0, 1))
+                    f_label = np.array(self._open(seed, "label"))
+                    mask_front = (f_label != classes[0]) * (f_label != classes[1])
+                    label = label * mask_front
+                    add_front = True
+            else:
+                if d is None:
+                    raise ValueError("sample_host: parameter 'front' is missing")
+                p["front"] = None
+                for k in range(5):
+                    seed = d.choice(self.syn)
+                    f_img, ops = self._jitter(self._open(seed, "color").convert("RGB"), None, d)
+                    f_label = np.array(self._open(seed, "label"))
+                    front_label = np.unique(f_label).tolist()[1:]        # drops the smallest value present, whatever it is
+                    if len(front_label) < self.front_num:
+                        continue
+                    front_label = d.pick(front_label, self.front_num)
+                    mk = (f_label != front_label[0]) * (f_label != front_label[1])
+                    t_label = label * mk
+                    if len(t_label.nonzero()[0]) > 1000:
+                        front, mask_front, label, add_front = np.transpose(np.array(f_img), (2, 0, 1)), mk, t_label, True
+                        p["front"] = (seed, ops, [int(c) for c in front_label])
+                        break
+        obj = meta["cls_indexes"].flatten().astype(np.int32)
+        mask_depth = depth != 0
+        idx = need("obj", lambda: self._draw_obj(d, line, [int(((label == o) * mask_depth).sum()) for o in obj]))
+        mask_label = label == obj[idx]
+        mask = mask_label * mask_depth
+        if self.add_noise:
+            img, p["ops"] = self._jitter(img, p.get("ops"), d)
+        rmin, rmax, cmin, cmax = get_bbox(mask_label)            # over the label mask alone: the depth does not enter it
+        img = np.transpose(np.array(img)[:, :, :3], (2, 0, 1))[:, rmin:rmax, cmin:cmax]
+        if self.is_syn(line):
+            if "back" in p:
+                seed, ops = p["back"]
+            else:
+                if d is None:
+                    raise ValueError("sample_host: parameter 'back' is missing")
+                seed, ops = d.choice(self.real), None
+            b_img, ops = self._jitter(self._open(seed, "color").convert("RGB"), ops, d)       # jittered also without add_noise
+            p["back"] = (seed, ops)
+            back = np.transpose(np.array(b_img), (2, 0, 1))[:, rmin:rmax, cmin:cmax]
+            img_masked = back * mask_back[rmin:rmax, cmin:cmax] + img                        # uint8: wraps modulo 256
+        else:
+            img_masked = img
+        if self.add_noise and add_front:
+            img_masked = img_masked * mask_front[rmin:rmax, cmin:cmax] + front[:, rmin:rmax, cmin:cmax] * ~(mask_front[rmin:rmax, cmin:cmax])
+        if self.is_syn(line):
+            img_masked = img_masked + np.asarray(need("noise", lambda: d.normal(img_masked.shape)), dtype=np.float64)
+        add_t = None                                             # drawn always (:175), used only with add_noise
+        if self.add_noise or "add_t" in p or d is not None:
+            add_t = np.array(need("add_t", lambda: [d.uniform(-self.noise_trans, self.noise_trans) for _ in range(3)]), dtype=np.float64)
+        choose = mask[rmin:rmax, cmin:cmax].flatten().nonzero()[0]
+        if len(choose) > self.num_pt:
+            def draw():
+                c_mask = np.zeros(len(choose), dtype=int)
+                c_mask[:self.num_pt] = 1
+                d.shuffle_array(c_mask)
+                return c_mask.nonzero()[0]
+            choose = choose[np.asarray(need("subset", draw))]
+        else:
+            choose = np.pad(choose, (0, self.num_pt - len(choose)), "wrap")
+        wc = cmax - cmin
+        depth_masked = depth[rmin:rmax, cmin:cmax].flatten()[choose][:, np.newaxis].astype(np.float32)
+        xmap_masked = (choose // wc + rmin)[:, np.newaxis].astype(np.float32)      # the reference's xmap holds the ROW index
+        ymap_masked = (choose % wc + cmin)[:, np.newaxis].astype(np.float32)
+        cam_scale = meta["factor_depth"][0][0]
+        pt2 = depth_masked / cam_scale                           # float32: a uint16 scalar does not promote it
+        pt0 = (ymap_masked - cam_cx) * pt2 / cam_fx
+        pt1 = (xmap_masked - cam_cy) * pt2 / cam_fy
+        cloud = np.concatenate((pt0, pt1, pt2), axis=1)
+        if self.add_noise:
+            cloud = np.add(cloud, add_t)
+        cls = int(obj[idx])
+        target, model_points = self._targets(meta, idx, cls, add_t, need("dellist", lambda: self._draw_dellist(d, cls)))
+        img_n = (torch.from_numpy(img_masked.astype(np.float32)) - torch.from_numpy(_MEAN)[:, None, None]) / torch.from_numpy(_STD)[:, None, None]
+        return (torch.from_numpy(cloud.astype(np.float32)), torch.LongTensor(choose[None].astype(np.int64)), img_n, torch.from_numpy(target),
+                torch.from_numpy(model_points), torch.LongTensor([cls - 1]))
+
+    # ---- device path ----------------------------------------------------------------------------------------------------------------------
+    def _resident(self, line):
+        """the decoded frames of one entry on the device (u8 [H,W,3], u16 [H,W], u8 [H,W]) and the sorted class list of its label, decoded
+        once and kept; seed frames (front, back) are entries like any other"""
+        r = self._res.get(line)
+        if r is None:
+            img, depth, label = (np.array(self._open(line, x)) for x in ("color", "depth", "label"))
+            # A 4-band colour file is refused too, although the host path (like the reference: `[:, :, :3]`, `.convert("RGB")`) drops its
+            # fourth band and goes on: ds[i] works on such a file, ds.batch() raises.  Convert such a tree to RGB once.
+            if (img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8 or depth.dtype != np.uint16 or label.dtype != np.uint8
+                    or label.ndim != 2 or img.shape[:2] != (img_width, img_length) or depth.shape != img.shape[:2] or label.shape != img.shape[:2]):
+                raise ValueError("entry %s: the builder takes %d x %d frames: 8-bit RGB, 16-bit depth and a one-band 8-bit label, got %s %s, "
+                                 "%s %s and %s %s" % (line, img_width, img_length, img.shape, img.dtype, depth.shape, depth.dtype, label.shape,
+                                                      label.dtype))
+            classes = np.unique(label).tolist()
+            if classes[-1] > NUM_CLASSES:
+                raise ValueError("entry %s: its label holds class %d, above the %d classes of the data set" % (line, classes[-1], NUM_CLASSES))
+            r = tuple(torch.from_numpy(np.ascontiguousarray(x)).to(self.device) for x in (img, depth, label)) + (classes,)
+            self._res[line] = r
+        return r
+
+    def batch(self, indices, params=None, return_params=False):
+        """The samples `[ds[i] for i in indices]` built on the device (augment.py, csrc/ycb.hip) -> a list of the reference's 6-tuples as
+        `DataLoader(batch_size=1)` delivers them: cloud[1,N,3] f32, choose[1,1,N] i64, img[1,3,Hc,Wc] f32, target[1,M,3] f32,
+        model_points[1,M,3] f32, idx[1,1] i64 -- views into one packed block per batch.  Every file is decoded once, on first use, and
+        stays on the GPU.
+
+        Read-backs: the overlap table (`ape_ycb_overlap`: which front candidate leaves more than 1000 labelled pixels, how many valid
+        pixels every object keeps), then the rows (`ape_ycb_rows`: extents and in-crop counts).  One upload: row prefixes, ranks and, for
+        `data_syn` samples, the float64 noise drawn on the host (24 bytes per crop pixel).
+
+        Draws.  Without `params` the batch draws what the samples would draw.  With per-sample seeded generators (the default) the five
+        front candidates of every sample are drawn ahead and counted in one launch, and each generator is rewound to its state after the
+        accepted candidate.  With reference_rng the draws of a sample follow those of the sample before it in the one global stream, and
+        several of them wait for a read-back, so the batch then builds sample after sample: that mode exists for parity with the
+        reference, not for speed.  return_params adds the parameter dicts used (see `sample_host`)."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("PoseDataset.batch builds its samples on the GPU (no CPU fallback in this build; ds[i] is the host path)")
+        if not hasattr(self.trancolor, "params"):
+            raise TypeError("PoseDataset.batch needs a jitter with params(uniform, shuffle) returning the op list (ColorJitterPIL or an object "
+                            "like it): the device path cannot run a bare callable trancolor, which works for ds[i] only")
+        indices = [int(i) for i in indices]
+        for i in indices:
+            if not 0 <= i < self.length:
+                raise IndexError("index %d outside the %d samples" % (i, self.length))
+        if params is not None and len(params) != len(indices):
+            raise ValueError("%d indices but %d parameter sets" % (len(indices), len(params)))
+        from autoposeestimation_amd.DenseFusion.datasets.ycb import augment as G
+        if self.reference_rng and params is None:
+            out, used = [], []
+            for i in indices:
+                s, ps = G.build(self, [i], None)
+                out += s
+                used += ps
+        else:
+            out, used = G.build(self, indices, params)
+        return (out, used) if return_params else out

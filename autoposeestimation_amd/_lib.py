@@ -180,9 +180,21 @@ SIGNATURES = {
     "ape_linemod_workspace_bytes": [_I, _I, _I],
     "ape_linemod_rows": [_P, _I, _I, _I, _P, _c.c_size_t, _P],
     "ape_linemod_samples": [_P, _I, _I, _I, _I, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P],
+    # YCB-Video samples (csrc/ycb.hip): DenseFusion/datasets/ycb/dataset.py:97-232; `ape_ycb_job` is mirrored next to its one user,
+    # DenseFusion/datasets/ycb/augment.py
+    "ape_ycb_overlap": [_P, _I, _I, _I, _P, _P],
+    "ape_ycb_rows_offset": [_I],
+    "ape_ycb_tables_offset": [_I, _I],
+    "ape_ycb_sel_offset": [_I, _I],
+    "ape_ycb_noise_offset": [_I, _I, _I],
+    "ape_ycb_rows": [_P, _I, _I, _I, _P, _c.c_size_t, _P],
+    "ape_ycb_samples": [_P, _I, _I, _I, _I, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P],
 }
 
 
+# The struct mirrors below are the ones tests/test_abi.py compares with the C compiler's layout.  They are not every mirror of the header:
+# those of `ape_linemod_job` and of `ape_ycb_job` / `ape_ycb_jitter` / `ape_ycb_pair` live next to their one user
+# (DenseFusion/datasets/{linemod,ycb}/augment.py) and get the same layout check in tests/test_linemod_host.py and tests/test_ycb_host.py.
 class AdamJob(_c.Structure):
     """Mirror of `ape_adam_job` (include/ape_hip.h)."""
     _fields_ = [("param", _c.c_void_p), ("grad", _c.c_void_p), ("exp_avg", _c.c_void_p), ("exp_avg_sq", _c.c_void_p), ("n", _c.c_long),
@@ -253,12 +265,14 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
              "ape_pose_train_workspace_bytes": _c.c_size_t, "ape_pose_train_image_offset": _c.c_size_t,
              "ape_pose_train_sample_bytes": _c.c_size_t,
              "ape_linemod_box_workspace_bytes": _c.c_size_t, "ape_linemod_rows_offset": _c.c_size_t,
-             "ape_linemod_tables_offset": _c.c_size_t, "ape_linemod_sel_offset": _c.c_size_t, "ape_linemod_workspace_bytes": _c.c_size_t}
+             "ape_linemod_tables_offset": _c.c_size_t, "ape_linemod_sel_offset": _c.c_size_t, "ape_linemod_workspace_bytes": _c.c_size_t,
+             "ape_ycb_rows_offset": _c.c_size_t, "ape_ycb_tables_offset": _c.c_size_t, "ape_ycb_sel_offset": _c.c_size_t,
+             "ape_ycb_noise_offset": _c.c_size_t}
 
 _lib = None
 
 
-ABI_VERSION = 11    # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 12    # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

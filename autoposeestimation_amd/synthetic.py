@@ -505,3 +505,151 @@ def linemod_tree(root, seed=0):
     with open(os.path.join(root, "models", "models_info.yml"), "w") as f:
         f.write("".join(info))
     return frames_of
+
+
+YCB_CLASSES = ["%03d_object" % (k + 1) for k in range(21)]
+# entries of the tree below, by what they are there for
+YCB_REAL_A, YCB_REAL_B, YCB_CAM2, YCB_SMALL, YCB_NONE = ("data/0001/000001", "data/0001/000002", "data/0061/000001", "data/0001/000003",
+                                                         "data/0001/000004")
+YCB_SYN_MULTI, YCB_SYN_SINGLE, YCB_SYN_COVER = "data_syn/000000", "data_syn/000001", "data_syn/000002"
+YCB_EDGE, YCB_SYN_HOLE = "data/0001/000005", "data_syn/000003"    # the over-1000 test of a front candidate at its threshold
+YCB_TRAIN = [YCB_REAL_A, YCB_REAL_B, YCB_CAM2, YCB_SYN_MULTI, YCB_SYN_SINGLE, YCB_SMALL]
+YCB_TRAIN_REJECTING = [YCB_REAL_A, YCB_REAL_B, YCB_SYN_SINGLE, YCB_SYN_COVER, YCB_NONE]
+YCB_TRAIN_THRESHOLD = [YCB_REAL_B, YCB_EDGE, YCB_SYN_HOLE]
+YCB_TEST = [YCB_REAL_A, YCB_CAM2, YCB_REAL_B]
+YCB_FAR_DEPTH = 15000
+# The classes of the test-list entries are those whose confidence head, with the seeded weights posenet_state_dict(21, 0), leaves at least
+# 1e-3 between its best pixel and the next on these shapes; the heads of others (2, 3, 8, 16, 20 ...) saturate and give no frame a margin.
+# Classes 13, 19 and 21 are among the symmetric five.
+# rois (class, x1, y1, x2, y2) beyond the objects': a class PoseCNN's labels hold no pixel of, a roi of no height
+YCB_LOST_ROIS = {YCB_REAL_A: [(17, 400.0, 100.0, 470.0, 160.0)], YCB_CAM2: [(7, 300.0, 200.0, 360.0, 201.0)]}
+# (class, 'e' ellipse | 'r' rectangle, first row, rows, first column, columns) per entry, painted in this order
+YCB_OBJECTS = {
+    YCB_REAL_A: [(1, "e", 0, 130, 0, 170), (9, "e", 200, 60, 300, 50), (5, "r", 300, 3, 400, 17), (21, "r", 350, 5, 100, 10)],
+    YCB_REAL_B: [(11, "r", 100, 40, 200, 40), (19, "r", 200, 80, 300, 80), (4, "e", 390, 90, 520, 120)],
+    YCB_CAM2: [(7, "e", 150, 100, 0, 90), (13, "e", 60, 70, 400, 110), (15, "e", 300, 120, 250, 60)],
+    YCB_SMALL: [(21, "r", 350, 5, 100, 10), (5, "r", 300, 3, 400, 17)],
+    YCB_NONE: [(21, "r", 350, 5, 100, 10)],
+    YCB_SYN_MULTI: [(3, "e", 40, 50, 50, 60), (9, "e", 215, 30, 310, 30), (12, "e", 380, 60, 500, 80)],
+    YCB_SYN_SINGLE: [(6, "e", 100, 80, 100, 90)],
+    YCB_SYN_COVER: [(13, "r", 0, 480, 0, 330), (14, "r", 0, 480, 330, 310)],
+    YCB_EDGE: [(19, "r", 200, 80, 300, 80), (2, "r", 100, 40, 100, 40)],
+    YCB_SYN_HOLE: [(13, "r", 0, 480, 0, 330), (14, "r", 0, 480, 330, 310)],
+}
+# (first row, rows, first column, columns) left unlabelled after the objects are painted: as a front, YCB_SYN_HOLE uncovers 25 x 40 = 1000
+# pixels inside class 19 of YCB_REAL_B and YCB_EDGE, and one more pixel that only YCB_EDGE labels
+YCB_HOLES = {YCB_SYN_HOLE: [(200, 25, 300, 40), (110, 1, 110, 1)]}
+
+
+def ycb_tree(root, seed=0):
+    """A small YCB_Video_Dataset tree (480 x 640 frames): `data/0001/...` and `data/0061/...` (the second camera), `data_syn/...`, each entry
+    with `-color.png`, `-depth.png`, `-label.png` and `-meta.mat` (`cls_indexes`, `poses` [3,4,n], `factor_depth` as uint16);
+    `models/<class>/points.xyz` for 21 classes (2600 points and more, within 7 cm); `results_PoseCNN_RSS2018/%06d.mat` for the test list;
+    and three config directories with `classes.txt` and the lists: `dataset_config` (YCB_TRAIN, YCB_TEST), `dataset_config_rejecting`
+    (YCB_TRAIN_REJECTING: every front candidate is skipped or rejected) and `dataset_config_threshold` (YCB_TRAIN_THRESHOLD: the only front
+    candidate leaves exactly 1000 labelled pixels of one frame and 1001 of the other).  What the entries hold, YCB_OBJECTS:
+      YCB_REAL_A     an object with pixels in row 0 and in column 0, one with exactly 51 valid pixels and one with exactly 50;
+      YCB_REAL_B     objects with extents of exactly 40 and 80, one with pixels in row 479 and in column 639;
+      YCB_CAM2       video 61: the second camera; an object with a pixel in column 0;
+      YCB_SMALL      the 51-pixel object behind the 50-pixel one (the object draw repeats; `choose` wraps); YCB_NONE: the 50-pixel one only;
+      YCB_SYN_MULTI  three classes over a bright background, so that the composite onto a real frame wraps modulo 256;
+      YCB_SYN_SINGLE one class: the front candidate that is skipped; YCB_SYN_COVER: two classes over the whole frame: as a front it leaves
+                     no labelled pixel, so it is rejected;
+      YCB_SYN_HOLE   the same two classes with YCB_HOLES left open: as a front it leaves exactly 1000 labelled pixels of YCB_REAL_B
+                     (rejected: not more than 1000) and exactly 1001 of YCB_EDGE (accepted).
+    The function asserts the border pixels and the two counts.  Deterministic in `seed`.  Shared by tools/gen_golden_ycb.py (which runs the REFERENCE's PoseDataset on it) and the YCB tests.
+    -> {"config": dir, "config_rejecting": dir, "config_threshold": dir, "toolbox": dir}"""
+    import os
+    import scipy.io as scio
+    from PIL import Image
+    rng = np.random.default_rng([78, int(seed)])
+    h, w = 480, 640
+    yy, xx = np.mgrid[0:h, 0:w]
+    for k, name in enumerate(YCB_CLASSES):
+        os.makedirs(os.path.join(root, "models", name), exist_ok=True)
+        pts = rng.uniform(-1, 1, (2600 + 11 * k, 3)) * [0.05 + 0.001 * k, 0.04, 0.03 + 0.002 * k]
+        with open(os.path.join(root, "models", name, "points.xyz"), "w") as f:
+            f.write("".join("%.6f %.6f %.6f\n" % tuple(p) for p in pts))
+    frames = {}
+    for line, objects in YCB_OBJECTS.items():
+        syn = line.startswith("data_syn")
+        os.makedirs(os.path.join(root, os.path.dirname(line)), exist_ok=True)
+        cam = (323.7872, 279.6921, 1077.836, 1078.189) if line == YCB_CAM2 else (312.9869, 241.3109, 1066.778, 1067.487)
+        label = np.zeros((h, w), np.uint8)
+        rgb = (rng.integers(0, 60, (h, w, 3)) + (150 if line == YCB_SYN_MULTI else 90)).astype(np.uint8)
+        depth = np.full((h, w), 11000, np.uint16) + (xx // 40).astype(np.uint16)
+        keep = np.zeros((h, w), bool)
+        poses = []
+        for cls, kind, r0, hh, c0, ww in objects:
+            if kind == "e":
+                q = ((yy - r0 - hh / 2) / (hh / 2)) ** 2 + ((xx - c0 - ww / 2) / (ww / 2)) ** 2
+                inside, ends = q < 1, q == 1
+                # the ends of the axes belong to the object, so that it touches its box (and with it the frame's border): painted without
+                # pixel noise, so that no other pixel of the tree depends on how many they are
+                label[ends] = cls
+                rgb[ends] = (CLASS_COLOURS[cls % len(CLASS_COLOURS)] * 0.8).astype(np.uint8)
+                depth[ends] = (8000 + 250 * np.sin(xx[ends] / 17.0) + 150 * np.cos(yy[ends] / 13.0)).astype(np.uint16)
+            else:
+                inside = (yy >= r0) & (yy < r0 + hh) & (xx >= c0) & (xx < c0 + ww)
+            label[inside] = cls
+            rgb[inside] = (CLASS_COLOURS[cls % len(CLASS_COLOURS)] * 0.8).astype(np.uint8) + rng.integers(0, 40, (int(inside.sum()), 3)).astype(np.uint8)
+            depth[inside] = (8000 + 250 * np.sin(xx[inside] / 17.0) + 150 * np.cos(yy[inside] / 13.0)).astype(np.uint16)
+            if hh * ww < 100:
+                keep |= inside                                   # the 51- and 50-pixel objects keep every depth value
+            R = rigid(rng.uniform(-1, 1), rng.uniform(-1, 1), rng.uniform(-3, 3), (0, 0, 0))[:3, :3]
+            t = [(c0 + ww / 2 - cam[0]) * 0.8 / cam[2], (r0 + hh / 2 - cam[1]) * 0.8 / cam[3], 0.8]
+            poses.append(np.concatenate([R, np.array(t)[:, None]], axis=1))
+        for r0, hh, c0, ww in YCB_HOLES.get(line, []):
+            label[r0:r0 + hh, c0:c0 + ww] = 0
+        depth[(rng.random((h, w)) < 0.03) & ~keep] = 0
+        Image.fromarray(rgb).save(os.path.join(root, line + "-color.png"), compress_level=1)
+        Image.fromarray(depth).save(os.path.join(root, line + "-depth.png"), compress_level=1)
+        Image.fromarray(label).save(os.path.join(root, line + "-label.png"))
+        scio.savemat(os.path.join(root, line + "-meta.mat"),
+                     {"cls_indexes": np.array([[o[0]] for o in objects], np.uint8), "poses": np.stack(poses, axis=2),
+                      "factor_depth": np.array([[10000]], np.uint16), "intrinsic_matrix": np.array([[cam[2], 0, cam[0]], [0, cam[3], cam[1]], [0, 0, 1.0]])})
+        frames[line] = (label, depth)
+    # the fixture holds what its docstring says
+    top_left, bottom_right, left = frames[YCB_REAL_A][0], frames[YCB_REAL_B][0], frames[YCB_CAM2][0]
+    assert top_left[0].any() and top_left[:, 0].any() and bottom_right[h - 1].any() and bottom_right[:, w - 1].any() and left[:, 0].any()
+    uncovered = frames[YCB_SYN_HOLE][0] == 0
+    assert int((frames[YCB_REAL_B][0][uncovered] != 0).sum()) == 1000 and int((frames[YCB_EDGE][0][uncovered] != 0).sum()) == 1001
+    dirs = {"config": os.path.join(root, "dataset_config"), "config_rejecting": os.path.join(root, "dataset_config_rejecting"),
+            "config_threshold": os.path.join(root, "dataset_config_threshold"), "toolbox": os.path.join(root, "YCB_Video_toolbox")}
+    # PoseCNN's detections of the test list: a roi a few pixels around every object, and as segmentation a 24 x 32 window of the object
+    # with a hole -- between 500 and 1000 valid pixels, so `choose` keeps every one and its wrap pad repeats only the first ones -- plus ONE pixel in the last corner of the roi's crop, on the
+    # background behind the object (YCB_FAR_DEPTH = 1.5 m against the object's 0.8 m): the confidence head answers that point with a
+    # maximum that stands clear of the second (tests/test_ycb_host.py::test_eval_fixture_guard).  The 51- and 50-pixel objects keep their
+    # pixels (no window); YCB_LOST_ROIS adds a roi whose class has no pixel in `labels` and one of no height: lost detections.
+    from autoposeestimation_amd.DenseFusion.datasets.ycb.dataset import bbox_from_extents
+    os.makedirs(os.path.join(dirs["toolbox"], "results_PoseCNN_RSS2018"), exist_ok=True)
+    for now, line in enumerate(YCB_TEST):
+        gt, depth = frames[line]
+        labels = np.zeros((h, w), np.uint8)
+        rois = []
+        for cls, kind, r0, hh, c0, ww in YCB_OBJECTS[line]:
+            roi = [0.0, float(cls), c0 - 4.5, r0 - 4.5, c0 + ww + 4.5, r0 + hh + 4.5]
+            rois.append(roi)
+            if hh * ww < 100:
+                labels[gt == cls] = cls
+                continue
+            wr, wc = r0 + hh // 2 - 12, c0 + ww // 2 - 16
+            labels[wr:wr + 24, wc:wc + 32][gt[wr:wr + 24, wc:wc + 32] == cls] = cls
+            labels[wr + 11:wr + 13, wc + 15:wc + 17] = 0
+            rmin, rmax, cmin, cmax = bbox_from_extents(int(roi[3]) + 1, int(roi[5]) - 2, int(roi[2]) + 1, int(roi[4]) - 2)
+            assert gt[rmax - 1, cmax - 1] == 0 and labels[rmax - 1, cmax - 1] == 0, (line, cls)
+            labels[rmax - 1, cmax - 1] = cls
+            depth[rmax - 1, cmax - 1] = YCB_FAR_DEPTH
+        for extra in YCB_LOST_ROIS.get(line, []):
+            rois.append([0.0] + [float(v) for v in extra])
+        Image.fromarray(depth).save(os.path.join(root, line + "-depth.png"), compress_level=1)
+        scio.savemat(os.path.join(dirs["toolbox"], "results_PoseCNN_RSS2018", "%06d.mat" % now), {"labels": labels, "rois": np.array(rois, np.float32)})
+    for key, train in (("config", YCB_TRAIN), ("config_rejecting", YCB_TRAIN_REJECTING), ("config_threshold", YCB_TRAIN_THRESHOLD)):
+        os.makedirs(dirs[key], exist_ok=True)
+        with open(os.path.join(dirs[key], "classes.txt"), "w") as f:
+            f.write("".join(n + "\n" for n in YCB_CLASSES))
+        with open(os.path.join(dirs[key], "train_data_list.txt"), "w") as f:
+            f.write("".join(n + "\n" for n in train))
+        with open(os.path.join(dirs[key], "test_data_list.txt"), "w") as f:
+            f.write("".join(n + "\n" for n in YCB_TEST))
+    return dirs

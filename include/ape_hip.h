@@ -849,6 +849,79 @@ int ape_linemod_rows(const ape_linemod_job* jobs_host, int B, int H, int W, void
 int ape_linemod_samples(const ape_linemod_job* jobs_host, int B, int H, int W, int N, const float* mean3_host, const float* std3_host,
                         void* out, size_t out_bytes, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- YCB-Video samples (csrc/ycb.hip, csrc/ycb_px.h; reference DenseFusion/datasets/ycb/dataset.py:97-232, tools/eval_ycb.py:136-190) ----
+ * ape_ycb_jitter: an ape_aug_jitter in 24 bytes, so that 16 jobs with three lists each still travel as kernel arguments: the ops in the
+ * order they run, code 0 (APE_JIT_END) ends the list; shift is the u8 hue shift.
+ * One job per sample: DEVICE pointers to the resident colour frame, 16-bit depth and one-band label (classes 0..21), and what the host
+ * drew.  back_rgb (or null): the real frame a `data_syn` sample is composited onto.  front_rgb / front_label (both or neither): the
+ * synthetic frame whose classes front_a, front_b occlude the object.  jit[0] / jit[1] / jit[2] jitter the frame / the background / the
+ * front (an empty list = none).  A pixel is a MEMBER when label == obj and the front label is neither front_a nor front_b, and VALID when
+ * its depth is != 0 as well.  Per crop pixel, in uint8 arithmetic that wraps modulo 256 as numpy's does (:150-167):
+ *   v = jittered frame; with back_rgb: v = jittered background * (label == 0) + v; with a front, where the front label is front_a or
+ *   front_b: v = jittered front; then x = (float)((double)v + noise) with noise (ws + noise_off: f64 [3][Hc][Wc] in the workspace;
+ *   noise_off < 0 = none) or (float)v, and (x - mean[c]) / std[c].
+ * The cloud is z = depth / cam_scale, x = (col - cam_cx) * z / cam_fx, y = (row - cam_cy) * z / cam_fy in float32; add_t (double) is
+ * added in float64 and rounded once when add_noise.  win_*: the rows [win_r0, win_r1) and columns [win_c0, win_c1) ape_ycb_rows counts
+ * in.  skip != 0: ape_ycb_samples writes nothing for the sample. */
+typedef struct ape_ycb_jitter {
+    uint8_t code[4];
+    uint8_t shift[4];
+    float factor[4];
+} ape_ycb_jitter;
+typedef struct ape_ycb_job {
+    const uint8_t* rgb;          /* [H][W][3] */
+    const uint16_t* depth;       /* [H][W] */
+    const uint8_t* label;        /* [H][W] */
+    const uint8_t* back_rgb;     /* [H][W][3] or null */
+    const uint8_t* front_rgb;    /* [H][W][3] or null */
+    const uint8_t* front_label;  /* [H][W] or null */
+    double add_t[3];
+    long long out_off;
+    long long noise_off;
+    ape_ycb_jitter jit[3];
+    int rmin, rmax, cmin, cmax;
+    int win_r0, win_r1, win_c0, win_c1;
+    int obj, front_a, front_b, add_noise, skip, reserved;
+    float cam_cx, cam_cy, cam_fx, cam_fy, cam_scale, reserved_f;
+} ape_ycb_job;
+APE_STATIC_ASSERT(sizeof(ape_ycb_jitter) == 24, "ape_ycb_jitter layout (mirrored by ycb/augment.py YcbJitter)");
+APE_STATIC_ASSERT(sizeof(ape_ycb_job) == 240, "ape_ycb_job layout (mirrored by ycb/augment.py YcbJob)");
+/* One (label, front label or null, depth) triple of ape_ycb_overlap: DEVICE pointers to [H][W] u8 / u8 / u16. */
+typedef struct ape_ycb_pair {
+    const uint8_t* label;
+    const uint8_t* front_label;
+    const uint16_t* depth;
+} ape_ycb_pair;
+/* table[p][a][f][d] (u32 [P][22][22][2], zeroed here): the number of pixels of triple p with label == a, front label == f (0 with a null
+ * front) and d = (depth != 0); a pixel with a class above 21 on either side is counted nowhere.  Per workgroup 968 counters in LDS, then
+ * one global integer add per non-zero counter: integers only, so two launches agree bit for bit.  The host derives from this one table
+ * both the over-1000 test of a front candidate and every object's valid-pixel count after its occlusion.  A null or misaligned pointer:
+ * APE_EINVAL, nothing launched and the table untouched. */
+int ape_ycb_overlap(const ape_ycb_pair* pairs_host, int P, int H, int W, uint32_t* table, void* stream);
+/* The workspace of a batch: [B][3][64] u64 luma partial sums (frame, background, front) | at ape_ycb_rows_offset(B): [B][H][3] i32 (the
+ * read-back) | at ape_ycb_tables_offset(B, H): [B][H] i32 exclusive row prefix, at ape_ycb_sel_offset(B, H): [B][N] i32 `sel`, at
+ * ape_ycb_noise_offset(B, H, N) (a multiple of 16): the f64 noise of the samples that have one, each at its job's noise_off (one upload
+ * covers the three).  One per stream; not shared by batches in flight at once.  A sample's bytes in the output block are those of
+ * ape_pose_train_image_offset / ape_pose_train_sample_bytes. */
+size_t ape_ycb_rows_offset(int B);
+size_t ape_ycb_tables_offset(int B, int H);
+size_t ape_ycb_sel_offset(int B, int H);
+size_t ape_ycb_noise_offset(int B, int H, int N);
+/* One wave per frame row: rows[b][y] = (the VALID pixels of row y inside the job's window -- 0 for a row outside it --, the first and the
+ * last column of the row's MEMBERS over the whole row: W and -1 when it has none); and per workgroup one partial of the integer L sum
+ * that the contrast op of each of the three lists needs, over the whole image it jitters.  The crop, add_t, noise_off and out_off are not
+ * read.  A window outside the frame, obj / front_a / front_b outside 1..21 (0..21 for the front classes without a front), a front with
+ * only one of its two pointers, a null or misaligned pointer, a short workspace: APE_EINVAL, nothing launched. */
+int ape_ycb_rows(const ape_ycb_job* jobs_host, int B, int H, int W, void* ws, size_t ws_bytes, void* stream);
+/* After the caller copied prefixes, sel[B][N] (the RANKS among the VALID pixels in row-major crop order that `choose` keeps) and the noise
+ * into the workspace.  Per sample without `skip`, at out + out_off: choose[j] = the flat in-crop index of the valid pixel of rank sel[j]
+ * inside the crop (0 and a zero point when there is none), points[j] its cloud point, img the normalised planar crop.  The refusals of
+ * ape_ycb_rows; a crop outside the frame, outside 40..480 x 40..640 or not a multiple of 40; noise_off not a multiple of 8 or its
+ * 24 * Hc * Wc bytes not inside the workspace; a sample that does not fit out_bytes, out or out_off not 16-byte aligned: APE_EINVAL,
+ * nothing launched. */
+int ape_ycb_samples(const ape_ycb_job* jobs_host, int B, int H, int W, int N, const float* mean3_host, const float* std3_host, void* out,
+                    size_t out_bytes, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
