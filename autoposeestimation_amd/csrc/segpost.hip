@@ -88,6 +88,7 @@ __global__ void seg_stats_kernel(const uint8_t* __restrict__ label, const float*
         uint8_t c = 0;
         if (in) {
             c = label[p];
+            if (c >= C) c = 0;        // a label outside [1, C) takes part in nothing (callers other than seg_argmax may hand one in)
             if (c) {
                 root = L[p];
                 fx = (unsigned long long)(score[p] * 1099511627776.0f);  // 2^40 fixed point, exact for p < 1
@@ -139,6 +140,7 @@ __global__ void seg_pick_max_kernel(const uint8_t* __restrict__ label, const int
     for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < npix; p += (long)gridDim.x * blockDim.x) {
         if (L[p] != (int)p) continue;
         const int b = p / HW, c = label[p];
+        if (c >= C) continue;                                          // root of a component of an out-of-range label
         if (hist[(long)b * C + c] <= (unsigned)min_pixels) continue;   // counts[i] > 100 (pipeline/utils.py:445)
         const double mean = use_sum ? (double)sum[p] : (double)sum[p] / (double)cnt[p];
         atomicMax(&best_key[(long)b * C + c], (unsigned long long)__double_as_longlong(mean));
@@ -153,6 +155,7 @@ __global__ void seg_pick_root_kernel(const uint8_t* __restrict__ label, const in
     for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < npix; p += (long)gridDim.x * blockDim.x) {
         if (L[p] != (int)p) continue;
         const int b = p / HW, c = label[p];
+        if (c >= C) continue;                                          // root of a component of an out-of-range label
         if (hist[(long)b * C + c] <= (unsigned)min_pixels) continue;
         const double mean = use_sum ? (double)sum[p] : (double)sum[p] / (double)cnt[p];
         if ((unsigned long long)__double_as_longlong(mean) == best_key[(long)b * C + c])
@@ -169,7 +172,7 @@ __global__ void seg_mask_kernel(const uint8_t* __restrict__ label, const int* __
     for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < npix; p += (long)gridDim.x * blockDim.x) {
         const int c = label[p];
         uint8_t o = 0;
-        if (c) {
+        if (c && c < C) {
             const int b = p / HW;
             if (L[p] == best_root[(long)b * C + c]) {
                 o = (uint8_t)c;
@@ -451,7 +454,8 @@ extern "C" int ape_seg_components_scored(const uint8_t* label, const float* scor
 {
     if (score_mode != APE_SEG_SCORE_MEAN && score_mode != APE_SEG_SCORE_SUM) return APE_EINVAL;
     const int use_sum = score_mode == APE_SEG_SCORE_SUM;
-    if (!label || !score || !objmap || !det || !workspace || B < 0 || H < 1 || W < 1 || C < 1 || C > kMaxCls) return APE_EINVAL;
+    if (!label || !score || !objmap || !det || !workspace || B < 0 || B > 65535 || H < 1 || W < 1 || C < 1 || C > kMaxCls)
+        return APE_EINVAL;            // (seg_stats_kernel has the frame in blockIdx.y)
     if (B == 0) return APE_OK;
     const long npix = (long)B * H * W;
     if (npix >= (1L << 31) - 1) return APE_EINVAL;
@@ -523,9 +527,10 @@ extern "C" int ape_backproject_f32(const uint16_t* depth, const int* objects, co
 extern "C" int ape_preprocess_u8_nhwc4(const uint8_t* rgb, const int* rects, float* out, int n, int H, int W, int Hc, int Wc,
                                        int div255, void* stream)
 {
-    if (!rgb || !rects || !out || n < 0 || H < 1 || W < 1 || Hc < 1 || Wc < 1 || Hc > H || Wc > W) return APE_EINVAL;
+    if (n < 0 || H < 1 || W < 1 || Hc < 1 || Wc < 1 || Hc > H || Wc > W) return APE_EINVAL;
+    if (n == 0) return APE_OK;       // (an empty rects / out tensor has a null pointer)
+    if (!rgb || !rects || !out) return APE_EINVAL;
     const long total = (long)n * Hc * Wc;
-    if (total == 0) return APE_OK;
     hipLaunchKernelGGL(crop_normalize_kernel, dim3(grid_for(total)), dim3(kT), 0, (hipStream_t)stream, rgb, rects, (float4*)out, H,
                        W, Hc, Wc, div255, total);
     return ape::check_launch("ape_preprocess_u8_nhwc4");
@@ -536,7 +541,8 @@ extern "C" int ape_label_trust_counts(const uint8_t* objmap, int cls, const uint
                                       const float* gate_min_max, int B, int H, int W, int cut0, int cut1, unsigned int* counts,
                                       void* stream)
 {
-    if (!objmap || !depth || !gate_min_max || !counts || B < 0 || H < 1 || W < 1 || cls < 1 || cls > 255) return APE_EINVAL;
+    if (!objmap || !depth || !gate_min_max || !counts || B < 0 || B > 65535 || H < 1 || W < 1 || cls < 1 || cls > 255)
+        return APE_EINVAL;
     if (B == 0) return APE_OK;
     int gx = ape::ceil_div((long)H * W, kT);
     gx = gx > 64 ? 64 : gx;

@@ -326,7 +326,10 @@ int ape_seg_head_f32(const float* feat, const float* w, const float* bias, int C
  *   pipeline/utils.py:437-469, DenseFusion/datasets/myDatasetAugmented/dataset.py:338-380.
  * label/score[B][H][W] -> objmap[B][H][W] u8 (class id inside the winning component of that class, else 0; the
  * reference's per-class mask is (objmap == cls) * 255) and det[B][C][5] i32 = (valid, rmin, rmax, cmin, cmax).
- * Classes with <= min_pixels pixels are skipped (reference: 100). */
+ * Classes with <= min_pixels pixels are skipped (reference: 100); the count is the class's in the frame, not one component's.
+ * label may hold ANY byte: a label of 0 or >= C takes part in nothing -- it is not counted, belongs to no component, scores for no
+ * class, objmap is 0 there and no det row depends on it (the result equals the run with those pixels set to 0).  1 <= C <= 64,
+ * B H W < 2^31 - 1, B < 65536 (the frame is a grid y index). */
 size_t ape_seg_components_workspace_bytes(int B, int H, int W, int C);
 /* The component score is selectable: APE_SEG_SCORE_MEAN = mean probability (pipeline/utils.py:456-462),
  * APE_SEG_SCORE_SUM = summed probability, the rule of do_cca (background_subtraction/utils.py:199-222: label 0/1,
