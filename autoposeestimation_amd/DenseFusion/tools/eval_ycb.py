@@ -2,7 +2,7 @@
 the test list the PoseCNN detections (`results_PoseCNN_RSS2018/%06d.mat`: `labels` and `rois`), per roi the crop of the roi's `get_bbox`
 (:54-90), the sample of :152-190, the estimator, the arg-max confidence pose, `iteration` rounds of refiner + float64 pose composition,
 and per frame two `.mat` files with `poses` as [n, 7] (quaternion, translation): one before the refinement, one after it.  The YCB
-toolbox's MATLAB evaluation of those files is not part of this package.
+toolbox's evaluation of those files (ADD-S / ADD AUC, the share below 2 cm) is DenseFusion/replace_ycb_toolbox of this package.
 
 The reference is a script that parses `sys.argv` and calls `.cuda()` at import; here it is `main(...)` with keyword arguments and an
 `if __name__ == "__main__"` block that keeps the three command-line flags.  The samples of `batch_size` frames are built on the GPU in

@@ -75,6 +75,12 @@ SIGNATURES = {
     "ape_adds_dis_batched_f32": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
     "ape_adds_select_f32": [_P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P],
     "ape_recentre_qt_f32": [_P, _P, _P, _I, _P],
+    # the YCB toolbox's pose errors (csrc/pose_errors.hip)
+    "ape_pose_errors_chunk": [],
+    "ape_pose_errors_queries": [],
+    "ape_pose_errors_lanes": [_c.c_long, _I],
+    "ape_pose_errors_workspace_bytes": [_c.c_long, _I],
+    "ape_pose_errors_f64": [_P, _P, _I, _c.c_long, _P, _P, _P, _P, _c.c_long, _I, _I, _P, _P, _c.c_size_t, _P],
     "ape_seg_argmax_f32": [_P, _I, _I, _P, _P, _c.c_long, _I, _P],
     "ape_seg_head_f32": [_P, _P, _P, _I, _P, _P, _c.c_long, _I, _P],
     "ape_seg_components_workspace_bytes": [_I, _I, _I, _I],
@@ -267,12 +273,12 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
              "ape_linemod_box_workspace_bytes": _c.c_size_t, "ape_linemod_rows_offset": _c.c_size_t,
              "ape_linemod_tables_offset": _c.c_size_t, "ape_linemod_sel_offset": _c.c_size_t, "ape_linemod_workspace_bytes": _c.c_size_t,
              "ape_ycb_rows_offset": _c.c_size_t, "ape_ycb_tables_offset": _c.c_size_t, "ape_ycb_sel_offset": _c.c_size_t,
-             "ape_ycb_noise_offset": _c.c_size_t}
+             "ape_ycb_noise_offset": _c.c_size_t, "ape_pose_errors_workspace_bytes": _c.c_size_t}
 
 _lib = None
 
 
-ABI_VERSION = 12    # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 13   # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

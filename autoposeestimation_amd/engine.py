@@ -1042,6 +1042,58 @@ def adds_dis_batched(pred_r, pred_t, model, target, symmetric):
     return dis
 
 
+# the tile sizes of csrc/pose_errors.hip, for the tests' edge shapes: reference points per LDS chunk, model points a workgroup owns at one
+# lane per point (POSE_ERRORS_QUERIES // lanes at more), and the lanes per model point a call may run with
+POSE_ERRORS_CHUNK = 1024
+POSE_ERRORS_QUERIES = 512
+POSE_ERRORS_LANES = (1, 4, 16, 64)
+
+
+def pose_errors_lanes(n_pairs, m_max):
+    """the lanes per model point ape_pose_errors_f64 takes for n_pairs = n_inst * n_src (instance, source) pairs and a longest model of m_max"""
+    return _lib.lib().ape_pose_errors_lanes(int(n_pairs), int(m_max))
+
+
+def pose_errors(models, offsets, cls, rt_gt, rt_est, valid):
+    """The YCB toolbox's adi, add, re and te (evaluate_poses_keyframe.m:148-217) of n_inst objects x n_src pose sources in one call, float64.
+    models[sum M_c, 3] f64: the model points of all classes; offsets[n_models + 1] i32 into it; cls[n_inst] i32 (0-based); rt_gt[n_inst, 3, 4]
+    and rt_est[n_inst, n_src, 3, 4] f64; valid[n_inst, n_src] u8 -> tensor[n_inst, n_src, 4] f64 = (adi, add, re in degrees, te); +inf where
+    valid is 0 (that pose is not read).  Everything is device memory; the table and the classes are checked here (two small reads)."""
+    lib = _lib.lib()
+    if (lib.ape_pose_errors_chunk(), lib.ape_pose_errors_queries()) != (POSE_ERRORS_CHUNK, POSE_ERRORS_QUERIES):
+        raise _lib.ApeError("engine.POSE_ERRORS_* do not mirror csrc/pose_errors.hip")
+    for name, t, dt in (("models", models, torch.float64), ("offsets", offsets, torch.int32), ("cls", cls, torch.int32),
+                        ("rt_gt", rt_gt, torch.float64), ("rt_est", rt_est, torch.float64), ("valid", valid, torch.uint8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
+            raise _lib.ApeError("pose_errors: %s must be a contiguous %s tensor on the device" % (name, dt))
+    if models.dim() != 2 or models.shape[1] != 3 or offsets.dim() != 1 or offsets.numel() < 2 or cls.dim() != 1:
+        raise _lib.ApeError("pose_errors: models[sum M, 3], offsets[n_models + 1] and cls[n_inst] expected, got %s, %s, %s"
+                            % (tuple(models.shape), tuple(offsets.shape), tuple(cls.shape)))
+    n_inst = cls.shape[0]
+    if rt_est.dim() != 4 or tuple(rt_est.shape[2:]) != (3, 4) or rt_est.shape[0] != n_inst or rt_est.shape[1] < 1:
+        raise _lib.ApeError("pose_errors: rt_est[n_inst, n_src >= 1, 3, 4] expected, got %s" % (tuple(rt_est.shape),))
+    n_src = rt_est.shape[1]
+    if tuple(rt_gt.shape) != (n_inst, 3, 4) or tuple(valid.shape) != (n_inst, n_src):
+        raise _lib.ApeError("pose_errors: rt_gt[n_inst, 3, 4] and valid[n_inst, n_src] expected, got %s, %s" % (tuple(rt_gt.shape), tuple(valid.shape)))
+    off = offsets.cpu().numpy().astype("int64")
+    n_models = off.size - 1
+    lengths = off[1:] - off[:-1]
+    if off[0] < 0 or (lengths < 0).any() or off[-1] > models.shape[0]:
+        raise _lib.ApeError("pose_errors: offsets must rise from >= 0 to at most %d rows, got %s" % (models.shape[0], off.tolist()))
+    out = torch.empty(n_inst, n_src, 4, dtype=torch.float64, device=models.device)
+    if n_inst == 0:
+        return out
+    lo, hi = (int(v) for v in torch.aminmax(cls))
+    if lo < 0 or hi >= n_models:
+        raise _lib.ApeError("pose_errors: classes %d..%d outside the table's 0..%d" % (lo, hi, n_models - 1))
+    m_max = max(1, int(lengths.max()))
+    nbytes = lib.ape_pose_errors_workspace_bytes(n_inst * n_src, m_max)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=models.device)
+    _lib.call.ape_pose_errors_f64(_lib.dptr(models), _lib.dptr(offsets), n_models, models.shape[0], _lib.dptr(cls), _lib.dptr(rt_gt),
+                                  _lib.dptr(rt_est), _lib.dptr(valid), n_inst, n_src, m_max, _lib.dptr(out), _lib.dptr(ws), ws.numel(), _st())
+    return out
+
+
 def adds_select(dis, std, pred_c, pred_r, pred_t, points, w):
     """-> out9 (loss, dis[which], q[4], t[3]) f32 on device, which i32[1]"""
     out = torch.empty(9, dtype=torch.float32, device=dis.device)

@@ -653,3 +653,35 @@ def ycb_tree(root, seed=0):
         with open(os.path.join(dirs[key], "test_data_list.txt"), "w") as f:
             f.write("".join(n + "\n" for n in YCB_TEST))
     return dirs
+
+
+def ycb_poses_files(root, dirs, result_dir, perturb=None, lost=()):
+    """`poses` files as tools/eval_ycb.py writes them (`%04d.mat`, [n_rois, 7]: quaternion wxyz, translation) for the test list of a tree made
+    by `ycb_tree(root)` (`dirs`: what it returned), taken from the ground truth instead of the networks: row k of frame `now` is the
+    ground-truth pose of the object whose class roi k of PoseCNN's file carries, followed by `perturb[(now, k)]` = (Euler angles (rx, ry,
+    rz) of `rigid`, translation offset): R_est = R_gt R(angles), t_est = t_gt + offset.  A roi whose class the frame does not hold, and
+    every (now, k) of `lost`, is the seven zeros of a lost detection.  -> {(now, k): pose f64[7]} as written"""
+    import os
+    import scipy.io as scio
+    from autoposeestimation_amd.DenseFusion.lib.transformations import quaternion_from_matrix
+    perturb = perturb or {}
+    os.makedirs(result_dir, exist_ok=True)
+    written = {}
+    for now, line in enumerate(YCB_TEST):
+        rois = np.asarray(scio.loadmat(os.path.join(dirs["toolbox"], "results_PoseCNN_RSS2018", "%06d.mat" % now))["rois"]).reshape(-1, 6)
+        meta = scio.loadmat(os.path.join(root, line + "-meta.mat"))
+        gt_cls = [int(c) for c in np.asarray(meta["cls_indexes"]).reshape(-1)]
+        gt_poses = np.asarray(meta["poses"], np.float64).reshape(3, 4, -1)
+        poses = np.zeros((rois.shape[0], 7))
+        for k in range(rois.shape[0]):
+            cls = int(rois[k, 1])
+            if cls in gt_cls and (now, k) not in lost:
+                rt = gt_poses[:, :, gt_cls.index(cls)]
+                angles, offset = perturb.get((now, k), ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0)))
+                T = np.eye(4)
+                T[:3, :3] = rt[:, :3] @ rigid(angles[0], angles[1], angles[2], (0, 0, 0))[:3, :3]
+                poses[k, :4] = quaternion_from_matrix(T, True)
+                poses[k, 4:] = rt[:, 3] + np.asarray(offset, np.float64)
+            written[(now, k)] = poses[k].copy()
+        scio.savemat(os.path.join(result_dir, "%04d.mat" % now), {"poses": poses})
+    return written

@@ -305,6 +305,24 @@ int ape_adds_select_f32(const float* dis, const float* stdv, const float* pred_c
                         void* stream);
 /* out[i] = (pts[i] - t) . ori_base(q/|q|), qt7 = (q[4], t[3]) on the device   loss.py:61-69, loss_refiner.py:51-60 */
 int ape_recentre_qt_f32(const float* pts, const float* qt7, float* out, int n, void* stream);
+/* The YCB-Video toolbox's four pose errors    DenseFusion/replace_ycb_toolbox/evaluate_poses_keyframe.m:148-217 (csrc/pose_errors.hip)
+ * for n_inst ground-truth objects x n_src pose sources in one call, float64 throughout.  models[n_points][3]: the model points of all
+ * classes; offsets[n_models + 1] i32: class c owns rows offsets[c] .. offsets[c + 1] (no upper limit on a model's length; m_max: the
+ * longest one, which sizes the workspace); cls[n_inst] i32 0-based; rt_gt[n_inst][12], rt_est[n_inst][n_src][12]: row-major 3 x 4;
+ * valid[n_inst][n_src] u8.  out[n_inst][n_src][4] = (adi, add, re, te):
+ *   adi  mean_i min_j |(R_gt p_i + t_gt) - (R_est p_j + t_est)|  (exhaustive search, squared distance (dx dx + dy dy) + dz dz, no FMA)
+ *   add  mean_i |(R_est p_i + t_est) - (R_gt p_i + t_gt)|
+ *   re   180 / pi acos(clamp(0.5 (trace(R_est inv(R_gt)) - 1), -1, 1)) with the general 3 x 3 inverse; te  |t_gt - t_est|
+ * valid == 0: four +inf, the pose is not read.  A class outside the table, or a model the table places outside models / makes longer than
+ * m_max: four NaN, nothing else is read.  est == gt gives four exact zeros.  Sums run in one fixed order, the same for every number of
+ * lanes per query the call may choose: results are bit-identical from run to run and from call size to call size.  All pointers are device memory. */
+int ape_pose_errors_chunk(void);      /* reference points per LDS chunk */
+int ape_pose_errors_queries(void);    /* model points a workgroup owns at one lane per point (fewer by the factor below otherwise) */
+int ape_pose_errors_lanes(long n_pairs, int m_max);   /* 1, 4, 16 or 64 lanes per model point for a call of n_pairs = n_inst * n_src */
+size_t ape_pose_errors_workspace_bytes(long n_pairs, int m_max);
+int ape_pose_errors_f64(const double* models, const int* offsets, int n_models, long n_points, const int* cls, const double* rt_gt,
+                        const double* rt_est, const unsigned char* valid, long n_inst, int n_src, int m_max, double* out, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 /* ---- segmentation post-processing, crop / point selection (byte and index work, bit-exact) ----------------------
  * softmax(+softmax) / argmax                 pipeline/utils.py:429-435 (predict's softmax activation, create_labels.py:23,
