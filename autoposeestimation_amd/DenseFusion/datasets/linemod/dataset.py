@@ -26,6 +26,7 @@ import torch
 import yaml
 from PIL import Image
 
+from autoposeestimation_amd.DenseFusion.datasets import packed
 from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented.dataset import ColorJitterPIL, _GlobalDraws, _SeededDraws, _MEAN, _STD
 
 border_list = [-1, 40, 80, 120, 160, 200, 240, 280, 320, 360, 400, 440, 480, 520, 560, 600, 640, 680]
@@ -376,17 +377,7 @@ class PoseDataset(torch.utils.data.Dataset):
         lost sample, which only the read-back tells: the batch draws it ahead and, when a sample does turn out lost, rewinds `random` to
         where that sample left it and builds the samples behind it as a batch of their own (extra launches in that rare case only).
         return_params adds the parameter dicts used (see `sample_host`)."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("PoseDataset.batch builds its samples on the GPU (no CPU fallback in this build; ds[i] is the host path)")
-        if self.add_noise and not hasattr(self.trancolor, "params"):
-            raise TypeError("PoseDataset.batch needs a jitter with params(uniform, shuffle) returning the op list (ColorJitterPIL or an object "
-                            "like it): the device path cannot run a bare callable trancolor, which works for ds[i] only")
-        indices = [int(i) for i in indices]
-        for i in indices:
-            if not 0 <= i < self.length:
-                raise IndexError("index %d outside the %d samples" % (i, self.length))
-        if params is not None and len(params) != len(indices):
-            raise ValueError("%d indices but %d parameter sets" % (len(indices), len(params)))
+        indices = packed.batch_indices(self, indices, params, self.add_noise)
         out, used, done = [], [], 0
         while done < len(indices):
             part, ps = self._batch_once(indices[done:], None if params is None else params[done:])
@@ -398,7 +389,6 @@ class PoseDataset(torch.utils.data.Dataset):
     def _batch_once(self, indices, params):
         """-> (samples, parameter dicts) of the first k <= len(indices) entries: all of them, unless reference_rng has to rewind (`batch`)"""
         from autoposeestimation_amd.DenseFusion.datasets.linemod import augment as G
-        from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented.augment import upload_targets
         given = params is not None
         ps, draws, metas, frames, boxes, rewind = [], [], [], [], [], []
         for k, i in enumerate(indices):                          # everything that depends on no pixel
@@ -438,15 +428,12 @@ class PoseDataset(torch.utils.data.Dataset):
                 if d is None:
                     raise ValueError("batch: sample %d has %d valid pixels, more than num = %d, and its parameters give no 'subset'"
                                      % (k, count, self.num))
-                c_mask = np.zeros(count, dtype=int)
-                c_mask[:self.num] = 1
-                d.shuffle_array(c_mask)
-                p["subset"] = c_mask.nonzero()[0]
+                p["subset"] = packed.draw_subset(d, count, self.num)
             if "dellist" not in p:
                 if d is None:
                     raise ValueError("batch: parameter 'dellist' of sample %d is missing" % k)
                 p["dellist"] = self._draw_dellist(d, metas[k][1])
-            sels.append(G.selection(count, self.num, p.get("subset")))
+            sels.append(packed.selection(count, self.num, p.get("subset")))
         sels += [None] * (len(indices) - keep)
         views = G.samples(st, sels, _MEAN, _STD)
         alive = [k for k in range(keep) if sels[k] is not None]
@@ -455,6 +442,6 @@ class PoseDataset(torch.utils.data.Dataset):
             (meta, obj), p = metas[k], ps[k]
             target, model_points = self._targets(meta, obj, np.array(p["add_t"], dtype=np.float64) if self.add_noise else None, p["dellist"])
             host.append((target, model_points, self.objlist.index(obj)))
-        up = dict(zip(alive, upload_targets(host, self.device))) if alive else {}
+        up = dict(zip(alive, packed.upload_targets(host, self.device))) if alive else {}
         out = [views[k] + up[k] if k in up else lost_sample(self.device) for k in range(keep)]
         return out, ps[:keep]

@@ -16,6 +16,7 @@ import torch
 
 from autoposeestimation_amd import _lib
 from autoposeestimation_amd import sample_jobs as J
+from autoposeestimation_amd.DenseFusion.datasets import packed
 from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented.dataset import bbox_from_extents
 
 
@@ -37,25 +38,6 @@ def make_job(params, h, w, rgb, depth, label, intr, depth_scale, to_meter, add_n
 
 def set_crop(job, box):
     job.rmin, job.rmax, job.cmin, job.cmax = [int(v) for v in box]
-
-
-def selection(count, n, subset=None):
-    """sel[n] i32: the RANKS, among the `count` valid pixels in row-major crop order, that `choose` keeps (dataset.py:250-257): the sorted
-    positions of the ones of the shuffled `c_mask` (`subset`) when count > n, else `np.pad(..., 'wrap')`: j % count"""
-    if count < 1:
-        raise ValueError("no valid pixel")
-    if count > n:
-        sel = np.asarray(subset, dtype=np.int64).reshape(-1)
-        if sel.size != n or (np.diff(sel) <= 0).any() or sel[0] < 0 or sel[-1] >= count:
-            raise ValueError("the subset must be %d increasing ranks below %d" % (n, count))
-        return sel.astype(np.int32)
-    return (np.arange(n, dtype=np.int64) % count).astype(np.int32)
-
-
-def row_prefix(rows):
-    """[..., H] counts per row -> the exclusive prefix along the rows, i32"""
-    rows = np.asarray(rows, dtype=np.int64)
-    return (np.cumsum(rows, axis=-1) - rows).astype(np.int32)
 
 
 def build_samples(samples, params, cams, num_pt, to_meter, add_noise, mean, std, select, names=None):
@@ -85,52 +67,19 @@ def build_samples(samples, params, cams, num_pt, to_meter, add_noise, mean, std,
     back = ws[e0:t0].cpu().numpy()                               # the one read-back of the batch
     ext = J.combine_extents(back[:r0 - e0].view(np.int32), 4)
     rows = back[r0 - e0:r0 - e0 + b * h * 4].view(np.int32).reshape(b, h)
-    tab = np.empty(b * h + b * n, np.int32)
-    tab[:b * h] = row_prefix(rows).reshape(-1)
-    offsets, total = [], 0
+    sels = []
     for i in range(b):
         if ext[i, 1] < 0:
             raise ValueError("sample %s: the label has no pixel equal to 255%s: get_bbox has no object to crop around"
                              % (name(i), " after its rotation" if jobs[i].rot.mode else ""))
-        box = bbox_from_extents(*ext[i])
         count = int(rows[i].sum())               # whole rows: every labelled pixel lies inside the crop (csrc/pose_train.hip)
         if count == 0:
             raise ValueError("sample %s: no pixel of the label has a depth: there is no point to choose" % (name(i),))
-        tab[b * h + i * n:b * h + (i + 1) * n] = selection(count, n, select(i, count))
-        set_crop(jobs[i], box)
-        jobs[i].out_off = total
-        offsets.append(total)
-        total += L.ape_pose_train_sample_bytes(n, box[1] - box[0], box[3] - box[2])
-    ws[t0:t0 + tab.nbytes].view(torch.int32).copy_(torch.from_numpy(tab))        # the one upload: row prefixes and ranks
+        sels.append(packed.selection(count, n, select(i, count)))
+        set_crop(jobs[i], bbox_from_extents(*ext[i]))
+    offsets, total = packed.plan(jobs, [True] * b, n)
+    packed.upload(ws, t0, packed.table(rows, sels, n))           # the one upload: row prefixes and ranks
     block = torch.empty(total, dtype=torch.uint8, device=dev)
     m, sd = J.norm(mean, std, 3)
     _lib.call.ape_pose_train_samples(jp, b, h, w, n, m, sd, _lib.dptr(block), block.numel(), _lib.dptr(ws), ws.numel(), _lib.stream_ptr())
-    img_off = L.ape_pose_train_image_offset(n)
-    views = []
-    for i, o in enumerate(offsets):
-        hc, wc = jobs[i].rmax - jobs[i].rmin, jobs[i].cmax - jobs[i].cmin
-        choose = block[o:o + 8 * n].view(torch.int64).view(1, 1, n)
-        points = block[o + 8 * n:o + 20 * n].view(torch.float32).view(1, n, 3)
-        img = block[o + img_off:o + img_off + 12 * hc * wc].view(torch.float32).view(1, 3, hc, wc)
-        views.append((points, choose, img))
-    return views
-
-
-def upload_targets(host, dev):
-    """host: per sample (target f32[M,3], model_points f32[M,3], class index) -> per sample (target[1,M,3], model_points[1,M,3], idx[1,1]
-    i64) on the device: views into one buffer, one copy per batch"""
-    sizes = [t.shape[0] * 12 for t, _, _ in host]
-    buf = np.empty(sum(2 * s + 8 for s in sizes), np.uint8)
-    o, offs = 0, []
-    for (t, mp, obj), s in zip(host, sizes):
-        buf[o:o + s] = np.ascontiguousarray(t).view(np.uint8).reshape(-1)
-        buf[o + s:o + 2 * s] = np.ascontiguousarray(mp).view(np.uint8).reshape(-1)
-        buf[o + 2 * s:o + 2 * s + 8] = np.array([obj], np.int64).view(np.uint8)
-        offs.append(o)
-        o += 2 * s + 8
-    d = torch.from_numpy(buf).to(dev)
-    out = []
-    for o, s in zip(offs, sizes):
-        out.append((d[o:o + s].view(torch.float32).view(1, -1, 3), d[o + s:o + 2 * s].view(torch.float32).view(1, -1, 3),
-                    d[o + 2 * s:o + 2 * s + 8].view(torch.int64).view(1, 1)))
-    return out
+    return packed.views(block, offsets, jobs, n)

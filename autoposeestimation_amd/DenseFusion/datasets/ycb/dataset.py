@@ -25,6 +25,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from autoposeestimation_amd.DenseFusion.datasets import packed
 # `get_bbox` (:251-289: sides up to the next entry of border_list, the centre kept, the box pushed back inside 480 x 640 -- LineMOD's clamps to
 # 479 / 639 are not in it), `border_list`, `img_width` and `img_length` are those of the sibling data set: the two files of the reference
 # hold the same text.  tests/test_ycb_host.py pins them to values recorded from THIS reference file.
@@ -368,17 +369,7 @@ class PoseDataset(torch.utils.data.Dataset):
         accepted candidate.  With reference_rng the draws of a sample follow those of the sample before it in the one global stream, and
         several of them wait for a read-back, so the batch then builds sample after sample: that mode exists for parity with the
         reference, not for speed.  return_params adds the parameter dicts used (see `sample_host`)."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("PoseDataset.batch builds its samples on the GPU (no CPU fallback in this build; ds[i] is the host path)")
-        if not hasattr(self.trancolor, "params"):
-            raise TypeError("PoseDataset.batch needs a jitter with params(uniform, shuffle) returning the op list (ColorJitterPIL or an object "
-                            "like it): the device path cannot run a bare callable trancolor, which works for ds[i] only")
-        indices = [int(i) for i in indices]
-        for i in indices:
-            if not 0 <= i < self.length:
-                raise IndexError("index %d outside the %d samples" % (i, self.length))
-        if params is not None and len(params) != len(indices):
-            raise ValueError("%d indices but %d parameter sets" % (len(indices), len(params)))
+        indices = packed.batch_indices(self, indices, params, True)
         from autoposeestimation_amd.DenseFusion.datasets.ycb import augment as G
         if self.reference_rng and params is None:
             out, used = [], []

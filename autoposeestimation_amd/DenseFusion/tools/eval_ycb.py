@@ -94,6 +94,7 @@ def frame_jobs(dataset_root, ycb_toolbox_dir, testlist, now, device):
 def build_samples(jobs, device, draws):
     """jobs: YcbJob list; draws: per job a generator with `shuffle_array` -> per job (points[1,N,3], choose[1,1,N], img[1,3,Hc,Wc]) on the
     device, or None when its crop holds no valid pixel"""
+    from autoposeestimation_amd.DenseFusion.datasets import packed
     from autoposeestimation_amd.DenseFusion.datasets.ycb import augment as G
     if not jobs:
         return []
@@ -108,13 +109,8 @@ def build_samples(jobs, device, draws):
         if count == 0:
             sels.append(None)
             continue
-        subset = None
-        if count > num_points:
-            c_mask = np.zeros(count, dtype=int)
-            c_mask[:num_points] = 1
-            draws[k].shuffle_array(c_mask)
-            subset = c_mask.nonzero()[0]
-        sels.append(G.selection(count, num_points, subset))
+        subset = packed.draw_subset(draws[k], count, num_points) if count > num_points else None
+        sels.append(packed.selection(count, num_points, subset))
     return G.samples(arr, ws, counts, sels, [None] * len(jobs), img_width, img_length, num_points)
 
 

@@ -9,11 +9,10 @@
 //                        lm_pick_kernel (per frame one 64-bit atomicMax of (w * h, first pixel earliest)), lm_box_kernel -> [B][4];
 //   lm_rows_kernel       one wave per row: the valid pixels of the row inside the crop, written by the wave that walked it, and the integer
 //                        L sum that ImageEnhance.Contrast needs (one partial per workgroup, added in index order);
-//   lm_samples_kernel    workgroups 0..kImgBlocks-1 of a sample write the normalised crop, the others one chosen point per wave: the row
-//                        by a binary search of the row prefix, the column by a ballot / popcount walk of that row inside the crop.
+//   lm_samples_kernel    workgroups 0..kImgBlocks-1 of a sample write the normalised crop, the others one chosen point per wave
+//                        (sample_points.h, over the crop).
 // The host only draws and does get_bbox's integer arithmetic between the launches.  Everything relies on -ffp-contract=off.
-#include "sample_batch.h"
-#include "pose_px.h"
+#include "sample_points.h"
 #include "ccl.h"
 
 namespace {
@@ -21,15 +20,16 @@ namespace {
 using namespace ape;
 
 constexpr int kT = 256, kWaves = kT / 64;
-constexpr int kImgBlocks = 96;       // workgroups per sample that write the crop (at most 480 * 640 pixels: <= 12.5 per thread)
 
 using LmBatch = SampleBatch<ape_linemod_job, 3>;
+
+// workspace: luma u64[B][kBlocks] | rows i32[B][H] | prefix | sel
+constexpr SampleLayout kLayout = {kBlocks * sizeof(unsigned long long), 1};
 
 struct LabelTable {
     const uint8_t* p[kJobs];
 };
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline int grid_for(long work) { long g = (work + kT - 1) / kT; return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g)); }
 
 // ---- largest-contour box -------------------------------------------------------------------------------------------------------------
@@ -113,6 +113,12 @@ __device__ __forceinline__ void lm_point(const ape_linemod_job& j, int x, int y,
         for (int k = 0; k < 3; ++k) p[k] = (float)((double)p[k] + j.add_t[k]);
 }
 
+struct LmPoints {
+    static __device__ Window window(const ape_linemod_job& j, int, int) { return crop_window(j); }
+    static __device__ bool valid(const ape_linemod_job& j, int, int W, int x, int y) { return lm_valid(j, W, x, y); }
+    static __device__ void point(const ape_linemod_job& j, int, int W, int x, int y, float* q) { lm_point(j, x, y, j.depth[(long)y * W + x], q); }
+};
+
 // grid (kBlocks, nb)
 __global__ __launch_bounds__(kT) void lm_rows_kernel(LmBatch bt, int job0, int H, int W, unsigned long long* __restrict__ luma, int* __restrict__ rows)
 {
@@ -142,8 +148,7 @@ __global__ __launch_bounds__(kT) void lm_rows_kernel(LmBatch bt, int job0, int H
 }
 
 // grid (kImgBlocks + ceil(N / kWaves), nb).  `prefix` and `sel` come from the caller through device memory, where the entry point cannot
-// look at them: the row found is always inside the frame, the columns walked are those of the (checked) crop, every store goes to the
-// slot of its point, and a rank without a pixel writes zeros.
+// look at them: see sample_point; the rows and columns walked are those of the (checked) crop.
 __global__ __launch_bounds__(kT) void lm_samples_kernel(LmBatch bt, int job0, int H, int W, int N, const unsigned long long* __restrict__ luma,
                                                         const int* __restrict__ prefix, const int* __restrict__ sel, unsigned char* __restrict__ out,
                                                         long img_off)
@@ -152,63 +157,18 @@ __global__ __launch_bounds__(kT) void lm_samples_kernel(LmBatch bt, int job0, in
     const ape_linemod_job& j = bt.j[blockIdx.y];
     if (j.skip) return;
     const int s = job0 + blockIdx.y;
-    const int Wc = j.cmax - j.cmin, Hc = j.rmax - j.rmin;
     unsigned char* base = out + j.out_off;
     if (blockIdx.x < kImgBlocks) {                   // the normalised crop (:117-126, :192), planar
         if (threadIdx.x == 0) s_mean = j.add_noise ? mean_from_partials(j.jit, luma + (long)s * kBlocks, H, W) : 0;
         __syncthreads();
         const int mean = s_mean;
         const int n_ops = j.add_noise ? j.jit.n_ops : 0;
-        const long plane = (long)Hc * Wc;
-        float* img = (float*)(base + img_off);
-        for (long i = (long)blockIdx.x * kT + threadIdx.x; i < plane; i += (long)kImgBlocks * kT) {
-            const int r = (int)(i / Wc), c = (int)(i % Wc);
-            int cr, cg, cb;
-            aug_jittered_rgb(j.rgb, j.jit, W, j.cmin + c, j.rmin + r, n_ops, mean, cr, cg, cb);
-            img[i] = ((float)cr - bt.mean[0]) / bt.stdv[0];
-            img[plane + i] = ((float)cg - bt.mean[1]) / bt.stdv[1];
-            img[2 * plane + i] = ((float)cb - bt.mean[2]) / bt.stdv[2];
-        }
+        write_crop<kT>(bt, j, (float*)(base + img_off),
+                       [&](int x, int y, int& r, int& g, int& b) { aug_jittered_rgb(j.rgb, j.jit, W, x, y, n_ops, mean, r, g, b); });
         return;
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pt = (blockIdx.x - kImgBlocks) * kWaves + wave;       // one chosen point per wave
-    if (pt >= N) return;
-    const int* pf = prefix + (long)s * H;
-    const int rank = sel[(long)s * N + pt];
-    const int y = pose_row_of_rank(pf, H, rank);
-    int rem = rank - pf[y];                          // the pixel's rank inside its row; wave-uniform like everything up to here
-    bool found = false;
-    long long* choose = (long long*)base;
-    float* p = (float*)(base + 8L * N) + 3L * pt;
-    for (int x0 = j.cmin; x0 < j.cmax && !found; x0 += 64) {
-        const int x = x0 + lane;
-        const bool v = x < j.cmax && lm_valid(j, W, x, y);
-        const unsigned long long m = __ballot(v);
-        const int c = __popcll(m);
-        if (rem >= 0 && rem < c) {
-            found = true;
-            if (v && __popcll(m & ((1ull << lane) - 1ull)) == rem) {       // exactly one lane
-                float q[3];
-                lm_point(j, x, y, j.depth[(long)y * W + x], q);
-                choose[pt] = (long long)(y - j.rmin) * Wc + (x - j.cmin);
-                p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
-            }
-        }
-        rem -= c;
-    }
-    if (!found && lane == 0) {
-        choose[pt] = 0;
-        p[0] = p[1] = p[2] = 0.f;
-    }
-}
-
-// get_bbox's crops: sides from border_list inside the frame
-bool crop_ok(const ape_linemod_job& j, int H, int W)
-{
-    const int hc = j.rmax - j.rmin, wc = j.cmax - j.cmin;
-    if (j.rmin < 0 || j.cmin < 0 || j.rmax > H || j.cmax > W || j.rmax <= j.rmin || j.cmax <= j.cmin) return false;
-    return hc >= 40 && hc <= 480 && wc >= 40 && wc <= 640 && hc % 40 == 0 && wc % 40 == 0;
+    const int pt = (blockIdx.x - kImgBlocks) * kWaves + (threadIdx.x >> 6);
+    if (pt < N) sample_point<LmPoints>(j, H, W, pt, N, prefix + (long)s * H, sel[(long)s * N + pt], base);
 }
 
 bool job_ok(const ape_linemod_job& j, int H, int W)
@@ -264,22 +224,10 @@ extern "C" int ape_linemod_boxes(const void* const* labels_host, int B, int H, i
     return check_launch("ape_linemod_boxes");
 }
 
-extern "C" size_t ape_linemod_rows_offset(int B) { return B < 1 ? 0 : (size_t)B * kBlocks * sizeof(unsigned long long); }
-
-extern "C" size_t ape_linemod_tables_offset(int B, int H)
-{
-    return B < 1 || H < 1 ? 0 : ape_linemod_rows_offset(B) + up16((size_t)B * H * sizeof(int));
-}
-
-extern "C" size_t ape_linemod_sel_offset(int B, int H)
-{
-    return B < 1 || H < 1 ? 0 : ape_linemod_tables_offset(B, H) + (size_t)B * H * sizeof(int);
-}
-
-extern "C" size_t ape_linemod_workspace_bytes(int B, int H, int N)
-{
-    return B < 1 || H < 1 || N < 1 ? 0 : up16(ape_linemod_sel_offset(B, H) + (size_t)B * N * sizeof(int));
-}
+extern "C" size_t ape_linemod_rows_offset(int B) { return kLayout.rows(B); }
+extern "C" size_t ape_linemod_tables_offset(int B, int H) { return kLayout.tables(B, H); }
+extern "C" size_t ape_linemod_sel_offset(int B, int H) { return kLayout.sel(B, H); }
+extern "C" size_t ape_linemod_workspace_bytes(int B, int H, int N) { return kLayout.end(B, H, N); }
 
 extern "C" int ape_linemod_rows(const ape_linemod_job* jobs, int B, int H, int W, void* ws, size_t ws_bytes, void* stream)
 {
@@ -308,10 +256,7 @@ extern "C" int ape_linemod_samples(const ape_linemod_job* jobs, int B, int H, in
     for (int i = 0; i < B; ++i) {
         const ape_linemod_job& j = jobs[i];
         if (!job_ok(j, H, W)) return APE_EINVAL;
-        if (j.skip) continue;
-        if (j.out_off < 0 || (j.out_off & 15)) return APE_EINVAL;
-        const size_t need = ape_pose_train_sample_bytes(N, j.rmax - j.rmin, j.cmax - j.cmin);
-        if ((size_t)j.out_off > out_bytes || out_bytes - (size_t)j.out_off < need) return APE_EINVAL;
+        if (!j.skip && !slot_ok(j, N, out_bytes)) return APE_EINVAL;
     }
     const int blocks = kImgBlocks + ceil_div(N, kWaves);
     const char* w = (const char*)ws;

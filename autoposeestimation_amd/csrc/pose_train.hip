@@ -6,8 +6,8 @@
 //                        ROTATED label's pixels == 255 (one partial of each per workgroup) and, per row, the number of valid pixels
 //                        (rotated label == 255 and rotated depth != 0), written by the wave that walked the row.  Plain stores, combined in
 //                        index order: exact whatever the schedule.
-//   pose_samples_kernel  workgroups 0..kImgBlocks-1 of a sample write the normalised crop, the others one chosen point per wave: the row
-//                        by a binary search of the row prefix, the column by a ballot / popcount walk of that one row.
+//   pose_samples_kernel  workgroups 0..kImgBlocks-1 of a sample write the normalised crop, the others one chosen point per wave
+//                        (sample_points.h, over whole rows).
 // Whole-row counts are in-crop counts: every labelled pixel lies inside get_bbox's crop.  With the tight extents [r0, r1) the rounded side
 // s' is an even number >= s = r1 - r0 (a multiple of 40), the centre is c = floor((r0 + r1) / 2) >= (r0 + r1 - 1) / 2, so
 // c - s'/2 <= (r0 + r1)/2 - s/2 = r0 and c + s'/2 >= r1 - 1/2, an integer, hence >= r1; a shift back inside the frame moves the box over
@@ -15,20 +15,29 @@
 // checks this over random extents.
 // The host only draws and does get_bbox's arithmetic; `target` / `model_points` depend on no pixel and stay with numpy's float64 there.
 // The per-pixel arithmetic is pose_px.h / aug_px.h (also compiled for the host, tools/check_pose_px.py); batch, reduction and job checks
-// are sample_batch.h, shared with the other two sample builders.
-#include "sample_batch.h"
-#include "pose_px.h"
+// and workspace layout are sample_batch.h, the crop writer and the chosen-point walk sample_points.h.
+#include "sample_points.h"
 
 namespace {
 
 using namespace ape;
 
 constexpr int kT = 256, kWaves = kT / 64;
-constexpr int kImgBlocks = 96;       // workgroups per sample that write the crop (at most 480 * 640 pixels: <= 12.5 per thread)
 
 using PoseBatch = SampleBatch<ape_pose_train_job, 3>;
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+// workspace: luma u64[B][kBlocks] | ext i32[B][kBlocks][4] | rows i32[B][H] | prefix | sel
+constexpr SampleLayout kLayout = {kBlocks * (sizeof(unsigned long long) + 4 * sizeof(int)), 1};
+
+// whole rows: every labelled pixel lies inside the crop (above)
+struct PosePoints {
+    static __device__ Window window(const ape_pose_train_job&, int H, int W) { return {0, H, 0, W}; }
+    static __device__ bool valid(const ape_pose_train_job& j, int H, int W, int x, int y) { return pose_valid(j, H, W, x, y); }
+    static __device__ void point(const ape_pose_train_job& j, int H, int W, int x, int y, float* q)
+    {
+        pose_point(j, x, y, pose_depth_at(j, H, W, x, y), q);
+    }
+};
 
 // grid (kBlocks, nb)
 __global__ __launch_bounds__(kT) void pose_stats_kernel(PoseBatch bt, int job0, int H, int W, unsigned long long* __restrict__ luma,
@@ -68,8 +77,7 @@ __global__ __launch_bounds__(kT) void pose_stats_kernel(PoseBatch bt, int job0, 
 }
 
 // grid (kImgBlocks + ceil(N / kWaves), nb).  `prefix` and `sel` come from the caller through device memory, where the entry point cannot
-// look at them: the row found is always inside the frame, every frame read is bounds-checked on its coordinates (pose_px.h), and a rank
-// without a pixel writes zeros.
+// look at them: see sample_point; every frame read is bounds-checked on its coordinates (pose_px.h).
 __global__ __launch_bounds__(kT) void pose_samples_kernel(PoseBatch bt, int job0, int H, int W, int N, const unsigned long long* __restrict__ luma,
                                                           const int* __restrict__ prefix, const int* __restrict__ sel, unsigned char* __restrict__ out,
                                                           long img_off)
@@ -77,56 +85,16 @@ __global__ __launch_bounds__(kT) void pose_samples_kernel(PoseBatch bt, int job0
     __shared__ int s_mean;
     const ape_pose_train_job& j = bt.j[blockIdx.y];
     const int s = job0 + blockIdx.y;
-    const int Wc = j.cmax - j.cmin, Hc = j.rmax - j.rmin;
     unsigned char* base = out + j.out_off;
     if (blockIdx.x < kImgBlocks) {                   // the normalised crop (:307-313), planar
         if (threadIdx.x == 0) s_mean = mean_from_partials(j.jit, luma + (long)s * kBlocks, H, W);
         __syncthreads();
         const int mean = s_mean;
-        const long plane = (long)Hc * Wc;
-        float* img = (float*)(base + img_off);
-        for (long i = (long)blockIdx.x * kT + threadIdx.x; i < plane; i += (long)kImgBlocks * kT) {
-            const int r = (int)(i / Wc), c = (int)(i % Wc);
-            int cr, cg, cb;
-            pose_rgb_at(j, H, W, j.cmin + c, j.rmin + r, mean, cr, cg, cb);
-            img[i] = ((float)cr - bt.mean[0]) / bt.stdv[0];
-            img[plane + i] = ((float)cg - bt.mean[1]) / bt.stdv[1];
-            img[2 * plane + i] = ((float)cb - bt.mean[2]) / bt.stdv[2];
-        }
+        write_crop<kT>(bt, j, (float*)(base + img_off), [&](int x, int y, int& r, int& g, int& b) { pose_rgb_at(j, H, W, x, y, mean, r, g, b); });
         return;
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pt = (blockIdx.x - kImgBlocks) * kWaves + wave;       // one chosen point per wave
-    if (pt >= N) return;
-    const int* pf = prefix + (long)s * H;
-    const int rank = sel[(long)s * N + pt];
-    const int y = pose_row_of_rank(pf, H, rank);
-    int rem = rank - pf[y];                          // the pixel's rank inside its row; wave-uniform like everything up to here
-    bool found = false;
-    for (int x0 = 0; x0 < W && !found; x0 += 64) {
-        const int x = x0 + lane;
-        const bool v = x < W && pose_valid(j, H, W, x, y);
-        const unsigned long long m = __ballot(v);
-        const int c = __popcll(m);
-        if (rem >= 0 && rem < c) {
-            found = true;
-            if (v && __popcll(m & ((1ull << lane) - 1ull)) == rem) {       // exactly one lane
-                long long* choose = (long long*)base;
-                float* p = (float*)(base + 8L * N) + 3L * pt;
-                float q[3];
-                pose_point(j, x, y, pose_depth_at(j, H, W, x, y), q);
-                choose[pt] = (long long)(y - j.rmin) * Wc + (x - j.cmin);
-                p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
-            }
-        }
-        rem -= c;
-    }
-    if (!found && lane == 0) {
-        long long* choose = (long long*)base;
-        float* p = (float*)(base + 8L * N) + 3L * pt;
-        choose[pt] = 0;
-        p[0] = p[1] = p[2] = 0.f;
-    }
+    const int pt = (blockIdx.x - kImgBlocks) * kWaves + (threadIdx.x >> 6);
+    if (pt < N) sample_point<PosePoints>(j, H, W, pt, N, prefix + (long)s * H, sel[(long)s * N + pt], base);
 }
 
 bool job_ok(const ape_pose_train_job& j, int H, int W)
@@ -138,37 +106,14 @@ bool job_ok(const ape_pose_train_job& j, int H, int W)
     return rotation_ok(j.rot, H, W) && jitter_ok(j.jit);
 }
 
-// get_bbox's crops: sides from border_list inside a 480 x 640 frame
-bool crop_ok(const ape_pose_train_job& j, int H, int W)
-{
-    const int hc = j.rmax - j.rmin, wc = j.cmax - j.cmin;
-    if (j.rmin < 0 || j.cmin < 0 || j.rmax > H || j.cmax > W) return false;
-    return hc >= 40 && hc <= 480 && wc >= 40 && wc <= 640 && hc % 40 == 0 && wc % 40 == 0;
-}
-
 }  // namespace
 
 extern "C" size_t ape_pose_train_extents_offset(int B) { return B < 1 ? 0 : (size_t)B * kBlocks * sizeof(unsigned long long); }
 
-extern "C" size_t ape_pose_train_rows_offset(int B)
-{
-    return B < 1 ? 0 : ape_pose_train_extents_offset(B) + (size_t)B * kBlocks * 4 * sizeof(int);         // a multiple of 16
-}
-
-extern "C" size_t ape_pose_train_tables_offset(int B, int H)
-{
-    return B < 1 || H < 1 ? 0 : ape_pose_train_rows_offset(B) + up16((size_t)B * H * sizeof(int));
-}
-
-extern "C" size_t ape_pose_train_sel_offset(int B, int H)
-{
-    return B < 1 || H < 1 ? 0 : ape_pose_train_tables_offset(B, H) + (size_t)B * H * sizeof(int);
-}
-
-extern "C" size_t ape_pose_train_workspace_bytes(int B, int H, int N)
-{
-    return B < 1 || H < 1 || N < 1 ? 0 : up16(ape_pose_train_sel_offset(B, H) + (size_t)B * N * sizeof(int));
-}
+extern "C" size_t ape_pose_train_rows_offset(int B) { return kLayout.rows(B); }
+extern "C" size_t ape_pose_train_tables_offset(int B, int H) { return kLayout.tables(B, H); }
+extern "C" size_t ape_pose_train_sel_offset(int B, int H) { return kLayout.sel(B, H); }
+extern "C" size_t ape_pose_train_workspace_bytes(int B, int H, int N) { return kLayout.end(B, H, N); }
 
 extern "C" size_t ape_pose_train_image_offset(int N) { return N < 1 ? 0 : up16((size_t)N * 20); }
 
@@ -203,10 +148,7 @@ extern "C" int ape_pose_train_samples(const ape_pose_train_job* jobs, int B, int
     if (ws_bytes < ape_pose_train_workspace_bytes(B, H, N)) return APE_EWORKSPACE;
     for (int i = 0; i < B; ++i) {
         const ape_pose_train_job& j = jobs[i];
-        if (!job_ok(j, H, W) || !crop_ok(j, H, W)) return APE_EINVAL;
-        if (j.out_off < 0 || (j.out_off & 15)) return APE_EINVAL;
-        const size_t need = ape_pose_train_sample_bytes(N, j.rmax - j.rmin, j.cmax - j.cmin);
-        if ((size_t)j.out_off > out_bytes || out_bytes - (size_t)j.out_off < need) return APE_EINVAL;
+        if (!job_ok(j, H, W) || !crop_ok(j, H, W) || !slot_ok(j, N, out_bytes)) return APE_EINVAL;
     }
     const int blocks = kImgBlocks + ceil_div(N, kWaves);
     const char* w = (const char*)ws;

@@ -1,6 +1,8 @@
-// What the three training-sample builders (bgsub_train.hip, seg_train.hip, pose_train.hip) share around their kernels: the batch of jobs
-// that travels as kernel arguments and the loop that launches it in chunks, the workgroup reduction of their statistics passes, the mean
-// that ImageEnhance.Contrast needs from the partial sums, and the host checks of what a job's rotation and jitter list may hold.
+// What the sample builders (bgsub_train.hip, seg_train.hip, pose_train.hip, linemod.hip, ycb.hip) share around their kernels: the batch of
+// jobs that travels as kernel arguments and the loop that launches it in chunks, the workgroup reduction of their statistics passes, the
+// mean that ImageEnhance.Contrast needs from the partial sums, and the host checks of what a job's rotation and jitter list may hold.  For
+// the three DenseFusion builders (the last three) also the host checks of a job's crop and output slot and the layout of their workspace;
+// what their samples kernels share on the device is sample_points.h.
 #pragma once
 #include <limits.h>
 
@@ -132,5 +134,36 @@ bool norm_ok(const float* mean, const float* stdv, SampleBatch<Job, C>& bt)
     }
     return true;
 }
+
+// ---- the DenseFusion builders: crop, output slot, workspace ------------------------------------------------------------------------------
+inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// get_bbox's crops: sides from border_list inside a 480 x 640 frame
+template <class Job>
+bool crop_ok(const Job& j, int H, int W)
+{
+    const int hc = j.rmax - j.rmin, wc = j.cmax - j.cmin;
+    if (j.rmin < 0 || j.cmin < 0 || j.rmax > H || j.cmax > W || j.rmax <= j.rmin || j.cmax <= j.cmin) return false;
+    return hc >= 40 && hc <= 480 && wc >= 40 && wc <= 640 && hc % 40 == 0 && wc % 40 == 0;
+}
+
+// the job's sample (choose | points | crop, ape_pose_train_sample_bytes) lies 16-byte aligned inside the packed block
+template <class Job>
+bool slot_ok(const Job& j, int N, size_t out_bytes)
+{
+    if (j.out_off < 0 || (j.out_off & 15)) return false;
+    const size_t need = ape_pose_train_sample_bytes(N, j.rmax - j.rmin, j.cmax - j.cmin);
+    return (size_t)j.out_off <= out_bytes && out_bytes - (size_t)j.out_off >= need;
+}
+
+// workspace of a builder: partials[B] (part_bytes each, a multiple of 16) | rows i32[B][H][row_ints] | prefix i32[B][H] | sel i32[B][N] | end
+struct SampleLayout {
+    size_t part_bytes;
+    int row_ints;
+    size_t rows(int B) const { return B < 1 ? 0 : (size_t)B * part_bytes; }
+    size_t tables(int B, int H) const { return B < 1 || H < 1 ? 0 : rows(B) + up16((size_t)B * H * row_ints * sizeof(int)); }
+    size_t sel(int B, int H) const { return B < 1 || H < 1 ? 0 : tables(B, H) + (size_t)B * H * sizeof(int); }
+    size_t end(int B, int H, int N) const { return B < 1 || H < 1 || N < 1 ? 0 : up16(sel(B, H) + (size_t)B * N * sizeof(int)); }
+};
 
 }  // namespace ape

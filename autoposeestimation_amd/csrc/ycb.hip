@@ -9,10 +9,10 @@
 //                        valid pixels every object keeps;
 //   ycb_rows_kernel      one wave per row: the valid pixels of the row inside a window, the first and last member column, and the integer
 //                        L sums that ImageEnhance.Contrast needs for the frame, the background and the front;
-//   ycb_samples_kernel   workgroups 0..kImgBlocks-1 of a sample write the normalised crop, the others one chosen point per wave: the row
-//                        by a binary search of the row prefix, the column by a ballot / popcount walk of that row inside the crop.
+//   ycb_samples_kernel   workgroups 0..kImgBlocks-1 of a sample write the normalised crop, the others one chosen point per wave
+//                        (sample_points.h, over the crop).
 // The host only draws and does get_bbox's integer arithmetic between the launches.  Everything relies on -ffp-contract=off.
-#include "sample_batch.h"
+#include "sample_points.h"
 #include "ycb_px.h"
 
 namespace {
@@ -20,7 +20,6 @@ namespace {
 using namespace ape;
 
 constexpr int kT = 256, kWaves = kT / 64;
-constexpr int kImgBlocks = 96;       // workgroups per sample that write the crop (at most 480 * 640 pixels: <= 12.5 per thread)
 constexpr int kClasses = 22;         // 0 (background) .. 21
 constexpr int kBins = kClasses * kClasses * 2;
 constexpr int kSrc = 3;              // jittered source images of a job: frame, background, front
@@ -30,7 +29,14 @@ struct PairBatch {
     ape_ycb_pair j[kJobs];
 };
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+// workspace: luma u64[B][kSrc][kBlocks] | rows i32[B][H][3] | prefix | sel | noise
+constexpr SampleLayout kLayout = {kSrc * kBlocks * sizeof(unsigned long long), 3};
+
+struct YcbPoints {
+    static __device__ Window window(const ape_ycb_job& j, int, int) { return crop_window(j); }
+    static __device__ bool valid(const ape_ycb_job& j, int, int W, int x, int y) { return ycb_valid(j, (long)y * W + x); }
+    static __device__ void point(const ape_ycb_job& j, int, int W, int x, int y, float* q) { ycb_point(j, x, y, j.depth[(long)y * W + x], q); }
+};
 
 // grid (kBlocks, nb)
 __global__ __launch_bounds__(kT) void ycb_overlap_kernel(PairBatch bt, int pair0, int HW, unsigned int* __restrict__ table)
@@ -107,8 +113,7 @@ __global__ __launch_bounds__(kT) void ycb_rows_kernel(YcbBatch bt, int job0, int
 }
 
 // grid (kImgBlocks + ceil(N / kWaves), nb).  `prefix` and `sel` come from the caller through device memory, where the entry point cannot
-// look at them: the row found is always inside the frame, the columns walked are those of the (checked) crop, every store goes to the
-// slot of its point, and a rank without a pixel writes zeros.
+// look at them: see sample_point; the rows and columns walked are those of the (checked) crop.
 __global__ __launch_bounds__(kT) void ycb_samples_kernel(YcbBatch bt, int job0, int H, int W, int N, const unsigned long long* __restrict__ luma,
                                                          const int* __restrict__ prefix, const int* __restrict__ sel, const char* __restrict__ ws,
                                                          unsigned char* __restrict__ out, long img_off)
@@ -117,7 +122,6 @@ __global__ __launch_bounds__(kT) void ycb_samples_kernel(YcbBatch bt, int job0, 
     const ape_ycb_job& j = bt.j[blockIdx.y];
     if (j.skip) return;
     const int s = job0 + blockIdx.y;
-    const int Wc = j.cmax - j.cmin, Hc = j.rmax - j.rmin;
     unsigned char* base = out + j.out_off;
     if (blockIdx.x < kImgBlocks) {                   // the normalised crop (:150-167, :229), planar
         if (threadIdx.x < kSrc) {
@@ -126,7 +130,8 @@ __global__ __launch_bounds__(kT) void ycb_samples_kernel(YcbBatch bt, int job0, 
         }
         __syncthreads();
         const int mean[kSrc] = {s_mean[0], s_mean[1], s_mean[2]};
-        const long plane = (long)Hc * Wc;
+        const int Wc = j.cmax - j.cmin;
+        const long plane = (long)(j.rmax - j.rmin) * Wc;
         const double* noise = j.noise_off >= 0 ? (const double*)(ws + j.noise_off) : nullptr;
         float* img = (float*)(base + img_off);
         for (long i = (long)blockIdx.x * kT + threadIdx.x; i < plane; i += (long)kImgBlocks * kT) {
@@ -137,37 +142,8 @@ __global__ __launch_bounds__(kT) void ycb_samples_kernel(YcbBatch bt, int job0, 
         }
         return;
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pt = (blockIdx.x - kImgBlocks) * kWaves + wave;       // one chosen point per wave
-    if (pt >= N) return;
-    const int* pf = prefix + (long)s * H;
-    const int rank = sel[(long)s * N + pt];
-    const int y = pose_row_of_rank(pf, H, rank);
-    int rem = rank - pf[y];                          // the pixel's rank inside its row; wave-uniform like everything up to here
-    bool found = false;
-    long long* choose = (long long*)base;
-    float* p = (float*)(base + 8L * N) + 3L * pt;
-    const bool row_in = y >= j.rmin && y < j.rmax;   // (a prefix the caller got wrong: no pixel, zeros)
-    for (int x0 = j.cmin; x0 < j.cmax && !found && row_in; x0 += 64) {
-        const int x = x0 + lane;
-        const bool v = x < j.cmax && ycb_valid(j, (long)y * W + x);
-        const unsigned long long m = __ballot(v);
-        const int c = __popcll(m);
-        if (rem >= 0 && rem < c) {
-            found = true;
-            if (v && __popcll(m & ((1ull << lane) - 1ull)) == rem) {       // exactly one lane
-                float q[3];
-                ycb_point(j, x, y, j.depth[(long)y * W + x], q);
-                choose[pt] = (long long)(y - j.rmin) * Wc + (x - j.cmin);
-                p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
-            }
-        }
-        rem -= c;
-    }
-    if (!found && lane == 0) {
-        choose[pt] = 0;
-        p[0] = p[1] = p[2] = 0.f;
-    }
+    const int pt = (blockIdx.x - kImgBlocks) * kWaves + (threadIdx.x >> 6);
+    if (pt < N) sample_point<YcbPoints>(j, H, W, pt, N, prefix + (long)s * H, sel[(long)s * N + pt], base);
 }
 
 bool list_ok(const ape_ycb_jitter& c) { return jitter_ok(ycb_jitter(c)); }
@@ -183,14 +159,6 @@ bool job_ok(const ape_ycb_job& j, int H, int W)
     if (j.win_r0 < 0 || j.win_r1 > H || j.win_r0 > j.win_r1 || j.win_c0 < 0 || j.win_c1 > W || j.win_c0 > j.win_c1) return false;
     if (!(j.cam_fx != 0.f) || !(j.cam_fy != 0.f) || !(j.cam_scale != 0.f)) return false;             // zero or NaN
     return list_ok(j.jit[0]) && list_ok(j.jit[1]) && list_ok(j.jit[2]);
-}
-
-// get_bbox's crops: sides from border_list inside the frame
-bool crop_ok(const ape_ycb_job& j, int H, int W)
-{
-    const int hc = j.rmax - j.rmin, wc = j.cmax - j.cmin;
-    if (j.rmin < 0 || j.cmin < 0 || j.rmax > H || j.cmax > W || j.rmax <= j.rmin || j.cmax <= j.cmin) return false;
-    return hc >= 40 && hc <= 480 && wc >= 40 && wc <= 640 && hc % 40 == 0 && wc % 40 == 0;
 }
 
 }  // namespace
@@ -211,19 +179,10 @@ extern "C" int ape_ycb_overlap(const ape_ycb_pair* pairs, int P, int H, int W, u
     return check_launch("ape_ycb_overlap");
 }
 
-extern "C" size_t ape_ycb_rows_offset(int B) { return B < 1 ? 0 : (size_t)B * kSrc * kBlocks * sizeof(unsigned long long); }
-
-extern "C" size_t ape_ycb_tables_offset(int B, int H)
-{
-    return B < 1 || H < 1 ? 0 : ape_ycb_rows_offset(B) + up16((size_t)B * H * 3 * sizeof(int));
-}
-
-extern "C" size_t ape_ycb_sel_offset(int B, int H) { return B < 1 || H < 1 ? 0 : ape_ycb_tables_offset(B, H) + (size_t)B * H * sizeof(int); }
-
-extern "C" size_t ape_ycb_noise_offset(int B, int H, int N)
-{
-    return B < 1 || H < 1 || N < 1 ? 0 : up16(ape_ycb_sel_offset(B, H) + (size_t)B * N * sizeof(int));
-}
+extern "C" size_t ape_ycb_rows_offset(int B) { return kLayout.rows(B); }
+extern "C" size_t ape_ycb_tables_offset(int B, int H) { return kLayout.tables(B, H); }
+extern "C" size_t ape_ycb_sel_offset(int B, int H) { return kLayout.sel(B, H); }
+extern "C" size_t ape_ycb_noise_offset(int B, int H, int N) { return kLayout.end(B, H, N); }
 
 extern "C" int ape_ycb_rows(const ape_ycb_job* jobs, int B, int H, int W, void* ws, size_t ws_bytes, void* stream)
 {
@@ -253,10 +212,7 @@ extern "C" int ape_ycb_samples(const ape_ycb_job* jobs, int B, int H, int W, int
         const ape_ycb_job& j = jobs[i];
         if (!job_ok(j, H, W)) return APE_EINVAL;
         if (j.skip) continue;
-        if (!crop_ok(j, H, W)) return APE_EINVAL;
-        if (j.out_off < 0 || (j.out_off & 15)) return APE_EINVAL;
-        const size_t need = ape_pose_train_sample_bytes(N, j.rmax - j.rmin, j.cmax - j.cmin);
-        if ((size_t)j.out_off > out_bytes || out_bytes - (size_t)j.out_off < need) return APE_EINVAL;
+        if (!crop_ok(j, H, W) || !slot_ok(j, N, out_bytes)) return APE_EINVAL;
         if (j.noise_off >= 0) {
             const size_t nb = (size_t)24 * (j.rmax - j.rmin) * (j.cmax - j.cmin);
             if ((j.noise_off & 7) || (size_t)j.noise_off < ape_ycb_noise_offset(B, H, N) || (size_t)j.noise_off > ws_bytes

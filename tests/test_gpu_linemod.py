@@ -132,10 +132,11 @@ def _edge_cases():
 
 def _build(frames, boxes, eval_mode, add_noise, params, subsets):
     """-> per sample the device views or None, and the counts"""
+    from autoposeestimation_amd.DenseFusion.datasets import packed
     from autoposeestimation_amd.DenseFusion.datasets.linemod import augment as G
     dev = [tuple(torch.from_numpy(x).to(DEV) for x in f) for f in frames]
     st = G.count(dev, params, boxes, eval_mode, add_noise, CAM, NUM)
-    sels = [None if c == 0 else G.selection(int(c), NUM, subsets[k]) for k, c in enumerate(st.counts)]
+    sels = [None if c == 0 else packed.selection(int(c), NUM, subsets[k]) for k, c in enumerate(st.counts)]
     return G.samples(st, sels, MEAN, STD), st.counts
 
 

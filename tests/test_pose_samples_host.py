@@ -11,7 +11,7 @@ import torch
 
 from conftest import REPO
 from autoposeestimation_amd import sample_jobs as J
-from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented import augment as G
+from autoposeestimation_amd.DenseFusion.datasets import packed as G
 from autoposeestimation_amd.DenseFusion.datasets.myDatasetAugmented.dataset import bbox_from_extents, get_bbox
 
 H, W = 480, 640
