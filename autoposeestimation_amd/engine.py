@@ -493,6 +493,8 @@ def unet_conv3x3(conv, a, b=None, ups=True, out=None, yoff=0):
     """relu(conv(cat([nearest_up2(a), b])) + bias) (ups=False: a at full resolution) -> out[B,H,W,ldy] channels yoff..yoff+Cout;
     conv: an engine.Conv (3x3 p1, the BN folded into weight and bias, precision bf16x3 | bf16) whose input channels are [a's | b's]"""
     bb, h, w, c1, c2, ldb = _unet_operands(conv, a, b, ups)
+    if conv.act != ACT_RELU:          # (the kernel's epilogue is bias + ReLU: another activation would be dropped without a word)
+        raise ValueError("the Unet decoder kernel's epilogue is ReLU; the layer's activation is %d" % conv.act)
     if not unet_conv3x3_supported(c1, c2, conv.cout, ups):
         raise ValueError("no Unet decoder kernel for C1 %d, C2 %d, Cout %d" % (c1, c2, conv.cout))
     if out is None:
@@ -519,6 +521,8 @@ def unet_conv3x3_seghead(conv, a, b=None, ups=False, double_softmax=True):
     bb, h, w, c1, c2, ldb = _unet_operands(conv, a, b, ups)
     if conv.cout > 16:
         raise ValueError("the fused head takes at most 16 classes")
+    if conv.act != ACT_NONE:          # (the softmax runs on conv + bias)
+        raise ValueError("the fused head applies no activation before the softmax; the layer's activation is %d" % conv.act)
     label = torch.empty(bb, h, w, dtype=torch.uint8, device=a.device)
     score = torch.empty(bb, h, w, dtype=torch.float32, device=a.device)
     klabel = "unet_conv3x3_kernel<%d,%s,1,8,true>" % (conv.nsplit, "true" if ups else "false")
