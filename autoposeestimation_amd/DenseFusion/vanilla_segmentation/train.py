@@ -1,0 +1,165 @@
+"""Drop-in for DenseFusion/vanilla_segmentation/train.py:36-106 -- Adam (lr 1e-4) on the cross-entropy of SegNet's logits,
+`model_current.pth` every 1000 batches, `model_{epoch}_{cost}.pth` whenever the test cost is the best so far, one log file per epoch and
+phase -- plus `segment_files`, which writes the label PNGs the DenseFusion evaluations read.
+
+    from types import SimpleNamespace
+    main(SimpleNamespace(dataset_root=..., batch_size=3, n_epochs=600, workers=10, lr=1e-4, logs_path='logs/',
+                         model_save_path='trained_models/', log_dir='logs/', resume_model=''))
+
+`opt` carries the reference's option names (nothing is parsed at import).  Optional extras: `train_list` / `test_list` (the two txt lists,
+default the YCB config's), `train_length` / `test_length` (5000 / 1000), `manualSeed`, `precision`."""
+import logging
+import os
+import random
+import time
+
+import numpy as np
+import torch
+
+from autoposeestimation_amd import autograd as A
+from autoposeestimation_amd.DenseFusion.vanilla_segmentation.data_controller import SegDataset
+from autoposeestimation_amd.DenseFusion.vanilla_segmentation.loss import Loss
+from autoposeestimation_amd.DenseFusion.vanilla_segmentation.segnet import SegNet
+
+_YCB_CONFIG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "datasets", "ycb", "dataset_config")
+
+
+def setup_logger(logger_name, log_file, level=logging.INFO):
+    """lib/utils.py:4-17 of the reference: a logger that writes to `log_file` and to the console"""
+    logger = logging.getLogger(logger_name)
+    formatter = logging.Formatter("%(asctime)s : %(message)s")
+    file_handler = logging.FileHandler(log_file, mode="w")
+    file_handler.setFormatter(formatter)
+    logger.setLevel(level)
+    logger.addHandler(file_handler)
+    stream_handler = logging.StreamHandler()
+    stream_handler.setFormatter(formatter)
+    logger.addHandler(stream_handler)
+    return logger
+
+
+def _close(logger):
+    for h in list(logger.handlers):
+        h.close()
+        logger.removeHandler(h)
+
+
+def train_step(model, optimizer, rgb, target, criterion=None):
+    """train.py:70-77: forward, zero_grad, loss, backward, step.  -> the loss (a device scalar; reading it checks the labels)"""
+    semantic = model(rgb)
+    optimizer.zero_grad()
+    semantic_loss = (criterion or Loss())(semantic, target)
+    semantic_loss.backward()
+    optimizer.step()
+    return semantic_loss.detach()
+
+
+@torch.no_grad()
+def evaluate(model, batches, criterion=None, log=None):
+    """train.py:86-101: the mean loss of the eval-mode model over `batches` of (rgb, target)"""
+    model.eval()
+    criterion = criterion or Loss()
+    total, n = 0.0, 0
+    for rgb, target in batches:
+        loss = criterion(model(rgb.cuda()), target.cuda()).item()
+        total += loss
+        n += 1
+        if log is not None:
+            log(n, loss)
+    return total / n
+
+
+def main(opt):
+    if getattr(opt, "manualSeed", None) is None:
+        opt.manualSeed = random.randint(1, 10000)
+    random.seed(opt.manualSeed)
+    np.random.seed(opt.manualSeed)
+    torch.manual_seed(opt.manualSeed)
+    train_list = getattr(opt, "train_list", None) or os.path.join(_YCB_CONFIG, "train_data_list.txt")
+    test_list = getattr(opt, "test_list", None) or os.path.join(_YCB_CONFIG, "test_data_list.txt")
+    dataset = SegDataset(opt.dataset_root, train_list, True, int(getattr(opt, "train_length", 5000)))
+    dataloader = torch.utils.data.DataLoader(dataset, batch_size=int(opt.batch_size), shuffle=True, num_workers=int(opt.workers))
+    test_dataset = SegDataset(opt.dataset_root, test_list, False, int(getattr(opt, "test_length", 1000)))
+    test_dataloader = torch.utils.data.DataLoader(test_dataset, batch_size=1, shuffle=True, num_workers=int(opt.workers))
+    print(len(dataset), len(test_dataset))
+
+    model = SegNet().cuda()
+    if getattr(opt, "precision", None):
+        model.set_precision(opt.precision)
+    os.makedirs(opt.model_save_path, exist_ok=True)
+    os.makedirs(opt.log_dir, exist_ok=True)
+    if opt.resume_model != "":
+        model.load_state_dict(torch.load("{0}/{1}".format(opt.model_save_path, opt.resume_model)))
+        for log in os.listdir(opt.log_dir):
+            os.remove(os.path.join(opt.log_dir, log))
+
+    model.train()                            # (the parameters become leaves before the optimizer takes them)
+    optimizer = A.Adam(model.parameters(), lr=float(opt.lr))
+    criterion = Loss()
+    best_val_cost = np.inf
+    st_time = time.time()
+    stamp = lambda: time.strftime("%Hh %Mm %Ss", time.gmtime(time.time() - st_time))  # noqa: E731
+    saved = []
+
+    for epoch in range(1, int(opt.n_epochs)):
+        model.train()
+        train_all_cost = 0.0
+        train_time = 0
+        logger = setup_logger("epoch%d" % epoch, os.path.join(opt.log_dir, "epoch_%d_log.txt" % epoch))
+        logger.info("Train time {0}".format(stamp() + ", " + "Training started"))
+        for rgb, target in dataloader:
+            loss = train_step(model, optimizer, rgb.cuda(), target.cuda(), criterion).item()
+            train_all_cost += loss
+            logger.info("Train time {0} Batch {1} CEloss {2}".format(stamp(), train_time, loss))
+            if train_time != 0 and train_time % 1000 == 0:
+                torch.save(model.state_dict(), os.path.join(opt.model_save_path, "model_current.pth"))
+            train_time += 1
+        train_all_cost = train_all_cost / train_time
+        logger.info("Train Finish Avg CEloss: {0}".format(train_all_cost))
+        _close(logger)
+
+        logger = setup_logger("epoch%d_test" % epoch, os.path.join(opt.log_dir, "epoch_%d_test_log.txt" % epoch))
+        logger.info("Test time {0}".format(stamp() + ", " + "Testing started"))
+        test_all_cost = evaluate(model, test_dataloader, criterion,
+                                 lambda n, loss: logger.info("Test time {0} Batch {1} CEloss {2}".format(stamp(), n, loss)))
+        logger.info("Test Finish Avg CEloss: {0}".format(test_all_cost))
+        _close(logger)
+
+        if test_all_cost <= best_val_cost:
+            best_val_cost = test_all_cost
+            saved.append(os.path.join(opt.model_save_path, "model_{}_{}.pth".format(epoch, test_all_cost)))
+            torch.save(model.state_dict(), saved[-1])
+            print("----------->BEST SAVED<-----------")
+    return saved
+
+
+NORM_MEAN, NORM_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+@torch.no_grad()
+def segment_files(model, colour_paths, out_paths, batch=8, value_map=None):
+    """Label every image of `colour_paths` with the eval-mode model and write the arg-max class map as a one-band PNG to the matching entry
+    of `out_paths`.  The input is data_controller's for a frame without noise: the 0..255 RGB values normalised with NORM_MEAN / NORM_STD.
+    value_map {class: value} rewrites the classes it names (the others become 0): {k: 255} gives the LineMOD `segnet_results` convention
+    (255 = the object) that datasets/linemod/dataset.py reads.  Images of one batch must share a size."""
+    from PIL import Image
+    if len(colour_paths) != len(out_paths):
+        raise ValueError("%d images, %d outputs" % (len(colour_paths), len(out_paths)))
+    model.eval()
+    dev = next(model.parameters()).device
+    mean = torch.tensor(NORM_MEAN, dtype=torch.float32, device=dev).view(1, 3, 1, 1)
+    std = torch.tensor(NORM_STD, dtype=torch.float32, device=dev).view(1, 3, 1, 1)
+    lut = None
+    if value_map is not None:
+        lut = torch.zeros(256, dtype=torch.uint8)
+        for k, v in value_map.items():
+            lut[int(k)] = int(v)
+    for i in range(0, len(colour_paths), batch):
+        frames = [np.array(Image.open(p).convert("RGB")) for p in colour_paths[i:i + batch]]
+        x = torch.from_numpy(np.stack(frames)).to(dev).permute(0, 3, 1, 2).float()
+        labels = model.predict_labels((x - mean) / std).cpu()
+        if lut is not None:
+            labels = lut[labels.long()]
+        for lab, path in zip(labels.numpy(), out_paths[i:i + batch]):
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            Image.fromarray(lab).save(path)

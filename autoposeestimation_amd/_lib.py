@@ -195,6 +195,12 @@ SIGNATURES = {
     "ape_ycb_noise_offset": [_I, _I, _I],
     "ape_ycb_rows": [_P, _I, _I, _I, _P, _c.c_size_t, _P],
     "ape_ycb_samples": [_P, _I, _I, _I, _I, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P],
+    # SegNet glue (csrc/segnet.hip): 2x2 max-pool with its winner codes, unpool, gather, cross-entropy
+    "ape_maxpool2x2_idx_nhwc_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "ape_max_unpool2x2_nhwc_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "ape_gather2x2_nhwc_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "ape_cross_entropy_workspace_bytes": [_c.c_long],
+    "ape_cross_entropy_f32": [_P, _I, _I, _P, _c.c_long, _F, _P, _P, _P, _c.c_size_t, _P],
 }
 
 
@@ -273,12 +279,13 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
              "ape_linemod_box_workspace_bytes": _c.c_size_t, "ape_linemod_rows_offset": _c.c_size_t,
              "ape_linemod_tables_offset": _c.c_size_t, "ape_linemod_sel_offset": _c.c_size_t, "ape_linemod_workspace_bytes": _c.c_size_t,
              "ape_ycb_rows_offset": _c.c_size_t, "ape_ycb_tables_offset": _c.c_size_t, "ape_ycb_sel_offset": _c.c_size_t,
-             "ape_ycb_noise_offset": _c.c_size_t, "ape_pose_errors_workspace_bytes": _c.c_size_t}
+             "ape_ycb_noise_offset": _c.c_size_t, "ape_pose_errors_workspace_bytes": _c.c_size_t,
+             "ape_cross_entropy_workspace_bytes": _c.c_size_t}
 
 _lib = None
 
 
-ABI_VERSION = 13   # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 14   # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

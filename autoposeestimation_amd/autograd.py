@@ -657,3 +657,64 @@ class SGD:
         _lib.call.ape_sgd_step_multi_f32(len(live), jobs, float(self.lr), float(self.momentum), float(self.dampening),
                                          float(self.weight_decay), int(bool(self.nesterov)), _st())
         refresh_banks(live)
+
+
+# ---- SegNet (csrc/segnet.hip): DenseFusion/vanilla_segmentation/segnet.py:74-121, loss.py:11-21 ---------------------------------------------
+class MaxPool2x2IdxFn(torch.autograd.Function):
+    """F.max_pool2d(x, kernel_size=2, stride=2, return_indices=True) on x[B,H,W,C]: returns y; the winners' codes (u8, 2 * dy + dx) stay
+    on the context and, for the model that unpools with them later, on `MaxPool2x2IdxFn.last_code` until the next forward.  Backward: the
+    unpool of dy."""
+    last_code = None
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _c(x)
+        y, code = E.maxpool2x2_idx(x)
+        ctx.code, ctx.hw = code, (x.shape[1], x.shape[2])
+        MaxPool2x2IdxFn.last_code = code
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return E.max_unpool2x2(_c(dy), ctx.code, *ctx.hw)
+
+
+def maxpool2x2_idx(x):
+    """-> (y on the tape, code)"""
+    y = MaxPool2x2IdxFn.apply(x)
+    code, MaxPool2x2IdxFn.last_code = MaxPool2x2IdxFn.last_code, None
+    return y, code
+
+
+class MaxUnpool2x2Fn(torch.autograd.Function):
+    """F.max_unpool2d(y, idx, 2, 2, output_size=(h, w)) with the codes of the pool.  Backward: the gather at the coded positions."""
+
+    @staticmethod
+    def forward(ctx, y, code, h, w):
+        ctx.code = code
+        return E.max_unpool2x2(_c(y), code, h, w)
+
+    @staticmethod
+    def backward(ctx, dx):
+        return E.gather2x2(_c(dx), ctx.code), None, None, None
+
+
+class CrossEntropyFn(torch.autograd.Function):
+    """nn.CrossEntropyLoss() (mean) over the pixels of NHWC logits[..., C] and u8 labels: -> (loss, bad), float64 scalars on the device:
+    the mean over the valid pixels and the number of labels >= C (not differentiable).  The forward already has the softmax, so it writes
+    d loss / d logits too; backward scales that by the incoming gradient.  A caller that reads the loss must treat bad != 0 as an error
+    (loss.loss_calculation does): torch raises in its forward, here the check rides on the read, without a synchronisation."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        logits = _c(logits)
+        out, dlogits = E.cross_entropy(logits, labels, want_grad=True)
+        ctx.save_for_backward(dlogits)
+        loss, bad = out[0], out[1]
+        ctx.mark_non_differentiable(bad)
+        return loss, bad
+
+    @staticmethod
+    def backward(ctx, g, _g_bad):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * g.to(dlogits.dtype), None

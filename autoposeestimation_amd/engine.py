@@ -617,6 +617,56 @@ def maxpool3x3s2(x):
     return y
 
 
+# ---- SegNet glue (csrc/segnet.hip) ----------------------------------------------------------------------------------------------------
+def maxpool2x2_idx(x):
+    """F.max_pool2d(x, 2, 2, return_indices=True) on x[B,H,W,C]: -> y[B,H//2,W//2,C] f32, code[B,H//2,W//2,C] u8 = 2 * dy + dx of each
+    window's winner (torch's CPU tie / NaN rule)"""
+    b, h, w, c = x.shape
+    y = torch.empty(b, h // 2, w // 2, c, dtype=torch.float32, device=x.device)
+    code = torch.empty(b, h // 2, w // 2, c, dtype=torch.uint8, device=x.device)
+    _lib.call.ape_maxpool2x2_idx_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(y), _lib.dptr(code), b, h, w, c, _st())
+    return y, code
+
+
+def max_unpool2x2(y, code, h, w):
+    """F.max_unpool2d(y, idx, 2, 2, output_size=(h, w)) for the codes of `maxpool2x2_idx`: y[B,h//2,w//2,C] -> x[B,h,w,C], every element
+    written (zeros off the coded positions and in an odd last row / column)"""
+    b, ho, wo, c = y.shape
+    if (ho, wo) != (h // 2, w // 2) or tuple(code.shape) != tuple(y.shape):
+        raise ValueError("max_unpool2x2: y %s / code %s do not pool a %d x %d map" % (tuple(y.shape), tuple(code.shape), h, w))
+    x = torch.empty(b, h, w, c, dtype=torch.float32, device=y.device)
+    _lib.call.ape_max_unpool2x2_nhwc_f32(_lib.dptr(y, torch.float32), _lib.dptr(code, torch.uint8), _lib.dptr(x), b, h, w, c, _st())
+    return x
+
+
+def gather2x2(x, code):
+    """y[B,H//2,W//2,C] = the element of each 2 x 2 window of x[B,H,W,C] that `code` names (the unpool's backward)"""
+    b, h, w, c = x.shape
+    if tuple(code.shape) != (b, h // 2, w // 2, c):
+        raise ValueError("gather2x2: code %s does not pool %s" % (tuple(code.shape), tuple(x.shape)))
+    y = torch.empty(b, h // 2, w // 2, c, dtype=torch.float32, device=x.device)
+    _lib.call.ape_gather2x2_nhwc_f32(_lib.dptr(x, torch.float32), _lib.dptr(code, torch.uint8), _lib.dptr(y), b, h, w, c, _st())
+    return y
+
+
+def cross_entropy(logits, labels, n_classes=None, g=1.0, want_grad=False):
+    """nn.CrossEntropyLoss() over the pixels of logits[..., ld] (classes = the first n_classes channels) and labels u8 of the leading shape.
+    -> out f64[2] on the device (the mean over the valid pixels; the number of labels >= n_classes, which the caller must treat as an
+    error when it reads the loss) and, with want_grad, dlogits = g * (softmax - onehot) / n_valid in the layout of `logits`."""
+    ld = logits.shape[-1]
+    c = ld if n_classes is None else int(n_classes)
+    p = logits.numel() // ld
+    if labels.numel() != p:
+        raise ValueError("cross_entropy: %d labels for %d pixels" % (labels.numel(), p))
+    out = torch.empty(2, dtype=torch.float64, device=logits.device)
+    dlogits = torch.empty_like(logits) if want_grad else None
+    nbytes = _lib.lib().ape_cross_entropy_workspace_bytes(p)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
+    _lib.call.ape_cross_entropy_f32(_lib.dptr(logits, torch.float32), ld, c, _lib.dptr(labels, torch.uint8), p, float(g), _lib.dptr(out),
+                                    _lib.dptr(dlogits), _lib.dptr(ws), nbytes, _st())
+    return out, dlogits
+
+
 def adaptive_avgpool(x, s):
     b, h, w, c = x.shape
     y = torch.empty(b, s, s, c, dtype=torch.float32, device=x.device)

@@ -135,6 +135,26 @@ def unet_state_dict(encoder="resnet34", seed=0, in_channels=3, classes=1):
         sd[key] = _normal(seed, key, shape, (2.0 / fan_in) ** 0.5)
     return sd
 
+def segnet_state_dict(seed=0, input_nbr=3, label_nbr=22):
+    """Synthetic weights with every key of DenseFusion/vanilla_segmentation/segnet.py:SegNet, in its state-dict order: He-normal
+    convolutions, biases ~ N(0, 0.1), gamma ~ U(0.5, 1.5), beta ~ N(0, 0.1), running statistics away from (0, 1) (mean +-0.2, variance
+    0.5..2): activations stay O(1) through the 26 layers"""
+    from autoposeestimation_amd.DenseFusion.vanilla_segmentation.segnet import layer_table
+    sd = OrderedDict()
+    for name, cin, cout, has_bn in layer_table(input_nbr, label_nbr):
+        k = "conv" + name
+        sd[k + ".weight"] = _normal(seed, k + "w", (cout, cin, 3, 3), (2.0 / (9 * cin)) ** 0.5)
+        sd[k + ".bias"] = _normal(seed, k + "b", (cout,), 0.1)
+        if has_bn:
+            k = "bn" + name
+            sd[k + ".weight"] = torch.from_numpy((0.5 + _rng(seed, k + "g").random(cout)).astype(np.float32))
+            sd[k + ".bias"] = _normal(seed, k + "b", (cout,), 0.1)
+            sd[k + ".running_mean"] = _uniform(seed, k + "m", (cout,), 0.2)
+            sd[k + ".running_var"] = torch.from_numpy((0.5 + 1.5 * _rng(seed, k + "v").random(cout)).astype(np.float32))
+            sd[k + ".num_batches_tracked"] = torch.tensor(1000, dtype=torch.int64)
+    return sd
+
+
 def _pointnet_spec(refine):
     c5 = 384 if refine else 256
     return [("feat.conv1.weight", (64, 3, 1)), ("feat.conv1.bias", (64,)),

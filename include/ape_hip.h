@@ -943,6 +943,31 @@ int ape_ycb_rows(const ape_ycb_job* jobs_host, int B, int H, int W, void* ws, si
 int ape_ycb_samples(const ape_ycb_job* jobs_host, int B, int H, int W, int N, const float* mean3_host, const float* std3_host, void* out,
                     size_t out_bytes, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- SegNet glue (csrc/segnet.hip): DenseFusion/vanilla_segmentation/segnet.py:74-121, loss.py:11-21 --------------------------------
+ * All NHWC fp32, C % 4 == 0, 16-byte aligned maps (codes 4-byte aligned).  APE_EINVAL: a negative size, C % 4 != 0, more than 2^31
+ * elements, a null or misaligned pointer to a non-empty buffer; APE_OK without a launch when there is nothing to write.
+ *
+ * F.max_pool2d(x, kernel_size=2, stride=2, return_indices=True): x[B][H][W][C] -> y[B][H/2][W/2][C] and code[B][H/2][W/2][C] (an odd
+ * last row / column is dropped), code = 2 * dy + dx of the winner.  ATen's CPU rule: scan (0,0) (0,1) (1,0) (1,1) from -inf at position
+ * 0 and take an element if `v > best || isnan(v)` -- the first of equal maxima, the last NaN. */
+int ape_maxpool2x2_idx_nhwc_f32(const float* x, float* y, uint8_t* code, int B, int H, int W, int C, void* stream);
+/* F.max_unpool2d(y, idx, 2, 2, output_size=(H, W)): EVERY element of x[B][H][W][C] is written -- y at the coded position of its window,
+ * 0 at the other three and in an odd last row / column -- by the one thread that owns its window (no memset, no scatter).  Also the
+ * backward of the pool above. */
+int ape_max_unpool2x2_nhwc_f32(const float* y, const uint8_t* code, float* x, int B, int H, int W, int C, void* stream);
+/* y[B][H/2][W/2][C] = the element of each 2x2 window of x[B][H][W][C] that code names: the backward of the unpool. */
+int ape_gather2x2_nhwc_f32(const float* x, const uint8_t* code, float* y, int B, int H, int W, int C, void* stream);
+/* nn.CrossEntropyLoss() (mean) over the P pixels of logits[P][ld], classes = channels 0..C-1 (1 <= C <= 64, C <= ld; channels
+ * C..ld-1 are never read), labels[P] u8.  out[0] = mean over the VALID pixels (label < C) of logsumexp(x) - x[label] (maximum subtracted,
+ * fp32 per pixel, summed in float64 in a fixed two-stage order: two launches agree bit for bit), out[1] = the number of pixels with a
+ * label >= C, which add nothing to the loss or the gradient.  dlogits (may be NULL): dlogits[p][c] = g * (softmax - onehot) / n_valid,
+ * channels C..ld-1 written 0.  Three launches with a gradient (terms + unscaled gradient, the mean, the scale), two without.
+ * P == 0 is NOT a no-op: `out` must still be defined, so the mean and the count are written -- NaN (0 / 0, torch's mean over nothing)
+ * and 0; dlogits is then untouched.  A short workspace: APE_EWORKSPACE. */
+size_t ape_cross_entropy_workspace_bytes(long P);
+int ape_cross_entropy_f32(const float* logits, int ld, int C, const uint8_t* labels, long P, float g, double* out, float* dlogits,
+                          void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
