@@ -201,6 +201,9 @@ SIGNATURES = {
     "ape_gather2x2_nhwc_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
     "ape_cross_entropy_workspace_bytes": [_c.c_long],
     "ape_cross_entropy_f32": [_P, _I, _I, _P, _c.c_long, _F, _P, _P, _P, _c.c_size_t, _P],
+    # overlays (csrc/overlay.hip): the color_prediction images of pipeline/utils.py:471-476,576-585 and the review screens' :280-286,362
+    "ape_overlay_stamp_counts_f64": [_P, _I, _P, _c.c_long, _P, _I, _P, _D, _D, _D, _D, _I, _P, _I, _I, _I, _I, _P],
+    "ape_overlay_blend_u8": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
 }
 
 
@@ -285,7 +288,7 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
 _lib = None
 
 
-ABI_VERSION = 14   # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 15  # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

@@ -1072,6 +1072,75 @@ def backproject(depth, objects, choose, intr, depth_scale):
     return pts
 
 
+# ---- overlays (csrc/overlay.hip) ------------------------------------------------------------------------------------------
+OVERLAY_F64, OVERLAY_U8 = 0, 1      # blend arithmetic: full_prediction's float64 images / the review screens' uint8 arrays
+_overlay_planes = {}
+
+
+def overlay_planes(j, b, h, w, device):
+    """the count planes [J,B,H,W] (u32 counts in an int32 tensor) of an overlay call: one cached buffer per device and stream, grown on
+    demand (the stamp call clears what it uses); fresh memory while a graph is being captured"""
+    n = j * b * h * w
+    if CAPTURING:
+        return torch.empty(n, dtype=torch.int32, device=device).view(j, b, h, w)
+    key = (str(device), torch.cuda.current_stream().cuda_stream)
+    buf = _overlay_planes.get(key)
+    if buf is None or buf.numel() < n:
+        buf = _overlay_planes[key] = torch.empty(n, dtype=torch.int32, device=device)
+    return buf[:n].view(j, b, h, w)
+
+
+def overlay_stamp_counts(objs_host, clouds, pose, n_cand, intr, point_size, planes):
+    """objs_host[n,4] int32 numpy (frame, first cloud row, rows, plane), clouds[sum M,3] f64, pose[n,7] (w,x,y,z,t) or [n,3,4] ([R|t]) f64,
+    n_cand[n] i32 or None -> planes[J,B,H,W] cleared, then one count per stamp centre whose stamp lies inside the image"""
+    import numpy as np
+    objs_host = np.ascontiguousarray(objs_host, dtype=np.int32).reshape(-1, 4)
+    n = objs_host.shape[0]
+    j, b, h, w = planes.shape
+    form = 0 if pose.dim() == 2 and pose.shape[1] == 7 else 1 if tuple(pose.shape[1:]) == (3, 4) else None
+    if form is None or pose.shape[0] != n or (n_cand is not None and n_cand.numel() != n) or clouds.dim() != 2 or clouds.shape[1] != 3:
+        raise _lib.ApeError("overlay_stamp_counts: pose[n,7] or [n,3,4], n_cand[n] and clouds[M,3] expected for %d objects, got %s, %s, %s"
+                            % (n, tuple(pose.shape), None if n_cand is None else tuple(n_cand.shape), tuple(clouds.shape)))
+    label = "overlay_stamp_counts_kernel"
+    e0 = _prof_begin(label)
+    _lib.call.ape_overlay_stamp_counts_f64(objs_host.ctypes.data_as(ctypes.c_void_p), n, _lib.dptr(clouds, torch.float64), clouds.shape[0],
+                                           _lib.dptr(pose, torch.float64), form, _lib.dptr(n_cand, torch.int32) if n_cand is not None else None,
+                                           float(intr["fx"]), float(intr["fy"]), float(intr["ppx"]), float(intr["ppy"]), int(point_size),
+                                           _lib.dptr(planes, torch.int32), j, b, h, w, _st())
+    rows = int(objs_host[:, 2].sum()) if n else 0
+    _prof_end(e0, label, "%dx%dx%d n%d pts%d" % (b, h, w, n, rows), 40.0 * rows, 24.0 * rows + 4.0 * rows + 4.0 * j * b * h * w)
+    return planes
+
+
+def overlay_blend(rgb, objmap, slot_obj, obj_cls, seg_colour, mark, n_cand, planes, point_size, mode):
+    """rgb[B,H,W,3] u8, objmap[B,H,W] u8 or None, slot_obj[B,J] i32, obj_cls[n] i32, seg_colour / mark [n,3] f64 or None (red), n_cand[n] i32
+    or None, planes[J,B,H,W] -> (seg[B,H,W,3], pose[B,H,W,3]) u8"""
+    j, b, h, w = planes.shape
+    n = obj_cls.numel()
+    if tuple(rgb.shape) != (b, h, w, 3) or tuple(slot_obj.shape) != (b, j) or (objmap is not None and tuple(objmap.shape) != (b, h, w)):
+        raise _lib.ApeError("overlay_blend: rgb[B,H,W,3], objmap[B,H,W] and slot_obj[B,J] expected for planes %s, got %s, %s, %s"
+                            % (tuple(planes.shape), tuple(rgb.shape), None if objmap is None else tuple(objmap.shape), tuple(slot_obj.shape)))
+    for name, t in (("seg_colour", seg_colour), ("mark", mark)):
+        if t is not None and tuple(t.shape) != (n, 3):
+            raise _lib.ApeError("overlay_blend: %s[%d,3] expected, got %s" % (name, n, tuple(t.shape)))
+    if n_cand is not None and n_cand.numel() != n:
+        raise _lib.ApeError("overlay_blend: n_cand[%d] expected, got %s" % (n, tuple(n_cand.shape)))
+    if rgb.data_ptr() & 3:
+        rgb = rgb.clone()               # (a view that starts inside an allocation: the kernel reads dwords)
+    seg = torch.empty_like(rgb)
+    pose_img = torch.empty_like(rgb)
+    label = "overlay_blend_kernel"
+    e0 = _prof_begin(label)
+    opt = lambda t, dt: _lib.dptr(t, dt) if t is not None else None  # noqa: E731
+    _lib.call.ape_overlay_blend_u8(_lib.dptr(rgb, torch.uint8), opt(objmap, torch.uint8), _lib.dptr(slot_obj, torch.int32),
+                                   _lib.dptr(obj_cls, torch.int32), opt(seg_colour, torch.float64), opt(mark, torch.float64),
+                                   opt(n_cand, torch.int32), n, _lib.dptr(planes, torch.int32), j, b, h, w, int(point_size), int(mode),
+                                   _lib.dptr(seg), _lib.dptr(pose_img), _st())
+    px = b * h * w
+    _prof_end(e0, label, "%dx%dx%d J%d" % (b, h, w, j), 12.0 * px, px * (3.0 + 1.0 + 4.0 * j + 6.0))
+    return seg, pose_img
+
+
 # ---- ADD / ADD-S ------------------------------------------------------------------------------------------------------
 def adds_dis(pred_r, pred_t, points, model, target, symmetric, want_pred=False, want_std=True):
     """pred_r[N,4], pred_t[N,3], points[N,3]|None, model[M,3], target[M,3] -> dis[N], std[N]|None, pred[N,M,3]|None"""

@@ -270,6 +270,12 @@ class FramePipeline:
         """Whole batch.  Returns dict(objects=[(frame,cls,rmin,rmax,cmin,cmax)], pose, n_cand, choose, objmap)."""
         return self.finish(self.begin(rgb, inject_logits, asynchronous=False), rgb, depth, meta, choose_override, seed)
 
+    def overlays(self, result, rgb, meta, point_clouds, color_dict, point_size=3):
+        """The live view's images of a batch that run() / finish() returned: (segmented[B,H,W,3], pose[B,H,W,3]) u8 on the device --
+        every class with a pose tinted with its colour, every object's model cloud stamped at its pose (pipeline/overlay.py)."""
+        from autoposeestimation_amd.pipeline import overlay
+        return overlay.overlays(self, result, rgb, meta, point_clouds, color_dict, point_size)
+
 
 def _as_u8_frame(image):
     arr = np.asarray(image)
@@ -285,8 +291,9 @@ def full_prediction(image, depth, meta, segmentor, estimator, refiner, to_tensor
         {'predictions': {cls_name: {'mask': u8[H,W] in {0,255}, 'position': f64[3] (m), 'rotation': f64[4] wxyz}},
          'elapsed_times': {'segmentation', 'pose_estimation', 'total'}}
     `to_tensor` / `normalize` are accepted for signature compatibility; the normalisation runs on the device.
-    `color_prediction` adds 'segmented_prediction' / 'pose_prediction' images (plain alpha blends; cv2 text/boxes are
-    skipped when OpenCV is absent).  Objects without a valid depth pixel are dropped like the reference (:530-531,623-635)."""
+    `color_prediction` adds the 'segmented_prediction' / 'pose_prediction' images, painted on the device (pipeline/overlay.py) and
+    copied down once.  `bbox` and `put_text` are accepted and ignored: cv2.rectangle / cv2.putText are out of scope (OpenCV's
+    rasteriser and font cannot be pinned without it).  Objects without a valid depth pixel are dropped like the reference (:530-531,623-635)."""
     if not cuda or not torch.cuda.is_available():
         raise RuntimeError("full_prediction needs the GPU: the MI355X path has no CPU fallback")
     start_time = time.time()
@@ -326,20 +333,14 @@ def full_prediction(image, depth, meta, segmentor, estimator, refiner, to_tensor
             output_dict["predictions"][name]["position"] = pose_h[i, 4:7].copy()
             output_dict["predictions"][name]["rotation"] = pose_h[i, 0:4].copy()
     if color_prediction:
-        from autoposeestimation_amd.pc_reconstruction import open3d_utils as pc_utils
-        seg_img = rgb_np.astype(np.float64)
-        pose_img = rgb_np.astype(np.float64)
-        for name, pred in output_dict["predictions"].items():
-            colour = np.asarray(color_dict[name]["value"], dtype=np.float64)
-            m = pred["mask"] != 0
-            seg_img[m] = seg_img[m] * 0.7 + colour * 0.3
-            if point_clouds is not None:
-                from autoposeestimation_amd.DenseFusion.lib.transformations import quaternion_matrix
-                R = quaternion_matrix(pred["rotation"])[:3, :3]
-                cloud = np.dot(point_clouds[class_names.index(name)], R.T) + pred["position"]
-                pose_img = pc_utils.pointcloud2image(pose_img, cloud, 3, meta["intr"], color=list(colour))
-        output_dict["segmented_prediction"] = np.clip(seg_img, 0, 255).astype(np.uint8)
-        output_dict["pose_prediction"] = np.clip(pose_img, 0, 255).astype(np.uint8)
+        # both images on the device, from the tensors the stages left there (pipeline/overlay.py); one copy down
+        from autoposeestimation_amd.pipeline import overlay
+        colours = {o[1] - 1: color_dict[class_names[o[1] - 1]]["value"] for o in objects if class_names[o[1] - 1] in output_dict["predictions"]}
+        colours.update({o[1] - 1: (0.0, 0.0, 0.0) for o in objects if o[1] - 1 not in colours})        # (dropped: n_cand == 0, never painted)
+        seg_d, pose_d = overlay.paint_predictions(rgb, objmap, objects, pose if objects else None, n_cand if objects else None,
+                                                  point_clouds, colours, meta["intr"], 3, "f64")
+        both = torch.stack([seg_d[0], pose_d[0]]).cpu().numpy()
+        output_dict["segmented_prediction"], output_dict["pose_prediction"] = both[0], both[1]
     output_dict["elapsed_times"]["pose_estimation"] = time.time() - start_time_pose
     output_dict["elapsed_times"]["total"] = time.time() - start_time
     return output_dict

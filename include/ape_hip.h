@@ -968,6 +968,42 @@ size_t ape_cross_entropy_workspace_bytes(long P);
 int ape_cross_entropy_f32(const float* logits, int ld, int C, const uint8_t* labels, long P, float g, double* out, float* dlogits,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* ---- overlays of the live view and of the label-review screens (csrc/overlay.hip) -------------------------------------------------
+ * Replaces the `color_prediction` painting of full_prediction, pipeline/utils.py:471-476 (class tint), :510-513 and :576-585 (model
+ * cloud stamped at the predicted pose) with pc_reconstruction/open3d_utils.py:233-243 (points2pixel) and :246-270 (pointcloud2image);
+ * and the arithmetic of visualise_segmentation_maks :280-286 and visualise_pose_label :357-362.
+ *
+ * Count planes: planes[J][B][H][W] u32; plane j of frame b belongs to the j-th object of that frame.
+ *
+ * Stamp counts.  objs_host[n][4] i32 (HOST) = (frame, first row, rows, plane) of each object: its model cloud is rows
+ * first .. first+rows-1 of clouds[total_points][3] f64.  pose_form 0: pose[n][7] f64 (w,x,y,z,tx,ty,tz), R as
+ * DenseFusion/lib/transformations.py:1254-1278 (quaternion_matrix); pose_form 1: pose[n][3][4] f64 row-major [R|t].  n_cand: NULL, or
+ * n_cand[n] i32 -- an object with n_cand <= 0 stamps nothing.  The call first clears all J*B*H*W counts, then per model point, in
+ * float64 with one rounding per multiply and add: p' = R.p + t (each row summed left to right), col = (long long) (x'/(z'/fx) + ppx),
+ * row = (long long) (y'/(z'/fy) + ppy) (truncation toward zero, points2pixel's int()); with step = (point_size-1)/2 the centre counts
+ * -- one integer atomic add -- only if row-step >= 0, col-step >= 0, row+step+1 <= H and col+step+1 <= W (the stamps that
+ * pointcloud2image keeps).  Points with z' == 0 or a projected coordinate that is not finite or outside int32 are skipped.
+ * APE_EINVAL, nothing enqueued: a null planes (or, with n > 0, objs_host / clouds / pose), point_size even or < 1, B, H, W or J <= 0,
+ * B*H*W >= 2^31, a frame outside 0..B-1, a plane outside 0..J-1, first + rows beyond total_points, a misaligned pointer. */
+int ape_overlay_stamp_counts_f64(const int32_t* objs_host, int n, const double* clouds, long total_points, const double* pose,
+                                 int pose_form, const int32_t* n_cand, double fx, double fy, double ppx, double ppy, int point_size,
+                                 uint32_t* planes, int J, int B, int H, int W, void* stream);
+/* Blend.  rgb[B][H][W][3] u8 -> seg_out, pose_out of the same shape, every byte written, in one pass.  slot_obj[B][J] i32 = the object
+ * that owns plane j of frame b, in painting order, or -1; obj_cls[n] i32 = the class whose pixels of objmap[B][H][W] u8 the object tints
+ * (<= 0: none; objmap NULL: no tint at all); seg_colour[n][3] and mark[n][3] f64 = its tint and its stamp colour (NULL: (255,0,0), the
+ * default of open3d_utils.py:251-255); n_cand as above: such an object is painted in neither image.
+ *   seg_out:  v*0.7 + colour*0.3 where the pixel's class is a painted object's class of its frame, else the frame's pixel.
+ *   pose_out: per object in plane order, k = its counts summed over the point_size x point_size neighbourhood of the pixel = the stamps
+ *             covering it; v = (mark*0.3) + (v*0.7) applied k times (the loop leaves early only when an application returns its input
+ *             bit for bit).
+ * mode 0 (full_prediction): v stays float64 through all blends, clip(0,255) and truncation to u8 once at the end.  mode 1 (the review
+ * screens, which blend into a uint8 array): v is truncated to u8 after every application; the tint likewise.
+ * APE_EINVAL, nothing enqueued: a null rgb / slot_obj / planes / seg_out / pose_out (or, with n > 0, obj_cls), aliased images, point_size even or < 1,
+ * B, H, W or J <= 0, an unknown mode, an image or table not aligned to its element (images: 4 bytes). */
+int ape_overlay_blend_u8(const uint8_t* rgb, const uint8_t* objmap, const int32_t* slot_obj, const int32_t* obj_cls,
+                         const double* seg_colour, const double* mark, const int32_t* n_cand, int n, const uint32_t* planes,
+                         int J, int B, int H, int W, int point_size, int mode, uint8_t* seg_out, uint8_t* pose_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
