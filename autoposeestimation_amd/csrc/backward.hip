@@ -9,14 +9,14 @@
 //   activation, bias, pooling, resize, log-softmax, gather, mean: one small streaming kernel each
 //   Adam                                 torch.optim.Adam's update rule on flat fp32 buffers
 // All tensors are NHWC fp32 as in the forward path.
-#include "common.h"
+#include "mfma_common.h"
 
 namespace {
 
-constexpr int kT = 256;
-static inline int grid_for(long n) { long g = (n + kT - 1) / kT; return (int)(g < 1 ? 1 : (g > 65535 ? 65535 : g)); }
+using namespace ape;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int kT = 256;
+constexpr int kGridCap = 65535;        // most workgroups of a grid-stride launch (ape::grid_for)
 
 // ---- convolution weight gradient ---------------------------------------------------------------------------------------
 // workgroup tile: 64 output channels x 64 weight columns (column n = tap * Cin + ci), 16 pixels per step, 4 waves each a
@@ -259,13 +259,6 @@ __global__ void adaptive_avgpool_bwd_kernel(const float* __restrict__ dy, float*
     }
 }
 
-__device__ __forceinline__ float src_index_b(int dst, float scale, bool align_corners)
-{
-    if (align_corners) return scale * (float)dst;
-    const float s = scale * ((float)dst + 0.5f) - 0.5f;
-    return s < 0.f ? 0.f : s;
-}
-
 // bilinear resize backward: scatter of every output gradient to its four sources (dx zeroed by the caller; fp32 atomics, the
 // summation order is not fixed -> last-bit differences between runs)
 __global__ void bilinear_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int B, int H, int W, int C, int Ho, int Wo,
@@ -278,7 +271,7 @@ __global__ void bilinear_bwd_kernel(const float* __restrict__ dy, float* __restr
         const int ox = t % Wo; t /= Wo;
         const int oy = t % Ho;
         const int b = t / Ho;
-        const float fy = src_index_b(oy, sh, align_corners), fx = src_index_b(ox, sw, align_corners);
+        const float fy = src_index(oy, sh, align_corners), fx = src_index(ox, sw, align_corners);
         const int y0 = (int)fy, x0 = (int)fx;
         const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
         const float ly1 = fy - (float)y0, lx1 = fx - (float)x0, ly0 = 1.f - ly1, lx0 = 1.f - lx1;
@@ -390,7 +383,7 @@ __global__ void pack_train_weights_kernel(const ape_pack_job* __restrict__ jobs)
         if (hi) {
             const __bf16 h = (__bf16)v;
             hi[i] = h;
-            hi[total + i] = (__bf16)(v - (float)h);
+            hi[total + i] = split_lo(v, h);
         }
     }
 }
@@ -433,9 +426,9 @@ static int wgrad_run(const float* x, const float* dy, float* dw, const ape_conv_
     hipLaunchKernelGGL(conv_wgrad_kernel, dim3(ape::ceil_div(ncols, WG_N), ape::ceil_div(p.Cout, WG_M), splits), dim3(kT), 0, st, x, dy,
                        ws, p, ncols, npix, pps);
     if (cin_param > 0)
-        hipLaunchKernelGGL(split_reduce_param_kernel, dim3(grid_for(nw)), dim3(kT), 0, st, ws, dw, p.Cout, cin_param, p.KH * p.KW, p.Cin, splits);
+        hipLaunchKernelGGL(split_reduce_param_kernel, dim3(ape::grid_for(nw, kT, kGridCap)), dim3(kT), 0, st, ws, dw, p.Cout, cin_param, p.KH * p.KW, p.Cin, splits);
     else
-        hipLaunchKernelGGL(split_reduce_kernel, dim3(grid_for(nw)), dim3(kT), 0, st, ws, dw, nw, splits);
+        hipLaunchKernelGGL(split_reduce_kernel, dim3(ape::grid_for(nw, kT, kGridCap)), dim3(kT), 0, st, ws, dw, nw, splits);
     return ape::check_launch(what);
 }
 
@@ -458,7 +451,7 @@ extern "C" int ape_act_bwd_f32(const float* dy, const float* ref, float* dx, lon
 {
     if (!dy || !dx || n < 0 || act < APE_ACT_NONE || act > APE_ACT_SIGMOID || (act != APE_ACT_NONE && !ref)) return APE_EINVAL;
     if (n == 0) return APE_OK;
-    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(n)), dim3(kT), 0, (hipStream_t)stream, dy, ref ? ref : dy, dx, n, act, alpha);
+    hipLaunchKernelGGL(act_bwd_kernel, dim3(ape::grid_for(n, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, dy, ref ? ref : dy, dx, n, act, alpha);
     return ape::check_launch("ape_act_bwd_f32");
 }
 
@@ -466,7 +459,7 @@ extern "C" int ape_prelu_f32(const float* x, float* y, long n, float alpha, void
 {
     if (!x || !y || n < 0) return APE_EINVAL;
     if (n == 0) return APE_OK;
-    hipLaunchKernelGGL(prelu_fwd_kernel, dim3(grid_for(n)), dim3(kT), 0, (hipStream_t)stream, x, y, n, alpha);
+    hipLaunchKernelGGL(prelu_fwd_kernel, dim3(ape::grid_for(n, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, x, y, n, alpha);
     return ape::check_launch("ape_prelu_f32");
 }
 
@@ -474,7 +467,7 @@ extern "C" int ape_prelu_f32(const float* x, float* y, long n, float alpha, void
 extern "C" int ape_prelu_dalpha_f32(const float* dy, const float* x, float* dalpha, long n, float* scratch1024, void* stream)
 {
     if (!dy || !x || !dalpha || !scratch1024 || n < 0) return APE_EINVAL;
-    int g = grid_for(n);
+    int g = ape::grid_for(n, kT, kGridCap);
     g = g > 1024 ? 1024 : g;
     hipLaunchKernelGGL(prelu_dalpha_kernel, dim3(g), dim3(kT), 0, (hipStream_t)stream, dy, x, scratch1024, n);
     hipLaunchKernelGGL(sum_small_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, scratch1024, dalpha, g);
@@ -494,7 +487,7 @@ extern "C" int ape_colsum_f32(const float* x, float* out, long rows, int C, int 
     groups = groups > 64 ? 64 : groups;
     const long rpg = (rows + groups - 1) / groups;
     hipLaunchKernelGGL(colsum_kernel, dim3(ape::ceil_div(C, 64), groups), dim3(kT), 0, st, x, scratch, rows, C, ld, off, rpg);
-    hipLaunchKernelGGL(split_reduce_kernel, dim3(grid_for(C)), dim3(kT), 0, st, scratch, out, (long)C, groups);
+    hipLaunchKernelGGL(split_reduce_kernel, dim3(ape::grid_for(C, kT, kGridCap)), dim3(kT), 0, st, scratch, out, (long)C, groups);
     return ape::check_launch("ape_colsum_f32");
 }
 
@@ -504,7 +497,7 @@ extern "C" int ape_maxpool3x3s2_bwd_nhwc_f32(const float* x, const float* dy, fl
     const long total = (long)B * H * W * C;
     if (total == 0) return APE_OK;
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    hipLaunchKernelGGL(maxpool3x3s2_bwd_kernel, dim3(grid_for(total)), dim3(kT), 0, (hipStream_t)stream, x, dy, dx, B, H, W, C, Ho, Wo);
+    hipLaunchKernelGGL(maxpool3x3s2_bwd_kernel, dim3(ape::grid_for(total, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, x, dy, dx, B, H, W, C, Ho, Wo);
     return ape::check_launch("ape_maxpool3x3s2_bwd_nhwc_f32");
 }
 
@@ -513,7 +506,7 @@ extern "C" int ape_adaptive_avgpool_bwd_nhwc_f32(const float* dy, float* dx, int
     if (!dy || !dx || B < 0 || H < 1 || W < 1 || C < 1 || S < 1) return APE_EINVAL;
     const long total = (long)B * H * W * C;
     if (total == 0) return APE_OK;
-    hipLaunchKernelGGL(adaptive_avgpool_bwd_kernel, dim3(grid_for(total)), dim3(kT), 0, (hipStream_t)stream, dy, dx, B, H, W, C, S);
+    hipLaunchKernelGGL(adaptive_avgpool_bwd_kernel, dim3(ape::grid_for(total, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, dy, dx, B, H, W, C, S);
     return ape::check_launch("ape_adaptive_avgpool_bwd_nhwc_f32");
 }
 
@@ -534,7 +527,7 @@ extern "C" int ape_bilinear_bwd_nhwc_f32(const float* dy, float* dx, int B, int 
         sh = (float)H / (float)Ho;
         sw = (float)W / (float)Wo;
     }
-    hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(grid_for(total)), dim3(kT), 0, st, dy, dx, B, H, W, C, Ho, Wo, sh, sw, align_corners);
+    hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(ape::grid_for(total, kT, kGridCap)), dim3(kT), 0, st, dy, dx, B, H, W, C, Ho, Wo, sh, sw, align_corners);
     return ape::check_launch("ape_bilinear_bwd_nhwc_f32");
 }
 
@@ -542,7 +535,7 @@ extern "C" int ape_log_softmax_bwd_rows_f32(const float* dy, const float* y, flo
 {
     if (!dy || !y || !dx || rows < 0 || C < 1) return APE_EINVAL;
     if (rows == 0) return APE_OK;
-    hipLaunchKernelGGL(log_softmax_bwd_kernel, dim3(grid_for(rows)), dim3(kT), 0, (hipStream_t)stream, dy, y, dx, rows, C);
+    hipLaunchKernelGGL(log_softmax_bwd_kernel, dim3(ape::grid_for(rows, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, dy, y, dx, rows, C);
     return ape::check_launch("ape_log_softmax_bwd_rows_f32");
 }
 
@@ -556,7 +549,7 @@ extern "C" int ape_scatter_add_rows_f32(const float* dy, const int64_t* index, f
     if (hipMemsetAsync(dx, 0, nin * sizeof(float), st) != hipSuccess) { ape::set_last_error("hipMemsetAsync"); return APE_ELAUNCH; }
     const long total = (long)B * n * C;
     if (total == 0) return APE_OK;
-    hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(grid_for(total)), dim3(kT), 0, st, dy, index, dx, B, rows_in, n, C);
+    hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(ape::grid_for(total, kT, kGridCap)), dim3(kT), 0, st, dy, index, dx, B, rows_in, n, C);
     return ape::check_launch("ape_scatter_add_rows_f32");
 }
 
@@ -565,7 +558,7 @@ extern "C" int ape_mean_rows_bwd_f32(const float* dy, float* dx, int B, int n, i
     if (!dy || !dx || B < 0 || n < 1 || C < 1) return APE_EINVAL;
     const long total = (long)B * n * C;
     if (total == 0) return APE_OK;
-    hipLaunchKernelGGL(mean_rows_bwd_kernel, dim3(grid_for(total)), dim3(kT), 0, (hipStream_t)stream, dy, dx, B, n, C);
+    hipLaunchKernelGGL(mean_rows_bwd_kernel, dim3(ape::grid_for(total, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, dy, dx, B, n, C);
     return ape::check_launch("ape_mean_rows_bwd_f32");
 }
 
@@ -577,7 +570,7 @@ extern "C" int ape_adam_step_f32(float* param, const float* grad, float* exp_avg
         return APE_EINVAL;
     if (n == 0) return APE_OK;
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(kT), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1,
+    hipLaunchKernelGGL(adam_kernel, dim3(ape::grid_for(n, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1,
                        beta2, eps, (float)bc1, (float)sqrt(bc2), weight_decay);
     return ape::check_launch("ape_adam_step_f32");
 }
@@ -595,7 +588,7 @@ extern "C" int ape_adam_step_multi_f32(int n, const ape_adam_job* jobs, float lr
         const int nb = n - i0 < kAdamJobs ? n - i0 : kAdamJobs;
         long nmax = 1;
         for (int i = 0; i < nb; ++i) { b.j[i] = jobs[i0 + i]; nmax = jobs[i0 + i].n > nmax ? jobs[i0 + i].n : nmax; }
-        int gx = grid_for(nmax);
+        int gx = ape::grid_for(nmax, kT, kGridCap);
         gx = gx > 256 ? 256 : gx;
         hipLaunchKernelGGL(adam_multi_kernel, dim3(gx, nb), dim3(kT), 0, (hipStream_t)stream, b, lr, beta1, beta2, eps, weight_decay);
     }
@@ -607,7 +600,7 @@ extern "C" int ape_pack_train_weights(int n, const ape_pack_job* jobs_device, lo
 {
     if (n < 0 || (n && !jobs_device) || max_elems < 0) return APE_EINVAL;
     if (n == 0 || max_elems == 0) return APE_OK;
-    int gx = grid_for(max_elems);
+    int gx = ape::grid_for(max_elems, kT, kGridCap);
     gx = gx > 128 ? 128 : gx;
     for (int i0 = 0; i0 < n; i0 += 65535)
         hipLaunchKernelGGL(pack_train_weights_kernel, dim3(gx, n - i0 < 65535 ? n - i0 : 65535), dim3(kT), 0, (hipStream_t)stream, jobs_device + i0);

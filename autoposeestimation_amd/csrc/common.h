@@ -22,6 +22,17 @@ static inline int check_launch(const char* what)
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
+// workgroups of a grid-stride launch: one thread per work item, at least one and at most `cap` workgroups (every file keeps its own
+// thread count and cap: what its kernels were measured with)
+static inline int grid_for(long work, int threads, int cap)
+{
+    const long g = (work + threads - 1) / threads;
+    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
+// workspace carving: every piece starts on a 256-byte boundary
+static inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
 // Per-(kernel, device) set-up of the kernels with more than 64 KB of dynamic LDS: hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a
 // per-DEVICE property and so is the compute-unit count the persistent grids are sized from -- a process may drive several devices
 // (one `static DeviceOnce` per kernel instantiation; devices 0..63).  Returns APE_OK and the current device's CU count (256 if unknown).

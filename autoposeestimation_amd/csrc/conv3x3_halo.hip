@@ -16,7 +16,7 @@
 // Numerics are identical to conv_bf16.hip (same split-bf16 x3 / plain bf16 products, fp32 accumulate), only the K order is
 // (channel chunk, tap) instead of (tap, channel) -- covered by the same conv tests.
 #include <type_traits>
-#include "common.h"
+#include "mfma_common.h"
 #include "seg_head.h"
 
 #ifdef APE_UPS_DEBUG
@@ -37,22 +37,18 @@ extern "C" int ape_ups_debug_read(unsigned* host_out, int reset)
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+using namespace ape;
 
 constexpr int TS = 16;          // output tile is TS x TS pixels
 constexpr int CK = 32;          // channels per chunk
-constexpr int LDH = CK;         // bf16 per LDS row of a WEIGHT tile: 64 B, unpadded, 16-B chunks XOR-swizzled (swz below)
+constexpr int LDH = CK;         // bf16 per LDS row of a WEIGHT tile: 64 B, unpadded, 16-B chunks XOR-swizzled (swz)
 // Halo image: ONE row per pixel holding the hi plane (64 B), the lo plane (64 B) and 32 B of padding: a 160-B pitch (96 B
 // = hi + padding for plain bf16).  With these pitches the 16 lanes of every ds_read_b128 lane group (rows r..r+3 / r+12..r+15
 // of one chunk, rows r+4..r+11 of the next) fall on 16 distinct 16-B bank slots (10 r + k, resp. 6 r + k, mod 16), exactly
 // like the XOR swizzle used before, but the address is LINEAR in the pixel: a tap shift is a compile-time byte offset folded
 // into the ds_read immediate instead of ~7 VALU operations per fragment read (the kernel spent 2 VALU instructions per MFMA).
 constexpr int halo_lda(int npl) { return npl == 2 ? 2 * CK + 16 : CK + 16; }     // bf16 elements per halo pixel
-// 16x16x32 fragments: lane l reads chunk l>>4 of row l&15; the ds_read_b128 lane groups then mix two chunks, and the chunk
-// permutation that keeps all 16 lanes on distinct bank slots is chunk ^ ((-(row>>2)) & 3)
-__device__ __forceinline__ int swz(int row, int chunk16) { return row * LDH + ((chunk16 ^ ((0 - (row >> 2)) & 3)) << 3); }
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+static_assert(LDH == 32, "swz() addresses rows of 32 bf16");
 // BN = 128: 8 waves = 4 (pixels) x 2 (channels), each 64 px x 64 cout, one workgroup per CU, halo double-buffered.
 // BN = 64:  4 waves along the pixel axis, each 64 px x 64 cout, halo single-buffered so that TWO workgroups share a CU
 //           (57 KB LDS each): one's prologue / chunk refill / epilogue is covered by the other's MFMAs.
@@ -75,15 +71,6 @@ struct HaloArgs {
     float* score;
     int head_c, head_dsm;
 };
-
-// NONE / RELU / PRELU as selects on loop-invariant scalars (a `switch` per element compiled to a cascade of scalar compares and branches
-// per element: ~1.8 k scalar instructions in a 256-element epilogue); same values bit for bit (1 * v == v, also for -0 and NaN)
-__device__ __forceinline__ float activate_h(float v, int act, float alpha)
-{
-    if (act == APE_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
-    const float neg = act == APE_ACT_RELU ? 0.f : (act == APE_ACT_PRELU ? alpha : 1.f) * v;
-    return v > 0.f ? v : neg;
-}
 
 template <int NSPLIT, int D, int BNH, bool UPS, bool HEAD>
 __global__ __launch_bounds__(halo_threads(BNH), 2) void conv3x3_halo_kernel(const HaloArgs a)
@@ -258,8 +245,8 @@ __global__ __launch_bounds__(halo_threads(BNH), 2) void conv3x3_halo_kernel(cons
             __bf16* dst = As + (size_t)buf * HP * LDA + px * LDA + c4 * 4;
             *reinterpret_cast<bf16x4*>(dst) = hi;
             if (NPL == 2) {
-                lo[0] = (__bf16)(v.x - (float)hi[0]); lo[1] = (__bf16)(v.y - (float)hi[1]);
-                lo[2] = (__bf16)(v.z - (float)hi[2]); lo[3] = (__bf16)(v.w - (float)hi[3]);
+                lo[0] = split_lo(v.x, hi[0]); lo[1] = split_lo(v.y, hi[1]);
+                lo[2] = split_lo(v.z, hi[2]); lo[3] = split_lo(v.w, hi[3]);
                 *reinterpret_cast<bf16x4*>(dst + CK) = lo;
             }
         }
@@ -455,8 +442,8 @@ __global__ __launch_bounds__(halo_threads(BNH), 2) void conv3x3_halo_kernel(cons
             if (p.act == APE_ACT_SIGMOID) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    xv[j] = make_float4(activate_h(acc[i][j][0] + cb[j].x, p.act, p.alpha), activate_h(acc[i][j][1] + cb[j].y, p.act, p.alpha),
-                                        activate_h(acc[i][j][2] + cb[j].z, p.act, p.alpha), activate_h(acc[i][j][3] + cb[j].w, p.act, p.alpha));
+                    xv[j] = make_float4(activate(acc[i][j][0] + cb[j].x, p.act, p.alpha), activate(acc[i][j][1] + cb[j].y, p.act, p.alpha),
+                                        activate(acc[i][j][2] + cb[j].z, p.act, p.alpha), activate(acc[i][j][3] + cb[j].w, p.act, p.alpha));
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
@@ -510,14 +497,14 @@ __global__ __launch_bounds__(halo_threads(BNH), 2) void conv3x3_halo_kernel(cons
             if (vec_ok && nvalid == 4) {
                 if (a.res) { vv[0] += rr[j].x; vv[1] += rr[j].y; vv[2] += rr[j].z; vv[3] += rr[j].w; }
                 *reinterpret_cast<float4*>(a.y + m * p.ldy + p.yoff + n) =
-                    sigm ? make_float4(activate_h(vv[0], p.act, p.alpha), activate_h(vv[1], p.act, p.alpha), activate_h(vv[2], p.act, p.alpha),
-                                       activate_h(vv[3], p.act, p.alpha))
+                    sigm ? make_float4(activate(vv[0], p.act, p.alpha), activate(vv[1], p.act, p.alpha), activate(vv[2], p.act, p.alpha),
+                                       activate(vv[3], p.act, p.alpha))
                          : make_float4(ape::act_fast(vv[0], af2), ape::act_fast(vv[1], af2), ape::act_fast(vv[2], af2), ape::act_fast(vv[3], af2));
             } else {
                 for (int k = 0; k < nvalid; ++k) {
                     float t = vv[k];
                     if (a.res) t += a.res[m * p.ldr + p.roff + n + k];
-                    a.y[m * p.ldy + p.yoff + n + k] = activate_h(t, p.act, p.alpha);
+                    a.y[m * p.ldy + p.yoff + n + k] = activate(t, p.act, p.alpha);
                 }
             }
         }

@@ -14,27 +14,15 @@
 // as with bf16x3 (24 frames: 9 flipped near-tie pixels either way, largest flipped margin 2.2e-5 against 1.6e-5, band 1e-4).
 // The input image comes from ape_s32_to_f16m6 (one pass over the S32 tensor); output formats, residual, bias, activations as halo_s32.
 #include <type_traits>
-#include "common.h"
-
-// timing-only ablation switches (results wrong when set): compiled IN only by `make ablations` (-DAPE_ABLATIONS -> ../libape_hip_abl.so, what
-// tools/mb_*_abl.py load).  In the product build they cost: the run-time tests around the MFMA rows, waits and DMA statements of halo_s32
-// were 1 ms of the 33 ms step (same-box A/B).
-#ifdef APE_ABLATIONS
-#define ABL(bit) (a.dbg & (bit))
-#else
-#define ABL(bit) 0
-#endif
+#include "mfma_common.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using namespace ape;
+using namespace ape::halo_ring;
+
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 struct HaloMxArgs {
     const char* x;          // F16M6 activations [B][H][W][ldx] (128-B lines per 32 channels)
@@ -54,22 +42,6 @@ struct HaloMxArgs {
                             // timing-only ablations: 4 = no epilogue stores, 8 = no residual loads, 32 = no cross terms (reads and MFMAs), 64 = no main MFMAs,
                             // 128 = no cross MFMAs (their reads stay), 256 = no in-loop DMA
 };
-
-// NONE / RELU / PRELU as selects on loop-invariant scalars (a `switch` per element compiled to a cascade of scalar compares and branches
-// per element: ~1.8 k scalar instructions in a 256-element epilogue); same values bit for bit (1 * v == v, also for -0 and NaN)
-__device__ __forceinline__ float act_h(float v, int act, float alpha)
-{
-    if (act == APE_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
-    const float neg = act == APE_ACT_RELU ? 0.f : (act == APE_ACT_PRELU ? alpha : 1.f) * v;
-    return v > 0.f ? v : neg;
-}
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define APE_DS_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
-#else
-#define APE_DS_READ(dst, addr, off) (void)(addr)
-#endif
-
 
 // fragment reads of HALF a tap's main operands (asm operands cannot name variables captured by a generic lambda, hence free functions): the
 // fp16 piece of two pixel rows at their own ring-row addresses and of two of the four 16-channel weight blocks (2 KB apart)
@@ -93,43 +65,6 @@ __device__ __forceinline__ void ds_read_field_b(u32x4 (&F)[2], unsigned lo_addr,
     APE_DS_READ(F[0], lo_addr, J * 2048);
     APE_DS_READ(F[1], hi_addr, J * 2048);
 }
-
-// keeps asm-read destinations allocated up to this point (a free function: asm operands cannot name variables captured by a generic
-// lambda; device pass only: the host pass cannot check a "v" constraint)
-__device__ __forceinline__ void keep_regs(const u32x4& a, const u32x4& b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" :: "v"(a), "v"(b));
-#endif
-}
-
-// s_waitcnt vmcnt(n) for a wave-uniform run-time n (the immediate must be a literal)
-__device__ __forceinline__ void wait_vmcnt(int n)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-#endif
-}
-
-constexpr int TS = 16;                  // output tile edge
-constexpr int HWP = 24;                 // pixels per ring row (3 DMA pieces); the halo needs 16 + 2 d <= 24 of them
-constexpr int ROW_B = HWP * 128;        // 3072 B
-constexpr int RING_ROWS = 32;
-constexpr int A_BYTES = RING_ROWS * ROW_B;          // 96 KB
-constexpr int B_TILE = 128 * 128;                   // one tap's weights: 128 rows x (hi 64 B | lo 64 B)
-constexpr int B_RING = 4;
-constexpr int LDS_BYTES = A_BYTES + B_RING * B_TILE;   // 160 KB
 
 template <int D>
 __global__ __launch_bounds__(512, 2) void halo_mx_kernel(const HaloMxArgs a)
@@ -176,9 +111,9 @@ __global__ __launch_bounds__(512, 2) void halo_mx_kernel(const HaloMxArgs a)
     // ---- DMA sources ---------------------------------------------------------------------------------------------------------
     const long x_bytes = (long)a.B * a.H * a.W * a.ldx * 4;
     const long w_bytes = (long)(a.Cout - n0) * K * 4;
-    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (int)(unsigned)x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (int)(unsigned)x_bytes, BUF_RSRC_FLAGS);
     const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(a.w + (long)n0 * K * 4), 0, (int)(w_bytes > 0x7FFFFFFFL ? 0x7FFFFFFFu : (unsigned)w_bytes), 0x00020000);
+        (void*)(a.w + (long)n0 * K * 4), 0, (int)(w_bytes > 0x7FFFFFFFL ? 0x7FFFFFFFu : (unsigned)w_bytes), BUF_RSRC_FLAGS);
     // the tile whose image is being streamed in ("DMA tile"): the current tile until its last chunk's tap 0, then the next one.
     // a halo piece = 8 pixels of one image row: lanes 8 j .. 8 j + 7 fetch pixel j's 128-B line, chunks permuted by the column swizzle
     int dma_b = cur_b, dma_y0 = cur_y0;
@@ -511,7 +446,7 @@ __global__ __launch_bounds__(512, 2) void halo_mx_kernel(const HaloMxArgs a)
                         char* yp = a.y + m * a.ldy * 4 + (cy >> 5) * 128 + (cy & 31) * 2;
                         bf16x4 h, l;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) { h[e] = (__bf16)vv[e]; l[e] = (__bf16)(vv[e] - (float)h[e]); }
+                        for (int e = 0; e < 4; ++e) { h[e] = (__bf16)vv[e]; l[e] = split_lo(vv[e], h[e]); }
                         *reinterpret_cast<bf16x4*>(yp) = h;
                         *reinterpret_cast<bf16x4*>(yp + 64) = l;
                     } else {
@@ -578,7 +513,6 @@ __global__ __launch_bounds__(512, 2) void halo_mx_kernel(const HaloMxArgs a)
     }
 #endif
 }
-#undef APE_DS_READ
 
 template <int D>
 int launch_halo_mx(const HaloMxArgs& a, hipStream_t st)

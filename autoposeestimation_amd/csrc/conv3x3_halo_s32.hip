@@ -24,16 +24,7 @@
 // LDS image: a pixel (a weight row) is 128 B = chunks 0..3 hi | 4..7 lo, chunk c of pixel column hx in slot c ^ ((hx >> 1) & 7)
 // (weights: row instead of hx); the permutation is applied to the per-lane DMA SOURCE address, inside the 128-B line.
 #include <type_traits>
-#include "common.h"
-
-// timing-only ablation switches (results wrong when set): compiled IN only by `make ablations` (-DAPE_ABLATIONS -> ../libape_hip_abl.so, what
-// tools/mb_*_abl.py load).  In the product build they cost: the run-time tests around the MFMA rows, waits and DMA statements of halo_s32
-// were 1 ms of the 33 ms step (same-box A/B).
-#ifdef APE_ABLATIONS
-#define ABL(bit) (a.dbg & (bit))
-#else
-#define ABL(bit) 0
-#endif
+#include "mfma_common.h"
 
 // S32 output: one 16-byte store per lane instead of two 8-byte ones (round 6, conv_gemm_s32.hip); APE_S32_WIDE_STORE=0 builds the two-store form
 #ifndef APE_S32_WIDE_STORE
@@ -42,11 +33,8 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
+using namespace ape;
+using namespace ape::halo_ring;
 
 struct HaloS32Args {
     const char* x;          // S32 activations [B][H][W][ldx]
@@ -66,22 +54,6 @@ struct HaloS32Args {
                             // timing-only ablations: 4 = no epilogue stores, 8 = no residual loads, 32 = two of the three MFMAs per product, 64 = no fragment-read waits, 128 = no per-tap barrier, 256 = no per-tap DMA wait,
                             // 512 = no in-loop DMA, 1024 = no MFMAs
 };
-
-// NONE / RELU / PRELU as selects on loop-invariant scalars (a `switch` per element compiled to a cascade of scalar compares and branches
-// per element: ~1.8 k scalar instructions in a 256-element epilogue); same values bit for bit (1 * v == v, also for -0 and NaN)
-__device__ __forceinline__ float act_h(float v, int act, float alpha)
-{
-    if (act == APE_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
-    const float neg = act == APE_ACT_RELU ? 0.f : (act == APE_ACT_PRELU ? alpha : 1.f) * v;
-    return v > 0.f ? v : neg;
-}
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define APE_DS_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
-#else
-#define APE_DS_READ(dst, addr, off) (void)(addr)
-#endif
-
 
 // fragment reads of HALF a tap (asm operands cannot name variables captured by a generic lambda, hence a free function): two
 // pixel rows (hi, lo) at their own ring-row addresses and two of the four 16-channel weight blocks (2 KB apart)
@@ -107,43 +79,6 @@ __device__ __forceinline__ void ds_read_b4(u32x4 (&Bf)[4][2], unsigned bh, unsig
     APE_DS_READ(Bf[2][0], bh, 4096); APE_DS_READ(Bf[2][1], bl, 4096);
     APE_DS_READ(Bf[3][0], bh, 6144); APE_DS_READ(Bf[3][1], bl, 6144);
 }
-
-// keeps asm-read destinations allocated up to this point (a free function: asm operands cannot name variables captured by a generic
-// lambda; device pass only: the host pass cannot check a "v" constraint)
-__device__ __forceinline__ void keep_regs(const u32x4& a, const u32x4& b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" :: "v"(a), "v"(b));
-#endif
-}
-
-// s_waitcnt vmcnt(n) for a wave-uniform run-time n (the immediate must be a literal)
-__device__ __forceinline__ void wait_vmcnt(int n)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-#endif
-}
-
-constexpr int TS = 16;                  // output tile edge
-constexpr int HWP = 24;                 // pixels per ring row (3 DMA pieces); the halo needs 16 + 2 d <= 24 of them
-constexpr int ROW_B = HWP * 128;        // 3072 B
-constexpr int RING_ROWS = 32;
-constexpr int A_BYTES = RING_ROWS * ROW_B;          // 96 KB
-constexpr int B_TILE = 128 * 128;                   // one tap's weights: 128 rows x (hi 64 B | lo 64 B)
-constexpr int B_RING = 4;
-constexpr int LDS_BYTES = A_BYTES + B_RING * B_TILE;   // 160 KB
 
 // PP ("ping-pong", round 6): the two waves of a SIMD (wave w and w + 4) run a tap's two segments in OPPOSITE order instead of in lockstep.
 // PMC of the lockstep form (profiles/r05_pmc_utilisation.txt): per tap and SIMD 1440 cycles with BOTH waves issuing matrix instructions and
@@ -216,9 +151,9 @@ __global__ __launch_bounds__(512, 2) void halo_s32_kernel(const HaloS32Args a)
     // ---- DMA sources ---------------------------------------------------------------------------------------------------------
     const long x_bytes = (long)a.B * a.H * a.W * a.ldx * 4;
     const long w_bytes = (long)(a.Cout - n0) * K * 4;
-    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (int)(unsigned)x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (int)(unsigned)x_bytes, BUF_RSRC_FLAGS);
     const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(a.w + (long)n0 * K * 4), 0, (int)(w_bytes > 0x7FFFFFFFL ? 0x7FFFFFFFu : (unsigned)w_bytes), 0x00020000);
+        (void*)(a.w + (long)n0 * K * 4), 0, (int)(w_bytes > 0x7FFFFFFFL ? 0x7FFFFFFFu : (unsigned)w_bytes), BUF_RSRC_FLAGS);
     // the tile whose image is being streamed in ("DMA tile"): the current tile until its last chunk's tap 0, then the next one.
     // a halo piece = 8 pixels of one image row: lanes 8 j .. 8 j + 7 fetch pixel j's 128-B line, chunks permuted by the column swizzle
     int dma_b = cur_b, dma_y0 = cur_y0;
@@ -451,7 +386,6 @@ __global__ __launch_bounds__(512, 2) void halo_s32_kernel(const HaloS32Args a)
         __builtin_amdgcn_sched_barrier(0);
     };
 
-
     // ---- PP form of one tap (see the note at the kernel's head): C(t) | barrier | L(t+1) + the duties of tap t | barrier ------------
     auto mfma_all = [&]() {
 #pragma unroll
@@ -616,7 +550,7 @@ __global__ __launch_bounds__(512, 2) void halo_s32_kernel(const HaloS32Args a)
                         char* yp = a.y + m * a.ldy * 4 + (cy >> 5) * 128 + (cy & 31) * 2;
                         bf16x4 h, l;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) { h[e] = (__bf16)vv[e]; l[e] = (__bf16)(vv[e] - (float)h[e]); }
+                        for (int e = 0; e < 4; ++e) { h[e] = (__bf16)vv[e]; l[e] = split_lo(vv[e], h[e]); }
 #if APE_S32_WIDE_STORE
                         if (wide) {
                             // ONE 16-byte store per lane (cf. conv_gemm_s32.hip): the lanes fc and fc ^ 1 of a pixel hold adjacent channel quads;
@@ -702,7 +636,6 @@ __global__ __launch_bounds__(512, 2) void halo_s32_kernel(const HaloS32Args a)
     }
 #endif
 }
-#undef APE_DS_READ
 
 template <int D, bool PP>
 int launch_halo_s32(const HaloS32Args& a, hipStream_t st)

@@ -15,13 +15,11 @@
 // LDS: four bf16 tiles (A_hi, A_lo, B_hi, B_lo), K-contiguous rows of 64 elements padded to 72 (144 B = 9 x 16-B slots, odd
 // => the 16 rows of a ds_read_b128 lane group hit 16 distinct bank slots); one ds_read_b128 is exactly one MFMA fragment
 // (lane l: row l&31, k = 8*(l>>5) + 0..7 of the 16-deep k-step).
-#include "common.h"
+#include "mfma_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+using namespace ape;
 
 // tile shapes: <BM=128, BN<=128, BK=64, 4 waves> for everything, <BM=256, BN=256, BK=32, 8 waves> for big GEMM-like layers
 // (Cout >= 256, M large): a 256x256 tile fetches 16 KB of operands per algorithmic MFLOP instead of 30 KB -- these layers
@@ -37,22 +35,6 @@ struct ConvArgsB {
     int M, K, Kp, m_tiles, n_tiles;
     long plane_stride;
 };
-
-// NONE / RELU / PRELU as selects on loop-invariant scalars (a `switch` per element compiled to a cascade of scalar compares and branches
-// per element: ~1.8 k scalar instructions in a 256-element epilogue); same values bit for bit (1 * v == v, also for -0 and NaN)
-__device__ __forceinline__ float activate(float v, int act, float alpha)
-{
-    if (act == APE_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
-    const float neg = act == APE_ACT_RELU ? 0.f : (act == APE_ACT_PRELU ? alpha : 1.f) * v;
-    return v > 0.f ? v : neg;
-}
-
-__device__ __forceinline__ void split4(const float4 v, bf16x4& hi, bf16x4& lo)
-{
-    hi[0] = (__bf16)v.x; hi[1] = (__bf16)v.y; hi[2] = (__bf16)v.z; hi[3] = (__bf16)v.w;
-    lo[0] = (__bf16)(v.x - (float)hi[0]); lo[1] = (__bf16)(v.y - (float)hi[1]);
-    lo[2] = (__bf16)(v.z - (float)hi[2]); lo[3] = (__bf16)(v.w - (float)hi[3]);
-}
 
 // DB = true: BK = 32, two LDS stages of unpadded 64-B rows whose four 16-B chunks are XOR-swizzled with (row >> 1) & 3
 // (conflict-free ds_read_b128 fragments and ds_write_b128 staging), ONE barrier per k-tile: the next tile is written into
@@ -333,7 +315,7 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, __bf16* __restr
         const float v = k < K ? w[n * K + k] : 0.f;
         const __bf16 hi = (__bf16)v;
         out[i] = hi;
-        out[total + i] = (__bf16)(v - (float)hi);
+        out[total + i] = split_lo(v, hi);
     }
 }
 

@@ -24,11 +24,11 @@
 //   chunk -- a permutation of k applied identically to A and B, which the sum does not see.
 //   blockIdx is remapped so that the N-tiles of one M-tile (which re-read the same A pixels) and neighbouring M-tiles
 //   (overlapping 3x3 halos) run on the same XCD and share its 4 MiB L2.
-#include "common.h"
+#include "mfma_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace ape;
 
 constexpr int BM = 128;
 constexpr int BK = 32;
@@ -44,15 +44,6 @@ struct ConvArgs {
     ape_conv_params p;
     int M, K, m_tiles, n_tiles;
 };
-
-// NONE / RELU / PRELU as selects on loop-invariant scalars (a `switch` per element compiled to a cascade of scalar compares and branches
-// per element: ~1.8 k scalar instructions in a 256-element epilogue); same values bit for bit (1 * v == v, also for -0 and NaN)
-__device__ __forceinline__ float activate(float v, int act, float alpha)
-{
-    if (act == APE_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
-    const float neg = act == APE_ACT_RELU ? 0.f : (act == APE_ACT_PRELU ? alpha : 1.f) * v;
-    return v > 0.f ? v : neg;
-}
 
 // BN = workgroup tile width; WM x WN = wave grid (WM*WN == 4)
 template <int BN, int WM, int WN>

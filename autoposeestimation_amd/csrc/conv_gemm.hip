@@ -16,14 +16,11 @@
 //     one pixel and the epilogue stores float4s straight from the registers -- no LDS staging pass, no barrier after the k-loop.
 // Loads are unconditional (coordinates clamped into the tensor); out-of-image taps are zeroed when the registers are
 // written to LDS, rows >= M and columns >= Cout are computed on clamped data and dropped by the epilogue.
-#include "common.h"
 #include "s32.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace ape;
 
 struct GemmArgs {
     const float* x;
@@ -40,32 +37,7 @@ struct GemmArgs {
     long split_stride;
 };
 
-// NONE / RELU / PRELU as selects on loop-invariant scalars (a `switch` per element compiled to a cascade of scalar compares and branches
-// per element: ~1.8 k scalar instructions in a 256-element epilogue); same values bit for bit (1 * v == v, also for -0 and NaN)
-__device__ __forceinline__ float activate(float v, int act, float alpha)
-{
-    if (act == APE_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
-    const float neg = act == APE_ACT_RELU ? 0.f : (act == APE_ACT_PRELU ? alpha : 1.f) * v;
-    return v > 0.f ? v : neg;
-}
-
-__device__ __forceinline__ void split8(const f32x4 v0, const f32x4 v1, bf16x8& hi, bf16x8& lo)
-{
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        hi[e] = (__bf16)v0[e];
-        lo[e] = (__bf16)(v0[e] - (float)hi[e]);
-        hi[4 + e] = (__bf16)v1[e];
-        lo[4 + e] = (__bf16)(v1[e] - (float)hi[4 + e]);
-    }
-}
-
-constexpr int BK = 32;
-
-// element offset of 16-B chunk c of tile row `row` (rows of 32 bf16)
-// (ds_read_b128 services the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ...: the permutation that keeps the 16 lanes of
-// a group on 16 distinct 16-B bank slots for the fragment map lane -> (row = lane & 15, chunk = lane >> 4) is chunk ^ (-(row >> 2) & 3))
-__device__ __forceinline__ int lds_off(int row, int c) { return row * BK + ((c ^ ((0 - (row >> 2)) & 3)) << 3); }
+constexpr int BK = 32;          // bf16 per LDS row: the rows swz() addresses
 
 // PURE: 1x1 / stride 1 / pad 0 (a row-major GEMM: row m of A starts at x + m * ldx + xoff)
 //
@@ -193,7 +165,7 @@ __device__ __forceinline__ void conv_gemm_body(const GemmArgs& a, const int orig
             const bool ok = PURE || ((a_ok >> i) & 1u);
             bf16x8 hi, lo;
             split8(ok ? areg[i][0] : z4, ok ? areg[i][1] : z4, hi, lo);
-            const int o = lds_off(srow + i * (NT / 4), sc);
+            const int o = swz(srow + i * (NT / 4), sc);
             *reinterpret_cast<bf16x8*>(a_tile(stage, 0) + o) = hi;
             if (NPL == 2) *reinterpret_cast<bf16x8*>(a_tile(stage, NPL - 1) + o) = lo;
         }
@@ -202,7 +174,7 @@ __device__ __forceinline__ void conv_gemm_body(const GemmArgs& a, const int orig
 #pragma unroll
             for (int i = 0; i < B_IT; ++i)
                 if (!B_RAGGED || i + 1 < B_IT || srow + i * (NT / 4) < BN)
-                    *reinterpret_cast<u32x4*>(b_tile(stage, pl) + lds_off(srow + i * (NT / 4), sc)) = breg[pl][i];
+                    *reinterpret_cast<u32x4*>(b_tile(stage, pl) + swz(srow + i * (NT / 4), sc)) = breg[pl][i];
     };
 
     f32x4 acc[TM][TN];
@@ -219,7 +191,7 @@ __device__ __forceinline__ void conv_gemm_body(const GemmArgs& a, const int orig
     auto read_b = [&](int stage) {
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const int o = lds_off(b_row0 + j * 16, fc);
+            const int o = swz(b_row0 + j * 16, fc);
             bh[j] = *reinterpret_cast<const bf16x8*>(b_tile(stage, 0) + o);
             if (NPL == 2) bl[j] = *reinterpret_cast<const bf16x8*>(b_tile(stage, NPL - 1) + o);
         }
@@ -230,7 +202,7 @@ __device__ __forceinline__ void conv_gemm_body(const GemmArgs& a, const int orig
     auto read_a_rows = [&](int stage, int i0, int r0, int n) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < n; ++i) {
-            const int o = lds_off(a_row0 + (i0 + i) * 16, fc);
+            const int o = swz(a_row0 + (i0 + i) * 16, fc);
             ah[r0 + i] = *reinterpret_cast<const bf16x8*>(a_tile(stage, 0) + o);
             if (NPL == 2) al[r0 + i] = *reinterpret_cast<const bf16x8*>(a_tile(stage, NPL - 1) + o);
         }

@@ -23,16 +23,7 @@
 //     register sets, two B sets, the B sets swap roles every k-tile), so no wave ever waits on the LDS port in front of its
 //     MFMAs: the freed staging registers are what pays for the second fragment set.
 #include <type_traits>
-#include "common.h"
-
-// timing-only ablation switches (results wrong when set): compiled IN only by `make ablations` (-DAPE_ABLATIONS -> ../libape_hip_abl.so, what
-// tools/mb_*_abl.py load).  In the product build they cost: the run-time tests around the MFMA rows, waits and DMA statements of halo_s32
-// were 1 ms of the 33 ms step (same-box A/B).
-#ifdef APE_ABLATIONS
-#define ABL(bit) (a.dbg & (bit))
-#else
-#define ABL(bit) 0
-#endif
+#include "mfma_common.h"
 
 // S32 output: one 16-byte store per lane and (pixel block, channel block) instead of two 8-byte ones (round 6; same bytes at the same addresses:
 // bit-identical tensors; up_2 mix -3.7 %, up_1 mix -1.8 %, tools/mb_gemm_s32.py).  APE_S32_WIDE_STORE=0 builds the two-store form.
@@ -42,11 +33,7 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
+using namespace ape;
 
 struct GemmS32Args {
     const char* x;          // S32 activations, row m at x + m * ldx * 4 (bytes)
@@ -69,23 +56,6 @@ struct GemmS32Args {
                             // 32: no static priority for waves 4-7; 64: one tile per workgroup (no persistent walk)
 };
 
-// NONE / RELU / PRELU as selects on loop-invariant scalars (a `switch` per element compiled to a cascade of scalar compares and branches
-// per element); same values bit for bit (1 * v == v, also for -0 and NaN)
-__device__ __forceinline__ float act_fn(float v, int act, float alpha)
-{
-    if (act == APE_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
-    const float neg = act == APE_ACT_RELU ? 0.f : (act == APE_ACT_PRELU ? alpha : 1.f) * v;
-    return v > 0.f ? v : neg;
-}
-
-
-// (the host pass of hipcc instantiates kernel bodies too and silently drops a kernel whose body holds an asm it cannot check
-// against the HOST target -- the library then lacks the kernel's stub -- so the statement exists in the device pass only)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define APE_DS_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
-#else
-#define APE_DS_READ(dst, addr, off) (void)(addr)
-#endif
 // four 16-row blocks x two planes of one operand half (block i at + i * 2048; the planes have their own base registers)
 template <int OFF>
 __device__ __forceinline__ void ds_read_frags4(u32x4 (&f)[4][2], unsigned hi, unsigned lo)
@@ -120,16 +90,6 @@ __device__ __forceinline__ void ds_read_blocks(u32x4 (&f)[N][2], unsigned hi, un
         APE_DS_READ(f[I][1], lo, I * 2048);
         ds_read_blocks<N, I + 1>(f, hi, lo);
     }
-}
-#undef APE_DS_READ
-
-// keeps asm-read destinations allocated up to this point (a free function: asm operands cannot name variables captured by a generic
-// lambda; device pass only: the host pass cannot check a "v" constraint)
-__device__ __forceinline__ void keep_regs(const u32x4& a, const u32x4& b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" :: "v"(a), "v"(b));
-#endif
 }
 
 constexpr int BM = 256;
@@ -204,14 +164,14 @@ __device__ __forceinline__ void gemm_s32_epilogue(const GemmS32Args& a, f32x4 (&
                     }
                 }
 #pragma unroll
-                for (int e = 0; e < 4; ++e) vv[e] = sigm ? act_fn(vv[e], a.act, a.alpha) : ape::act_fast(vv[e], af);
+                for (int e = 0; e < 4; ++e) vv[e] = sigm ? activate(vv[e], a.act, a.alpha) : ape::act_fast(vv[e], af);
                 if (ABL(256)) continue;              // (timing only: no stores)
                 if (a.out_fmt == APE_FMT_S32) {
                     const int cy = a.yoff + n;
                     char* yp = a.y + (size_t)m * a.ldy * 4 + (cy >> 5) * 128 + (cy & 31) * 2;
                     bf16x4 h, l;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { h[e] = (__bf16)vv[e]; l[e] = (__bf16)(vv[e] - (float)h[e]); }
+                    for (int e = 0; e < 4; ++e) { h[e] = (__bf16)vv[e]; l[e] = split_lo(vv[e], h[e]); }
 #if APE_S32_WIDE_STORE
                     if (wide) {
                         // ONE 16-byte store per lane instead of two 8-byte ones: the lanes fc and fc ^ 1 of a pixel (16 lanes apart) hold adjacent
@@ -284,12 +244,12 @@ __device__ __forceinline__ void gemm_s32_body(const GemmS32Args& a)
     auto make_rs_a = [&](int m0_, int mend_) {
         const long a_bytes = ((long)(mend_ - m0_) * a.ldx - a.xoff) * 4;
         return __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + ((long)m0_ * a.ldx + a.xoff) * 4), 0,
-                                                 (int)(a_bytes > 0xFFFFFFFFL ? 0xFFFFFFFFu : (unsigned)a_bytes), 0x00020000);
+                                                 (int)(a_bytes > 0xFFFFFFFFL ? 0xFFFFFFFFu : (unsigned)a_bytes), BUF_RSRC_FLAGS);
     };
     auto make_rs_b = [&](int n0_, int img_) {
         const long b_bytes = (long)(a.Cout - n0_) * a.K * 4;
         return __builtin_amdgcn_make_buffer_rsrc((void*)(a.w + (long)img_ * a.w_img_stride + (long)n0_ * a.K * 4), 0,
-                                                 (int)(b_bytes > 0xFFFFFFFFL ? 0xFFFFFFFFu : (unsigned)b_bytes), 0x00020000);
+                                                 (int)(b_bytes > 0xFFFFFFFFL ? 0xFFFFFFFFu : (unsigned)b_bytes), BUF_RSRC_FLAGS);
     };
     int m0, m_end, img, n0 = (logical % a.n_tiles) * BN;
     tile_rows(logical / a.n_tiles, m0, m_end, img);
@@ -550,7 +510,6 @@ __device__ __forceinline__ void gemm_s32_body(const GemmS32Args& a)
 #endif
 }
 
-
 // ---- PP ("ping-pong", round 6; cf. conv3x3_halo_s32.hip): the two waves of a SIMD (wave w and w + 4) run a k-tile's matrix segment C (all of
 // its MFMAs from ONE fragment set) and its load segment L (the fragment reads of the next k-tile, the DMA pieces) in OPPOSITE order, with one
 // barrier per k-tile and wave: waves 0-3 close their interval behind L (C(t) L(t+1) |), waves 4-7 behind C (L(t) C(t) |).  PMC of the lockstep
@@ -602,12 +561,12 @@ __device__ __forceinline__ void gemm_s32_pp_body(const GemmS32Args& a)
     auto make_rs_a = [&](int m0_, int mend_) {
         const long a_bytes = ((long)(mend_ - m0_) * a.ldx - a.xoff) * 4;
         return __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + ((long)m0_ * a.ldx + a.xoff) * 4), 0,
-                                                 (int)(a_bytes > 0xFFFFFFFFL ? 0xFFFFFFFFu : (unsigned)a_bytes), 0x00020000);
+                                                 (int)(a_bytes > 0xFFFFFFFFL ? 0xFFFFFFFFu : (unsigned)a_bytes), BUF_RSRC_FLAGS);
     };
     auto make_rs_b = [&](int n0_, int img_) {
         const long b_bytes = (long)(a.Cout - n0_) * a.K * 4;
         return __builtin_amdgcn_make_buffer_rsrc((void*)(a.w + (long)img_ * a.w_img_stride + (long)n0_ * a.K * 4), 0,
-                                                 (int)(b_bytes > 0xFFFFFFFFL ? 0xFFFFFFFFu : (unsigned)b_bytes), 0x00020000);
+                                                 (int)(b_bytes > 0xFFFFFFFFL ? 0xFFFFFFFFu : (unsigned)b_bytes), BUF_RSRC_FLAGS);
     };
     int m0, m_end, img, n0 = (logical % a.n_tiles) * BN;
     tile_rows(logical / a.n_tiles, m0, m_end, img);
@@ -868,7 +827,7 @@ __global__ void pack_weights_s32k_kernel(const float* __restrict__ w, __bf16* __
         const __bf16 h = (__bf16)v;
         __bf16* g = out + (n * (K / 32) + k / 32) * 64;
         g[k % 32] = h;
-        g[32 + k % 32] = (__bf16)(v - (float)h);
+        g[32 + k % 32] = split_lo(v, h);
     }
 }
 
@@ -890,8 +849,7 @@ __global__ void f32_to_s32_kernel(const float4* __restrict__ x, char* __restrict
         const int c = (int)(i - row * (C / 4)) * 4;
         const float4 v = x[i];
         bf16x4 h, l;
-        h[0] = (__bf16)v.x; h[1] = (__bf16)v.y; h[2] = (__bf16)v.z; h[3] = (__bf16)v.w;
-        l[0] = (__bf16)(v.x - (float)h[0]); l[1] = (__bf16)(v.y - (float)h[1]); l[2] = (__bf16)(v.z - (float)h[2]); l[3] = (__bf16)(v.w - (float)h[3]);
+        split4(v, h, l);
         char* p = y + row * C * 4 + (c >> 5) * 128 + (c & 31) * 2;
         *reinterpret_cast<bf16x4*>(p) = h;
         *reinterpret_cast<bf16x4*>(p + 64) = l;
@@ -981,15 +939,10 @@ extern "C" int ape_conv_gemm_s32_per_image(const void* x_s32, const void* w_s32k
 // row-major, padded to 64 columns with zeros.
 namespace {
 constexpr int PSP_CELLS = 50, PSP_KPAD = 64;
-__device__ __forceinline__ float psp_src_index(int dst, float scale)        // ATen area_pixel_compute_source_index, align_corners = False (= ops.hip src_index)
-{
-    const float s = scale * ((float)dst + 0.5f) - 0.5f;
-    return s < 0.f ? 0.f : s;
-}
 // bilinear weight of prior cell `i` (0 .. S-1 along one axis) for output index `o` of `n`: ape_psp_prior_sum_f32's own expressions
 __device__ __forceinline__ float psp_axis_weight(int o, int n, int S, int i)
 {
-    const float f = psp_src_index(o, (float)S / (float)n);
+    const float f = src_index(o, (float)S / (float)n, false);
     const int i0 = (int)f;
     const int i1 = i0 + (i0 < S - 1 ? 1 : 0);
     const float l1 = f - (float)i0, l0 = 1.f - l1;
@@ -1018,7 +971,7 @@ __global__ void psp_fill_coeffs_kernel(char* __restrict__ x, int B, int h, int w
         }
         bf16x4 hi, lo;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { hi[e] = (__bf16)v[e]; lo[e] = (__bf16)(v[e] - (float)hi[e]); }
+        for (int e = 0; e < 4; ++e) { hi[e] = (__bf16)v[e]; lo[e] = split_lo(v[e], hi[e]); }
         const int c = coff + q * 4;
         char* p = x + pix0 * ld * 4 + (c >> 5) * 128 + (c & 31) * 2;
         const long frame = (long)h * w * ld * 4;
@@ -1056,7 +1009,7 @@ __global__ void psp_pack_weights_kernel(const char* __restrict__ wf, const float
                 else if (j < 14) v = z3[((long)b * 9 + (j - 5)) * Cout + co];
                 else if (j < PSP_CELLS) v = z6[((long)b * 36 + (j - 14)) * Cout + co];
                 const __bf16 hh = (__bf16)v;
-                h8[e] = piece < 4 ? hh : (__bf16)(v - (float)hh);
+                h8[e] = piece < 4 ? hh : split_lo(v, hh);
             }
             val = *reinterpret_cast<const uint4*>(h8);
         }

@@ -30,7 +30,7 @@ struct LabelTable {
     const uint8_t* p[kJobs];
 };
 
-inline int grid_for(long work) { long g = (work + kT - 1) / kT; return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g)); }
+constexpr int kGridCap = 16384;        // most workgroups of a grid-stride launch (ape::grid_for)
 
 // ---- largest-contour box -------------------------------------------------------------------------------------------------------------
 // grid (gx, nb): mask[f0 + y][q] = label == 255
@@ -213,7 +213,7 @@ extern "C" int ape_linemod_boxes(const void* const* labels_host, int B, int H, i
         for (int i = 0; i < nb; ++i) tb.p[i] = (const uint8_t*)labels_host[f0 + i];
         hipLaunchKernelGGL(lm_mask_kernel, dim3(gx, nb), dim3(kT), 0, st, tb, f0, HW, mask);
     }
-    const int g = grid_for(npix);
+    const int g = ape::grid_for(npix, kT, kGridCap);
     hipLaunchKernelGGL(ccl_init_kernel, dim3(g), dim3(kT), 0, st, mask, L, W, npix);
     hipLaunchKernelGGL(ccl_merge_kernel, dim3(g), dim3(kT), 0, st, mask, L, H, W, npix);
     hipLaunchKernelGGL(ccl_compress_kernel, dim3(g), dim3(kT), 0, st, L, npix, (unsigned long long*)nullptr, (unsigned int*)nullptr);

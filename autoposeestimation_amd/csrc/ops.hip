@@ -9,15 +9,15 @@
 //   head output layer           network.py:115-126 (conv4_{r,t,c} evaluated only for the selected object + sigmoid)
 // Each is one pass over its input (algorithmic bytes = bytes read + bytes written once); grids are sized to
 // >= 2048 workgroups-worth of work and grid-stride the rest.
-#include "common.h"
 #include <map>
 #include <mutex>
 #include "s32.h"
 
 namespace {
 
+using ape::src_index;
 constexpr int kThreads = 256;
-inline int grid_for(long work) { long g = (work + kThreads - 1) / kThreads; return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
+constexpr int kGridCap = 8192;        // most workgroups of a grid-stride launch (ape::grid_for)
 
 __global__ void maxpool3x3s2_kernel(const float4* __restrict__ x, float4* __restrict__ y, int B, int H, int W, int C4,
                                     int Ho, int Wo)
@@ -164,13 +164,6 @@ __global__ void avgpool_bins_kernel(const float4* __restrict__ atoms, const Pool
         const float inv = 1.f / (float)((pl.ye[pl.yb[si][oy]] - pl.ye[pl.ya[si][oy]]) * (pl.xe[pl.xb[si][ox]] - pl.xe[pl.xa[si][ox]]));
         reinterpret_cast<float4*>(pl.out[si])[((long)(b * S + oy) * S + ox) * C4 + c] = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
     }
-}
-
-__device__ __forceinline__ float src_index(int dst, float scale, bool align_corners)
-{
-    if (align_corners) return scale * (float)dst;
-    const float s = scale * ((float)dst + 0.5f) - 0.5f;  // ATen area_pixel_compute_source_index
-    return s < 0.f ? 0.f : s;
 }
 
 __global__ void bilinear_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W, int C4, int ldx4,
@@ -760,7 +753,7 @@ extern "C" int ape_maxpool3x3s2_nhwc_f32(const float* x, float* y, int B, int H,
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const long total = (long)B * Ho * Wo * (C / 4);
     if (total == 0) return APE_OK;
-    hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(grid_for(total)), dim3(kThreads), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(ape::grid_for(total, kThreads, kGridCap)), dim3(kThreads), 0, (hipStream_t)stream,
                        (const float4*)x, (float4*)y, B, H, W, C / 4, Ho, Wo);
     return ape::check_launch("ape_maxpool3x3s2_nhwc_f32");
 }
@@ -843,7 +836,7 @@ extern "C" int ape_adaptive_avgpool_multi_nhwc_ld(const void* x, int in_fmt, flo
         hipLaunchKernelGGL(avgpool_atoms_kernel<false>, dim3(B * pl.ny, ape::ceil_div(C / 4, 64)), dim3(256), 0, st, (const float4*)x,
                            (float4*)workspace, pl, H, W, C / 4, ldx / 4);
     const long total = (long)B * bins_total * (C / 4);
-    hipLaunchKernelGGL(avgpool_bins_kernel, dim3(grid_for(total)), dim3(kThreads), 0, st, (const float4*)workspace, pl, B, H, W, C / 4,
+    hipLaunchKernelGGL(avgpool_bins_kernel, dim3(ape::grid_for(total, kThreads, kGridCap)), dim3(kThreads), 0, st, (const float4*)workspace, pl, B, H, W, C / 4,
                        bins_total);
     return ape::check_launch("ape_adaptive_avgpool_multi_nhwc_f32");
 }
@@ -864,7 +857,7 @@ extern "C" int ape_bilinear_nhwc_f32(const float* x, float* y, int B, int H, int
     }
     const long total = (long)B * Ho * Wo * (C / 4);
     if (total == 0) return APE_OK;
-    hipLaunchKernelGGL(bilinear_kernel, dim3(grid_for(total)), dim3(kThreads), 0, (hipStream_t)stream, x, y, B, H, W, C / 4,
+    hipLaunchKernelGGL(bilinear_kernel, dim3(ape::grid_for(total, kThreads, kGridCap)), dim3(kThreads), 0, (hipStream_t)stream, x, y, B, H, W, C / 4,
                        ldx / 4, Ho, Wo, ldy / 4, yoff / 4, sh, sw, align_corners, accumulate);
     return ape::check_launch("ape_bilinear_nhwc_f32");
 }
@@ -874,7 +867,7 @@ extern "C" int ape_gather_rows_f32(const float* x, const int64_t* index, float* 
     if (!x || !index || !y || B < 0 || rows_in < 1 || n < 0 || C < 4 || C % 4) return APE_EINVAL;
     const long total = (long)B * n * (C / 4);
     if (total == 0) return APE_OK;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(total)), dim3(kThreads), 0, (hipStream_t)stream, (const float4*)x,
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(ape::grid_for(total, kThreads, kGridCap)), dim3(kThreads), 0, (hipStream_t)stream, (const float4*)x,
                        index, (float4*)y, B, rows_in, n, C / 4);
     return ape::check_launch("ape_gather_rows_f32");
 }
@@ -886,7 +879,7 @@ extern "C" int ape_ups_patch_gather_f32(const float* x, const int64_t* index, fl
     if (total == 0) return APE_OK;
     const float sh = 2 * h > 1 ? (float)(h - 1) / (float)(2 * h - 1) : 0.f;
     const float sw = 2 * w > 1 ? (float)(w - 1) / (float)(2 * w - 1) : 0.f;
-    hipLaunchKernelGGL(ups_patch_gather_kernel, dim3(grid_for(total)), dim3(kThreads), 0, (hipStream_t)stream, (const float4*)x, index,
+    hipLaunchKernelGGL(ups_patch_gather_kernel, dim3(ape::grid_for(total, kThreads, kGridCap)), dim3(kThreads), 0, (hipStream_t)stream, (const float4*)x, index,
                        (float4*)out, B, h, w, C / 4, n, sh, sw);
     return ape::check_launch("ape_ups_patch_gather_f32");
 }
@@ -895,7 +888,7 @@ extern "C" int ape_log_softmax_rows_f32(const float* x, float* y, long rows, int
 {
     if (!x || !y || rows < 0 || C < 1) return APE_EINVAL;
     if (rows == 0) return APE_OK;
-    hipLaunchKernelGGL(log_softmax_rows_kernel, dim3(grid_for(rows)), dim3(kThreads), 0, (hipStream_t)stream, x, y, rows, C);
+    hipLaunchKernelGGL(log_softmax_rows_kernel, dim3(ape::grid_for(rows, kThreads, kGridCap)), dim3(kThreads), 0, (hipStream_t)stream, x, y, rows, C);
     return ape::check_launch("ape_log_softmax_rows_f32");
 }
 
@@ -915,7 +908,7 @@ extern "C" int ape_pad3to4_f32(const float* x, float* y, long rows, void* stream
 {
     if (!x || !y || rows < 0) return APE_EINVAL;
     if (rows == 0) return APE_OK;
-    hipLaunchKernelGGL(pad3to4_kernel, dim3(grid_for(rows)), dim3(kThreads), 0, (hipStream_t)stream, x, (float4*)y, rows);
+    hipLaunchKernelGGL(pad3to4_kernel, dim3(ape::grid_for(rows, kThreads, kGridCap)), dim3(kThreads), 0, (hipStream_t)stream, x, (float4*)y, rows);
     return ape::check_launch("ape_pad3to4_f32");
 }
 
@@ -1009,7 +1002,7 @@ extern "C" int ape_psp_prior_sum_f32(const float* z1, const float* z2, const flo
     if (!z1 || !z2 || !z3 || !z6 || !out || B < 0 || h < 1 || w < 1 || C < 4 || C % 4) return APE_EINVAL;
     const long total = (long)B * w * (C / 4);      // one thread per (image, column, 4 channels)
     if (total == 0) return APE_OK;
-    hipLaunchKernelGGL(psp_prior_sum_kernel, dim3(grid_for(total)), dim3(kThreads), 0, (hipStream_t)stream, (const float4*)z1,
+    hipLaunchKernelGGL(psp_prior_sum_kernel, dim3(ape::grid_for(total, kThreads, kGridCap)), dim3(kThreads), 0, (hipStream_t)stream, (const float4*)z1,
                        (const float4*)z2, (const float4*)z3, (const float4*)z6, (float4*)out, B, h, w, C / 4);
     return ape::check_launch("ape_psp_prior_sum_f32");
 }

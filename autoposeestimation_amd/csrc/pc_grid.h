@@ -28,6 +28,13 @@ struct Grid {
     double h;
 };
 
+// a Grid as the arguments of an extern "C" entry point (GRID_ARGS -> MAKE_GRID: `Grid g`), and the per-cloud arrays of the batched entry
+// points (BGRID_ARGS -> BGRID(c): cloud c's Grid)
+#define GRID_ARGS const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n, double cell
+#define MAKE_GRID Grid g{sorted, (const u64*)keys, order, origin3, n, cell}
+#define BGRID_ARGS const double* const* sorted, const unsigned long long* const* keys, const unsigned* const* order, const double* const* origin3, const int* gn, double cell
+#define BGRID(c) Grid{sorted[c], (const u64*)keys[c], order[c], origin3[c], gn[c], cell}
+
 __device__ __forceinline__ int lower_bound(const u64* keys, int n, u64 k)
 {
     int lo = 0, hi = n;

@@ -22,7 +22,7 @@ namespace {
 
 constexpr int kT = 256;
 typedef unsigned long long u64;
-inline int grid_for(long work, int cap = 4096) { long g = (work + kT - 1) / kT; return (int)(g < 1 ? 1 : (g > cap ? cap : g)); }
+constexpr int kGridCap = 4096;        // most workgroups of a grid-stride launch (ape::grid_for)
 
 struct Mat4 { double m[16]; };
 
@@ -474,7 +474,7 @@ __device__ __forceinline__ void select_rows_kernel_body(const double* __restrict
 }
 
 
-size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+using ape::align_up;
 
 struct Carver {
     char* p; char* end;
@@ -1095,9 +1095,9 @@ int keys_and_sort(int nb, const double* const* pts, const int* n, const int* off
     Batch<BSort> bs{};
     int mg1 = 1, mg2 = 1, nmax = 1;
     for (int c = 0; c < nb; ++c) {
-        const int g = n[c] > 0 ? grid_for(n[c], 1024) : 0;
+        const int g = n[c] > 0 ? ape::grid_for(n[c], kT, 1024) : 0;
         bp.t[c] = BPts{pts[c], part + (size_t)c * (1024 * 6 + 8), part + (size_t)c * (1024 * 6 + 8) + 1024 * 6, n[c], g};
-        bk.t[c] = BKeys{pts[c], bp.t[c].out6, k0 + off[c], i0 + off[c], origin ? origin[c] : nullptr, n[c], n[c] > 0 ? grid_for(n[c]) : 0, h, shift};
+        bk.t[c] = BKeys{pts[c], bp.t[c].out6, k0 + off[c], i0 + off[c], origin ? origin[c] : nullptr, n[c], n[c] > 0 ? ape::grid_for(n[c], kT, kGridCap) : 0, h, shift};
         bs.t[c] = BSort{k0 + off[c], i0 + off[c], k_out[c], i_out[c], ks + off[c], is + off[c], reinterpret_cast<int*>(bp.t[c].out6 + 7), bp.t[c].out6, h, shift, n[c], bk.t[c].gx};
         mg1 = g > mg1 ? g : mg1;
         mg2 = bk.t[c].gx > mg2 ? bk.t[c].gx : mg2;
@@ -1145,11 +1145,11 @@ extern "C" int ape_surface_points_batch_f64(int nb, const uint8_t* const* label,
     const int n = H * W;
     Batch<BSurf> b{};
     for (int c = 0; c < nb; ++c)
-        b.t[c] = BSurf{label[c], depth[c], pix_ws + (size_t)c * n, n_out + c, points[c], load_mat(T16_host + c * 16), n, W, grid_for(n),
+        b.t[c] = BSurf{label[c], depth[c], pix_ws + (size_t)c * n, n_out + c, points[c], load_mat(T16_host + c * 16), n, W, ape::grid_for(n, kT, kGridCap),
                        intr4_host[c * 4], intr4_host[c * 4 + 1], intr4_host[c * 4 + 2], intr4_host[c * 4 + 3]};
     hipStream_t st = (hipStream_t)stream;
     launch_batch(surface_compact_batch, b, nb, 1, kCT, st);
-    launch_batch(surface_points_batch, b, nb, grid_for(n), kT, st);
+    launch_batch(surface_points_batch, b, nb, ape::grid_for(n, kT, kGridCap), kT, st);
     return ape::check_launch("ape_surface_points_batch_f64");
 }
 
@@ -1179,7 +1179,7 @@ extern "C" int ape_voxel_down_sample_batch_f64(int nb, const double* const* pts,
     Batch<BVox> bv{};
     int mg = 1;
     for (int c = 0; c < nb; ++c) {
-        bv.t[c] = BVox{pts[c], k1 + off[c], i1 + off[c], head + off[c], scan + off[c], out[c], n_out + c, n[c], n[c] > 0 ? grid_for(n[c]) : 0};
+        bv.t[c] = BVox{pts[c], k1 + off[c], i1 + off[c], head + off[c], scan + off[c], out[c], n_out + c, n[c], n[c] > 0 ? ape::grid_for(n[c], kT, kGridCap) : 0};
         mg = bv.t[c].gx > mg ? bv.t[c].gx : mg;
     }
     launch_batch(heads_batch, bv, nb, mg, kT, st);
@@ -1214,16 +1214,12 @@ extern "C" int ape_grid_build_batch_f64(int nb, const double* const* pts, const 
     Batch<BGather> bg{};
     int mg = 1;
     for (int c = 0; c < nb; ++c) {
-        bg.t[c] = BGather{pts[c], order[c], sorted[c], n[c], n[c] > 0 ? grid_for(n[c]) : 0};
+        bg.t[c] = BGather{pts[c], order[c], sorted[c], n[c], n[c] > 0 ? ape::grid_for(n[c], kT, kGridCap) : 0};
         mg = bg.t[c].gx > mg ? bg.t[c].gx : mg;
     }
     launch_batch(gather_batch, bg, nb, mg, kT, st);
     return ape::check_launch("ape_grid_build_batch_f64");
 }
-
-/* per-cloud grid description for the batched searches: the arguments of GRID_ARGS as arrays */
-#define BGRID_ARGS const double* const* sorted, const unsigned long long* const* keys, const unsigned* const* order, const double* const* origin3, const int* gn, double cell
-#define BGRID(c) Grid{sorted[c], (const u64*)keys[c], order[c], origin3[c], gn[c], cell}
 
 /* op 0: radius count (count[c][nq]); op 1: hybrid normals (normals[c][nq][3], max_nn); op 2: k-NN mean distance of the grid's own points
  * (mean[c][gn], k) -- the queries q[c] (nq[c] rows) are ignored for op 2 */
@@ -1266,7 +1262,7 @@ extern "C" int ape_select_points_batch_f64(int mode, int nb, const double* const
     int mg = 1, off = 0;
     for (int c = 0; c < nb; ++c) {
         if (n[c] < 0) return APE_EINVAL;
-        b.t[c] = BSel{pts[c], mode == 0 ? count[c] : nullptr, mode == 1 ? mean[c] : nullptr, sel_ws + off, n_out + c, out[c], n[c], n[c] > 0 ? grid_for(n[c]) : 0,
+        b.t[c] = BSel{pts[c], mode == 0 ? count[c] : nullptr, mode == 1 ? mean[c] : nullptr, sel_ws + off, n_out + c, out[c], n[c], n[c] > 0 ? ape::grid_for(n[c], kT, kGridCap) : 0,
                       thr_count, mode == 1 ? thr_mean_host[c] : 0.0, mode};
         off += n[c];
         mg = b.t[c].gx > mg ? b.t[c].gx : mg;
@@ -1286,7 +1282,7 @@ extern "C" int ape_moments_batch_f64(int nb, const double* const* pts, const int
     int mg = 1;
     for (int c = 0; c < nb; ++c) {
         if (n[c] < 0) return APE_EINVAL;
-        b.t[c] = BMom{pts[c], (double*)ws + (size_t)c * 512 * 9, out9 + c * 9, n[c], n[c] > 0 ? grid_for(n[c], 512) : 0};
+        b.t[c] = BMom{pts[c], (double*)ws + (size_t)c * 512 * 9, out9 + c * 9, n[c], n[c] > 0 ? ape::grid_for(n[c], kT, 512) : 0};
         mg = b.t[c].gx > mg ? b.t[c].gx : mg;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -1307,7 +1303,7 @@ extern "C" int ape_mahalanobis_batch_f64(int nb, const double* const* pts, const
         int mg = 1, m = nb - c0 < 8 ? nb - c0 : 8;
         for (int c = 0; c < m; ++c) {
             if (n[c0 + c] < 0) return APE_EINVAL;
-            b.t[c] = BMaha{pts[c0 + c], out[c0 + c], n[c0 + c], n[c0 + c] > 0 ? grid_for(n[c0 + c]) : 0, {}};
+            b.t[c] = BMaha{pts[c0 + c], out[c0 + c], n[c0 + c], n[c0 + c] > 0 ? ape::grid_for(n[c0 + c], kT, kGridCap) : 0, {}};
             for (int i = 0; i < 12; ++i) b.t[c].mc.v[i] = mc12_host[(c0 + c) * 12 + i];
             mg = b.t[c].gx > mg ? b.t[c].gx : mg;
         }
@@ -1325,7 +1321,7 @@ extern "C" int ape_transform_points_batch_f64(int nb, double* const* pts, double
     int mg = 1;
     for (int c = 0; c < nb; ++c) {
         if (n[c] < 0) return APE_EINVAL;
-        b.t[c] = BXform{pts[c], normals ? normals[c] : nullptr, load_mat(T16_host + c * 16), n[c], n[c] > 0 ? grid_for(n[c]) : 0};
+        b.t[c] = BXform{pts[c], normals ? normals[c] : nullptr, load_mat(T16_host + c * 16), n[c], n[c] > 0 ? ape::grid_for(n[c], kT, kGridCap) : 0};
         mg = b.t[c].gx > mg ? b.t[c].gx : mg;
     }
     launch_batch(transform_batch, b, nb, mg, kT, (hipStream_t)stream);
@@ -1344,7 +1340,7 @@ extern "C" int ape_concat_points_batch_f64(int nb, const double* const* a, const
         const int n2 = b && nb_rows ? nb_rows[c] : 0;
         if (na[c] < 0 || n2 < 0) return APE_EINVAL;
         const int tot = na[c] + n2;
-        bt.t[c] = BCopy{a[c], b ? b[c] : nullptr, out[c], na[c], n2, tot > 0 ? grid_for(3L * tot) : 0};
+        bt.t[c] = BCopy{a[c], b ? b[c] : nullptr, out[c], na[c], n2, tot > 0 ? ape::grid_for(3L * tot, kT, kGridCap) : 0};
         mg = bt.t[c].gx > mg ? bt.t[c].gx : mg;
     }
     launch_batch(concat_batch, bt, nb, mg, kT, (hipStream_t)stream);
@@ -1373,7 +1369,7 @@ extern "C" int ape_icp_run_batch_f64(int kind, int nb, BGRID_ARGS, double* const
         const bool on = ns[c] > 0 && gn[c] > 0;
         if (ns[c] < 0 || gn[c] < 0 || (on && kind == 1 && !tgt_normals[c])) return APE_EINVAL;
         b.t[c] = BIcp{BGRID(c), src[c], tgt[c], kind == 1 ? tgt_normals[c] : nullptr, corr[c], dist2[c], (double*)ws + (size_t)c * 512 * 29, sums[c], state[c],
-                      ns[c], on ? ape::ceil_div((long)ns[c] * kG, (long)kT) : 0, on ? grid_for(ns[c], 512) : 0};
+                      ns[c], on ? ape::ceil_div((long)ns[c] * kG, (long)kT) : 0, on ? ape::grid_for(ns[c], kT, 512) : 0};
         mg_nn = b.t[c].gx_nn > mg_nn ? b.t[c].gx_nn : mg_nn;
         mg_sum = b.t[c].gx_sum > mg_sum ? b.t[c].gx_sum : mg_sum;
     }
@@ -1392,8 +1388,6 @@ extern "C" int ape_icp_run_batch_f64(int kind, int nb, BGRID_ARGS, double* const
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The two steps of an ICP evaluation as calls of their own, for a loop that solves on the host (registration_icp(host_solve=True), the
 // LAPACK check of icp_step): the batch kernels above with ONE record and no state word -- same per-cloud grid sizes, same bits.
-#define GRID_ARGS const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n, double cell
-
 extern "C" int ape_grid_nn1_f64(GRID_ARGS, const double* q, int nq, double max_dist, int* idx, double* dist2, void* stream)
 {
     if (!sorted || !keys || !order || !origin3 || !q || !idx || !dist2 || n < 1 || nq < 0 || max_dist > cell) return APE_EINVAL;
@@ -1413,7 +1407,7 @@ extern "C" int ape_icp_sums_f64(int kind, const double* src, const double* tgt, 
     if (kind < 2 && (!tgt || !corr || !dist2)) return APE_EINVAL;
     if (kind == 1 && !tgt_normals) return APE_EINVAL;
     const int nv = kind == 0 ? 17 : kind == 1 ? 29 : 9;
-    const int g = grid_for(n, 512);
+    const int g = ape::grid_for(n, kT, 512);
     if (ws_bytes < (size_t)g * nv * 8) return APE_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     double* part = (double*)ws;

@@ -33,7 +33,7 @@ constexpr int kNNBlocks = 2048;           // blocks a feature_nn launch aims at 
 constexpr int kMaxBatch = 16;             // pairs / clouds per launch, as pointcloud.hip
 template <class T> struct Batch { T t[kMaxBatch]; };
 
-size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+using ape::align_up;
 
 __device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 __device__ __forceinline__ void cross3(const double* a, const double* b, double* c)
@@ -641,10 +641,6 @@ int validate_launch(int nb, const Grid* g, const Hyp* h, const int* const* kept,
 
 }  // namespace
 
-#define GRID_ARGS const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n, double cell
-#define MAKE_GRID Grid g{sorted, (const u64*)keys, order, origin3, n, cell}
-#define BGRID_ARGS const double* const* sorted, const unsigned long long* const* keys, const unsigned* const* order, const double* const* origin3, const int* gn, double cell
-#define BGRID(c) Grid{sorted[c], (const u64*)keys[c], order[c], origin3[c], gn[c], cell}
 #define APE_BATCH_CHECK(nb) if ((nb) < 1 || (nb) > kMaxBatch) return APE_EINVAL
 
 extern "C" size_t ape_fpfh_workspace_bytes(int n, int max_nn) { return fpfh_ws(n, max_nn); }

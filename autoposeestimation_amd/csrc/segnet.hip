@@ -11,7 +11,7 @@
 namespace {
 
 constexpr int kT = 256;
-inline int grid_for(long work) { long g = (work + kT - 1) / kT; return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
+constexpr int kGridCap = 8192;        // most workgroups of a grid-stride launch (ape::grid_for)
 
 // torch's CPU rule (ATen max_pool2d_with_indices: `(val > maxval) || isnan(val)` from -inf, index of the window's first element): the
 // first of equal maxima wins, 0.0 against -0.0 keeps the first, an all -inf window keeps position 0, the last NaN in scan order wins
@@ -217,7 +217,7 @@ extern "C" int ape_maxpool2x2_idx_nhwc_f32(const float* x, float* y, uint8_t* co
     const long total = (long)B * Ho * Wo * (C / 4);
     if (total == 0) return APE_OK;
     if (!x || !y || !code || !aligned16(x) || !aligned16(y) || ((uintptr_t)code & 3u)) return APE_EINVAL;
-    hipLaunchKernelGGL(maxpool2x2_idx_kernel, dim3(grid_for(total)), dim3(kT), 0, (hipStream_t)stream, (const float4*)x, (float4*)y,
+    hipLaunchKernelGGL(maxpool2x2_idx_kernel, dim3(ape::grid_for(total, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, (const float4*)x, (float4*)y,
                        (uchar4*)code, B, H, W, C / 4, Ho, Wo);
     return ape::check_launch("ape_maxpool2x2_idx_nhwc_f32");
 }
@@ -230,7 +230,7 @@ extern "C" int ape_max_unpool2x2_nhwc_f32(const float* y, const uint8_t* code, f
     if (total == 0) return APE_OK;
     if (!x || !aligned16(x)) return APE_EINVAL;
     if ((long)B * Ho * Wo > 0 && (!y || !code || !aligned16(y) || ((uintptr_t)code & 3u))) return APE_EINVAL;
-    hipLaunchKernelGGL(max_unpool2x2_kernel, dim3(grid_for(total)), dim3(kT), 0, (hipStream_t)stream, (const float4*)y, (const uchar4*)code,
+    hipLaunchKernelGGL(max_unpool2x2_kernel, dim3(ape::grid_for(total, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, (const float4*)y, (const uchar4*)code,
                        (float4*)x, B, H, W, C / 4, Ho, Wo, Hc, Wc);
     return ape::check_launch("ape_max_unpool2x2_nhwc_f32");
 }
@@ -242,7 +242,7 @@ extern "C" int ape_gather2x2_nhwc_f32(const float* x, const uint8_t* code, float
     const long total = (long)B * Ho * Wo * (C / 4);
     if (total == 0) return APE_OK;
     if (!x || !y || !code || !aligned16(x) || !aligned16(y) || ((uintptr_t)code & 3u)) return APE_EINVAL;
-    hipLaunchKernelGGL(gather2x2_kernel, dim3(grid_for(total)), dim3(kT), 0, (hipStream_t)stream, (const float4*)x, (const uchar4*)code,
+    hipLaunchKernelGGL(gather2x2_kernel, dim3(ape::grid_for(total, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, (const float4*)x, (const uchar4*)code,
                        (float4*)y, B, H, W, C / 4, Ho, Wo);
     return ape::check_launch("ape_gather2x2_nhwc_f32");
 }
@@ -274,7 +274,7 @@ extern "C" int ape_cross_entropy_f32(const float* logits, int ld, int C, const u
     hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(kT), 0, st, part, nb, P, g, out, scale);
     if (dlogits && P > 0) {
         const long n = P * (long)ld, n4 = aligned16(dlogits) ? n / 4 : 0;
-        hipLaunchKernelGGL(ce_scale_kernel, dim3(grid_for(n4 > 0 ? n4 : n)), dim3(kT), 0, st, dlogits, n4, n, scale);
+        hipLaunchKernelGGL(ce_scale_kernel, dim3(ape::grid_for(n4 > 0 ? n4 : n, kT, kGridCap)), dim3(kT), 0, st, dlogits, n4, n, scale);
     }
     return ape::check_launch("ape_cross_entropy_f32");
 }

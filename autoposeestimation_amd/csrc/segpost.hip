@@ -21,15 +21,17 @@
 //   choose_points  ordered stream compaction of (object map == cls) & (depth != 0) inside the crop, then N picks
 //   backproject    float32 pin-hole back-projection, bit-identical to the numpy arithmetic
 //   crop_normalize u8 RGB -> NHWC4 f32 (x[/255] - mean) / std
-#include "common.h"
+#include "mfma_common.h"
 #include "seg_head.h"
 #include "aug_px.h"
 #include "ccl.h"                 // union-find labelling: ccl_init_kernel, ccl_merge_kernel, ccl_compress_kernel
 
 namespace {
 
+using namespace ape;
+
 constexpr int kT = 256;
-inline int grid_for(long work) { long g = (work + kT - 1) / kT; return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g)); }
+constexpr int kGridCap = 16384;        // most workgroups of a grid-stride launch (ape::grid_for)
 
 // ---------------------------------------------------------------------------------------------------------------
 __global__ void seg_argmax_kernel(const float* __restrict__ logits, int ld, int C, uint8_t* __restrict__ label,
@@ -402,7 +404,6 @@ __global__ __launch_bounds__(kT) void label_trust_kernel(const uint8_t* __restri
 // classes, columns = 16 pixels): lane (px = l&15, kq = l>>4) loads four float4 of its pixel (k = 16 j + 4 kq + e), the 16
 // weight operands per lane stay in registers for the whole kernel, and each pixel's 16 logits end up 4 per lane on the four
 // lanes {px, px+16, px+32, px+48}, so max / arg-max / exp-sums need only two xor-shuffles.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(kT) void seg_head_kernel(const float4* __restrict__ feat, const float* __restrict__ w, const float* __restrict__ bias,
                                                       int C, uint8_t* __restrict__ label, float* __restrict__ score, long npix, int double_softmax)
@@ -436,7 +437,7 @@ extern "C" int ape_seg_argmax_f32(const float* logits, int ld, int C, uint8_t* l
 {
     if (!logits || !label || !score || C < 1 || C > kMaxCls || ld < C || npix < 0) return APE_EINVAL;
     if (npix == 0) return APE_OK;
-    hipLaunchKernelGGL(seg_argmax_kernel, dim3(grid_for(npix)), dim3(kT), 0, (hipStream_t)stream, logits, ld, C, label, score,
+    hipLaunchKernelGGL(seg_argmax_kernel, dim3(ape::grid_for(npix, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, logits, ld, C, label, score,
                        npix, double_softmax);
     return ape::check_launch("ape_seg_argmax_f32");
 }
@@ -469,7 +470,7 @@ extern "C" int ape_seg_components_scored(const uint8_t* label, const float* scor
     unsigned int* hist = (unsigned int*)ws;                       ws += (size_t)B * C * 4;
     int* best_root = (int*)ws;                                    ws += (size_t)B * C * 4;
     int* tight = (int*)ws;
-    const int g = grid_for(npix);
+    const int g = ape::grid_for(npix, kT, kGridCap);
     // (sum / cnt are zeroed where they are used, at the component roots, by ccl_compress_kernel.  Kernels, not hipMemsetAsync: memset nodes of a
     // captured HIP graph did not re-zero on replay -- tools/attic/probes/graph_probe.py)
     const int BC = B * C;
@@ -531,7 +532,7 @@ extern "C" int ape_preprocess_u8_nhwc4(const uint8_t* rgb, const int* rects, flo
     if (n == 0) return APE_OK;       // (an empty rects / out tensor has a null pointer)
     if (!rgb || !rects || !out) return APE_EINVAL;
     const long total = (long)n * Hc * Wc;
-    hipLaunchKernelGGL(crop_normalize_kernel, dim3(grid_for(total)), dim3(kT), 0, (hipStream_t)stream, rgb, rects, (float4*)out, H,
+    hipLaunchKernelGGL(crop_normalize_kernel, dim3(ape::grid_for(total, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, rgb, rects, (float4*)out, H,
                        W, Hc, Wc, div255, total);
     return ape::check_launch("ape_preprocess_u8_nhwc4");
 }
@@ -579,7 +580,7 @@ extern "C" int ape_bgsub_features_f32(const uint8_t* f_rgb, const uint8_t* b_rgb
         a.mean[c] = mean7_host[c];
         a.stdv[c] = std7_host[c];
     }
-    hipLaunchKernelGGL(bgsub_features_kernel, dim3(grid_for(npix)), dim3(kT), 0, (hipStream_t)stream, f_rgb, b_rgb, f_depth, b_depth,
+    hipLaunchKernelGGL(bgsub_features_kernel, dim3(ape::grid_for(npix, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, f_rgb, b_rgb, f_depth, b_depth,
                        gate_min_max, a, (float4*)out, diff_or_null, H * W, npix);
     return ape::check_launch("ape_bgsub_features_f32");
 }

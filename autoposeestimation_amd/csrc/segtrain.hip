@@ -16,7 +16,7 @@
 namespace {
 
 constexpr int kT = 256;
-static inline int grid_for(long n) { long g = (n + kT - 1) / kT; return (int)(g < 1 ? 1 : (g > 65535 ? 65535 : g)); }
+constexpr int kGridCap = 65535;        // most workgroups of a grid-stride launch (ape::grid_for)
 constexpr int kBnGroups = 1024;         // most row groups of the BN reductions (partials slab: kBnGroups x C x 2 doubles)
 
 // ---- BatchNorm statistics -------------------------------------------------------------------------------------------------
@@ -470,7 +470,7 @@ extern "C" int ape_bn_train_fwd_f32(const float* x, const float* gamma, const fl
     hipLaunchKernelGGL(bn_stats_finish_kernel, dim3(ape::ceil_div(C, 64)), dim3(64), 0, st, x, part, groups, rows, C, eps, momentum, mean,
                        invstd, running_mean, running_var, num_batches_tracked);
     const long total = rows * C;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(total)), dim3(kT), 0, st, x, mean, invstd, gamma, beta, residual, y, total, C,
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(ape::grid_for(total, kT, kGridCap)), dim3(kT), 0, st, x, mean, invstd, gamma, beta, residual, y, total, C,
                        act == APE_ACT_RELU ? 1 : 0);
     return ape::check_launch("ape_bn_train_fwd_f32");
 }
@@ -489,7 +489,7 @@ extern "C" int ape_bn_train_bwd_f32(const float* dy, const float* y, const float
     hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3(ape::ceil_div(C, 64)), dim3(64), 0, st, part, groups, rows, C, dgamma, dbeta, coef);
     if (dx || dres) {
         const long total = rows * C;
-        hipLaunchKernelGGL(bn_bwd_dx_kernel, dim3(grid_for(total)), dim3(kT), 0, st, dy, y, x, mean, invstd, gamma, coef, dx, dres, total, C);
+        hipLaunchKernelGGL(bn_bwd_dx_kernel, dim3(ape::grid_for(total, kT, kGridCap)), dim3(kT), 0, st, dy, y, x, mean, invstd, gamma, coef, dx, dres, total, C);
     }
     return ape::check_launch("ape_bn_train_bwd_f32");
 }
@@ -499,7 +499,7 @@ extern "C" int ape_upsample_nearest2x_bwd_f32(const float* dy, int ld, int off, 
     if (!dy || !dx || B < 0 || h < 1 || w < 1 || C < 1 || off < 0 || off + C > ld) return APE_EINVAL;
     const long total = (long)B * h * w * C;
     if (total == 0) return APE_OK;
-    hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(grid_for(total)), dim3(kT), 0, (hipStream_t)stream, dy, dx, B, h, w, C, ld, off);
+    hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(ape::grid_for(total, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, dy, dx, B, h, w, C, ld, off);
     return ape::check_launch("ape_upsample_nearest2x_bwd_f32");
 }
 
@@ -507,7 +507,7 @@ extern "C" int ape_softmax_rows_f32(const float* x, float* y, long rows, int C, 
 {
     if (!x || !y || rows < 0 || C < 1) return APE_EINVAL;
     if (rows == 0) return APE_OK;
-    hipLaunchKernelGGL(softmax_rows_kernel, dim3(grid_for(rows)), dim3(kT), 0, (hipStream_t)stream, x, y, rows, C);
+    hipLaunchKernelGGL(softmax_rows_kernel, dim3(ape::grid_for(rows, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, x, y, rows, C);
     return ape::check_launch("ape_softmax_rows_f32");
 }
 
@@ -515,7 +515,7 @@ extern "C" int ape_softmax_rows_bwd_f32(const float* dy, const float* y, float* 
 {
     if (!dy || !y || !dx || rows < 0 || C < 1) return APE_EINVAL;
     if (rows == 0) return APE_OK;
-    hipLaunchKernelGGL(softmax_rows_bwd_kernel, dim3(grid_for(rows)), dim3(kT), 0, (hipStream_t)stream, dy, y, dx, rows, C);
+    hipLaunchKernelGGL(softmax_rows_bwd_kernel, dim3(ape::grid_for(rows, kT, kGridCap)), dim3(kT), 0, (hipStream_t)stream, dy, y, dx, rows, C);
     return ape::check_launch("ape_softmax_rows_bwd_f32");
 }
 
@@ -574,7 +574,7 @@ extern "C" int ape_jaccard_bwd_f32(const float* logits, const long* strides_host
     const float* coef = (const float*)((const double*)ws + blocks * K * 3);
     const unsigned* flags = (const unsigned*)(coef + (size_t)2 * K * ncol);
     const long npix = (long)B * H * W;
-    int groups = grid_for(npix);
+    int groups = ape::grid_for(npix, kT, kGridCap);
     groups = groups > 4096 ? 4096 : groups;
     hipLaunchKernelGGL(jaccard_bwd_kernel, dim3(groups), dim3(kT), 0, (hipStream_t)stream, logits, mk_strides(strides_host), labels, npix, ncol,
                        H, W, C, coef, flags, gscale, dlogits, mk_strides(dstrides_host));
@@ -591,7 +591,7 @@ extern "C" int ape_confusion_add(const float* pred_scores, const long* pred_stri
     const long npix = (long)B * H * W;
     if (npix == 0) return APE_OK;
     const long zero[4] = {0, 0, 0, 0};
-    int groups = grid_for(npix);
+    int groups = ape::grid_for(npix, kT, kGridCap);
     groups = groups > 1024 ? 1024 : groups;
     hipLaunchKernelGGL(confusion_kernel, dim3(groups), dim3(kT), 0, (hipStream_t)stream, pred_scores,
                        mk_strides(pred_scores ? pred_strides_host : zero), pred_labels, tgt_scores, mk_strides(tgt_scores ? tgt_strides_host : zero),
@@ -614,7 +614,7 @@ extern "C" int ape_sgd_step_multi_f32(int n, const ape_sgd_job* jobs, float lr, 
             if (momentum == 0.f) b.j[i].momentum_buffer = nullptr;
             nmax = jobs[i0 + i].n > nmax ? jobs[i0 + i].n : nmax;
         }
-        int gx = grid_for(nmax);
+        int gx = ape::grid_for(nmax, kT, kGridCap);
         gx = gx > 256 ? 256 : gx;
         hipLaunchKernelGGL(sgd_multi_kernel, dim3(gx, nb), dim3(kT), 0, (hipStream_t)stream, b, lr, momentum, dampening, weight_decay, nesterov);
     }

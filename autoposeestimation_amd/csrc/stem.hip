@@ -16,13 +16,11 @@
 // rects[o][0] at (rects[o][1], rects[o][2]); NULL rects: whole frames -- and ToTensor / Normalize (pipeline/utils.py:421-427, 556-560)
 // run on the way into LDS with ape_preprocess_u8_nhwc4's own expressions, so the results are bit for bit those of the two launches
 // while the fp32 NHWC4 image (16 B per pixel: 315 MB written and read back per 64 frames) never exists.
-#include "common.h"
+#include "mfma_common.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace ape;
 
 constexpr int PTY = 4, PTX = 8;                 // pooled tile
 constexpr int CR = 2 * PTY + 1, CC = 2 * PTX + 1;   // conv outputs under it: 9 x 17
@@ -77,7 +75,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const void* __restric
                 const int kx = 2 * kq + (j >> 2), ch = j & 3;
                 const float v = kx < 7 ? w[((co * 7 + ky) * 7 + kx) * 4 + ch] : 0.f;
                 bh[cb][ky][j] = (__bf16)v;
-                bl[cb][ky][j] = (__bf16)(v - (float)bh[cb][ky][j]);
+                bl[cb][ky][j] = split_lo(v, bh[cb][ky][j]);
             }
     }
     // ---- this lane's A fragment origin per row block: element offset of patch pixel (2 cy, 2 cx + 2 kq) ----------------------
@@ -137,8 +135,8 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const void* __restric
             hi[0] = (__bf16)v.x; hi[1] = (__bf16)v.y; hi[2] = (__bf16)v.z; hi[3] = (__bf16)v.w;
             *reinterpret_cast<bf16x4*>(patch + e * 4) = hi;
             if (NPL == 2) {
-                lo[0] = (__bf16)(v.x - (float)hi[0]); lo[1] = (__bf16)(v.y - (float)hi[1]);
-                lo[2] = (__bf16)(v.z - (float)hi[2]); lo[3] = (__bf16)(v.w - (float)hi[3]);
+                lo[0] = split_lo(v.x, hi[0]); lo[1] = split_lo(v.y, hi[1]);
+                lo[2] = split_lo(v.z, hi[2]); lo[3] = split_lo(v.w, hi[3]);
                 *reinterpret_cast<bf16x4*>(patch + NPATCH * 4 + e * 4) = lo;
             }
         }

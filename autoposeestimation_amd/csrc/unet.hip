@@ -16,13 +16,12 @@
 // Epilogues: (1) folded-BN bias + ReLU, fp32 NHWC store into y[.., yoff + co] (ldy); (2) HEAD, classes <= 16 (NC = 1): bias, then
 // csrc/seg_head.h's softmax (+ softmax) / arg-max / tie rule, label u8 + score f32 per pixel -- the logits are never stored.
 // Pixel and element offsets are 64-bit: at B = 64 the 240 x 320 x 128 virtual input of decoder block 3 is 629 M elements.
-#include "common.h"
+#include "mfma_common.h"
 #include "seg_head.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace ape;
 
 constexpr int UNET_WAVES = 4;
 
@@ -38,16 +37,6 @@ struct UnetArgs {
     long plane_stride;
     int lda, C1, ldb, C2, Ctot, K, H, W, Cout, ldy, yoff, head_dsm;
 };
-
-__device__ __forceinline__ void split8(const float4 v0, const float4 v1, bf16x8& hi, bf16x8& lo)
-{
-    const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        hi[e] = (__bf16)v[e];
-        lo[e] = (__bf16)(v[e] - (float)hi[e]);
-    }
-}
 
 template <int NSPLIT, bool UPS, int NC, int NP, bool HEAD>
 __global__ __launch_bounds__(64 * UNET_WAVES) void unet_conv3x3_kernel(const UnetArgs g)

@@ -23,15 +23,12 @@
 // Persistent workgroups (one per CU) walk the tiles in an XCD-contiguous order; the next tile's pixels are requested as soon as the
 // current tile's matrix phase is over and land during its gather phases.
 #include <type_traits>
-#include "common.h"
 #include "s32.h"
 #include "seg_head.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
+using namespace ape;
 
 // diagnostic build only (make stamps -> libape_hip_stamps.so, tools/stamp_upfuse.py): s_memtime sums per (workgroup, wave) and segment of the tile loop
 #ifdef APE_UPFUSE_STAMPS
@@ -46,13 +43,6 @@ typedef __attribute__((address_space(3))) void lds_void;
     } while (0)
 #else
 #define STAMP(i) do { } while (0)
-#endif
-
-// timing-only ablation switches (results wrong when set): compiled into the diagnostic build only
-#ifdef APE_UPFUSE_ABLATIONS
-#define ABL(bit) (a.dbg & (bit))
-#else
-#define ABL(bit) 0
 #endif
 
 struct UpFuseArgs {
@@ -87,8 +77,6 @@ constexpr int xa_bytes(int G) { return G * RA * COLS * 128; }
 constexpr int xb_bytes(int G) { return G * RB * COLS * 128; }
 constexpr int lds_bytes(int G) { return xa_bytes(G) + xb_bytes(G) + SB_BYTES + HW_BYTES + HB_BYTES + CB_BYTES; }
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // Both interpolations are built from the hand-written two-channel instructions below (v_pk_fma_f32 / v_pk_mul_f32 with an op_sel weight
 // broadcast); APE_NO_ASM_MATH = 1 writes the same arithmetic in C (hipcc's SLP vectoriser then emits packed instructions of its own, with two
 // v_mov per broadcast in places: 1.5 % slower at bench size, same bits).
@@ -282,7 +270,7 @@ __global__ __launch_bounds__(NW * 64) void upconv_fused_kernel(const UpFuseArgs 
         if (ABL(16)) return;
         const int iyb = ty0 / 2 - 1, ixb = tx0 / 2 - 1;
         const unsigned long long base = reinterpret_cast<unsigned long long>(a.x) + (unsigned long long)tb * (unsigned long long)frame;
-        const i32x4 rs = {(int)(unsigned)base, (int)(unsigned)((base >> 32) & 0xFFFFu), (int)frame, 0x00020000};
+        const i32x4 rs = {(int)(unsigned)base, (int)(unsigned)((base >> 32) & 0xFFFFu), (int)frame, BUF_RSRC_FLAGS};
         int ln_d = lane;
         asm volatile("" : "+v"(ln_d));
         auto piece = [&](int p) __attribute__((always_inline)) {
@@ -307,7 +295,7 @@ __global__ __launch_bounds__(NW * 64) void upconv_fused_kernel(const UpFuseArgs 
     // ---- the weights of this wave's (kx, slab): three taps x 16 rows x G channel groups, hi | lo
     bf16x8 wh[G][3], wl[G][3];
     {
-        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, 9 * 64 * G * 128, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, 9 * 64 * G * 128, BUF_RSRC_FLAGS);
         const unsigned wv = (unsigned)((lane & 15) * (G * 128) + (lane >> 4) * 16);
 #pragma unroll
         for (int g = 0; g < G; ++g)
