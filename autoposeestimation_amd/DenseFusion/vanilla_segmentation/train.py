@@ -7,7 +7,9 @@ phase -- plus `segment_files`, which writes the label PNGs the DenseFusion evalu
                          model_save_path='trained_models/', log_dir='logs/', resume_model=''))
 
 `opt` carries the reference's option names (nothing is parsed at import).  Optional extras: `train_list` / `test_list` (the two txt lists,
-default the YCB config's), `train_length` / `test_length` (5000 / 1000), `manualSeed`, `precision`."""
+default the YCB config's), `train_length` / `test_length` (5000 / 1000), `manualSeed`, `precision`, and `device_samples`: when set, both
+loops take their batches from `SegDataset.batch` -- samples built on the GPU from a cache of decoded frames (augment.py), the same draws
+from the same generators -- and no DataLoader or worker process is used (`workers` is then ignored).  Absent means false."""
 import logging
 import os
 import random
@@ -54,6 +56,23 @@ def train_step(model, optimizer, rgb, target, criterion=None):
     return semantic_loss.detach()
 
 
+class DeviceBatches:
+    """what the loops iterate over with `device_samples`: per pass ceil(len(dataset) / batch_size) batches of `SegDataset.batch`, the last
+    one short, as a DataLoader without `drop_last` delivers them"""
+
+    def __init__(self, dataset, batch_size):
+        self.dataset, self.batch_size = dataset, int(batch_size)
+
+    def __len__(self):
+        return (len(self.dataset) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        left = len(self.dataset)
+        while left > 0:
+            yield self.dataset.batch(min(self.batch_size, left))
+            left -= self.batch_size
+
+
 @torch.no_grad()
 def evaluate(model, batches, criterion=None, log=None):
     """train.py:86-101: the mean loss of the eval-mode model over `batches` of (rgb, target)"""
@@ -77,10 +96,14 @@ def main(opt):
     torch.manual_seed(opt.manualSeed)
     train_list = getattr(opt, "train_list", None) or os.path.join(_YCB_CONFIG, "train_data_list.txt")
     test_list = getattr(opt, "test_list", None) or os.path.join(_YCB_CONFIG, "test_data_list.txt")
-    dataset = SegDataset(opt.dataset_root, train_list, True, int(getattr(opt, "train_length", 5000)))
-    dataloader = torch.utils.data.DataLoader(dataset, batch_size=int(opt.batch_size), shuffle=True, num_workers=int(opt.workers))
-    test_dataset = SegDataset(opt.dataset_root, test_list, False, int(getattr(opt, "test_length", 1000)))
-    test_dataloader = torch.utils.data.DataLoader(test_dataset, batch_size=1, shuffle=True, num_workers=int(opt.workers))
+    device = "cuda" if getattr(opt, "device_samples", False) else None
+    dataset = SegDataset(opt.dataset_root, train_list, True, int(getattr(opt, "train_length", 5000)), device=device)
+    test_dataset = SegDataset(opt.dataset_root, test_list, False, int(getattr(opt, "test_length", 1000)), device=device)
+    if device is not None:
+        dataloader, test_dataloader = DeviceBatches(dataset, opt.batch_size), DeviceBatches(test_dataset, 1)
+    else:
+        dataloader = torch.utils.data.DataLoader(dataset, batch_size=int(opt.batch_size), shuffle=True, num_workers=int(opt.workers))
+        test_dataloader = torch.utils.data.DataLoader(test_dataset, batch_size=1, shuffle=True, num_workers=int(opt.workers))
     print(len(dataset), len(test_dataset))
 
     model = SegNet().cuda()

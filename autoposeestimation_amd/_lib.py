@@ -201,6 +201,11 @@ SIGNATURES = {
     "ape_gather2x2_nhwc_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
     "ape_cross_entropy_workspace_bytes": [_c.c_long],
     "ape_cross_entropy_f32": [_P, _I, _I, _P, _c.c_long, _F, _P, _P, _P, _c.c_size_t, _P],
+    # SegNet training samples (csrc/segnet_samples.hip): vanilla_segmentation/data_controller.py:43-93; `ape_segnet_job` is mirrored next to
+    # its one user, DenseFusion/vanilla_segmentation/augment.py
+    "ape_segnet_samples_frames_offset": [_I],
+    "ape_segnet_samples_prepare": [_P, _I, _I, _I, _P, _c.c_size_t, _P],
+    "ape_segnet_samples": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _c.c_size_t, _P],
     # overlays (csrc/overlay.hip): the color_prediction images of pipeline/utils.py:471-476,576-585 and the review screens' :280-286,362
     "ape_overlay_stamp_counts_f64": [_P, _I, _P, _c.c_long, _P, _I, _P, _D, _D, _D, _D, _I, _P, _I, _I, _I, _I, _P],
     "ape_overlay_blend_u8": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
@@ -208,8 +213,9 @@ SIGNATURES = {
 
 
 # The struct mirrors below are the ones tests/test_abi.py compares with the C compiler's layout.  They are not every mirror of the header:
-# those of `ape_linemod_job` and of `ape_ycb_job` / `ape_ycb_jitter` / `ape_ycb_pair` live next to their one user
-# (DenseFusion/datasets/{linemod,ycb}/augment.py) and get the same layout check in tests/test_linemod_host.py and tests/test_ycb_host.py.
+# those of `ape_linemod_job`, of `ape_ycb_job` / `ape_ycb_jitter` / `ape_ycb_pair` and of `ape_segnet_job` live next to their one user
+# (DenseFusion/datasets/{linemod,ycb}/augment.py, DenseFusion/vanilla_segmentation/augment.py) and get the same layout check in
+# tests/test_linemod_host.py, tests/test_ycb_host.py and tests/test_segnet_samples_host.py.
 class AdamJob(_c.Structure):
     """Mirror of `ape_adam_job` (include/ape_hip.h)."""
     _fields_ = [("param", _c.c_void_p), ("grad", _c.c_void_p), ("exp_avg", _c.c_void_p), ("exp_avg_sq", _c.c_void_p), ("n", _c.c_long),
@@ -283,12 +289,12 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
              "ape_linemod_tables_offset": _c.c_size_t, "ape_linemod_sel_offset": _c.c_size_t, "ape_linemod_workspace_bytes": _c.c_size_t,
              "ape_ycb_rows_offset": _c.c_size_t, "ape_ycb_tables_offset": _c.c_size_t, "ape_ycb_sel_offset": _c.c_size_t,
              "ape_ycb_noise_offset": _c.c_size_t, "ape_pose_errors_workspace_bytes": _c.c_size_t,
-             "ape_cross_entropy_workspace_bytes": _c.c_size_t}
+             "ape_cross_entropy_workspace_bytes": _c.c_size_t, "ape_segnet_samples_frames_offset": _c.c_size_t}
 
 _lib = None
 
 
-ABI_VERSION = 15  # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 16  # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

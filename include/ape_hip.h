@@ -968,6 +968,44 @@ size_t ape_cross_entropy_workspace_bytes(long P);
 int ape_cross_entropy_f32(const float* logits, int ld, int C, const uint8_t* labels, long P, float g, double* out, float* dlogits,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* ---- SegNet training samples (csrc/segnet_samples.hip, csrc/segnet_px.h; reference DenseFusion/vanilla_segmentation/
+ * data_controller.py:43-93) -------------------------------------------------------------------------------------------------------------
+ * One job per sample: DEVICE pointers to the resident colour frame and one-band label and what the host drew.  back_rgb / back_label
+ * (both or neither) make the job a `data_syn` one: the frame is brightened (ImageEnhance.Brightness: pil_blend(0, v, bright), 1.5 in the
+ * reference), blurred -- Pillow's box blur of ImageFilter.GaussianBlur, three passes along the rows and then three along the columns of
+ *   out = (c * blur_ww + (l + r) * blur_fw + 2^23) >> 24, stored as u8 after every pass, the end pixel standing in for a missing
+ * neighbour -- and jittered by jit[0]; then, per pixel, v = (double)v + noise, v = (double)(jit[1](back_rgb) * (label == 0)) + v,
+ * label' = back_label * (label == 0) + label in uint8.  noise: f64 [3][H][W] in the workspace at noise_off, in un-flipped coordinates;
+ * blur_off: where the prepare launch leaves the blurred frame u8 [H][W][3] in the workspace.  A job without a background is a real frame:
+ * jit[0] of the raw frame (an empty list = none) and its label.  flip: 0 left-right, 1 up-down, 2 both, 3 neither, applied last.
+ * Output: rgb[c] = ((float)v - mean[c]) / std[c] on the 0..255 scale, target = label'. */
+typedef struct ape_segnet_job {
+    const uint8_t* rgb;          /* [H][W][3] */
+    const uint8_t* label;        /* [H][W] */
+    const uint8_t* back_rgb;     /* [H][W][3] or null */
+    const uint8_t* back_label;   /* [H][W] or null */
+    long long noise_off;
+    long long blur_off;
+    ape_aug_jitter jit[2];
+    float bright;
+    uint32_t blur_ww, blur_fw;
+    int flip;
+} ape_segnet_job;
+APE_STATIC_ASSERT(sizeof(ape_segnet_job) == 168, "ape_segnet_job layout (mirrored by vanilla_segmentation/augment.py SegnetJob)");
+/* The workspace of a batch: [B][2][64] u64 luma partial sums (frame, background) | from ape_segnet_samples_frames_offset(B) (a multiple
+ * of 16) on, wherever the jobs' blur_off (a multiple of 16, H*W*3 bytes) and noise_off (a multiple of 8, 24*H*W bytes) say; the caller
+ * keeps these regions apart.  One per stream; not shared by batches in flight at once. */
+size_t ape_segnet_samples_frames_offset(int B);
+/* Launch A: writes the blurred frame of every `data_syn` job and, per workgroup, one partial of the integer L sum the contrast op of
+ * each list needs, over the image it jitters as it is when the op runs.  flip and noise_off are not read.  APE_EINVAL, nothing launched:
+ * a null or half-given pointer, a list jitter_ok refuses, blur_ww + 2 * blur_fw above 2^24, a NaN bright, a blur_off that is misaligned
+ * or whose frame does not lie inside the workspace behind the sums; a short workspace: APE_EWORKSPACE. */
+int ape_segnet_samples_prepare(const ape_segnet_job* jobs_host, int B, int H, int W, void* ws, size_t ws_bytes, void* stream);
+/* Launch B, after the caller copied the noise into the workspace: rgb[B][3][H][W] f32, target[B][H][W] i64.  The refusals of launch A;
+ * a flip outside 0..3; a noise_off that is misaligned or whose planes do not lie inside the workspace behind the sums. */
+int ape_segnet_samples(const ape_segnet_job* jobs_host, int B, int H, int W, const float* mean3_host, const float* std3_host, float* rgb,
+                       long long* target, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- overlays of the live view and of the label-review screens (csrc/overlay.hip) -------------------------------------------------
  * Replaces the `color_prediction` painting of full_prediction, pipeline/utils.py:471-476 (class tint), :510-513 and :576-585 (model
  * cloud stamped at the predicted pose) with pc_reconstruction/open3d_utils.py:233-243 (points2pixel) and :246-270 (pointcloud2image);
