@@ -204,6 +204,15 @@ SIGNATURES = {
     # SegNet training samples (csrc/segnet_samples.hip): vanilla_segmentation/data_controller.py:43-93; `ape_segnet_job` is mirrored next to
     # its one user, DenseFusion/vanilla_segmentation/augment.py
     "ape_segnet_samples_frames_offset": [_I],
+    "ape_rgbd_gate_f64": [_P, _P, _P, _I, _I, _I, _P],
+    "ape_rgbd_plane_fill_f64": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "ape_rgbd_box_f64": [_P, _P, _I, _I, _I, _I, _P],
+    "ape_rgbd_score_f64": [_P, _P, _P, _P, _P, _I, _P, _D, _P, _P, _I, _I, _I, _P],
+    "ape_rgbd_morph_f64": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "ape_rgbd_wrap_u8": [_P, _P, _c.c_long, _P],
+    "ape_rgbd_cca_workspace_bytes": [_I, _I, _I],
+    "ape_rgbd_component_stats": [_P, _P, _P, _P, _I, _I, _I, _P, _c.c_size_t, _P],
+    "ape_rgbd_cca_round": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _c.c_size_t, _P],
     "ape_segnet_samples_prepare": [_P, _I, _I, _I, _P, _c.c_size_t, _P],
     "ape_segnet_samples": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _c.c_size_t, _P],
     # overlays (csrc/overlay.hip): the color_prediction images of pipeline/utils.py:471-476,576-585 and the review screens' :280-286,362
@@ -289,12 +298,13 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
              "ape_linemod_tables_offset": _c.c_size_t, "ape_linemod_sel_offset": _c.c_size_t, "ape_linemod_workspace_bytes": _c.c_size_t,
              "ape_ycb_rows_offset": _c.c_size_t, "ape_ycb_tables_offset": _c.c_size_t, "ape_ycb_sel_offset": _c.c_size_t,
              "ape_ycb_noise_offset": _c.c_size_t, "ape_pose_errors_workspace_bytes": _c.c_size_t,
-             "ape_cross_entropy_workspace_bytes": _c.c_size_t, "ape_segnet_samples_frames_offset": _c.c_size_t}
+             "ape_cross_entropy_workspace_bytes": _c.c_size_t, "ape_segnet_samples_frames_offset": _c.c_size_t,
+             "ape_rgbd_cca_workspace_bytes": _c.c_size_t}
 
 _lib = None
 
 
-ABI_VERSION = 16  # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 17  # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

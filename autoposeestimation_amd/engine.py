@@ -1233,3 +1233,107 @@ def recentre_qt(pts, qt7):
     _lib.call.ape_recentre_qt_f32(_lib.dptr(pts, torch.float32), _lib.dptr(qt7, torch.float32), _lib.dptr(out),
                                   pts.shape[0], _st())
     return out
+
+
+# ---- classical RGB-D labeller (csrc/label_rgbd.hip; label_generator/utils.py) -------------------------------------------------------
+RGBD_MODE_RGB, RGBD_MODE_HSV, RGBD_MODE_BOTH = 0, 1, 2
+_F64 = torch.float64
+
+
+def rgbd_gate(depth, measure_dist):
+    """depth[B,H,W] u16, measure_dist[B] f64 -> f64 [B,H,W]: the value inside measure_dist +- 150, else 0"""
+    b, h, w = depth.shape
+    out = torch.empty(b, h, w, dtype=_F64, device=depth.device)
+    _lib.call.ape_rgbd_gate_f64(_lib.dptr(depth, torch.uint16), _lib.dptr(measure_dist, _F64), _lib.dptr(out), b, h, w, _st())
+    return out
+
+
+def rgbd_plane_fill(b_depth, pts, valid, window):
+    """the centre window (r0, r1, c0, c1) of the gated background depth b_depth[B,H,W] f64, IN PLACE: holes filled from the plane through
+    pts[B,3,3] f64, then the 5 x 5 box filter; frames with valid[B] i32 == 0 stay as they are"""
+    b, h, w = b_depth.shape
+    r0, r1, c0, c1 = window
+    tmp = torch.empty(b, r1 - r0, c1 - c0, dtype=_F64, device=b_depth.device)
+    _lib.call.ape_rgbd_plane_fill_f64(_lib.dptr(b_depth, _F64), _lib.dptr(pts, _F64), _lib.dptr(valid, torch.int32), _lib.dptr(tmp), b, h, w,
+                                      r0, r1, c0, c1, _st())
+    return b_depth
+
+
+def rgbd_score(f_rgb, b_rgb, f_depth, b_depth, measure_dist, mode, weights, depth_weight, threshold):
+    """-> (score, color) f64 [B,H,W]; weights: up to six channel weights; depth_weight <= 0: no depth term (the depth arguments may be None)"""
+    b, h, w, _ = f_rgb.shape
+    score = torch.empty(b, h, w, dtype=_F64, device=f_rgb.device)
+    color = torch.empty_like(score)
+    w7 = (ctypes.c_double * 7)(*([float(v) for v in weights] + [0.0] * (6 - len(weights)) + [float(depth_weight)]))
+    _lib.call.ape_rgbd_score_f64(_lib.dptr(f_rgb, torch.uint8), _lib.dptr(b_rgb, torch.uint8),
+                                 _lib.dptr(f_depth, torch.uint16) if f_depth is not None else None,
+                                 _lib.dptr(b_depth, _F64) if b_depth is not None else None,
+                                 _lib.dptr(measure_dist, _F64) if measure_dist is not None else None, mode,
+                                 ctypes.cast(w7, ctypes.c_void_p), float(threshold), _lib.dptr(score), _lib.dptr(color), b, h, w, _st())
+    return score, color
+
+
+def rgbd_morph(img, k, dilate, out=None):
+    """erode / dilate of img[B,H,W] f64 with a k x k all-ones kernel; out may be img"""
+    b, h, w = img.shape
+    out = torch.empty_like(img) if out is None else out
+    tmp = torch.empty_like(img)
+    _lib.call.ape_rgbd_morph_f64(_lib.dptr(img, _F64), _lib.dptr(out, _F64), _lib.dptr(tmp), b, h, w, int(k), int(bool(dilate)), _st())
+    return out
+
+
+def rgbd_open_close(img, open, close):
+    """MORPH_OPEN with `open`, then MORPH_CLOSE with `close` (0 skips); img itself is never written: it is returned when both are skipped"""
+    cur = img
+    for k, dil in ((open, 0), (open, 1), (close, 1), (close, 0)):
+        if k > 0:
+            cur = rgbd_morph(cur, k, dil, out=None if cur is img else cur)
+    return cur
+
+
+def rgbd_wrap_u8(img):
+    out = torch.empty(img.shape, dtype=torch.uint8, device=img.device)
+    _lib.call.ape_rgbd_wrap_u8(_lib.dptr(img, _F64), _lib.dptr(out), img.numel(), _st())
+    return out
+
+
+def _rgbd_ws(b, h, w, device):
+    nbytes = _lib.lib().ape_rgbd_cca_workspace_bytes(b, h, w)
+    if nbytes == 0 and b:
+        raise ValueError("batch of %d frames of %d x %d is outside the labeller's limits" % (b, h, w))
+    return _workspace(max(nbytes, 256), device)
+
+
+def rgbd_component_stats(img):
+    """img[B,H,W] f64 -> root i32 (index of the component's first pixel in the batch, -1 = background), and at those first pixels
+    count u32 and sum f64 of img over the component"""
+    b, h, w = img.shape
+    root = torch.empty(b, h, w, dtype=torch.int32, device=img.device)
+    count = torch.empty(b, h, w, dtype=torch.uint32, device=img.device)
+    total = torch.empty(b, h, w, dtype=_F64, device=img.device)
+    ws = _rgbd_ws(b, h, w, img.device)
+    _lib.call.ape_rgbd_component_stats(_lib.dptr(img, _F64), _lib.dptr(root), _lib.dptr(count), _lib.dptr(total), b, h, w, _lib.dptr(ws),
+                                       ws.numel(), _st())
+    return root, count, total
+
+
+def rgbd_cca_round(img, color, min_size, by_size, remove_one_std=False, final=False, want_mean_std=False):
+    """one component round on img[B,H,W] f64: color is masked (and cut) IN PLACE, or with final=True the u8 mask is returned"""
+    b, h, w = img.shape
+    out = torch.empty(b, h, w, dtype=torch.uint8, device=img.device) if final else None
+    ms = torch.empty(b, 2, dtype=_F64, device=img.device) if want_mean_std else None
+    ws = _rgbd_ws(b, h, w, img.device)
+    _lib.call.ape_rgbd_cca_round(_lib.dptr(img, _F64), _lib.dptr(color, _F64), _lib.dptr(out) if final else None,
+                                 _lib.dptr(ms) if want_mean_std else None, b, h, w, int(min_size), int(bool(by_size)),
+                                 int(bool(remove_one_std)), _lib.dptr(ws), ws.numel(), _st())
+    if want_mean_std:
+        return (out if final else color), ms
+    return out if final else color
+
+
+def rgbd_box(img, k=5):
+    """the reference's `smoothing`: k x k box filter of img[B,H,W] f64 with float32 taps, BORDER_REFLECT_101"""
+    b, h, w = img.shape
+    out = torch.empty_like(img)
+    _lib.call.ape_rgbd_box_f64(_lib.dptr(img, _F64), _lib.dptr(out), b, h, w, int(k), _st())
+    return out

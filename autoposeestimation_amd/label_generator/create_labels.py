@@ -275,3 +275,62 @@ def create_pose_data(root, classes, ds_name, reference_point=np.array([]), new_p
         dist.all_reduce(t)
         stats = {k: int(v) for k, v in zip(keys, t.cpu().tolist())}
     return stats, times
+
+
+# ---- "Create Labels", mode 'gen': the classical RGB-D labeller over a data directory (reference :443-530) ----------------
+def _read_gen_batch(foreground_path, background_path, ids, reference_point):
+    """decode one batch on the host -> (f_rgb, b_rgb, f_depth, b_depth, measure_dist) arrays, seconds spent decoding"""
+    from autoposeestimation_amd.data_generation import sample_io as io
+    t0 = time.perf_counter()
+    f_rgb = np.stack([io.read_color(foreground_path, s) for s in ids])
+    b_rgb = np.stack([io.read_color(background_path, s) for s in ids])
+    f_depth = np.stack([io.read_depth(foreground_path, s) for s in ids])
+    b_depth = np.stack([io.read_depth(background_path, s) for s in ids])
+    dist = np.array([np.linalg.norm(reference_point - io.robot2cam(io.read_meta(foreground_path, s))[:3, 3]) for s in ids], dtype=np.float64)
+    return (f_rgb, b_rgb, f_depth, b_depth, dist), time.perf_counter() - t0
+
+
+def create_labels(object_name, root, reference_point=np.array([]), plot=False, hsv=False, both=True, batch=16, timing=None):
+    """reference :443-530: for every directory of `data_generation/data/<object_name>` but `background` and `extra`, pair frame idx with
+    background frame idx, label the pair with createLabel_RGBD(threshold=30, open=6, close=6, remove_one_std=True) at
+    measure_dist = |reference_point - camera position| and write `label_generator/data/<object_name>/<dir>/<idx>.gen.label.png`.
+    `batch` frame pairs go through the device per pass while host threads decode the next batches (`sharding.prefetched`); `timing` (a dict) receives the seconds
+    spent in all and in PNG decode.  Parity with OpenCV unpinned (label_generator/utils.py).  An empty `reference_point` raises ValueError:
+    the reference then reads an unbound `intr`."""
+    from autoposeestimation_amd import sharding
+    from autoposeestimation_amd.data_generation import sample_io as io
+    from autoposeestimation_amd.label_generator.utils import label_frames_rgbd
+    if plot:
+        raise NotImplementedError("plot=True is a matplotlib debugging view of the reference; not provided")
+    reference_point = np.asarray(reference_point, dtype=np.float64).reshape(-1)
+    if reference_point.size == 0:
+        raise ValueError("create_labels needs a reference_point: the depth gate is measure_dist +- 150 around it")
+    if not torch.cuda.is_available():
+        raise RuntimeError("create_labels runs on the GPU only (no CPU fallback in this build)")
+    device = torch.device("cuda:0")
+    object_path = os.path.join(root, "data_generation/data", object_name)
+    dirs = sorted(os.listdir(object_path))
+    background_path = os.path.join(object_path, "background")
+    if "background" not in dirs:
+        raise ValueError("background does not exist in object_path: {}".format(object_path))
+    dirs.remove("background")
+    if "extra" in dirs:
+        dirs.remove("extra")
+    if len(dirs) < 1:
+        raise ValueError("no foreground")
+    n = int(len(os.listdir(background_path)) / 3)
+    jobs = [(d, ["{:06d}".format(i) for i in range(i0, min(n, i0 + batch))]) for d in dirs for i0 in range(0, n, batch)]
+    ns, counter, t_decode, t_start = n * len(dirs), 0, 0.0, time.perf_counter()
+    load = lambda job: _read_gen_batch(os.path.join(object_path, job[0]), background_path, job[1], reference_point)  # noqa: E731
+    for (d, ids), (arrays, dt) in zip(jobs, sharding.prefetched(jobs, load, workers=2, window=2)):
+        t_decode += dt
+        f_rgb, b_rgb, f_depth, b_depth, dist = (torch.from_numpy(a).to(device) for a in arrays)
+        labels = label_frames_rgbd(f_rgb, b_rgb, f_depth, b_depth, dist, threshold=30, hsv=hsv, both=both, close=6, open=6,
+                                   remove_one_std=True).cpu().numpy()
+        save_dir = os.path.join(root, "label_generator/data", object_name, d)
+        for s, lab in zip(ids, labels):
+            io.write_label(save_dir, s, "gen", lab)
+        counter += len(ids)
+        print("number = {}/{}".format(counter, ns))
+    if timing is not None:
+        timing.update(seconds=time.perf_counter() - t_start, decode_seconds=t_decode, frames=counter)

@@ -1042,6 +1042,47 @@ int ape_overlay_blend_u8(const uint8_t* rgb, const uint8_t* objmap, const int32_
                          const double* seg_colour, const double* mark, const int32_t* n_cand, int n, const uint32_t* planes,
                          int J, int B, int H, int W, int point_size, int mode, uint8_t* seg_out, uint8_t* pose_out, void* stream);
 
+/* ---- classical RGB-D labeller   label_generator/utils.py:45-364 (createLabel_RGBD), csrc/label_rgbd.hip ------------------------
+ * A batch of frame pairs [B][H][W], float64 where the reference is.  Parity with OpenCV unpinned: cvtColor, morphologyEx, filter2D and
+ * connectedComponents follow the documented semantics restated in tests/label_rgbd_reference.py.  B <= 65535, B H W < 2^31 - 64. */
+#define APE_RGBD_MODE_RGB 0
+#define APE_RGBD_MODE_HSV 1
+#define APE_RGBD_MODE_BOTH 2
+/* depth u16 -> out f64: the value inside [measure_dist[b] - 150, measure_dist[b] + 150], else 0 (:102-108) */
+int ape_rgbd_gate_f64(const uint16_t* depth, const double* measure_dist, double* out, int B, int H, int W, void* stream);
+/* the centre window rows r0..r1-1, columns c0..c1-1 of the gated background depth, in place (:135-159): holes take
+ * norm of (row, col, Z) of the plane through pts[B][3][3] f64 = three (row, col, depth) window points, then the 5 x 5 box filter with
+ * float32 taps and BORDER_REFLECT_101 over the window.  valid[B] i32 == 0 leaves the frame alone.  tmp: f64 [B][r1-r0][c1-c0]. */
+int ape_rgbd_plane_fill_f64(double* b_depth, const double* pts, const int* valid, double* tmp, int B, int H, int W, int r0, int r1,
+                            int c0, int c1, void* stream);
+/* smoothing (:26-30): filter2D with ones((k, k), float32) / (k k), BORDER_REFLECT_101, the taps summed in row-major order; dst != src */
+int ape_rgbd_box_f64(const double* src, double* dst, int B, int H, int W, int k, void* stream);
+/* the score (:179-251) in one pass: channel differences (HSV through OpenCV's 8-bit integer formula), hue times 256/180, clip at 100,
+ * weights7_host[0..5] per channel, summed left to right -> color; plus the clipped depth difference times weights7_host[6] when that
+ * is > 0 (f_depth is gated here, b_depth is the prepared f64 frame, the mutual zeroing of :165-166 happens per pixel); values below
+ * threshold become 0 -> score.  Without a depth term f_depth, b_depth and measure_dist may be NULL. */
+int ape_rgbd_score_f64(const uint8_t* f_rgb, const uint8_t* b_rgb, const uint16_t* f_depth, const double* b_depth,
+                       const double* measure_dist, int mode, const double* weights7_host, double threshold, double* score,
+                       double* color, int B, int H, int W, void* stream);
+/* erode (dilate == 0) or dilate with a k x k all-ones kernel anchored at k / 2: min / max over offsets -(k/2) .. k-1-(k/2) of the
+ * in-image pixels, rows then columns.  dst may be src; tmp (same size) may be neither. */
+int ape_rgbd_morph_f64(const double* src, double* dst, double* tmp, int B, int H, int W, int k, int dilate, void* stream);
+/* np.array(img, dtype=np.uint8) of a non-negative image: truncate toward zero, wrap modulo 256 */
+int ape_rgbd_wrap_u8(const double* img, uint8_t* out, long npix, void* stream);
+size_t ape_rgbd_cca_workspace_bytes(int B, int H, int W);
+/* 8-connected components of the wrapped image's non-zero pixels: root[p] = the batch-wide index of the component's first pixel in
+ * raster order (-1: background); at those pixels count = the component's size and sum = the sum of img over it (elsewhere 0).  The sum
+ * is accumulated in integer fixed point (2^-52 units): it does not depend on the order of arrival. */
+int ape_rgbd_component_stats(const double* img, int* root, unsigned int* count, double* sum, int B, int H, int W, void* workspace,
+                             size_t workspace_bytes, void* stream);
+/* one component round (:271-315 with by_size == 0, :330-355 with by_size == 1): among the components of img with more than min_size
+ * pixels the one with the largest int(mean of img) or the largest size wins, strict '>' in raster order; without a winner the
+ * reference's uni[0] is kept: the background region, or everything when no pixel is background.  color is zeroed outside the kept
+ * label in place; remove_one_std then zeroes its pixels below mean - std of its non-zero pixels (mean_std_or_null[B][2] receives the
+ * two).  With out_or_null the final mask (255 where the kept colour score is non-zero) is written instead and color is left alone. */
+int ape_rgbd_cca_round(const double* img, double* color, uint8_t* out_or_null, double* mean_std_or_null, int B, int H, int W,
+                       int min_size, int by_size, int remove_one_std, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
