@@ -218,6 +218,9 @@ SIGNATURES = {
     # overlays (csrc/overlay.hip): the color_prediction images of pipeline/utils.py:471-476,576-585 and the review screens' :280-286,362
     "ape_overlay_stamp_counts_f64": [_P, _I, _P, _c.c_long, _P, _I, _P, _D, _D, _D, _D, _I, _P, _I, _I, _I, _I, _P],
     "ape_overlay_blend_u8": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    # label-quality audit (csrc/label_audit.hip): compute_IoU's counts and the comparison image of experiments/gt_test.py:105-120,160-194
+    "ape_label_pair_counts_u8": [_P, _I, _I, _I, _P, _I, _P, _P],
+    "ape_label_pair_blend_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _D, _D, _P, _P],
 }
 
 
@@ -304,7 +307,7 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
 _lib = None
 
 
-ABI_VERSION = 17  # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 18  # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

@@ -1337,3 +1337,36 @@ def rgbd_box(img, k=5):
     out = torch.empty_like(img)
     _lib.call.ape_rgbd_box_f64(_lib.dptr(img, _F64), _lib.dptr(out), b, h, w, int(k), _st())
     return out
+
+
+# ---- label-quality audit (csrc/label_audit.hip; experiments/gt_test.py) ---------------------------------------------------------------
+def label_pair_counts(labels, pairs):
+    """labels[B,L,H,W] u8 (L <= 8 label planes per sample, non-zero = foreground), pairs: up to 16 plane pairs (a, b) -> int64 [B,P,4]:
+    per sample and pair the pixels with a fg & b fg, a fg & b bg, a bg & b fg, both bg -- compute_IoU's tp, fp, fn, tn, its naming"""
+    if labels.dim() != 4:
+        raise ValueError("labels must be [B, L, H, W], got %s" % (tuple(labels.shape),))
+    b, l, h, w = labels.shape
+    flat = [int(v) for pr in pairs for v in pr]
+    if not flat or len(flat) % 2 or any(len(pr) != 2 for pr in pairs):
+        raise ValueError("pairs must be a non-empty list of (a, b) plane indices")
+    p = len(flat) // 2
+    counts = torch.empty(b, p, 4, dtype=torch.int64, device=labels.device)
+    table = (ctypes.c_int32 * (2 * p))(*flat)
+    _lib.call.ape_label_pair_counts_u8(_lib.dptr(labels, torch.uint8), b, l, h * w, ctypes.cast(table, ctypes.c_void_p), p, _lib.dptr(counts),
+                                       _st())
+    return counts
+
+
+def label_pair_blend(rgb, labels, first, second, c0, c1):
+    """rgb[B,H,W,3] u8, labels[B,L,H,W] u8, first = (plane_a, ch_a), second = (plane_b, ch_b) -> u8 [B,H,W,3]: the frame with
+    `v*c0 + label*c1` (float64, truncated) in channel ch_a where plane_a is set, then the same for plane_b / ch_b on that result"""
+    if rgb.dim() != 4 or rgb.shape[3] != 3 or labels.dim() != 4 or labels.shape[0] != rgb.shape[0] or tuple(labels.shape[2:]) != tuple(rgb.shape[1:3]):
+        raise ValueError("rgb must be [B, H, W, 3] and labels [B, L, H, W] of the same frames, got %s and %s"
+                         % (tuple(rgb.shape), tuple(labels.shape)))
+    if labels.device != rgb.device:
+        raise ValueError("rgb is on %s, labels on %s" % (rgb.device, labels.device))
+    b, h, w, _ = rgb.shape
+    out = torch.empty_like(rgb)
+    _lib.call.ape_label_pair_blend_u8(_lib.dptr(rgb, torch.uint8), _lib.dptr(labels, torch.uint8), b, labels.shape[1], h, w, int(first[0]),
+                                      int(first[1]), int(second[0]), int(second[1]), float(c0), float(c1), _lib.dptr(out), _st())
+    return out

@@ -705,3 +705,47 @@ def ycb_poses_files(root, dirs, result_dir, perturb=None, lost=()):
             written[(now, k)] = poses[k].copy()
         scio.savemat(os.path.join(result_dir, "%04d.mat" % now), {"poses": poses})
     return written
+
+
+# ---- the label-quality test's three directory trees (experiments/gt_test.py:12-14,49-57) ---------------------------------------------
+GT_TEST_ROTATIONS = ("foreground", "foreground180")
+
+
+def gt_test_tree(root, classes=("Disk", "Joint"), n=3, h=12, w=16, seed=0):
+    """`experiments/data/gt_test`, `label_generator/data` and `data_generation/data` under `root` for `n` samples per class and rotation
+    directory: the hand annotation is a random rectangle, saved as an RGBA PNG (red and opaque inside, transparent black outside: what
+    annotation tools write); `new_pred`, `pred` and `gen` are its vertical, horizontal and double flip, each with a different edge of
+    the rectangle trimmed (so the two one-sided counts of a pair differ), saved as `L` PNGs with the values 255, 255 and 1; the colour
+    frame is uniform noise.  Deterministic in `seed`.  -> {(cls, rot): [sample ids]}"""
+    import os
+    from PIL import Image
+    ids = {}
+    for cls in classes:
+        for rot in GT_TEST_ROTATIONS:
+            gt_dir = os.path.join(root, "experiments", "data", "gt_test", cls, rot)
+            lab_dir = os.path.join(root, "label_generator", "data", cls, rot)
+            img_dir = os.path.join(root, "data_generation", "data", cls, rot)
+            for d in (gt_dir, lab_dir, img_dir):
+                os.makedirs(d, exist_ok=True)
+            ids[(cls, rot)] = []
+            for i in range(n):
+                sid = "%06d" % i
+                rng = _rng(seed, "gt_test/%s/%s/%s" % (cls, rot, sid))
+                r0, c0 = int(rng.integers(0, h // 2)), int(rng.integers(0, w // 2))
+                r1, c1 = int(rng.integers(r0 + max(1, h // 3), h + 1)), int(rng.integers(c0 + max(1, w // 3), w + 1))
+                mask = np.zeros((h, w), dtype=bool)
+                mask[r0:r1, c0:c1] = True
+                rgba = np.zeros((h, w, 4), dtype=np.uint8)
+                rgba[mask] = (255, 0, 0, 255)
+                Image.fromarray(rgba, "RGBA").save(os.path.join(gt_dir, sid + ".color.mask.0.png"))
+                trimmed = []
+                for dr0, dc0, dr1, dc1 in ((1, 0, 0, 0), (0, 2, 0, 0), (0, 0, 1, 1)):
+                    m = np.zeros((h, w), dtype=bool)
+                    m[r0 + dr0:r1 - dr1, c0 + dc0:c1 - dc1] = True
+                    trimmed.append(m)
+                for kind, lab, value in (("new_pred", trimmed[0][::-1], 255), ("pred", trimmed[1][:, ::-1], 255),
+                                         ("gen", trimmed[2][::-1, ::-1], 1)):
+                    Image.fromarray(lab.astype(np.uint8) * np.uint8(value), "L").save(os.path.join(lab_dir, "%s.%s.label.png" % (sid, kind)))
+                Image.fromarray(rng.integers(0, 256, (h, w, 3), dtype=np.uint8), "RGB").save(os.path.join(img_dir, sid + ".color.png"))
+                ids[(cls, rot)].append(sid)
+    return ids

@@ -1083,6 +1083,24 @@ int ape_rgbd_component_stats(const double* img, int* root, unsigned int* count, 
 int ape_rgbd_cca_round(const double* img, double* color, uint8_t* out_or_null, double* mean_std_or_null, int B, int H, int W,
                        int min_size, int by_size, int remove_one_std, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- label-quality audit   experiments/gt_test.py (compute_IoU :160-194, the comparison image :105-120), csrc/label_audit.hip -------
+ * labels: u8 [B][L][HW], L label planes per sample, densely packed: plane p of sample b starts at byte (b L + p) HW, whatever its
+ * alignment.  A pixel is foreground when its byte is not zero.  B L HW < 2^31. */
+/* counts u64 [B][P][4] for the P plane pairs pairs_host[P][2] = (a, b) of every sample, in the reference's order and under its names:
+ * a fg and b fg ("tp"), a fg and b bg ("fp"), a bg and b fg ("fn"), both bg ("tn") -- the four values 0, 1, 2, 3 of its uint8
+ * difference; "fp" and "fn" are swapped against the textbook meaning when a is the ground truth, which is restated, not corrected.
+ * One pass: every plane is read once and serves all pairs.  counts (8-byte aligned) is cleared on the stream first and every entry is
+ * written: a second call overwrites.  Integer sums, exact and independent of the order of arrival.  1 <= L <= 8, 1 <= P <= 16;
+ * APE_EINVAL (nothing enqueued) for a null pointer, a size out of range, a pair index outside 0..L-1 or a misaligned counts. */
+int ape_label_pair_counts_u8(const uint8_t* labels, int B, int L, int HW, const int32_t* pairs_host, int P, uint64_t* counts,
+                             void* stream);
+/* out u8 [B][H][W][3] = rgb, then where labels[plane_a] != 0: out[ch_a] = u8(trunc(double(out[ch_a]) c0 + double(label_a) c1)), then
+ * the same with plane_b and ch_b on what the first step left (it matters when ch_a == ch_b).  float64, the product and the sum rounded
+ * separately; a result outside 0..255 wraps modulo 256 (unpinned: the reference's c0 + c1 = 1 keeps it inside).  Every byte of out is
+ * written.  APE_EINVAL for a null pointer, out overlapping rgb, a channel outside 0..2, a plane outside 0..L-1, a size below 1. */
+int ape_label_pair_blend_u8(const uint8_t* rgb, const uint8_t* labels, int B, int L, int H, int W, int plane_a, int ch_a, int plane_b,
+                            int ch_b, double c0, double c1, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
