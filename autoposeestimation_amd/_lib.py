@@ -144,6 +144,11 @@ SIGNATURES = {
     "ape_ransac_batch_workspace_bytes": [_I, _P, _I, _I],
     "ape_ransac_hypotheses_batch_f64": [_I, _P, _P, _P, _P, _P, _I, _P, _D, _D, _I, _I, _I, _P, _P, _P, _c.c_size_t, _P],
     "ape_ransac_validate_batch_f64": [_I, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _D, _P, _P, _P, _c.c_size_t, _P],
+    # fast global registration (csrc/registration.hip, batched forms only: the one-pair call is a batch of one)
+    "ape_fgr_mutual_batch": [_I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ape_fgr_workspace_bytes": [_I, _I],
+    "ape_fgr_tuples_batch_f64": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _D, _I, _I, _I, _P, _P, _P, _c.c_size_t, _P],
+    "ape_fgr_optimize_batch_f64": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _D, _D, _I, _P, _P, _P],
     # segmentor training (csrc/segtrain.hip)
     "ape_bn_workspace_bytes": [_I],
     "ape_bn_train_fwd_f32": [_P] * 10 + [_c.c_long, _I, _F, _F, _I, _P, _c.c_size_t, _P],
@@ -289,7 +294,7 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
              "ape_conv2d_wgrad_workspace_bytes": _c.c_size_t, "ape_conv_gemm_splitk_workspace_bytes": _c.c_size_t,
              "ape_fpfh_workspace_bytes": _c.c_size_t, "ape_feature_nn1_workspace_bytes": _c.c_size_t, "ape_ransac_workspace_bytes": _c.c_size_t,
              "ape_fpfh_batch_workspace_bytes": _c.c_size_t, "ape_feature_nn1_batch_workspace_bytes": _c.c_size_t,
-             "ape_ransac_batch_workspace_bytes": _c.c_size_t,
+             "ape_ransac_batch_workspace_bytes": _c.c_size_t, "ape_fgr_workspace_bytes": _c.c_size_t,
              "ape_bn_workspace_bytes": _c.c_size_t, "ape_jaccard_workspace_bytes": _c.c_size_t,
              "ape_bgsub_train_workspace_bytes": _c.c_size_t, "ape_seg_train_workspace_bytes": _c.c_size_t,
              "ape_seg_train_extents_offset": _c.c_size_t, "ape_seg_train_tables_offset": _c.c_size_t,
@@ -307,7 +312,7 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
 _lib = None
 
 
-ABI_VERSION = 18  # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 19  # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

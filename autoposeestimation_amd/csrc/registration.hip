@@ -10,6 +10,9 @@
 //                        max_validation of them in iteration order
 //   ransac_validate_*    every kept hypothesis against the whole source cloud (nearest target within max_correspondence_distance through
 //                        the target's grid), fixed-order sums, then the winner by (fitness desc, rmse asc, iteration asc)
+//   fgr_*                fast global registration on the same features: the mutual matches in source order, the tuple test in chunks of
+//                        trials (the first maximum_tuple_count passing ones in trial order), each cloud's mean and largest centred norm,
+//                        and the whole Gauss-Newton optimisation of a pair in one workgroup (correspondences in LDS)
 // The neighbour lists of pass 1 are written out (12 B per entry) rather than recomputed in pass 2: the selection -- min(max_nn, candidates)
 // rounds of a 32-lane shuffle reduction over the candidate list -- is most of pass 1's time, and re-reading 1.2 KB per point is not.
 // Every kernel is written in the batched form of pointcloud.hip ("BATCHED forms"): a by-value table of up to kMaxBatch per-pair argument
@@ -482,6 +485,288 @@ __global__ __launch_bounds__(kT) void ransac_select_kernel(const Batch<BVal> bt)
     out[16] = bf; out[17] = br; out[18] = bc; out[19] = bk; out[20] = bk >= 0 ? (double)kept[bk] : -1.0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Fast global registration (Zhou, Park, Koltun, ECCV 2016; open3d 0.9 FastGlobalRegistration.cpp restated).
+// fgr_mutual_kernel: one block per pair walks the source in kT-sized steps and keeps, in ascending i, the pairs (i, nn_st[i]) whose
+// match points back (nn_ts[nn_st[i]] == i) -- the ordered in-block compaction of ransac_hyp_kernel with a running base.
+struct BMut { const int* nn_st; const int* nn_ts; int* ms; int* mt; int* n_mutual; int ns, nt; };
+
+__global__ __launch_bounds__(kT) void fgr_mutual_kernel(const Batch<BMut> bt)
+{
+    const BMut& a = bt.t[blockIdx.x];
+    const int* __restrict__ nn_st = a.nn_st;
+    const int* __restrict__ nn_ts = a.nn_ts;
+    const int ns = a.nt > 0 ? a.ns : 0, nt = a.nt;
+    __shared__ int wc[kT / 64];
+    const int wave = threadIdx.x / 64, wl = threadIdx.x % 64;
+    int base = 0;
+    for (int i0 = 0; i0 < ns; i0 += kT) {
+        const int i = i0 + threadIdx.x;
+        int j = -1;
+        bool pass = false;
+        if (i < ns) {
+            j = nn_st[i];
+            pass = j >= 0 && j < nt && nn_ts[j] == i;
+        }
+        const unsigned long long m = __ballot(pass);
+        __syncthreads();
+        if (wl == 0) wc[wave] = __popcll(m);
+        __syncthreads();
+        int off = 0, tot = 0;
+        for (int w = 0; w < kT / 64; ++w) { off += w < wave ? wc[w] : 0; tot += wc[w]; }
+        if (pass) {
+            const int o = base + off + __popcll(m & ((1ULL << wl) - 1ULL));
+            a.ms[o] = i;
+            a.mt[o] = j;
+        }
+        base += tot;
+    }
+    if (threadIdx.x == 0) *a.n_mutual = base;
+}
+
+// the tuple test: trial t draws three positions of the mutual list (the RANSAC sampler's form) and passes when every edge of the source
+// triangle and its target twin are within tuple_scale of each other, both ways, strictly.  Trials [t0, t0 + n_t) of pair blockIdx.y,
+// below the pair's own limit of 100 * ncorr; the passing trial indices go to blist / bcount exactly as ransac_hyp_kernel's, and
+// ransac_append_kernel keeps the first max_tuples of them
+struct BTup { const double* src; const double* tgt; const int* ms; const int* mt; const int* n_mutual; const int* n_kept; int* blist; int* bcount; u64 seed; int lim; };   // lim = min(ns, nt): a count beyond it is not a mutual list's
+
+__device__ __forceinline__ int fgr_draw(u64 seed, int t, int k, int ncorr)
+{
+    return (int)(splitmix64((seed << 32) ^ (u64)(3LL * t + k)) % (u64)ncorr);
+}
+
+__global__ __launch_bounds__(kT) void fgr_tuple_kernel(const Batch<BTup> bt, int t0, int n_t, int max_tuples, double tuple_scale)
+{
+    const BTup& a = bt.t[blockIdx.y];
+    if (*a.n_kept >= max_tuples) return;
+    const double* __restrict__ src = a.src;
+    const double* __restrict__ tgt = a.tgt;
+    const int ncorr = *a.n_mutual;
+    __shared__ int wc[kT / 64];
+    const int gid = blockIdx.x * kT + threadIdx.x;
+    bool pass = false;
+    if (gid < n_t && ncorr > 0 && ncorr <= a.lim && (long long)t0 + gid < 100LL * ncorr) {
+        int si[3], ti[3];
+        for (int k = 0; k < 3; ++k) {
+            const int r = fgr_draw(a.seed, t0 + gid, k, ncorr);
+            si[k] = a.ms[r];
+            ti[k] = a.mt[r];
+        }
+        pass = true;
+        for (int k = 0; k < 3; ++k) {
+            const double* sa = src + (size_t)si[k] * 3; const double* sb = src + (size_t)si[(k + 1) % 3] * 3;
+            const double* ta = tgt + (size_t)ti[k] * 3; const double* tb = tgt + (size_t)ti[(k + 1) % 3] * 3;
+            const double es[3] = {sa[0] - sb[0], sa[1] - sb[1], sa[2] - sb[2]}, et[3] = {ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2]};
+            const double li = sqrt(dot3(es, es)), lj = sqrt(dot3(et, et));
+            if (!(li * tuple_scale < lj && lj * tuple_scale < li)) pass = false;
+        }
+    }
+    const unsigned long long m = __ballot(pass);
+    const int wave = threadIdx.x / 64, wl = threadIdx.x % 64;
+    if (wl == 0) wc[wave] = __popcll(m);
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int w = 0; w < kT / 64; ++w) { off += w < wave ? wc[w] : 0; tot += wc[w]; }
+    if (pass) a.blist[(size_t)blockIdx.x * kT + off + __popcll(m & ((1ULL << wl) - 1ULL))] = t0 + gid;
+    if (threadIdx.x == 0) a.bcount[blockIdx.x] = tot;
+}
+
+// mean and largest centred norm of one cloud: blockIdx.x = 0 source / 1 target, blockIdx.y = pair; thread t sums points t, t + kT, ... in
+// order, the block folds the kT partials by a halving tree -> norm8[x * 4 ..] = (mean[3], max |p - mean|); zeros for an empty cloud
+struct BCen { const double* pts[2]; int n[2]; double* norm8; };
+
+__global__ __launch_bounds__(kT) void fgr_center_kernel(const Batch<BCen> bt)
+{
+    const BCen& a = bt.t[blockIdx.y];
+    const double* __restrict__ p = a.pts[blockIdx.x];
+    const int n = a.n[blockIdx.x];
+    __shared__ double sh[3][kT];
+    double s[3] = {0, 0, 0};
+    for (int i = threadIdx.x; i < n; i += kT) for (int d = 0; d < 3; ++d) s[d] += p[(size_t)i * 3 + d];
+    for (int d = 0; d < 3; ++d) sh[d][threadIdx.x] = s[d];
+    __syncthreads();
+    for (int m = kT / 2; m >= 1; m >>= 1) {
+        if ((int)threadIdx.x < m) for (int d = 0; d < 3; ++d) sh[d][threadIdx.x] += sh[d][threadIdx.x + m];
+        __syncthreads();
+    }
+    double mu[3];
+    for (int d = 0; d < 3; ++d) mu[d] = n > 0 ? sh[d][0] / (double)n : 0.0;
+    __syncthreads();
+    double mx = 0.0;
+    for (int i = threadIdx.x; i < n; i += kT) {
+        const double e[3] = {p[(size_t)i * 3] - mu[0], p[(size_t)i * 3 + 1] - mu[1], p[(size_t)i * 3 + 2] - mu[2]};
+        const double v = sqrt(dot3(e, e));
+        if (v > mx) mx = v;
+    }
+    sh[0][threadIdx.x] = mx;
+    __syncthreads();
+    for (int m = kT / 2; m >= 1; m >>= 1) {
+        if ((int)threadIdx.x < m && sh[0][threadIdx.x + m] > sh[0][threadIdx.x]) sh[0][threadIdx.x] = sh[0][threadIdx.x + m];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double* out = a.norm8 + blockIdx.x * 4;
+        out[0] = mu[0]; out[1] = mu[1]; out[2] = mu[2]; out[3] = sh[0][0];
+    }
+}
+
+// x = -(L D L^T)^-1 b without pivoting; false at the first pivot that is not finite and positive
+__device__ bool fgr_ldlt_solve(const double A[6][6], const double b[6], double x[6])
+{
+    double L[6][6], D[6];
+    for (int j = 0; j < 6; ++j) {
+        double d = A[j][j];
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k] * D[k];
+        if (!(d > 0.0) || !(d < INFINITY)) return false;
+        D[j] = d;
+        for (int i = j + 1; i < 6; ++i) {
+            double v = A[i][j];
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k] * D[k];
+            L[i][j] = v / d;
+        }
+    }
+    double y[6];
+    for (int i = 0; i < 6; ++i) {
+        double v = b[i];
+        for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
+        y[i] = v;
+    }
+    for (int i = 0; i < 6; ++i) y[i] /= D[i];
+    for (int i = 5; i >= 0; --i) {
+        double v = y[i];
+        for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
+        x[i] = v;
+    }
+    for (int i = 0; i < 6; ++i) x[i] = -x[i];
+    return true;
+}
+
+// The whole optimisation of pair blockIdx.x in one workgroup.  The correspondences (three per kept trial, re-drawn from the trial index)
+// are loaded once into LDS as (p target, q source), centred and scaled, one row per coordinate; a thread owns entries t, t + kT, ... for the whole loop, so the
+// list needs no barrier.  An iteration: every thread adds its entries' 27 sums (upper triangle of JTJ, then JTr) in entry order, a wave
+// folds its 64 lanes by a butterfly of shuffles (every lane ends with the same bits), thread 0 adds the kT / 64 wave totals in wave order,
+// solves by LDL^T and builds the update (TransformVector6dToMatrix4d), and all threads move their q.  Nothing is written to global memory
+// before the end.  out[24]: [0..15] T in the clouds' own units, [16] iterations run, [17] scale, [18] the last par, [19] correspondences
+struct BFgr { const double* src; const double* tgt; const int* ms; const int* mt; const int* n_mutual; const int* kept; const double* norm8; double* out; u64 seed; int ns, nt, nk; };
+
+constexpr int kFgrMaxCorr = 3000;
+
+__global__ __launch_bounds__(kT) void fgr_optimize_kernel(const Batch<BFgr> bt, int use_absolute_scale, int decrease_mu, double division_factor,
+                                                          double max_corr_dist, int n_iter)
+{
+    extern __shared__ __attribute__((aligned(16))) double fgr_pq[];          // [6][nc]: p.xyz then q.xyz, a row per coordinate, so that
+                                                                             // the lanes of a wave touch consecutive doubles
+    __shared__ double wsum[kT / 64][27];
+    __shared__ double delta[12];
+    __shared__ int ok;
+    const BFgr& a = bt.t[blockIdx.x];
+    const double* __restrict__ nm = a.norm8;
+    double* __restrict__ out = a.out;
+    const int nc = 3 * a.nk;
+    const int ncorr = *a.n_mutual;
+    const double scale = nm[3] > nm[7] ? nm[3] : nm[7];
+    const double sg = use_absolute_scale ? 1.0 : scale;
+    double par = use_absolute_scale ? scale : 1.0;
+    if (nc < 10 || ncorr < 1 || ncorr > a.ns || ncorr > a.nt) {              // too few correspondences: the identity
+        if (threadIdx.x == 0) {
+            for (int e = 0; e < 16; ++e) out[e] = (e % 5 == 0) ? 1.0 : 0.0;
+            out[16] = 0.0; out[17] = scale; out[18] = par; out[19] = (double)nc;
+        }
+        return;
+    }
+    for (int c = threadIdx.x; c < nc; c += kT) {
+        const int r = fgr_draw(a.seed, a.kept[c / 3], c % 3, ncorr);
+        const int i = a.ms[r], j = a.mt[r];
+        for (int d = 0; d < 3; ++d) {
+            fgr_pq[d * nc + c] = (a.tgt[(size_t)j * 3 + d] - nm[4 + d]) / sg;
+            fgr_pq[(3 + d) * nc + c] = (a.src[(size_t)i * 3 + d] - nm[d]) / sg;
+        }
+    }
+    double T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};                     // thread 0's: rows 0..2 of the normalised transformation
+    const int wave = threadIdx.x / 64, wl = threadIdx.x % 64;
+    int it = 0;
+    for (; it < n_iter; ++it) {
+        if (decrease_mu && it % 4 == 0 && par > max_corr_dist) par /= division_factor;
+        double acc[27];
+#pragma unroll
+        for (int v = 0; v < 27; ++v) acc[v] = 0.0;
+        for (int c = threadIdx.x; c < nc; c += kT) {
+            const double* e = fgr_pq + c;
+            const double q[3] = {e[3 * nc], e[4 * nc], e[5 * nc]};
+            const double r[3] = {e[0] - q[0], e[nc] - q[1], e[2 * nc] - q[2]};
+            const double w = par / (dot3(r, r) + par);
+            const double s = w * w;
+            const double J[3][6] = {{0.0, -q[2], q[1], -1.0, 0.0, 0.0}, {q[2], 0.0, -q[0], 0.0, -1.0, 0.0}, {-q[1], q[0], 0.0, 0.0, 0.0, -1.0}};
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                int v = 0;
+#pragma unroll
+                for (int x = 0; x < 6; ++x) {
+                    const double sj = s * J[k][x];
+#pragma unroll
+                    for (int y = x; y < 6; ++y) { acc[v] += sj * J[k][y]; ++v; }
+                    acc[21 + x] += sj * r[k];
+                }
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < 27; ++v) {
+            double t = acc[v];
+            for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m, 64);
+            if (wl == 0) wsum[wave][v] = t;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double A[6][6], b[6], x[6];
+            int v = 0;
+            for (int p = 0; p < 6; ++p)
+                for (int q = p; q < 6; ++q) {
+                    double t = wsum[0][v];
+                    for (int w = 1; w < kT / 64; ++w) t += wsum[w][v];
+                    A[p][q] = A[q][p] = t;
+                    ++v;
+                }
+            for (int p = 0; p < 6; ++p) {
+                double t = wsum[0][21 + p];
+                for (int w = 1; w < kT / 64; ++w) t += wsum[w][21 + p];
+                b[p] = t;
+            }
+            const bool solved = fgr_ldlt_solve(A, b, x);
+            if (solved) {
+                const double cx = cos(x[0]), sx = sin(x[0]), cy = cos(x[1]), sy = sin(x[1]), cz = cos(x[2]), sz = sin(x[2]);
+                // TransformVector6dToMatrix4d: R = Rz(x2) Ry(x1) Rx(x0), as icp_step in pointcloud.hip
+                const double Rx[3][3] = {{1, 0, 0}, {0, cx, -sx}, {0, sx, cx}}, Ry[3][3] = {{cy, 0, sy}, {0, 1, 0}, {-sy, 0, cy}}, Rz[3][3] = {{cz, -sz, 0}, {sz, cz, 0}, {0, 0, 1}};
+                double T1[3][3], U[12], Tn[12];
+                for (int p = 0; p < 3; ++p) for (int q = 0; q < 3; ++q) T1[p][q] = (Rz[p][0] * Ry[0][q] + Rz[p][1] * Ry[1][q]) + Rz[p][2] * Ry[2][q];
+                for (int p = 0; p < 3; ++p) {
+                    for (int q = 0; q < 3; ++q) U[p * 4 + q] = (T1[p][0] * Rx[0][q] + T1[p][1] * Rx[1][q]) + T1[p][2] * Rx[2][q];
+                    U[p * 4 + 3] = x[3 + p];
+                }
+                for (int p = 0; p < 3; ++p)
+                    for (int q = 0; q < 4; ++q)
+                        Tn[p * 4 + q] = ((U[p * 4] * T[q] + U[p * 4 + 1] * T[4 + q]) + U[p * 4 + 2] * T[8 + q]) + (q == 3 ? U[p * 4 + 3] : 0.0);
+                for (int e = 0; e < 12; ++e) { T[e] = Tn[e]; delta[e] = U[e]; }
+            }
+            ok = solved ? 1 : 0;
+        }
+        __syncthreads();
+        if (!ok) break;
+        for (int c = threadIdx.x; c < nc; c += kT) {
+            double* e = fgr_pq + c;
+            const double x = e[3 * nc], y = e[4 * nc], z = e[5 * nc];
+            for (int p = 0; p < 3; ++p) e[(3 + p) * nc] = ((delta[p * 4] * x + delta[p * 4 + 1] * y) + delta[p * 4 + 2] * z) + delta[p * 4 + 3];
+        }
+    }
+    if (threadIdx.x == 0) {                                                  // original scale: R kept, t = sg t_norm + mean_t - R mean_s
+        for (int p = 0; p < 3; ++p) {
+            for (int q = 0; q < 3; ++q) out[p * 4 + q] = T[p * 4 + q];
+            out[p * 4 + 3] = (sg * T[p * 4 + 3] + nm[4 + p]) - ((T[p * 4] * nm[0] + T[p * 4 + 1] * nm[1]) + T[p * 4 + 2] * nm[2]);
+        }
+        out[12] = 0.0; out[13] = 0.0; out[14] = 0.0; out[15] = 1.0;
+        out[16] = (double)it; out[17] = scale; out[18] = par; out[19] = (double)nc;
+    }
+}
+
 int validate_blocks(int ns)
 {
     const int g = ape::ceil_div(ns, kGroups);
@@ -639,6 +924,12 @@ int validate_launch(int nb, const Grid* g, const Hyp* h, const int* const* kept,
     return ape::check_launch(what);
 }
 
+size_t fgr_ws(int chunk)
+{
+    const size_t nb = (size_t)ape::ceil_div(chunk < 1 ? 1 : chunk, kT);
+    return align_up(nb * kT * 4) + align_up(nb * 4);
+}
+
 }  // namespace
 
 #define APE_BATCH_CHECK(nb) if ((nb) < 1 || (nb) > kMaxBatch) return APE_EINVAL
@@ -781,4 +1072,96 @@ extern "C" int ape_ransac_validate_batch_f64(int nb, BGRID_ARGS, const double* c
         kp[c] = kept + (size_t)c * kept_stride;
     }
     return validate_launch(nb, g, h, kp, n_kept_host, max_dist, result, fit_rmse, ws, ws_bytes, (hipStream_t)stream, "ape_ransac_validate_batch_f64");
+}
+
+// ---- fast global registration ---------------------------------------------------------------------------------------------------------
+extern "C" size_t ape_fgr_workspace_bytes(int nb, int chunk)
+{
+    if (nb < 1 || nb > kMaxBatch) return 0;
+    return (size_t)nb * fgr_ws(chunk);
+}
+
+extern "C" int ape_fgr_mutual_batch(int nb, const int* const* nn_st, const int* ns, const int* const* nn_ts, const int* nt, int* const* mutual_s,
+                                    int* const* mutual_t, int* n_mutual, void* stream)
+{
+    APE_BATCH_CHECK(nb);
+    if (!nn_st || !ns || !nn_ts || !nt || !mutual_s || !mutual_t || !n_mutual) return APE_EINVAL;
+    Batch<BMut> b{};
+    for (int c = 0; c < nb; ++c) {
+        if (ns[c] < 0 || nt[c] < 0) return APE_EINVAL;
+        const bool on = ns[c] > 0 && nt[c] > 0;
+        if (on && (!nn_st[c] || !nn_ts[c] || !mutual_s[c] || !mutual_t[c])) return APE_EINVAL;
+        b.t[c] = BMut{nn_st[c], nn_ts[c], mutual_s[c], mutual_t[c], n_mutual + c, on ? ns[c] : 0, on ? nt[c] : 0};
+    }
+    hipLaunchKernelGGL(fgr_mutual_kernel, dim3(nb), dim3(kT), 0, (hipStream_t)stream, b);
+    return ape::check_launch("ape_fgr_mutual_batch");
+}
+
+extern "C" int ape_fgr_tuples_batch_f64(int nb, const double* const* src, const int* ns, const double* const* tgt, const int* nt,
+                                        const int* const* mutual_s, const int* const* mutual_t, const int* n_mutual, const long* seed_host,
+                                        double tuple_scale, int trial_begin, int n_trials, int max_tuples, int* kept, int* n_kept, void* ws,
+                                        size_t ws_bytes, void* stream)
+{
+    APE_BATCH_CHECK(nb);
+    if (!src || !ns || !tgt || !nt || !mutual_s || !mutual_t || !n_mutual || !seed_host || !kept || !n_kept || !ws || trial_begin < 0 ||
+        n_trials < 0 || trial_begin > 0x7fffffff - n_trials || max_tuples < 1)
+        return APE_EINVAL;
+    if (n_trials == 0) return APE_OK;
+    if (ws_bytes < (size_t)nb * fgr_ws(n_trials)) return APE_EWORKSPACE;
+    const int nblk = ape::ceil_div(n_trials, kT);
+    Batch<BTup> b{};
+    Batch<BHyp> ba{};
+    char* p = (char*)ws;
+    for (int c = 0; c < nb; ++c) {
+        if (ns[c] < 0 || nt[c] < 0) return APE_EINVAL;
+        const int lim = ns[c] < nt[c] ? ns[c] : nt[c];
+        if (lim > 0 && (!src[c] || !tgt[c] || !mutual_s[c] || !mutual_t[c])) return APE_EINVAL;
+        int* blist = (int*)p;
+        int* bcount = (int*)(p + align_up((size_t)nblk * kT * 4));
+        p += fgr_ws(n_trials);
+        b.t[c] = BTup{src[c], tgt[c], mutual_s[c], mutual_t[c], n_mutual + c, n_kept + c, blist, bcount, (u64)seed_host[c], lim};
+        ba.t[c] = BHyp{Hyp{}, kept + (size_t)c * max_tuples, n_kept + c, blist, bcount};
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(fgr_tuple_kernel, dim3(nblk, nb), dim3(kT), 0, st, b, trial_begin, n_trials, max_tuples, tuple_scale);
+    hipLaunchKernelGGL(ransac_append_kernel, dim3(1, nb), dim3(kT), 0, st, ba, nblk, max_tuples);
+    return ape::check_launch("ape_fgr_tuples_batch_f64");
+}
+
+extern "C" int ape_fgr_optimize_batch_f64(int nb, const double* const* src, const int* ns, const double* const* tgt, const int* nt,
+                                          const int* const* mutual_s, const int* const* mutual_t, const int* n_mutual, const long* seed_host,
+                                          const int* kept, int kept_stride, const int* n_kept_host, int use_absolute_scale, int decrease_mu,
+                                          double division_factor, double max_corr_dist, int iteration_number, double* norm8, double* result,
+                                          void* stream)
+{
+    APE_BATCH_CHECK(nb);
+    if (!src || !ns || !tgt || !nt || !mutual_s || !mutual_t || !n_mutual || !seed_host || !kept || !n_kept_host || !norm8 || !result ||
+        kept_stride < 1 || iteration_number < 0)
+        return APE_EINVAL;
+    Batch<BCen> bc{};
+    Batch<BFgr> b{};
+    int mk = 0;
+    for (int c = 0; c < nb; ++c) {
+        if (ns[c] < 0 || nt[c] < 0 || n_kept_host[c] < 0 || n_kept_host[c] > kept_stride || 3 * n_kept_host[c] > kFgrMaxCorr) return APE_EINVAL;
+        const bool on = ns[c] > 0 && nt[c] > 0;
+        if (on && (!src[c] || !tgt[c] || !mutual_s[c] || !mutual_t[c])) return APE_EINVAL;
+        if (!on && n_kept_host[c] > 0) return APE_EINVAL;
+        bc.t[c] = BCen{{src[c], tgt[c]}, {ns[c], nt[c]}, norm8 + (size_t)c * 8};
+        b.t[c] = BFgr{src[c], tgt[c], mutual_s[c], mutual_t[c], n_mutual + c, kept + (size_t)c * kept_stride, norm8 + (size_t)c * 8,
+                      result + (size_t)c * 24, (u64)seed_host[c], ns[c], nt[c], n_kept_host[c]};
+        mk = n_kept_host[c] > mk ? n_kept_host[c] : mk;
+    }
+    static std::atomic<unsigned long long> attr_devs{0};                   // the dynamic-LDS attribute is per device
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return APE_ELAUNCH;
+    if (!(attr_devs.load(std::memory_order_relaxed) >> dev & 1ULL)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(fgr_optimize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kFgrMaxCorr * 6 * 8) != hipSuccess)
+            return APE_ELAUNCH;
+        attr_devs.fetch_or(1ULL << dev, std::memory_order_relaxed);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(fgr_center_kernel, dim3(2, nb), dim3(kT), 0, st, bc);
+    hipLaunchKernelGGL(fgr_optimize_kernel, dim3(nb), dim3(kT), (size_t)(mk < 1 ? 1 : mk) * 3 * 6 * 8, st, b, use_absolute_scale, decrease_mu, division_factor,
+                       max_corr_dist, iteration_number);
+    return ape::check_launch("ape_fgr_optimize_batch_f64");
 }

@@ -16,6 +16,8 @@ too: `compute_fpfh_feature`, `feature_nn` and `registration_ransac` below take l
 of csrc/registration.hip (two FPFH launches for all clouds, one hypothesis chunk for every pair that is not yet full, one copy of all
 `n_kept` words per chunk, one validation for all pairs).  `pointcloud.registration_ransac_based_on_feature_matching` stays the one-pair
 reference of it (the same kernels launched with nb = 1); tests/test_gpu_registration_batch.py compares the two bit for bit.
+`registration_fast` is fast global registration on the same features (mutual matches, tuple test, one optimisation launch per batch); its
+one-pair form `pointcloud.registration_fast_based_on_feature_matching` is a batch of one.
 """
 import ctypes
 import math
@@ -577,6 +579,116 @@ def registration_ransac(sources, targets, source_features, target_features, max_
     return out
 
 
+def registration_fast(sources, targets, source_features, target_features, options):
+    """[pointcloud.registration_fast_based_on_feature_matching(s, t, fs, ft, option)] for pairs advancing together (`options`: one per
+    pair, None = the defaults; pairs are grouped by equal option values, the seed apart, and a group runs 16 pairs per launch).  Two
+    feature_nn passes, one mutual-filter launch and one copy of the counts, the tuple test in chunks (a pair that is full, or past its own
+    100 * ncorr trials, adds nothing; one copy of the kept counts per chunk), then centring and the whole optimisation in two launches and
+    the ICP evaluation of the results.  A pair's lists, sums and result depend on that pair alone, so they equal the one-pair call's bit
+    for bit -- which is this function with one-element lists.  A pair with an empty cloud gets the identity and zero counts.
+    Beside the documented fields a result carries `matches` ([mutual, 2] source / target indices) and `kept` (the kept trial indices)."""
+    n = len(sources)
+    if not (len(targets) == len(source_features) == len(target_features) == len(options) == n):
+        raise ValueError("sources, targets, source_features, target_features and options must have one entry per pair")
+    opts = [o if o is not None else PC.FastGlobalRegistrationOption() for o in options]
+    for i in range(n):
+        if int(opts[i].iteration_number) < 0:
+            raise ValueError("iteration_number must not be negative")
+        if source_features[i].num() != len(sources[i]) or target_features[i].num() != len(targets[i]):
+            raise ValueError("features and clouds differ in size")
+        if int(opts[i].maximum_tuple_count) > PC._FGR_MAX_TUPLES:
+            raise ValueError("maximum_tuple_count > %d is not supported" % PC._FGR_MAX_TUPLES)
+    out = [None] * n
+    groups = {}
+    for i in range(n):
+        o = opts[i]
+        if len(sources[i]) == 0 or len(targets[i]) == 0:
+            r = PC.RegistrationResult(np.eye(4), 0.0, 0.0, 0)
+            r.mutual, r.tuples, r.iterations = 0, 0, 0
+            r.matches, r.kept = np.zeros((0, 2), np.int64), np.zeros(0, np.int64)
+            out[i] = r
+            continue
+        key = (float(o.division_factor), bool(o.use_absolute_scale), bool(o.decrease_mu), float(o.maximum_correspondence_distance),
+               int(o.iteration_number), float(o.tuple_scale), int(o.maximum_tuple_count))
+        groups.setdefault(key, []).append(i)
+    L = _lib.lib()
+    for (div, use_abs, dec_mu, mcd, n_iter, tuple_scale, max_tuples), live in groups.items():
+        nn_st = feature_nn([source_features[i] for i in live], [target_features[i] for i in live])
+        nn_ts = feature_nn([target_features[i] for i in live], [source_features[i] for i in live])
+        Ts = [None] * len(live)
+        for idx in _chunks(live):
+            sel = [live[j] for j in idx]
+            nb = len(sel)
+            dev = sources[sel[0]].device
+            ns, nt = [len(sources[i]) for i in sel], [len(targets[i]) for i in sel]
+            src, tgt = [sources[i]._p for i in sel], [targets[i]._p for i in sel]
+            for t in src + tgt:
+                _lib.dptr(t, _D)
+            match = torch.empty(2, nb, max(min(a, b) for a, b in zip(ns, nt)), dtype=torch.int32, device=dev)     # rows: the pairs' lists
+            ms, mt = [match[0, m] for m in range(nb)], [match[1, m] for m in range(nb)]
+            n_mutual = torch.zeros(nb, dtype=torch.int32, device=dev)
+            _lib.call.ape_fgr_mutual_batch(nb, _ptrs([nn_st[j] for j in idx]), _ints(ns), _ptrs([nn_ts[j] for j in idx]), _ints(nt), _ptrs(ms), _ptrs(mt),
+                                           _lib.dptr(n_mutual), _st())
+            ncorr = n_mutual.cpu().numpy()                    # ONE copy of all pairs' counts
+            seeds = _longs([opts[i].seed for i in sel])
+            pair = (_ptrs(src), _ints(ns), _ptrs(tgt), _ints(nt), _ptrs(ms), _ptrs(mt), _lib.dptr(n_mutual), seeds)
+            stride = max(max_tuples, 1)
+            kept = torch.empty(nb, stride, dtype=torch.int32, device=dev)
+            n_kept = torch.zeros(nb, dtype=torch.int32, device=dev)
+            k = np.zeros(nb, np.int32)
+            trials = 100 * ncorr.astype(np.int64)
+            if max_tuples > 0 and trials.max() > 0:
+                if trials.max() >= 1 << 31:
+                    raise ValueError("too many mutual matches for the 32-bit trial index")
+                t_end = int(trials.max())
+                chunk, cap = min(PC._FGR_CHUNK[0], t_end), min(PC._FGR_CHUNK[1], t_end)
+                ws = torch.empty(L.ape_fgr_workspace_bytes(nb, max(chunk, cap)), dtype=torch.uint8, device=dev)
+                t0 = 0
+                while t0 < t_end:                               # bounded by the largest pair's 100 * ncorr
+                    c = min(chunk, t_end - t0)
+                    _lib.call.ape_fgr_tuples_batch_f64(nb, *pair, tuple_scale, t0, c, max_tuples, _lib.dptr(kept), _lib.dptr(n_kept), _lib.dptr(ws),
+                                                       ws.numel(), _st())
+                    t0 += c
+                    k = n_kept.cpu().numpy()                  # ONE copy of all pairs' counters per chunk
+                    if ((k >= max_tuples) | (trials <= t0)).all():
+                        break
+                    chunk = min(chunk * 2, cap)
+            norm8 = torch.empty(nb, 8, dtype=_D, device=dev)
+            res = torch.empty(nb, 24, dtype=_D, device=dev)
+            _lib.call.ape_fgr_optimize_batch_f64(nb, *pair, _lib.dptr(kept), stride, _ints(k), int(use_abs), int(dec_mu), div, mcd, n_iter,
+                                                 _lib.dptr(norm8), _lib.dptr(res), _st())
+            r_all, kept_all, match_all = res.cpu().numpy(), kept.cpu().numpy(), match.cpu().numpy()
+            for m, i in enumerate(sel):
+                r = PC.RegistrationResult(r_all[m, :16].reshape(4, 4).copy(), 0.0, 0.0, 0)
+                r.mutual, r.tuples, r.iterations = int(ncorr[m]), int(k[m]), int(round(r_all[m, 16]))
+                r.matches = match_all[:, m, :r.mutual].T.astype(np.int64)
+                r.kept = kept_all[m, :r.tuples].astype(np.int64)
+                out[i] = r
+                Ts[idx[m]] = r.transformation
+        if mcd > 0.0:                                         # fitness / rmse / correspondences: the ICP path's evaluation of T, no iteration
+            states = icp_states([sources[i] for i in live], [targets[i] for i in live], mcd, Ts, 0, PC.ICPConvergenceCriteria(max_iteration=0))
+            for i, st in zip(live, states):
+                out[i].fitness, out[i].inlier_rmse, out[i].correspondence_count = float(st[2]), float(st[3]), int(st[4])
+    return out
+
+
+def execute_fast_global_registration_batch(sources_down, targets_down, voxel_size):
+    """[open3d_utils.execute_fast_global_registration(s, t, None, None, voxel_size)]: FPFH (radius 5 * voxel, max_nn 100) of all clouds,
+    then fast global registration with maximum_correspondence_distance 0.5 * voxel and the other defaults"""
+    n = len(sources_down)
+    feats = compute_fpfh_feature(list(sources_down) + list(targets_down), voxel_size * 5, 100)
+    opt = PC.FastGlobalRegistrationOption(maximum_correspondence_distance=voxel_size * 0.5)
+    return registration_fast(sources_down, targets_down, feats[:n], feats[n:], [opt] * n)
+
+
+def _global_registration_batch(method):
+    if method == "ransac":
+        return execute_global_registration_batch
+    if method == "fgr":
+        return execute_fast_global_registration_batch
+    raise ValueError("global_method must be 'ransac' or 'fgr', not %r" % (method,))
+
+
 def execute_global_registration_batch(sources_down, targets_down, voxel_size):
     """[open3d_utils.execute_global_registration(s, t, None, None, voxel_size)] (reference :28-49): FPFH (radius 5 * voxel, max_nn 100) of
     all clouds, then RANSAC on the feature matches: distance 1.5 * voxel, ransac_n 4, edge length 0.9, 4 000 000 iterations / 500
@@ -599,17 +711,18 @@ def get_surface_batch(views, intr, min_friends, min_dist, nb_neighbors, voxel_si
     return remove_statistical_outlier(clouds, nb_neighbors, std_ratios, hint)
 
 
-def icp_regression_batch(targets, sources, voxel_size, threshold, icp_point2point=True, icp_point2plane=True, global_regression=False):
+def icp_regression_batch(targets, sources, voxel_size, threshold, icp_point2point=True, icp_point2plane=True, global_regression=False,
+                         global_method="ransac"):
     """[open3d_utils.icp_regression(t, s, ...)[2]] (reference :63-122): down-sample + normals of both clouds, p2p then p2plane ICP;
     global_regression: the RANSAC transformations of execute_global_registration_batch are the initial guesses of the ICP stages, or the
-    result when both are off"""
+    result when both are off; global_method='fgr' takes those of execute_fast_global_registration_batch instead"""
     n = len(targets)
     tg = estimate_normals(voxel_down_sample(targets, voxel_size), voxel_size * 2, 30)        # preprocess_point_cloud(target.clone(), voxel)
     sr = estimate_normals(voxel_down_sample(sources, voxel_size), voxel_size * 2, 30)
     criteria = PC.ICPConvergenceCriteria(relative_fitness=1e-2, relative_rmse=1e-2, max_iteration=100)
     Ts = [np.identity(4) for _ in range(n)]
     if global_regression:
-        Ts = [r.transformation for r in execute_global_registration_batch(sr, tg, voxel_size)]
+        Ts = [r.transformation for r in _global_registration_batch(global_method)(sr, tg, voxel_size)]
     if icp_point2point:
         Ts = registration_icp(sr, tg, threshold, Ts, 0, criteria)
     if icp_point2plane:

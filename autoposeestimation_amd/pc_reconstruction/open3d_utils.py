@@ -81,6 +81,27 @@ def execute_global_registration(source_down, target_down, source_fpfh, target_fp
         _pc.RANSACConvergenceCriteria(4000000, 500))
 
 
+def execute_fast_global_registration(source_down, target_down, source_fpfh, target_fpfh, voxel_size):
+    """The open3d tutorial's fast global registration in execute_global_registration's place: FastGlobalRegistrationOption with
+    maximum_correspondence_distance = 0.5 * voxel on the same FPFH features (a None feature is computed here, radius 5 * voxel, max_nn
+    100).  Seeded and reproducible (pointcloud.registration_fast_based_on_feature_matching)."""
+    param = _pc.KDTreeSearchParamHybrid(radius=voxel_size * 5, max_nn=100)
+    if source_fpfh is None:
+        source_fpfh = _pc.compute_fpfh_feature(source_down, param)
+    if target_fpfh is None:
+        target_fpfh = _pc.compute_fpfh_feature(target_down, param)
+    return _pc.registration_fast_based_on_feature_matching(
+        source_down, target_down, source_fpfh, target_fpfh, _pc.FastGlobalRegistrationOption(maximum_correspondence_distance=voxel_size * 0.5))
+
+
+def _global_registration(method):
+    if method == "ransac":
+        return execute_global_registration
+    if method == "fgr":
+        return execute_fast_global_registration
+    raise ValueError("global_method must be 'ransac' or 'fgr', not %r" % (method,))
+
+
 def refine_registration(source, target, result_ransac, voxel_size):
     """reference :51-59: point-to-plane ICP at 0.4 * voxel from a previous result"""
     return _pc.registration_icp(source, target, voxel_size * 0.4, result_ransac.transformation,
@@ -88,15 +109,16 @@ def refine_registration(source, target, result_ransac, voxel_size):
 
 
 def icp_regression(target, source, voxel_size=5, threshold=100, global_regression=False, icp_point2point=True,
-                   icp_point2plane=True, plot=False):
+                   icp_point2plane=True, plot=False, global_method="ransac"):
     """reference :63-122.  Returns (target_down, source_down, T); like the reference, `target` is copied and `source` is not
     (both are only read).  global_regression: FPFH features of both down-sampled clouds and RANSAC on their matches
-    (execute_global_registration) give the initial guess of the ICP stages, or the result when both are off."""
+    (execute_global_registration) give the initial guess of the ICP stages, or the result when both are off; global_method='fgr'
+    (ours, looked at only then) takes execute_fast_global_registration instead."""
     target, _ = preprocess_point_cloud(target.clone(), voxel_size)
     source, _ = preprocess_point_cloud(source, voxel_size)
     init_tf = np.identity(4)
     if global_regression:
-        init_tf = execute_global_registration(source, target, None, None, voxel_size).transformation
+        init_tf = _global_registration(global_method)(source, target, None, None, voxel_size).transformation
     criteria = _pc.ICPConvergenceCriteria(relative_fitness=1e-2, relative_rmse=1e-2, max_iteration=100)
     if icp_point2point:
         init_tf = _pc.registration_icp(source, target, threshold, init_tf, _pc.TransformationEstimationPointToPoint(),
@@ -120,8 +142,9 @@ def _post_filter(cloud, min_friends, min_dist, nb_neighbors, voxel_size=None):
 
 
 def align_point_clouds(point_clouds, min_friends, min_dist, nb_neighbors, plot=False, global_regression=False,
-                       icp_point2point=True, icp_point2plane=False, voxel_size=5, threshold=50):
-    """reference :125-168: register every further cloud to the growing target with p2p ICP, merge, down-sample, filter"""
+                       icp_point2point=True, icp_point2plane=False, voxel_size=5, threshold=50, global_method="ransac"):
+    """reference :125-168: register every further cloud to the growing target with p2p ICP, merge, down-sample, filter
+    (global_method: icp_regression's)"""
     target = point_clouds[0]
     for source in point_clouds[1:]:
         diff = np.array(source.get_center()) - np.array(target.get_center())
@@ -129,7 +152,7 @@ def align_point_clouds(point_clouds, min_friends, min_dist, nb_neighbors, plot=F
             source.translate(translation=[0, -30 - diff[1], 0])
         target, source, init_tf = icp_regression(target, source, voxel_size=voxel_size, threshold=threshold,
                                                  global_regression=global_regression, icp_point2point=True,
-                                                 icp_point2plane=False, plot=plot)
+                                                 icp_point2plane=False, plot=plot, global_method=global_method)
         source = source.transform(init_tf)
         target.points = np.concatenate((np.array(source.points), np.array(target.points)))
         target = target.voxel_down_sample(voxel_size=voxel_size)

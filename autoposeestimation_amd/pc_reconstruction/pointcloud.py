@@ -433,6 +433,46 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
     return res
 
 
+# ---- fast global registration on the same features (Zhou, Park, Koltun, ECCV 2016; csrc/registration.hip fgr_*) ----------------------
+_FGR_CHUNK = (1 << 14, 1 << 20)      # trials of the first tuple-test chunk, and the cap the chunk doubles up to
+_FGR_MAX_TUPLES = 1000               # 3 * 1000 correspondences x (p, q) fill the optimisation kernel's LDS
+
+
+class FastGlobalRegistrationOption:
+    """open3d.registration.FastGlobalRegistrationOption.  The defaults are open3d 0.9's Python defaults as recalled from memory (open3d is
+    not installed here: UNPINNED); `seed` is ours and seeds the tuple sampler."""
+
+    def __init__(self, division_factor=1.4, use_absolute_scale=False, decrease_mu=False, maximum_correspondence_distance=0.025,
+                 iteration_number=64, tuple_scale=0.95, maximum_tuple_count=1000, seed=0):
+        self.division_factor, self.use_absolute_scale, self.decrease_mu = division_factor, use_absolute_scale, decrease_mu
+        self.maximum_correspondence_distance, self.iteration_number = maximum_correspondence_distance, iteration_number
+        self.tuple_scale, self.maximum_tuple_count, self.seed = tuple_scale, maximum_tuple_count, seed
+
+
+def registration_fast_based_on_feature_matching(source, target, source_feature, target_feature, option=None):
+    """open3d 0.9 registration::FastGlobalRegistration restated, on the device (DESIGN.md section 6g).  open3d is not installed, so parity
+    with it is UNPINNED; the numpy restatement tests/fgr_reference.py is the specification.  The transformation maps source onto target.
+
+    1. Mutual matches: the pairs (i, nn_st[i]) with nn_ts[nn_st[i]] == i in ascending i (feature_nn both ways); `ncorr` of them.
+    2. Tuple test: trial t < 100 * ncorr draws the positions r_k = splitmix64((seed << 32) ^ (3 t + k)) mod ncorr, k < 3 (the RANSAC
+       sampler's form; open3d draws with rand()), and passes when for the edges 0-1, 1-2, 2-0 the source length li and the target length
+       lj satisfy li * tuple_scale < lj and lj * tuple_scale < li (strict: a repeated draw fails).  The first maximum_tuple_count
+       (<= 1000) passing trials in trial order each contribute their three pairs to the correspondence list.
+    3. Both clouds are centred on their means and divided by scale_global = the largest centred point norm of both (1 with
+       use_absolute_scale, where the robust penalty starts at par = that norm instead of 1).
+    4. With fewer than 10 correspondences the result is the identity.  Otherwise iteration_number Gauss-Newton steps on
+       sum s |p - T q|^2, s = (par / (|p - q|^2 + par))^2, 6x6 LDL^T solve, T <- TransformVector6dToMatrix4d(x) . T; decrease_mu divides
+       par by division_factor every fourth step while it is above maximum_correspondence_distance.  A pivot that is not finite and
+       positive ends the loop with the T so far -- open3d would return NaN there, this does not.
+    5. Back to the clouds' units: R kept, t = scale_global * t + mean_target - R mean_source.
+
+    fitness, inlier_rmse and correspondence_count are the ICP evaluation of T at maximum_correspondence_distance (in the clouds' own
+    units), by the ICP path's kernels.  Beside open3d's fields the result carries `mutual` (ncorr), `tuples` (kept trials) and
+    `iterations` (steps run).  The same inputs give the same bits on every run, alone or in a batch (batched.registration_fast: this call
+    is a batch of one)."""
+    return _B.registration_fast([source], [target], [source_feature], [target_feature], [option])[0]
+
+
 def surface_points(label, depth, intr, robot2cam, device="cuda"):
     """label u8[H,W], depth (integer sensor units) [H,W] -> PointCloud of the valid pixels in the robot frame (mm)."""
     if torch.is_tensor(label) and torch.is_tensor(depth) and label.is_cuda and depth.is_cuda and (label.dtype != torch.uint8 or depth.dtype != torch.uint16):

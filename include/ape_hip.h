@@ -528,6 +528,34 @@ int ape_ransac_validate_batch_f64(int nb, const double* const* sorted, const uns
                                   const int* kept, int kept_stride, const int* n_kept_host, double max_dist, double* result,
                                   double* const* fit_rmse, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- fast global registration (Zhou, Park, Koltun 2016; open3d 0.9 registration_fast_based_on_feature_matching restated, DESIGN.md
+ * section 6g) for nb <= 16 pairs in lock step; a pair with ns[c] == 0 or nt[c] == 0 is skipped (its pointers may be NULL).
+ * Mutual matches: the pairs (i, nn_st[c][i]) with nn_ts[c][nn_st[c][i]] == i, in ascending i, to mutual_s[c] / mutual_t[c] (capacity
+ * min(ns[c], nt[c]) ints each) and their count to n_mutual[c] (device, [nb]).  One launch. */
+int ape_fgr_mutual_batch(int nb, const int* const* nn_st, const int* ns, const int* const* nn_ts, const int* nt, int* const* mutual_s,
+                         int* const* mutual_t, int* n_mutual, void* stream);
+/* Workspace of ape_fgr_tuples_batch_f64 for chunks of up to `chunk` trials. */
+size_t ape_fgr_workspace_bytes(int nb, int chunk);
+/* The tuple test, trials [trial_begin, trial_begin + n_trials) below the pair's own limit of 100 * n_mutual[c]: trial t draws the three
+ * positions r_k = splitmix64(((uint64_t)seed << 32) ^ (3 t + k)) mod n_mutual[c] of the mutual list and passes when, for each of the edges
+ * 0-1, 1-2 and 2-0, the source length li and the target length lj satisfy li * tuple_scale < lj and lj * tuple_scale < li.  The passing
+ * trial indices are appended IN TRIAL ORDER to kept[c * max_tuples ..] / n_kept[c] (device; the caller zeroes n_kept before the first
+ * chunk) until max_tuples are kept; a full pair's blocks are no-ops.  Two launches. */
+int ape_fgr_tuples_batch_f64(int nb, const double* const* src, const int* ns, const double* const* tgt, const int* nt,
+                             const int* const* mutual_s, const int* const* mutual_t, const int* n_mutual, const long* seed_host,
+                             double tuple_scale, int trial_begin, int n_trials, int max_tuples, int* kept, int* n_kept, void* ws,
+                             size_t ws_bytes, void* stream);
+/* Centring / scale and the optimisation, two launches.  norm8[nb][8] (device, written): mean and largest centred norm of the source,
+ * then of the target.  Pair c's correspondences are the three re-drawn pairs of each of its n_kept_host[c] <= 1000 kept trials
+ * (kept[c * kept_stride ..]); fewer than 10 give the identity.  One workgroup per pair holds them in LDS, runs iteration_number
+ * Gauss-Newton steps (27 fixed-order sums, 6x6 LDL^T, T <- update . T) and stops early at a pivot that is not finite and positive.
+ * result[nb][24] (device): [0..15] T in the clouds' units, [16] iterations run, [17] scale, [18] the last par, [19] correspondences. */
+int ape_fgr_optimize_batch_f64(int nb, const double* const* src, const int* ns, const double* const* tgt, const int* nt,
+                               const int* const* mutual_s, const int* const* mutual_t, const int* n_mutual, const long* seed_host,
+                               const int* kept, int kept_stride, const int* n_kept_host, int use_absolute_scale, int decrease_mu,
+                               double division_factor, double max_corr_dist, int iteration_number, double* norm8, double* result,
+                               void* stream);
+
 /* ape_conv3x3_halo_bf16 for a 64-channel layer (the segmentor's up_3, pspnet.py:51) with ape_seg_head_f32 fused into its
  * epilogue: the [B][H][W][64] activation is never written, label[B][H][W] u8 / score[B][H][W] f32 are (bit-identical to the
  * unfused pair).  params->Cout must be 64, no residual; params->ups as in ape_conv3x3_halo_bf16. */
