@@ -1,6 +1,7 @@
 """Inputs for the edge-shape tests of csrc/unet.hip (decoder conv and fused head) and of the split-K form of csrc/conv_gemm.hip, each named
 for the shape and the branch it reaches.  tests/test_conv_edges_host.py proves the guards and the branch-reached claims on the CPU;
-tests/test_gpu_unet_edges.py and tests/test_gpu_splitk_edges.py run them.
+tests/test_gpu_unet_edges.py and tests/test_gpu_splitk_edges.py run them.  Below them, under the same input rules, the cases of the LDS-halo
+3x3 kernels (csrc/conv3x3_halo.hip, csrc/conv3x3_halo_s32.hip): proofs in tests/test_halo_edges_host.py, run by tests/test_gpu_halo_edges.py.
 
 Input rules ("Pinned at edge shapes" of the Unet decoder kernel and the split-K GEMM):
  1. fixed seeds; activations ~ N(0, 1), weights ~ N(0, 1) / sqrt(K) (head: 2 / sqrt(K), logits of scale >= 1), so outputs are of scale 1..10;
@@ -253,3 +254,186 @@ def splitk_inputs(name):
 def splitk_expected(name, nsplit):
     g, x, w, bias, res = splitk_inputs(name)
     return R.conv(x, w, g, nsplit, bias, res)
+
+
+# ---- csrc/conv3x3_halo.hip: ape_conv3x3_halo_bf16 through its raw entry point -------------------------------------------------------------------------
+# (the engine routes only maps whose 16 x 16 tiles are at least 80 % full; the ABI takes any H, W >= 1)
+S32_SENTINEL = -194.0                   # every bf16 of an S32 output buffer before the call (bits 0xC342 in both planes)
+_H = R.halo_geometry
+_PRELU = dict(act=R.ACT_PRELU, alpha=0.25)
+HALO_CASES = {
+    # name: (geometry, bias: None | "shared" | "per_image", residual)
+    "d1_n64_1x1x1_cin32_one_chunk_cout4_null_bias_act_none": (_H(1, 1, 1, 32, 4, 1, ldx=40, xoff=4, ldy=12, yoff=4), None, False),
+    "d4_n64_1x3x5_off_centre_taps_outside_cout13_scalar_nvalid1_sigmoid": (
+        _H(1, 3, 5, 64, 13, 4, act=R.ACT_SIGMOID, ldx=76, xoff=8, ldy=24, yoff=4), "shared", False),
+    "d2_n128_1x3x5_cin96_cout65_63_empty_rows_scalar_by_ldy": (_H(1, 3, 5, 96, 65, 2, act=R.ACT_RELU, ldx=104, xoff=4, ldy=70, yoff=4), "shared", False),
+    "d1_n128_2x1x33_cout129_second_channel_tile_of_one_scalar_by_yoff_per_image_bias": (
+        _H(2, 1, 33, 64, 129, 1, ldx=72, xoff=4, ldy=136, yoff=2, bias_bstride=136, **_PRELU), "per_image", False),
+    "d2_n64_1x9x1_cin32_cout64_scalar_by_roff_null_bias": (
+        _H(1, 9, 1, 32, 64, 2, act=R.ACT_RELU, ldx=36, xoff=4, ldy=72, yoff=4, ldr=72, roff=2), None, True),
+    "d1_n128_1x16x16_one_full_tile_cin96_cout128_vector_residual_slice": (
+        _H(1, 16, 16, 96, 128, 1, ldx=104, xoff=8, ldy=140, yoff=8, ldr=136, roff=4, **_PRELU), "shared", True),
+    "d4_n128_1x17x16_second_tile_row_of_one_cout200_sigmoid": (
+        _H(1, 17, 16, 32, 200, 4, act=R.ACT_SIGMOID, ldx=52, xoff=16, ldy=208, yoff=4, bias_bstride=204), "per_image", False),
+    "d2_n128_3x13x17_second_tile_column_of_one_six_workgroups_act_none": (
+        _H(3, 13, 17, 64, 128, 2, ldx=96, xoff=32, ldy=136, yoff=4, ldr=136, roff=4, bias_bstride=132), "per_image", True),
+    "d1_n64_3x13x17_cin96_single_buffer_refill_odd_chunks": (_H(3, 13, 17, 96, 64, 1, act=R.ACT_RELU, ldx=100, xoff=4, ldy=72, yoff=4), "shared", False),
+    "d4_n64_2x32x48_cin64_cout64_null_bias_vector_residual": (
+        _H(2, 32, 48, 64, 64, 4, ldx=76, xoff=8, ldy=72, yoff=4, ldr=68, roff=4, **_PRELU), None, True),
+    # fused x2 up-sampling (dil 1): H, W are the up-sampled map's
+    "ups_n64_1x1x1_to_2x2_cin32_cout64": (_H(1, 2, 2, 32, 64, 1, 1, act=R.ACT_RELU, ldx=36, xoff=0, ldy=72, yoff=4), "shared", False),
+    "ups_n128_2x5x7_to_10x14_xoff8_cout128_vector_residual": (
+        _H(2, 10, 14, 64, 128, 1, 1, act=R.ACT_RELU, ldx=76, xoff=8, ldy=136, yoff=4, ldr=132, roff=4), "shared", True),
+    "ups_n64_1x8x8_to_16x16_cin96_cout4_per_image_bias": (_H(1, 16, 16, 96, 4, 1, 1, ldx=100, xoff=0, ldy=12, yoff=4, bias_bstride=8, **_PRELU), "per_image", False),
+    "ups_n128_3x9x12_to_18x24_cout65_null_bias_sigmoid": (_H(3, 18, 24, 32, 65, 1, 1, act=R.ACT_SIGMOID, ldx=40, xoff=0, ldy=72, yoff=4), None, False),
+}
+
+
+def _operands(g, bias_kind, with_res, gen, s32_in=False):
+    """x (float32, unread channels NaN), w, bias (flat, NaN between the per-image rows) | None, res (float32, NaN outside its slice) | None"""
+    hl, wl = (g["H"] >> 1, g["W"] >> 1) if g["ups"] else (g["H"], g["W"])
+    x = torch.full((g["B"], hl, wl, g["ldx"]), NAN)
+    x[..., g["xoff"]:g["xoff"] + g["Cin"]] = torch.randn(g["B"], hl, wl, g["Cin"], generator=gen)
+    w = torch.randn(g["Cout"], g["Cin"], 3, 3, generator=gen) / math.sqrt(9 * g["Cin"])
+    bias = None
+    if bias_kind == "shared":
+        bias = torch.randn(g["Cout"], generator=gen)
+    elif bias_kind == "per_image":
+        bias = torch.full((g["B"], g["bias_bstride"]), NAN)
+        bias[:, :g["Cout"]] = torch.randn(g["B"], g["Cout"], generator=gen)
+        bias = bias.reshape(-1)
+    res = None
+    if with_res:
+        res = torch.full((g["B"], g["H"], g["W"], g["ldr"]), NAN)
+        res[..., g["roff"]:g["roff"] + g["Cout"]] = torch.randn(g["B"], g["H"], g["W"], g["Cout"], generator=gen)
+    return x, w, bias, res
+
+
+@functools.lru_cache(maxsize=None)
+def halo_inputs(name):
+    """-> geometry, x[B,H,W,ldx] (with ups: [B,H/2,W/2,ldx]), w[Cout,Cin,3,3], bias | None, res[B,H,W,ldr] | None"""
+    g, bias_kind, with_res = HALO_CASES[name]
+    return (g,) + _operands(g, bias_kind, with_res, torch.Generator().manual_seed(2000 + list(HALO_CASES).index(name)))
+
+
+@functools.lru_cache(maxsize=None)
+def halo_expected(name, nsplit):
+    g, x, w, bias, res = halo_inputs(name)
+    return R.halo_conv(x, w, g, nsplit, bias, res)
+
+
+def halo_branches(g, with_res):
+    """what conv3x3_halo_kernel<NSPLIT, D, BNH, UPS> meets on this geometry (restated from its index arithmetic and its launcher)"""
+    bnh = 64 if g["Cout"] <= 64 else 128
+    tx, ty, nt = -(-g["W"] // 16), -(-g["H"] // 16), -(-g["Cout"] // bnh)
+    vec_ok = g["ldy"] % 4 == 0 and g["yoff"] % 4 == 0 and (not with_res or (g["ldr"] % 4 == 0 and g["roff"] % 4 == 0))
+    return dict(D=g["dil"], BNH=bnh, ups=g["ups"], tiles_x=tx, tiles_y=ty, n_tiles=nt, workgroups=g["B"] * tx * ty * nt,
+                last_tile_rows=g["H"] - 16 * (ty - 1), last_tile_cols=g["W"] - 16 * (tx - 1), empty_weight_rows=nt * bnh - g["Cout"],
+                chunks=g["Cin"] // 32, a_double=bnh == 128, vec_ok=vec_ok, nvalid_last=g["Cout"] % 4 or 4,
+                scalar=(not vec_ok) or g["Cout"] % 4 != 0)
+
+
+# ---- csrc/conv3x3_halo_s32.hip: ape_conv3x3_halo_s32 ---------------------------------------------------------------------------------------------------
+# name: (geometry, bias kind, residual: None | "f32" | "s32", output: "f32" | "s32").  ldx, xoff are multiples of 32 and the unread 32-channel
+# groups of the S32 operand hold NaN patterns in every bf16.  The kernel reads a bias row as float4: a per-image bias needs bias_bstride % 4 == 0
+# (and a 16-byte aligned base), which the ABI does not check -- every case here keeps to it.
+_F32_OUT = lambda cout: dict(ldy=cout + 12, yoff=4)  # noqa: E731
+# the S32 output windows of a 160-channel buffer: Cout 136 at 8 takes the wide store, Cout 132 at 0 and Cout 128 at 4 the narrow one
+_S32_AT_8, _S32_AT_0, _S32_AT_4 = dict(ldy=160, yoff=8), dict(ldy=160, yoff=0), dict(ldy=160, yoff=4)
+
+
+HALO_S32_CASES = {
+    "d1_1x1x1_cin32_xoff32_f32_out_null_bias_act_none": (_H(1, 1, 1, 32, 128, 1, ldx=64, xoff=32, **_F32_OUT(128)), None, None, "f32"),
+    "d4_1x3x5_cin64_xoff64_s32_wide_store": (_H(1, 3, 5, 64, 136, 4, act=R.ACT_RELU, ldx=128, xoff=64, **_S32_AT_8), "shared", None, "s32"),
+    "d2_2x12x16_rpw3_every_tile_cin96_xoff32_s32_narrow_by_cout132_s32_residual": (
+        _H(2, 12, 16, 96, 132, 2, ldx=128, xoff=32, ldr=160, roff=4, bias_bstride=136, **_PRELU, **_S32_AT_0), "per_image", "s32", "s32"),
+    "d1_1x13x16_rpw4_cin160_s32_narrow_by_yoff4_f32_residual_sigmoid": (
+        _H(1, 13, 16, 160, 128, 1, act=R.ACT_SIGMOID, ldx=160, xoff=0, ldr=136, roff=4, **_S32_AT_4), "shared", "f32", "s32"),
+    "d2_1x17x9_last_tile_row_rpw1_f32_residual_per_image_bias": (
+        _H(1, 17, 9, 64, 128, 2, act=R.ACT_RELU, ldx=64, xoff=0, ldr=140, roff=4, bias_bstride=132, **_F32_OUT(128)), "per_image", "f32", "f32"),
+    "d4_1x21x33_last_tile_row_rpw2_cout200_two_channel_tiles_sigmoid": (
+        _H(1, 21, 33, 32, 200, 4, act=R.ACT_SIGMOID, ldx=32, xoff=0, **_F32_OUT(200)), None, None, "f32"),
+    "d1_2x28x17_last_tile_row_rpw3_beside_one_column_tile_s32_wide_s32_residual": (
+        _H(2, 28, 17, 96, 136, 1, ldx=96, xoff=0, ldr=160, roff=4, **_PRELU, **_S32_AT_8), "shared", "s32", "s32"),
+}
+# the persistent walk: more tiles than compute units (ncu, read from the device), so the geometry is a function of ncu.
+# H = 17, W = 1: two tile rows per image, rpw 4 then rpw 1.  The kernel deals the logical tiles to the 8 XCDs in contiguous runs and a
+# workgroup's next tile is grid / 8 logical tiles further on: with two tiles per image and an even stride the two tiles of a workgroup have
+# the SAME rpw in cases a, b (tests/test_halo_edges_host.py proves which); case d (three tile rows per image, rpw 4, 4, 1) is the one whose
+# workgroups 0 and 1 walk from an rpw = 4 tile into an rpw = 1 tile.
+HALO_S32_WALK_CASES = {
+    "walk_a_two_extra_tiles_f32_residual": (lambda ncu: _H(ncu // 2 + 1, 17, 1, 64, 128, 1, act=R.ACT_RELU, ldx=64, ldr=132, roff=4, **_F32_OUT(128)),
+                                            "shared", "f32", "f32"),
+    "walk_a_two_extra_tiles_s32_out": (lambda ncu: _H(ncu // 2 + 1, 17, 1, 64, 128, 1, act=R.ACT_RELU, ldx=64, ldy=128, yoff=0), "shared", None, "s32"),
+    "walk_b_cout132_two_channel_tiles_four_extra_tiles": (lambda ncu: _H(ncu // 4 + 1, 17, 1, 64, 132, 1, ldx=64, **_PRELU, **_F32_OUT(132)),
+                                                          "shared", None, "f32"),
+    "walk_c_cin96_odd_chunks_one_workgroup_per_tile": (lambda ncu: _H(ncu // 2 + 1, 17, 1, 96, 128, 1, act=R.ACT_RELU, ldx=96, ldr=132, roff=4,
+                                                                        **_F32_OUT(128)), "shared", "f32", "f32"),
+    "walk_d_three_tile_rows_seam_rpw4_into_rpw1_s32_out": (lambda ncu: _H(ncu // 3 + 1, 33, 1, 64, 128, 1, act=R.ACT_RELU, ldx=64, ldy=128, yoff=0),
+                                                           "shared", None, "s32"),
+}
+HALO_S32_NAMES = list(HALO_S32_CASES) + list(HALO_S32_WALK_CASES)
+
+
+def halo_s32_case(name, ncu=256):
+    if name in HALO_S32_CASES:
+        return HALO_S32_CASES[name]
+    mk, bias_kind, res_kind, out = HALO_S32_WALK_CASES[name]
+    return mk(ncu), bias_kind, res_kind, out
+
+
+@functools.lru_cache(maxsize=None)
+def halo_s32_inputs(name, ncu=256):
+    """-> geometry, (hi, lo) planes of x [B,H,W,ldx], w, bias | None, res: None | float32 [B,H,W,ldr] | its (hi, lo) planes, output format.
+    R.s32_pack(hi, lo) is the device operand"""
+    g, bias_kind, res_kind, out = halo_s32_case(name, ncu)
+    x, w, bias, res = _operands(g, bias_kind, res_kind is not None, torch.Generator().manual_seed(3000 + HALO_S32_NAMES.index(name)))
+    if res_kind == "s32":
+        res = R.split(res)
+    return g, R.split(x), w, bias, res, out
+
+
+@functools.lru_cache(maxsize=None)
+def halo_s32_expected(name, nsplit, ncu=256):
+    """nsplit 3: the kernel's products; 0: the plain float64 convolution of hi + lo"""
+    g, x, w, bias, res, _ = halo_s32_inputs(name, ncu)
+    return R.halo_conv(x, w, g, nsplit, bias, res)
+
+
+def halo_s32_rpw(g, y0):
+    """rows per pixel-row group of waves in a tile at image row y0 (rows_per_wave of halo_s32_kernel)"""
+    return (min(g["H"] - y0, 16) + 3) >> 2
+
+
+def halo_s32_walk(g, ncu):
+    """(grid, [[(image, y0, x0, channel tile) of every tile a workgroup walks, in order] per workgroup]) by launch_halo_s32's grid rule and
+    the kernel's decode()"""
+    tx, ty, nt = -(-g["W"] // 16), -(-g["H"] // 16), -(-g["Cout"] // 128)
+    nwg = g["B"] * tx * ty * nt
+    unit, grid = 8 * nt, nwg
+    if nwg > ncu and ncu >= unit and (g["Cin"] // 32) % 2 == 0:
+        grid = ncu // unit * unit
+    q, r = divmod(nwg, 8)
+    walks = []
+    for wg in range(grid):
+        tiles = []
+        for orig in range(wg, nwg, grid):
+            xcd = orig % 8
+            logical = (xcd * (q + 1) if xcd < r else r * (q + 1) + (xcd - r) * q) + orig // 8
+            n_tile, mt = logical % nt, logical // nt
+            b, trem = divmod(mt, tx * ty)
+            tiles.append((b, trem // tx * 16, trem % tx * 16, n_tile))
+        walks.append(tiles)
+    return grid, walks
+
+
+def halo_s32_branches(g, res_kind, out, ncu=256):
+    tx, ty, nt = -(-g["W"] // 16), -(-g["H"] // 16), -(-g["Cout"] // 128)
+    grid, walks = halo_s32_walk(g, ncu)
+    return dict(D=g["dil"], tiles_x=tx, tiles_y=ty, n_tiles=nt, workgroups=g["B"] * tx * ty * nt, grid=grid, chunks=g["Cin"] // 32,
+                rpw=[halo_s32_rpw(g, 16 * t) for t in range(ty)], last_tile_cols=g["W"] - 16 * (tx - 1), empty_weight_rows=nt * 128 - g["Cout"],
+                wide=out == "s32" and g["Cout"] % 8 == 0 and g["yoff"] % 8 == 0,
+                narrow=out == "s32" and not (g["Cout"] % 8 == 0 and g["yoff"] % 8 == 0),
+                max_tiles_per_workgroup=max(len(t) for t in walks),
+                seam=any(halo_s32_rpw(g, a[1]) != halo_s32_rpw(g, b[1]) for t in walks for a, b in zip(t, t[1:])),
+                one_channel_tile_per_workgroup=all(len({t[3] for t in tl}) == 1 for tl in walks))

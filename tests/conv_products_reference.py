@@ -1,5 +1,6 @@
-"""Plain float64 restatement of what csrc/unet.hip and the split-K form of csrc/conv_gemm.hip compute: the sum of the very products the
-kernels form.  torch on the CPU only; reads nothing but its arguments.
+"""Plain float64 restatement of what csrc/unet.hip, the split-K form of csrc/conv_gemm.hip and the LDS-halo 3x3 kernels (csrc/conv3x3_halo.hip
+with its fused x2 up-sampling, csrc/conv3x3_halo_s32.hip on pre-split S32 operands) compute: the sum of the very products the kernels form.
+torch on the CPU only; reads nothing but its arguments.
 
 Operand split, as pack_weights_kernel (weights) and split8 (activations) do it, in float32 with round-to-nearest-even:
     hi = bf16(v),  lo = bf16(v - float(hi))
@@ -7,15 +8,18 @@ and per 32-deep k-tile the kernels add   a_lo . w_hi,  a_hi . w_lo,  a_hi . w_hi
 accumulator.  Every product of two bf16 values is exact in float32, so a float64 sum of them differs from the kernel's result by the
 float32 accumulation alone.  nsplit = 0 stands for the unrounded operands (the plain float64 convolution).
 
-The k-tiles come out of generators in the kernels' order (unet: tap outer, 32-channel chunk inner; conv_gemm: chunk outer, tap inner), so
+The k-tiles come out of generators in the kernels' order (unet: tap outer, 32-channel chunk inner; conv_gemm and halo: chunk outer, tap inner), so
 the same code serves the float64 sum (`total`), the float32 emulation of the kernels' accumulation (`accumulate_f32`) and the mutated
-copies (`mutate`: the names of wrong rules, each one a defect the edge cases must be able to see; tests/test_conv_edges_host.py)."""
+copies (`mutate`: the names of wrong rules, each one a defect the edge cases must be able to see; tests/test_conv_edges_host.py,
+tests/test_halo_edges_host.py)."""
 import torch
 
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_SIGMOID = 0, 1, 2, 3
 BK = 32
+# wrong rules only the LDS-halo family can follow (tests/test_halo_edges_host.py names their cases)
+HALO_MUTATIONS = ("left_column_wraps", "ups_half_pixel", "ups_weights_swapped", "residual_hi_only")
 MUTATIONS = ("drop_cross_term", "nearest_rounds_up", "chunk_at_c1_from_a", "border_clamped", "split_starts_at_tap0", "last_split_dropped",
-             "bias_of_image0", "residual_without_roff", "last_maximum")
+             "bias_of_image0", "residual_without_roff", "last_maximum") + HALO_MUTATIONS
 
 
 def split(v):
@@ -26,6 +30,10 @@ def split(v):
 
 
 def _parts(v, nsplit):
+    """v: float values, or the (hi, lo) planes of an operand that is already split (S32)"""
+    if isinstance(v, tuple):
+        hi, lo = v
+        return {"v": hi.double() + lo.double()} if nsplit == 0 else {"hi": hi.double(), "lo": lo.double()}
     if nsplit == 0:
         return {"v": v.double()}
     hi, lo = split(v)
@@ -139,7 +147,8 @@ def n_ktiles(g):
 
 
 def conv_tile(x, w, g, nsplit, kt, mutate=()):
-    """the term products [M, Cout] of k-tile kt of the general convolution; K order = 32-channel chunk outer, taps inner"""
+    """the term products [M, Cout] of k-tile kt of the general convolution; K order = 32-channel chunk outer, taps inner.
+    x: float32 NHWC, or the (hi, lo) planes of an S32 operand"""
     taps = g["KH"] * g["KW"]
     chunk, tap = divmod(kt, taps)
     ky, kx = divmod(tap, g["KW"])
@@ -147,8 +156,23 @@ def conv_tile(x, w, g, nsplit, kt, mutate=()):
     ix = torch.arange(g["Wo"]) * g["stride"] - g["pad"] + kx * g["dil"]
     inside = ((iy >= 0) & (iy < g["H"]))[:, None] & ((ix >= 0) & (ix < g["W"]))[None, :]
     c0 = g["xoff"] + chunk * BK
-    v = x[:, iy.clamp(0, g["H"] - 1)][:, :, ix.clamp(0, g["W"] - 1)][..., c0:c0 + BK]
-    v = torch.where(inside[None, :, :, None], v, torch.zeros((), dtype=v.dtype)).reshape(-1, BK)
+    if "border_clamped" in mutate:
+        inside = torch.ones_like(inside)
+    wraps = None
+    if "left_column_wraps" in mutate:
+        # a tap left or right of the row reads whatever pixel lies there in linear memory (zero only outside the whole tensor)
+        lin = (torch.arange(g["B"])[:, None, None] * g["H"] + iy[None, :, None]) * g["W"] + ix[None, None, :]
+        wraps = ((iy >= 0) & (iy < g["H"]))[None, :, None] & ~inside[None] & (lin >= 0) & (lin < g["B"] * g["H"] * g["W"])
+        lin = lin.clamp(0, g["B"] * g["H"] * g["W"] - 1)
+
+    def gather(t):
+        v = t[:, iy.clamp(0, g["H"] - 1)][:, :, ix.clamp(0, g["W"] - 1)][..., c0:c0 + BK]
+        v = torch.where(inside[None, :, :, None], v, torch.zeros((), dtype=v.dtype))
+        if wraps is not None:
+            v = torch.where(wraps[..., None], t.reshape(-1, t.shape[-1])[lin][..., c0:c0 + BK], v)
+        return v.reshape(-1, BK)
+
+    v = tuple(gather(t) for t in x) if isinstance(x, tuple) else gather(x)
     vp, wp = _parts(v, nsplit), _parts(w[:, chunk * BK:(chunk + 1) * BK, ky, kx], nsplit)
     return [vp[ta] @ wp[tw].T for ta, tw in _terms(nsplit, mutate)]
 
@@ -181,7 +205,11 @@ def conv_epilogue(s, g, bias, res, mutate=()):
         s = s + bias.double().reshape(-1)[(img * g["bias_bstride"])[:, None] + torch.arange(Cout)[None, :]]
     if res is not None:
         roff = 0 if "residual_without_roff" in mutate else g["roff"]
-        s = s + res.double().reshape(M, g["ldr"])[:, roff:roff + Cout]
+        if isinstance(res, tuple):                # an S32 residual: float(hi) + float(lo)
+            r = res[0].double() if "residual_hi_only" in mutate else res[0].double() + res[1].double()
+        else:
+            r = res.double()
+        s = s + r.reshape(M, g["ldr"])[:, roff:roff + Cout]
     if g["act"] == ACT_RELU:
         s = s.clamp(min=0)
     elif g["act"] == ACT_PRELU:
@@ -211,3 +239,85 @@ def conv_splitk_f32(x, w, g, nsplit, nk_per, bias=None, res=None):
     if res is not None:
         v = v + res.float().reshape(M, g["ldr"])[:, g["roff"]:g["roff"] + Cout]
     return conv_epilogue(v.double(), dict(g, bias_bstride=0), None, None).float()
+
+
+# ---- csrc/conv3x3_halo.hip, csrc/conv3x3_halo_s32.hip ---------------------------------------------------------------------------------------------
+def halo_geometry(B, H, W, Cin, Cout, dil=1, ups=0, **kw):
+    """3x3 / stride 1 / pad == dil; H, W: the map the convolution runs on (with ups the x2 up-sampling of the [B, H/2, W/2, ldx] operand)"""
+    return dict(conv_geometry(B, H, W, Cin, Cout, k=3, pad=dil, dil=dil, **kw), ups=ups)
+
+
+def _ups_axis(n_lo, mutate=()):
+    """source index pair and the weight of the second, per output coordinate of the x2 axis (ups_tbl of conv3x3_halo.hip), float32"""
+    n = 2 * n_lo
+    o = torch.arange(n, dtype=torch.float32)
+    if "ups_half_pixel" in mutate:
+        f = ((o + 0.5) * 0.5 - 0.5).clamp(min=0)
+    else:
+        f = (torch.tensor(float(n_lo - 1), dtype=torch.float32) / torch.tensor(float(n - 1), dtype=torch.float32)) * o
+    i0 = f.to(torch.int64)
+    l1 = f - i0.float()
+    return i0, i0 + (i0 < n_lo - 1).long(), l1
+
+
+def ups2x_f32(x, mutate=()):
+    """x[B,hl,wl,C] float32 -> its bilinear x2 sample (align_corners=True) [B,2hl,2wl,C], float32 with one rounding per operation in the
+    order of ups_lerp: o = ly0 (lx0 r0 + lx1 r1) + ly1 (lx0 r2 + lx1 r3)"""
+    x = x.float()
+    y0, y1, ly1 = _ups_axis(x.shape[1], mutate)
+    x0, x1, lx1 = _ups_axis(x.shape[2], mutate)
+    ly0, lx0 = 1.0 - ly1, 1.0 - lx1
+    if "ups_weights_swapped" in mutate:
+        lx0, lx1 = lx1, lx0
+    ly0, ly1, lx0, lx1 = ly0[None, :, None, None], ly1[None, :, None, None], lx0[None, None, :, None], lx1[None, None, :, None]
+    r0, r1, r2, r3 = x[:, y0][:, :, x0], x[:, y0][:, :, x1], x[:, y1][:, :, x0], x[:, y1][:, :, x1]
+    return ly0 * (lx0 * r0 + lx1 * r1) + ly1 * (lx0 * r2 + lx1 * r3)
+
+
+def halo_operand(x, g, mutate=()):
+    """the tensor the nine taps read and the geometry that addresses it: with ups the float32 up-sampling of the channel slice"""
+    if not g["ups"]:
+        return x, g
+    return ups2x_f32(x[..., g["xoff"]:g["xoff"] + g["Cin"]], mutate), dict(g, xoff=0, ldx=g["Cin"])
+
+
+def halo_tiles(x, w, g, nsplit, mutate=()):
+    """the k-tiles of a halo case in the kernels' order (32-channel chunk outer, tap inner); x: float32 NHWC or S32 (hi, lo) planes"""
+    xv, gv = halo_operand(x, g, mutate)
+    return conv_tiles(xv, w, gv, nsplit, None, mutate)
+
+
+def halo_conv(x, w, g, nsplit, bias=None, res=None, mutate=()):
+    return conv_epilogue(total(halo_tiles(x, w, g, nsplit, mutate)), g, bias, res, mutate)
+
+
+def halo_conv_f32(x, w, g, nsplit, bias=None, res=None):
+    """float32 emulation of the halo kernels: the k-tiles accumulate in float32 in their order, then bias, residual and activation"""
+    v = accumulate_f32(halo_tiles(x, w, g, nsplit))
+    M, Cout = v.shape
+    if bias is not None:
+        img = torch.arange(M) // (g["Ho"] * g["Wo"])
+        v = v + bias.float().reshape(-1)[(img * g["bias_bstride"])[:, None] + torch.arange(Cout)[None, :]]
+    if res is not None:
+        r = (res[0].float() + res[1].float()) if isinstance(res, tuple) else res.float()
+        v = v + r.reshape(M, g["ldr"])[:, g["roff"]:g["roff"] + Cout]
+    return conv_epilogue(v.double(), dict(g, bias_bstride=0), None, None).float()
+
+
+# ---- the S32 layout (engine.S32): per pixel and 32-channel group 128 B = 32 bf16 hi | 32 bf16 lo ------------------------------------------------------
+def s32_pack(hi, lo):
+    """(hi, lo)[..., C] of bf16-representable values -> the float32-typed buffer [..., C] that holds their S32 bytes"""
+    C = hi.shape[-1]
+    bits = [t.to(torch.bfloat16).view(torch.int16).reshape(t.shape[:-1] + (C // BK, BK)) for t in (hi, lo)]
+    return torch.cat(bits, -1).reshape(hi.shape[:-1] + (2 * C,)).contiguous().view(torch.float32)
+
+
+def s32_unpack(t):
+    """the float32-typed S32 buffer [..., C] -> its (hi, lo) planes [..., C] as float32"""
+    C = t.shape[-1]
+    b = t.contiguous().view(torch.int16).reshape(t.shape[:-1] + (C // BK, 2, BK))
+    return tuple(b[..., k, :].reshape(t.shape).contiguous().view(torch.bfloat16).float() for k in (0, 1))
+
+
+def s32_from_f32(v):
+    return s32_pack(*split(v))

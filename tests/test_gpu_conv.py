@@ -156,27 +156,45 @@ def test_fused_upsample_conv_equals_materialised(shape, precision):
 
 
 @pytest.mark.parametrize("precision", ["bf16x3", "bf16"])
-# b = 3 below; the larger cases launch 900 / 663 / 1575 workgroups (more than 256 CUs x 2) for every UPS x HEAD instantiation
+# b = 3 below; the larger cases launch 900 / 663 / 1575 workgroups (more than 256 CUs x 2) for every UPS x HEAD instantiation; the last four are
+# maps of one pixel, smaller than a tile's halo, and a ragged up-sampled one
 @pytest.mark.parametrize("ups,h,w", [(True, 24, 40), (False, 48, 80), (True, 21, 33), (True, 120, 160), (True, 136, 104), (True, 200, 168),
-                                     (False, 240, 320), (False, 272, 208), (False, 400, 336)])
+                                     (False, 240, 320), (False, 272, 208), (False, 400, 336), (False, 1, 1), (False, 3, 5), (True, 1, 1), (True, 9, 12)])
 def test_halo_conv_with_fused_seg_head_is_bit_identical_to_the_unfused_pair(precision, ups, h, w):
     """ape_conv3x3_halo_seghead_bf16 == ape_conv3x3_halo_bf16 followed by ape_seg_head_f32 (labels and scores bit for bit),
-    incl. ragged tiles and the fused x2 up-sampling"""
+    incl. ragged tiles and the fused x2 up-sampling, for 5, 1 and 16 classes.  Maps the engine does not route to the halo kernels (tiles less
+    than 80 % full) go through the two raw entry points."""
+    import ctypes
+    from autoposeestimation_amd import _lib
     from autoposeestimation_amd import engine as E
     g = torch.Generator().manual_seed(h * 100 + w)
-    b, c = 3, 5
+    b = 3
     x = torch.randn(b, h, w, 64, generator=g).to("cuda")
     wt = (torch.randn(64, 64, 3, 3, generator=g) * (2.0 / 576) ** 0.5).to("cuda")
     bias = (torch.randn(64, generator=g) * 0.1).to("cuda")
-    hw = (torch.randn(c, 64, generator=g) * 0.3).to("cuda").contiguous()
-    hb = (torch.randn(c, generator=g) * 0.1).to("cuda")
+    heads = [((torch.randn(c, 64, generator=g) * 0.3).to("cuda").contiguous(), (torch.randn(c, generator=g) * 0.1).to("cuda")) for c in (5, 1, 16)]
     conv = E.Conv(wt, bias, 1, 1, 1, E.ACT_PRELU, alpha=0.25, device="cuda", precision=precision)
-    feat = conv(x, upsample2x=ups)
-    want_label, want_score = E.seg_head(feat, hw, hb, True)
-    label, score = E.conv_seg_head(conv, x, hw, hb, True, upsample2x=ups)
-    assert label.shape == want_label.shape
-    assert torch.equal(label, want_label) and torch.equal(score, want_score)
-    assert len(torch.unique(label)) > 1
+    routed = ups or E.tiles16_mostly_full(h, w)
+    if routed:
+        feat = conv(x, upsample2x=ups)
+    else:
+        p = E.conv_params(conv, b, h, w, 64, 64)          # (the unrouted maps are never up-sampled)
+        feat = torch.empty(b, h, w, 64, device="cuda")
+        _lib.call.ape_conv3x3_halo_bf16(_lib.dptr(x), _lib.dptr(conv.wp), _lib.dptr(conv.bias), None, _lib.dptr(feat), ctypes.byref(p), conv.nsplit,
+                                        _lib.stream_ptr())
+    for hw, hb in heads:
+        c = hw.shape[0]
+        want_label, want_score = E.seg_head(feat, hw, hb, True)
+        if routed:
+            label, score = E.conv_seg_head(conv, x, hw, hb, True, upsample2x=ups)
+        else:
+            label, score = torch.empty(b, h, w, dtype=torch.uint8, device="cuda"), torch.empty(b, h, w, device="cuda")
+            _lib.call.ape_conv3x3_halo_seghead_bf16(_lib.dptr(x), _lib.dptr(conv.wp), _lib.dptr(conv.bias), ctypes.byref(p), conv.nsplit, _lib.dptr(hw),
+                                                    _lib.dptr(hb), c, _lib.dptr(label), _lib.dptr(score), 1, _lib.stream_ptr())
+        assert label.shape == want_label.shape
+        assert torch.equal(label, want_label) and torch.equal(score, want_score)
+        if c > 1 and (h, w) != (1, 1):
+            assert len(torch.unique(label)) > 1
 
 
 
