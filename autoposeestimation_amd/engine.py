@@ -1072,6 +1072,34 @@ def backproject(depth, objects, choose, intr, depth_scale):
     return pts
 
 
+def icp_polish(points4, n_cand, obj_class, models, pose, max_correspondence_distance, criteria, min_fitness=0.0):
+    """Depth ICP polish of a batch of objects in ONE launch (csrc/icp_polish.hip): points4[n,N,4] f32 as `backproject` leaves
+    them, n_cand[n] i32, obj_class[n] (row of `models` per object: an int32 device tensor, or a host sequence that is checked against the
+    table and uploaded), models = pipeline.polish.ModelSet, pose[n,7] f64 (w,x,y,z,tx,ty,tz), criteria with relative_fitness /
+    relative_rmse / max_iteration -> (pose_out[n,7] f64, stats[n,4] f64 = fitness, inlier rmse, correspondences, stop reason).
+    Enqueues on the current stream, reads nothing back: safe inside a graph capture."""
+    n, npts = int(points4.shape[0]), int(points4.shape[1])
+    if not torch.is_tensor(obj_class) or not obj_class.is_cuda:
+        host = [int(c) for c in (obj_class.tolist() if torch.is_tensor(obj_class) else obj_class)]
+        bad = [c for c in host if not 0 <= c < models.n_classes]
+        if bad:
+            raise ValueError("icp_polish: class %d is outside the model table (%d classes)" % (bad[0], models.n_classes))
+        obj_class = torch.tensor(host, dtype=torch.int32).to(points4.device)
+    if float(max_correspondence_distance) > models.cell:
+        raise ValueError("icp_polish: max_correspondence_distance %g exceeds the cell size %g the model grids were built for"
+                         % (max_correspondence_distance, models.cell))
+    if tuple(points4.shape[2:]) != (4,) or n_cand.shape[0] != n or obj_class.shape[0] != n or tuple(pose.shape) != (n, 7):
+        raise ValueError("icp_polish: points4[n,N,4], n_cand[n], obj_class[n] and pose[n,7] must agree")
+    pose_out = torch.empty(n, 7, dtype=torch.float64, device=points4.device)
+    stats = torch.empty(n, 4, dtype=torch.float64, device=points4.device)
+    _lib.call.ape_icp_polish_batch_f64(n, _lib.dptr(points4, torch.float32), _lib.dptr(n_cand, torch.int32), npts, _lib.dptr(obj_class, torch.int32),
+                                       _lib.dptr(models.table, torch.int64), models.n_classes, models.max_points, models.cell,
+                                       _lib.dptr(pose, torch.float64), float(max_correspondence_distance), float(criteria.relative_fitness),
+                                       float(criteria.relative_rmse), int(criteria.max_iteration), float(min_fitness), _lib.dptr(pose_out),
+                                       _lib.dptr(stats), _st())
+    return pose_out, stats
+
+
 # ---- overlays (csrc/overlay.hip) ------------------------------------------------------------------------------------------
 OVERLAY_F64, OVERLAY_U8 = 0, 1      # blend arithmetic: full_prediction's float64 images / the review screens' uint8 arrays
 _overlay_planes = {}

@@ -33,9 +33,19 @@ def _pose_stream():
 
 class FramePipeline:
     def __init__(self, segmentor, estimator, refiner, class_names, num_points=1000, refine_mode="live_compat",
-                 min_pixels=100, iterations=2, pose_stream=False, pose_graphs=False, low_latency=False):
+                 min_pixels=100, iterations=2, pose_stream=False, pose_graphs=False, low_latency=False, icp_polish=None):
         if refine_mode not in ("live_compat", "iterative"):
             raise ValueError(refine_mode)
+        # icp_polish: None (the default: not a launch, not a bit changes), or a pipeline.polish.IcpPolish -- every bucket then ends with the
+        # one-launch depth ICP polish (csrc/icp_polish.hip) of its objects against their classes' model clouds, on the bucket's own
+        # back-projection: it rides the pose stream and the bucket graphs.  The result dict gains `fit` [n,4] f64 (fitness, inlier rmse,
+        # correspondences, stop reason) and `pose_raw` (what `pose` held without the switch); `pose` holds the polished pose.
+        if icp_polish is not None:
+            from autoposeestimation_amd.pipeline.polish import IcpPolish
+            if not isinstance(icp_polish, IcpPolish):
+                raise TypeError("icp_polish must be None or a pipeline.polish.IcpPolish")
+            icp_polish.check_clouds(len(class_names))
+        self.icp_polish = icp_polish
         self.segmentor, self.estimator, self.refiner = segmentor, estimator, refiner
         self.class_names = list(class_names)
         self.n_cls = len(self.class_names) + 1          # + background (pipeline/utils.py:695)
@@ -93,7 +103,8 @@ class FramePipeline:
     # -- stage 2: pose for a list of detected objects --------------------------------------------------------------
     def poses(self, rgb, depth, objmap, objects, meta, choose_override=None, seed=0):
         """objects: list of (frame, cls, rmin, rmax, cmin, cmax).  Returns (pose[n,7] f64 cuda, n_cand[n] i32 cuda,
-        choose[n,N] i64 cuda) in the order of `objects`."""
+        choose[n,N] i64 cuda) in the order of `objects`; with `icp_polish` two more: (..., fit[n,4] f64, pose_raw[n,7] f64), and `pose`
+        is the polished one."""
         t_host = time.perf_counter()
         try:
             with E.low_latency(self.low_latency):
@@ -113,6 +124,10 @@ class FramePipeline:
             pose_all = torch.zeros(n, 7, dtype=torch.float64, device=dev)
             ncand_all = torch.zeros(n, dtype=torch.int32, device=dev)
             choose_all = torch.zeros(n, self.num_points, dtype=torch.int64, device=dev)
+            more_all = (torch.zeros(n, 4, dtype=torch.float64, device=dev), torch.zeros(n, 7, dtype=torch.float64, device=dev)) if self.icp_polish is not None else ()
+        if self.icp_polish is not None:                 # (upload + grids once per cloud set, before anything is captured)
+            from autoposeestimation_amd.pipeline.polish import ModelSet
+            ModelSet.cached(self.icp_polish.point_clouds, dev, self.icp_polish.max_correspondence_distance)
         use_graphs = self.pose_graphs and choose_override is None and E.PROFILE is None and not torch.cuda.is_current_stream_capturing()
         if use_graphs:
             if self._static_objmap is None or self._static_objmap.shape != objmap.shape:
@@ -140,29 +155,31 @@ class FramePipeline:
                 if side is not None:            # a replay: on one of the bucket streams, beside the other buckets' replays
                     side.wait_event(start)
                     with torch.cuda.stream(side):
-                        pose, n_cand, choose = self._bucket_replay(rgb, depth, both_h, hc, wc, meta, seed, key_stream=cur)
-                        for t in (pose, n_cand, choose):
+                        pose, n_cand, choose, *more = self._bucket_replay(rgb, depth, both_h, hc, wc, meta, seed, key_stream=cur)
+                        for t in (pose, n_cand, choose, *more):
                             t.record_stream(cur)
                         ev = torch.cuda.Event()
                         ev.record(side)
                     joins.append(ev)
                     cur.wait_event(ev)
                 else:
-                    pose, n_cand, choose = self._bucket_replay(rgb, depth, both_h, hc, wc, meta, seed)
+                    pose, n_cand, choose, *more = self._bucket_replay(rgb, depth, both_h, hc, wc, meta, seed)
             else:
-                pose, n_cand, choose = self._bucket(rgb, depth, objmap, both_h.to(dev, non_blocking=True), hc, wc, meta, seed,
+                pose, n_cand, choose, *more = self._bucket(rgb, depth, objmap, both_h.to(dev, non_blocking=True), hc, wc, meta, seed,
                                                     None if choose_override is None else {j: choose_override.get(i) for j, i in enumerate(ids.tolist())})
             if single:
-                return pose, n_cand, choose
+                return (pose, n_cand, choose, *more)
             ids_t = torch.from_numpy(ids.astype(np.int64)).pin_memory().to(dev, non_blocking=True)
             pose_all.index_copy_(0, ids_t, pose)
             ncand_all.index_copy_(0, ids_t, n_cand)
             choose_all.index_copy_(0, ids_t, choose)
-        return pose_all, ncand_all, choose_all
+            for dst, t in zip(more_all, more):
+                dst.index_copy_(0, ids_t, t)
+        return (pose_all, ncand_all, choose_all, *more_all)
 
     def _bucket(self, rgb, depth, objmap, both, hc, wc, meta, seed, override=None):
         """the pose stage of ONE crop-size bucket: both[n,9] i32 on the device = (frame, cls, rmin, rmax, cmin, cmax | frame, rmin, cmin);
-        -> pose[n,7] f64, n_cand[n] i32, choose[n,N] i64"""
+        -> pose[n,7] f64, n_cand[n] i32, choose[n,N] i64 (with `icp_polish`: the polished pose, then fit[n,4] f64 and the unpolished pose)"""
         dev = rgb.device
         objs, rects = both[:, :6].contiguous(), both[:, 6:9].contiguous()
         choose, n_cand = E.choose_points(objmap, depth, objs, self.num_points, seed)
@@ -183,6 +200,13 @@ class FramePipeline:
             for _ in range(self.iterations):
                 out = self.refiner.forward_batch(E.pose_recentre(pts4, pose), emb, obj_idx)
                 E.pose_compose(pose, out[:, 0:4], out[:, 4:7])
+        if self.icp_polish is not None:
+            from autoposeestimation_amd.pipeline.polish import ModelSet, polish_poses
+            ip = self.icp_polish
+            models = ModelSet.cached(ip.point_clouds, dev, ip.max_correspondence_distance)
+            polished, fit = polish_poses(depth, objs, choose, n_cand, pose, meta, models, ip.max_correspondence_distance, ip.criteria, ip.min_fitness,
+                                         points4=pts4)
+            return polished, n_cand, choose, fit, pose
         return pose, n_cand, choose
 
     def _graph_key(self, rgb, depth, n, hc, wc, meta, stream):
@@ -257,17 +281,19 @@ class FramePipeline:
                     self.side.wait_stream(torch.cuda.current_stream())
                 objmap.record_stream(self.side)         # allocated on the caller's stream, read by the pose stage on the side stream
                 with torch.cuda.stream(self.side):
-                    pose, n_cand, choose = self.poses(rgb, depth, objmap, objects, meta, choose_override, seed)
-                return {"objects": objects, "pose": pose, "n_cand": n_cand, "choose": choose, "objmap": objmap, "stream": self.side}
-            pose, n_cand, choose = self.poses(rgb, depth, objmap, objects, meta, choose_override, seed)
+                    pose, n_cand, choose, *more = self.poses(rgb, depth, objmap, objects, meta, choose_override, seed)
+                return {"objects": objects, "pose": pose, "n_cand": n_cand, "choose": choose, "objmap": objmap, "stream": self.side,
+                        **dict(zip(("fit", "pose_raw"), more))}
+            pose, n_cand, choose, *more = self.poses(rgb, depth, objmap, objects, meta, choose_override, seed)
         else:
             pose = torch.zeros(0, 7, dtype=torch.float64, device=rgb.device)
             n_cand = torch.zeros(0, dtype=torch.int32, device=rgb.device)
             choose = torch.zeros(0, self.num_points, dtype=torch.int64, device=rgb.device)
-        return {"objects": objects, "pose": pose, "n_cand": n_cand, "choose": choose, "objmap": objmap}
+            more = (torch.zeros(0, 4, dtype=torch.float64, device=rgb.device), pose.clone()) if self.icp_polish is not None else ()
+        return {"objects": objects, "pose": pose, "n_cand": n_cand, "choose": choose, "objmap": objmap, **dict(zip(("fit", "pose_raw"), more))}
 
     def run(self, rgb, depth, meta, inject_logits=None, choose_override=None, seed=0):
-        """Whole batch.  Returns dict(objects=[(frame,cls,rmin,rmax,cmin,cmax)], pose, n_cand, choose, objmap)."""
+        """Whole batch.  Returns dict(objects=[(frame,cls,rmin,rmax,cmin,cmax)], pose, n_cand, choose, objmap[, fit, pose_raw])."""
         return self.finish(self.begin(rgb, inject_logits, asynchronous=False), rgb, depth, meta, choose_override, seed)
 
     def overlays(self, result, rgb, meta, point_clouds, color_dict, point_size=3):
@@ -286,14 +312,26 @@ def _as_u8_frame(image):
 
 def full_prediction(image, depth, meta, segmentor, estimator, refiner, to_tensor, normalize, device, cuda, color_dict,
                     class_names=None, point_clouds=None, plot=False, color_prediction=False, bbox=False, put_text=False,
-                    refine_mode="live_compat", choose_override=None):
+                    refine_mode="live_compat", choose_override=None, icp_polish=False, icp_params=None):
     """Reference signature (pipeline/utils.py:410-411) and output dict:
         {'predictions': {cls_name: {'mask': u8[H,W] in {0,255}, 'position': f64[3] (m), 'rotation': f64[4] wxyz}},
          'elapsed_times': {'segmentation', 'pose_estimation', 'total'}}
     `to_tensor` / `normalize` are accepted for signature compatibility; the normalisation runs on the device.
     `color_prediction` adds the 'segmented_prediction' / 'pose_prediction' images, painted on the device (pipeline/overlay.py) and
     copied down once.  `bbox` and `put_text` are accepted and ignored: cv2.rectangle / cv2.putText are out of scope (OpenCV's
-    rasteriser and font cannot be pinned without it).  Objects without a valid depth pixel are dropped like the reference (:530-531,623-635)."""
+    rasteriser and font cannot be pinned without it).  Objects without a valid depth pixel are dropped like the reference (:530-531,623-635).
+    `icp_polish=True` (needs `point_clouds`) ends the pose stage with the depth ICP polish (pipeline/polish.py): 'position' / 'rotation'
+    then hold the polished pose and every prediction gains 'fitness' and 'inlier_rmse'; `icp_params`: an IcpPolish, or a dict of its
+    max_correspondence_distance / criteria / min_fitness."""
+    polish = None
+    if icp_polish:
+        from autoposeestimation_amd.pipeline.polish import IcpPolish
+        if point_clouds is None:
+            raise ValueError("full_prediction(icp_polish=True) needs point_clouds: the model clouds the depth points are registered to")
+        if isinstance(icp_params, IcpPolish):
+            polish = IcpPolish(point_clouds, icp_params.max_correspondence_distance, icp_params.criteria, icp_params.min_fitness)
+        else:
+            polish = IcpPolish(point_clouds, **dict(icp_params or {}))
     if not cuda or not torch.cuda.is_available():
         raise RuntimeError("full_prediction needs the GPU: the MI355X path has no CPU fallback")
     start_time = time.time()
@@ -305,7 +343,8 @@ def full_prediction(image, depth, meta, segmentor, estimator, refiner, to_tensor
         depth_np = depth_np.astype(np.uint16)
     rgb = torch.from_numpy(rgb_np).to(device).unsqueeze(0)
     dep = torch.from_numpy(depth_np).to(device).unsqueeze(0)
-    pipe = FramePipeline(segmentor, estimator, refiner, class_names, refine_mode=refine_mode, low_latency=True)       # (one frame per call: the live loop)
+    pipe = FramePipeline(segmentor, estimator, refiner, class_names, refine_mode=refine_mode, low_latency=True,       # (one frame per call: the live loop)
+                         icp_polish=polish)
     objmap, det = pipe.segment(rgb)
     det_h = det.cpu().numpy()
     objmap_h = objmap[0].cpu().numpy()
@@ -322,8 +361,9 @@ def full_prediction(image, depth, meta, segmentor, estimator, refiner, to_tensor
         ov = None
         if choose_override is not None:
             ov = {i: choose_override.get(class_names[o[1] - 1]) for i, o in enumerate(objects)}
-        pose, n_cand, _ = pipe.poses(rgb, dep, objmap, objects, meta, ov)
+        pose, n_cand, _, *more = pipe.poses(rgb, dep, objmap, objects, meta, ov)
         pose_h, n_cand_h = pose.cpu().numpy(), n_cand.cpu().numpy()
+        fit_h = more[0].cpu().numpy() if more else None
         for i, o in enumerate(objects):
             name = class_names[o[1] - 1]
             if n_cand_h[i] == 0:
@@ -332,6 +372,9 @@ def full_prediction(image, depth, meta, segmentor, estimator, refiner, to_tensor
                 continue
             output_dict["predictions"][name]["position"] = pose_h[i, 4:7].copy()
             output_dict["predictions"][name]["rotation"] = pose_h[i, 0:4].copy()
+            if fit_h is not None:
+                output_dict["predictions"][name]["fitness"] = float(fit_h[i, 0])
+                output_dict["predictions"][name]["inlier_rmse"] = float(fit_h[i, 1])
     if color_prediction:
         # both images on the device, from the tensors the stages left there (pipeline/overlay.py); one copy down
         from autoposeestimation_amd.pipeline import overlay

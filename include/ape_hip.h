@@ -556,6 +556,32 @@ int ape_fgr_optimize_batch_f64(int nb, const double* const* src, const int* ns, 
                                double division_factor, double max_corr_dist, int iteration_number, double* norm8, double* result,
                                void* stream);
 
+/* ---- depth ICP polish of the pose stage (csrc/icp_polish.hip) ------------------------------------------------------------------------
+ * For each of n objects: open3d 0.9 RegistrationICP with TransformationEstimationPointToPoint (the loop of ape_icp_run_batch_f64,
+ * kind 0) of the object's observed points onto its class's model cloud, all iterations in ONE launch, one workgroup per object; nothing
+ * is read back or allocated, and no argument is a host array, so the call can be captured in a HIP graph.
+ *   points4[n][N][4] f32   what ape_backproject_f32 wrote (camera frame, metres); object i's source is its first
+ *                          ns = min(n_cand[i], N) rows widened to float64 -- the rows behind them are never read.  N <= 2048.
+ *   obj_class[n] i32       row of model_table the object registers to
+ *   model_table[n_classes][5] i64 (device, built once per cloud set): the addresses of the class's search grid as
+ *                          ape_grid_build_batch_f64 wrote it -- sorted [M][3] f64, keys [M] u64, order [M] u32, origin [3] f64 -- and M.
+ *                          Every grid has cell size `cell` >= max_dist; max_model_points >= every M (it sizes the LDS staging of the
+ *                          grid: a class with more points is searched in global memory).
+ *   pose_in[n][7] f64      (w, x, y, z, tx, ty, tz) as the pose stage leaves it; init = inverse([R(q / |q|) | t])
+ *   pose_out[n][7] f64     inverse(T), quaternion as ape_pose_compose_f64 writes it (q[0] >= 0)
+ *   stats[n][4] f64        fitness, inlier rmse, correspondences, stop reason (1 converged by the relative criteria, 2 fewer than 3
+ *                          correspondences, 3 iteration limit: state[37] of ape_icp_run_batch_f64)
+ * pose_out[i] is pose_in[i] bit for bit when no update was applied (ns < 3, too few correspondences at the first evaluation,
+ * max_iteration 0) and when the final fitness is below min_fitness (stats stay the registration's).  An object with ns == 0 reports
+ * (0, 0, 0, 2).  obj_class lives on the device, so a class outside the table cannot be refused on the host: such an object, or one
+ * whose table row has M < 1, passes its pose through with stats (0, 0, 0, 0).  The sums are added in an order that depends on ns
+ * alone: an object's result has the same bits alone and in any batch.
+ * APE_EINVAL (with ape_last_error): n < 0, N outside 1..2048, max_dist <= 0, cell < max_dist, an empty table, max_iteration < 0. */
+int ape_icp_polish_batch_f64(int n, const float* points4, const int* n_cand, int N, const int* obj_class, const int64_t* model_table,
+                             int n_classes, int max_model_points, double cell, const double* pose_in, double max_dist,
+                             double relative_fitness, double relative_rmse, int max_iteration, double min_fitness, double* pose_out,
+                             double* stats, void* stream);
+
 /* ape_conv3x3_halo_bf16 for a 64-channel layer (the segmentor's up_3, pspnet.py:51) with ape_seg_head_f32 fused into its
  * epilogue: the [B][H][W][64] activation is never written, label[B][H][W] u8 / score[B][H][W] f32 are (bit-identical to the
  * unfused pair).  params->Cout must be 64, no residual; params->ups as in ape_conv3x3_halo_bf16. */

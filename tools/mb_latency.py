@@ -1,5 +1,8 @@
 """Single-frame latency of the live path (FramePipeline.run on ONE 640x480 frame: what main.py's 'Run Live Prediction' does per frame),
-host wall clock from resident inputs to the pose on the host.  python tools/mb_latency.py"""
+host wall clock from resident inputs to the pose on the host.  python tools/mb_latency.py [--icp-polish]
+--icp-polish: every batch size a second time with FramePipeline(icp_polish=...) (pipeline/polish.py), the two pipelines alternating frame
+by frame; the model clouds are the detected objects' own depth points in the model frame of the unpolished pose, turned by 2 degrees and
+shifted by 2 mm, so every point finds a partner and the polish runs a realistic number of iterations."""
 import os
 import sys
 import time
@@ -20,21 +23,50 @@ for m in (seg, est, ref):
     m.set_precision("bf16x3")
 pipe = FramePipeline(seg, est, ref, bench.CLASSES, num_points=1000, refine_mode="live_compat", pose_stream=False,
                      low_latency=os.environ.get("APE_LOW_LATENCY", "1") != "0")       # (what full_prediction uses; APE_LOW_LATENCY=0: the batched default)
+
+
+def polished_pipeline(rgb, depth):
+    """a second pipeline with the depth ICP polish on; clouds from one unpolished run of the same frames (see the module docstring)"""
+    from autoposeestimation_amd import engine as E
+    from autoposeestimation_amd.pipeline.polish import IcpPolish
+    out = pipe.run(rgb, depth, S.REALSENSE_META, seed=0)
+    pts4 = E.backproject(depth, torch.tensor(out["objects"], dtype=torch.int32).to(dev), out["choose"], S.REALSENSE_META["intr"], S.REALSENSE_META["depth_scale"])
+    pose, n_cand = out["pose"].cpu().numpy(), out["n_cand"].cpu().numpy()
+    clouds = {k: S.model_cloud(k + 1).astype(np.float64) for k in range(len(bench.CLASSES))}
+    a = np.radians(2.0)
+    turn = np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
+    for i, o in enumerate(out["objects"]):
+        w, x, y, z = pose[i, :4] / np.linalg.norm(pose[i, :4])
+        R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+        m = (pts4[i, :min(int(n_cand[i]), 1000), :3].cpu().numpy().astype(np.float64) - pose[i, 4:7]) @ R        # R^T (p - t)
+        clouds[o[1] - 1] = (m - m.mean(0)) @ turn.T + m.mean(0) + np.array([0.0015, -0.001, 0.0008])
+    return FramePipeline(seg, est, ref, bench.CLASSES, num_points=1000, refine_mode="live_compat", pose_stream=False, low_latency=pipe.low_latency,
+                         icp_polish=IcpPolish(clouds))
+
+
 for b in (1, 4):
     rgb = torch.from_numpy(np.stack([f[0] for f in frames[:b]])).to(dev)
     depth = torch.from_numpy(np.stack([f[1] for f in frames[:b]])).to(dev)
+    pipes = {"": pipe}
+    if "--icp-polish" in sys.argv:
+        pipes[" icp_polish"] = polished_pipeline(rgb, depth)
     for _ in range(5):
-        out = pipe.run(rgb, depth, S.REALSENSE_META, seed=0)
-        out["pose"].cpu()
+        for p_ in pipes.values():
+            out = p_.run(rgb, depth, S.REALSENSE_META, seed=0)
+            out["pose"].cpu()
     torch.cuda.synchronize()
-    ts = []
+    ts = {k: [] for k in pipes}
     for i in range(30):
-        t0 = time.perf_counter()
-        out = pipe.run(rgb, depth, S.REALSENSE_META, seed=i)
-        p = out["pose"].cpu()
-        ts.append(time.perf_counter() - t0)
-    ts = np.sort(ts) * 1e3
-    print("batch %d: median %.2f ms  min %.2f ms  (%d objects)" % (b, ts[len(ts) // 2], ts[0], len(out["objects"])))
+        for k, p_ in pipes.items():
+            t0 = time.perf_counter()
+            out = p_.run(rgb, depth, S.REALSENSE_META, seed=i)
+            p = out["pose"].cpu()
+            ts[k].append(time.perf_counter() - t0)
+    for k, t in ts.items():
+        t = np.sort(t) * 1e3
+        extra = "" if not k else "  fitness %s" % np.round(out["fit"][:, 0].cpu().numpy(), 3).tolist()
+        print("batch %d%s: median %.2f ms  min %.2f ms  (%d objects)%s" % (b, k, t[len(t) // 2], t[0], len(out["objects"]), extra))
 
 if os.environ.get("APE_LAT_PROFILE"):
     import cProfile
