@@ -31,7 +31,8 @@ struct GemmArgs {
     ape_conv_params p;
     int M, Kp, m_tiles, n_tiles, nk;
     int out_fmt;       // APE_FMT_F32 | APE_FMT_S32 (pre-split output for the S32 consumers; needs ldy % 32 == 0 and the vector path)
-    int dbg;           // ablation bits (timing experiments only, results are wrong): 1 no in-loop global loads, 2 no in-loop LDS restage, 4 no MFMAs
+    int dbg;           // ablation bits (timing experiments only, results are wrong): 1 no in-loop global loads, 2 no in-loop LDS restage, 4 no MFMAs;
+                       // 16 (results unchanged): variant 0 never chooses the rows form
     long plane_stride;
     int nk_per;        // split-K (training tape, small M): blockIdx.y takes k-tiles [y * nk_per, ...) and writes RAW sums to y + blockIdx.y * split_stride; 0 = off
     long split_stride;
@@ -376,6 +377,155 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_multi_kernel(const GemmMulti
     conv_gemm_body<NSPLIT, 128, 128, 2, 2, true, false, false>(m.a[pi], blk - m.first[pi]);
 }
 
+// ---- The small-M form of the PURE 1x1 convolution (variant 7, "rows"): the pose networks' layers that run on one row per crop (M = 64
+// at 64 crops, M = 1 at batch 1).  On the 128x128 block such a layer is Cout / 128 = 1..15 workgroups on a 256-CU chip, each walking
+// K = 256..1024 alone with one LDS round trip and one barrier per k-tile: 15..37 us of latency chain for at most 0.25 GFLOP.
+// Here a one-wave workgroup owns one 16 x 16 output block (16 channels x 16 rows), so a layer gets Cout / 16 * ceil(M / 16) workgroups.
+// (The four row blocks of M = 64 as four waves of ONE workgroup were measured first: a fragment load touches 16 cache lines, and four
+// waves behind one compute unit's address unit took 17.6 us for 1024 -> 1920 where one wave, M = 16, took 7.5.)  There is no LDS stage and no barrier: lane (frow, fc) holds, in conv_gemm_kernel's fragments, chunk fc (8 of
+// the 32 k elements) of weight row n0 + frow and of activation row mb + frow -- 16 contiguous bytes per weight plane and 32 of fp32
+// activations -- which it loads straight from global memory.  The loads of ROWS_KC k-tiles are issued together and the next chunk's before
+// this chunk's matrix instructions, so a layer costs about one memory round trip per 2 * ROWS_KC k-tiles plus its MFMAs.
+// Every output element is the very sum conv_gemm_kernel forms: k-tiles ascending into ONE accumulator, per k-tile mfma(w_hi, x_lo),
+// mfma(w_lo, x_hi), mfma(w_hi, x_hi) on the same k elements in the same operand positions, split8 on the fp32 activations, the same
+// epilogue statements.  No split-K, no cross-wave sums.
+constexpr int ROWS_KC = 8;          // k-tiles per load chunk (nsplit 3: 8 x 16 = 128 registers of loads in flight per buffer, two buffers)
+constexpr int ROWS_MAX_M = 128;     // the variant-0 rule takes this form up to here: it is ahead of the 128x128 block while it has fewer than ~1900 one-wave
+                                    // workgroups (Cout / 16 x M / 16; 1024 -> 1920: 10.8 / 17.9 / 33.4 us at M = 64 / 128 / 256 against 32.5 .. 33)
+
+struct RowsFrag { f32x4 x0, x1; u32x4 wh, wl; };
+
+template <int NPL, int N>
+__device__ __forceinline__ void rows_load(RowsFrag (&f)[N], const float* xr, const __bf16* wr, long plane_stride, int t0)
+{
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int k = (t0 + i) * BK;
+        f[i].x0 = *reinterpret_cast<const f32x4*>(xr + k);
+        f[i].x1 = *reinterpret_cast<const f32x4*>(xr + k + 4);
+        f[i].wh = *reinterpret_cast<const u32x4*>(wr + k);
+        if (NPL == 2) f[i].wl = *reinterpret_cast<const u32x4*>(wr + plane_stride + k);
+    }
+}
+
+template <int NPL, int N>
+__device__ __forceinline__ void rows_mfma(const RowsFrag (&f)[N], f32x4& acc)
+{
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        bf16x8 ah, al;
+        split8(f[i].x0, f[i].x1, ah, al);
+        const bf16x8 bh = __builtin_bit_cast(bf16x8, f[i].wh);
+        if (NPL == 2) {
+            const bf16x8 bl = __builtin_bit_cast(bf16x8, f[i].wl);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, al, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl, ah, acc, 0, 0, 0);
+        }
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, ah, acc, 0, 0, 0);
+    }
+}
+
+template <int NSPLIT>
+__global__ __launch_bounds__(64) void conv_rows_kernel(const GemmArgs a)
+{
+    constexpr int NPL = NSPLIT == 3 ? 2 : 1;
+    constexpr int KC = ROWS_KC;
+    const ape_conv_params& p = a.p;
+    const int lane = threadIdx.x;
+    const int frow = lane & 15, fc = lane >> 4;
+    // workgroup -> (channel block, row block): consecutive workgroup ids go round the 8 XCDs, so the a.m_tiles row blocks that share a
+    // channel block's weights are dealt to ONE XCD (its L2 then fetches those weights once); ids past the last channel block do nothing
+    const int xcd = (int)blockIdx.x % 8, seq = (int)blockIdx.x / 8;
+    const int n0 = ((seq / a.m_tiles) * 8 + xcd) * 16;
+    const int mb = (seq % a.m_tiles) * 16;
+    if (n0 >= p.Cout) return;
+
+    // rows >= M and channels >= Cout are computed on clamped data and dropped by the epilogue, as in conv_gemm_kernel
+    const int m = mb + frow;
+    const bool mok = m < a.M;
+    const int mc = mok ? m : a.M - 1;
+    const int nw = n0 + frow < p.Cout ? n0 + frow : p.Cout - 1;
+    const float* const xr = a.x + (size_t)mc * p.ldx + p.xoff + fc * 8;
+    const __bf16* const wr = a.w + (size_t)nw * a.Kp + fc * 8;
+
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const int nk = a.nk;
+    int t = 0;
+    if (nk >= KC) {
+        RowsFrag fa[KC], fb[KC];
+        rows_load<NPL, KC>(fa, xr, wr, a.plane_stride, 0);
+#pragma unroll 1
+        for (;;) {
+            const bool more_b = t + 2 * KC <= nk;
+            if (more_b) rows_load<NPL, KC>(fb, xr, wr, a.plane_stride, t + KC);
+            rows_mfma<NPL, KC>(fa, acc);
+            t += KC;
+            if (!more_b) break;
+            const bool more_a = t + 2 * KC <= nk;
+            if (more_a) rows_load<NPL, KC>(fa, xr, wr, a.plane_stride, t + KC);
+            rows_mfma<NPL, KC>(fb, acc);
+            t += KC;
+            if (!more_a) break;
+        }
+    }
+    // the K tail (K / 32 is not a multiple of ROWS_KC): chunks of 4, 2 and 1 k-tiles, still in ascending order
+    if (nk - t >= 4) {
+        RowsFrag f[4];
+        rows_load<NPL, 4>(f, xr, wr, a.plane_stride, t);
+        rows_mfma<NPL, 4>(f, acc);
+        t += 4;
+    }
+    if (nk - t >= 2) {
+        RowsFrag f[2];
+        rows_load<NPL, 2>(f, xr, wr, a.plane_stride, t);
+        rows_mfma<NPL, 2>(f, acc);
+        t += 2;
+    }
+    if (nk - t >= 1) {
+        RowsFrag f[1];
+        rows_load<NPL, 1>(f, xr, wr, a.plane_stride, t);
+        rows_mfma<NPL, 1>(f, acc);
+    }
+
+    // ---- conv_gemm_kernel's epilogue for one fragment: lane (frow, fc) holds channels n0 + 4 fc .. + 3 of row mb + frow
+    const int n = n0 + fc * 4;
+    if (!mok || n >= p.Cout) return;
+    const bool vec_ok = (p.ldy % 4 == 0) && (p.yoff % 4 == 0);
+    const ape::ActFast af = ape::act_fast_make(p.act, p.alpha);
+    const bool sigm = p.act == APE_ACT_SIGMOID;
+    const float* brow = (a.bias && p.bias_bstride) ? a.bias + (size_t)(m / (p.Ho * p.Wo)) * p.bias_bstride : nullptr;
+    float vv[4] = {acc[0], acc[1], acc[2], acc[3]};
+    const int nvalid = min(4, p.Cout - n);
+    if (vec_ok && nvalid == 4) {
+        if (brow) { vv[0] += brow[n]; vv[1] += brow[n + 1]; vv[2] += brow[n + 2]; vv[3] += brow[n + 3]; }
+        else if (a.bias) { vv[0] += a.bias[n]; vv[1] += a.bias[n + 1]; vv[2] += a.bias[n + 2]; vv[3] += a.bias[n + 3]; }
+        const float4 o4 = sigm ? make_float4(activate(vv[0], p.act, p.alpha), activate(vv[1], p.act, p.alpha), activate(vv[2], p.act, p.alpha),
+                                             activate(vv[3], p.act, p.alpha))
+                               : make_float4(ape::act_fast(vv[0], af), ape::act_fast(vv[1], af), ape::act_fast(vv[2], af), ape::act_fast(vv[3], af));
+        *reinterpret_cast<float4*>(a.y + (size_t)m * p.ldy + p.yoff + n) = o4;
+    } else {
+        for (int k = 0; k < nvalid; ++k) {
+            float tv = vv[k];
+            if (a.bias) tv += (brow ? brow : a.bias)[n + k];
+            a.y[(size_t)m * p.ldy + p.yoff + n + k] = activate(tv, p.act, p.alpha);
+        }
+    }
+}
+
+// the rows form takes: pure 1x1, fp32 in and out, no residual (the caller checks M against its own bound)
+bool rows_takes(const GemmArgs& a, bool pure)
+{
+    return pure && !a.res && a.out_fmt == APE_FMT_F32 && ((long)ape::ceil_div(a.p.Cout, 16) + 7) * ape::ceil_div(a.M, 16) < (1L << 31);
+}
+
+template <int NSPLIT>
+void launch_rows(GemmArgs& a, hipStream_t st)
+{
+    a.m_tiles = ape::ceil_div(a.M, 16);                    // 16-row blocks
+    a.n_tiles = ape::ceil_div(a.p.Cout, 16);
+    hipLaunchKernelGGL((conv_rows_kernel<NSPLIT>), dim3(ape::ceil_div(a.n_tiles, 8) * 8 * a.m_tiles), dim3(64), 0, st, a);
+}
+
 template <int NSPLIT, int BM, int BN, int WM, int WN, bool PP = false>
 void launch(GemmArgs& a, bool pure, hipStream_t st)
 {
@@ -450,7 +600,8 @@ bool supported(const ape_conv_params& p)
 extern "C" int ape_conv_gemm_supported(const ape_conv_params* params) { return params && supported(*params) ? 1 : 0; }
 
 /* variant: 0 = chosen from the shape; 1 = 256x256 block (8 waves); 2 = 128x128 block (4 waves); 3 = 256x64 block (4 waves);
- * 4 = 256x192 block (8 waves; Cout = 576 of the up_2 channel mix is 3 x 192) */
+ * 4 = 256x192 block (8 waves; Cout = 576 of the up_2 channel mix is 3 x 192); 7 = the small-M "rows" form (pure 1x1, fp32 out, no residual:
+ * APE_EINVAL otherwise), which variant 0 takes up to 128 rows; variant 0 | 0x100 chooses among the block shapes only (A/B) */
 extern "C" int ape_conv_gemm_bf16(const float* x, const void* w_packed, const float* bias, const float* residual, float* y,
                                   const ape_conv_params* params, int nsplit, int variant, void* stream)
 {
@@ -465,7 +616,7 @@ extern "C" int ape_conv_gemm_bf16_fmt(const float* x, const void* w_packed, cons
     if (out_fmt != APE_FMT_F32 && out_fmt != APE_FMT_S32) return APE_EINVAL;
     if (out_fmt == APE_FMT_S32 && params && (params->ldy % 32 || params->Cout % 4 || params->yoff % 4 || (residual && (params->ldr % 4 || params->roff % 4))))
         return APE_EINVAL;
-    if (!x || !w_packed || !y || !params || (nsplit != 1 && nsplit != 3) || variant < 0 || (variant & 15) > 6) return APE_EINVAL;
+    if (!x || !w_packed || !y || !params || (nsplit != 1 && nsplit != 3) || variant < 0 || (variant & 15) > 7) return APE_EINVAL;
     const ape_conv_params& p = *params;
     if (!supported(p)) return APE_EINVAL;
     if (residual && p.roff + p.Cout > p.ldr) return APE_EINVAL;
@@ -485,10 +636,13 @@ extern "C" int ape_conv_gemm_bf16_fmt(const float* x, const void* w_packed, cons
     variant &= 15;
     const bool pure = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0;
     hipStream_t st = (hipStream_t)stream;
+    if (variant == 7 && !rows_takes(a, pure)) return APE_EINVAL;
     if (variant == 0) {
         const int waste256 = ape::ceil_div(p.Cout, 256) * 256 - p.Cout;
         const int waste192 = ape::ceil_div(p.Cout, 192) * 192 - p.Cout;
-        if (p.Cout <= 64) variant = 3;
+        // a handful of rows (the pose heads: one row per crop): one wave per 16 x 16 output block, operands straight from global memory
+        if (M <= ROWS_MAX_M && !(a.dbg & 16) && rows_takes(a, pure)) variant = 7;
+        else if (p.Cout <= 64) variant = 3;
         // the 256-row blocks need about a chip's worth of workgroups (256 CUs); below that the 128x128 block fills it better
         else if (p.Cout >= 256 && waste256 * 8 <= p.Cout && K >= 256 && (long)ape::ceil_div(M, 256) * ape::ceil_div(p.Cout, 256) >= 192) variant = 1;
         else if (p.Cout >= 192 && waste192 * 8 <= p.Cout && K >= 256 && (long)ape::ceil_div(M, 256) * ape::ceil_div(p.Cout, 192) >= 192) variant = 4;
@@ -502,6 +656,8 @@ extern "C" int ape_conv_gemm_bf16_fmt(const float* x, const void* w_packed, cons
         if (nsplit == 3) launch<3, 256, 64, 4, 1>(a, pure, st); else launch<1, 256, 64, 4, 1>(a, pure, st);
     } else if (variant == 4) {
         if (nsplit == 3) launch<3, 256, 192, 2, 4>(a, pure, st); else launch<1, 256, 192, 2, 4>(a, pure, st);
+    } else if (variant == 7) {
+        if (nsplit == 3) launch_rows<3>(a, st); else launch_rows<1>(a, st);
     } else if (variant == 5) {
         if (nsplit == 3) launch<3, 256, 256, 2, 4, true>(a, pure, st); else launch<1, 256, 256, 2, 4, true>(a, pure, st);
     } else {

@@ -90,7 +90,7 @@ struct PoolPlan {
 };
 
 // grid (B * ny, C4 / 64): one atom ROW per workgroup; the 4 waves split its pixel rows, a lane owns one float4 of channels and
-// keeps one accumulator per atom column
+// keeps one accumulator per atom column.  (The form before avgpool_atom_kernel below; launched under APE_POOL_ATOM_ROWS for A/B.)
 template <bool S32IN>
 __global__ __launch_bounds__(256) void avgpool_atoms_kernel(const float4* __restrict__ x, float4* __restrict__ atoms, const PoolPlan pl,
                                                             int H, int W, int C4, int ld4)
@@ -140,6 +140,48 @@ __global__ __launch_bounds__(256) void avgpool_atoms_kernel(const float4* __rest
             for (int k = 0; k < 3; ++k) { t.x += part[k][a][lane].x; t.y += part[k][a][lane].y; t.z += part[k][a][lane].z; t.w += part[k][a][lane].w; }
             atoms[(((long)b * pl.ny + ay) * pl.nx + a) * C4 + c] = t;
         }
+    }
+}
+
+// grid (B * ny * nx, C4 / 64): one ATOM per workgroup -- ten times the workgroups of the atom-row form on the 6 x 10 atoms of a 60 x 80 map
+// (7680 against 768 at 64 frames, 6400 against 640 on the crops' 20 x 20 maps, where 640 workgroups of 1..2 pixel rows per wave left most of
+// the chip waiting on single loads) and one accumulator per lane, so eight pixels' loads are in flight before the first add.  Every
+// (atom, channel) keeps the atom-row form's order of additions: wave g sums the rows y = ye[ay] + g, + 4, .. with ascending columns into
+// one accumulator, then acc_0 + part_0 + part_1 + part_2.  Same bits (tests/test_gpu_pool_atoms.py).
+template <bool S32IN>
+__global__ __launch_bounds__(256) void avgpool_atom_kernel(const float4* __restrict__ x, float4* __restrict__ atoms, const PoolPlan pl,
+                                                           int H, int W, int C4, int ld4)
+{
+    __shared__ float4 part[3][64];
+    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int ax = blockIdx.x % pl.nx, ay = (blockIdx.x / pl.nx) % pl.ny, b = blockIdx.x / (pl.nx * pl.ny);
+    const int c = blockIdx.y * 64 + lane;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < C4) {
+        auto load = [&](long pix) { return S32IN ? ape::s32_load4(x, pix, ld4, c) : x[pix * ld4 + c]; };
+        auto add = [&](const float4 v) { acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w; };
+        const int x0 = pl.xe[ax], xend = pl.xe[ax + 1];
+        for (int y = pl.ye[ay] + g; y < pl.ye[ay + 1]; y += 4) {
+            const long row = (long)(b * H + y) * W;
+            int xx = x0;
+            for (; xx + 8 <= xend; xx += 8) {
+                const float4 v0 = load(row + xx), v1 = load(row + xx + 1), v2 = load(row + xx + 2), v3 = load(row + xx + 3);
+                const float4 v4 = load(row + xx + 4), v5 = load(row + xx + 5), v6 = load(row + xx + 6), v7 = load(row + xx + 7);
+                add(v0); add(v1); add(v2); add(v3); add(v4); add(v5); add(v6); add(v7);
+            }
+            for (; xx + 4 <= xend; xx += 4) {
+                const float4 v0 = load(row + xx), v1 = load(row + xx + 1), v2 = load(row + xx + 2), v3 = load(row + xx + 3);
+                add(v0); add(v1); add(v2); add(v3);
+            }
+            for (; xx < xend; ++xx) add(load(row + xx));
+        }
+    }
+    if (g > 0) part[g - 1][lane] = acc;
+    __syncthreads();
+    if (g == 0 && c < C4) {
+        float4 t = acc;
+        for (int k = 0; k < 3; ++k) { t.x += part[k][lane].x; t.y += part[k][lane].y; t.z += part[k][lane].z; t.w += part[k][lane].w; }
+        atoms[(((long)b * pl.ny + ay) * pl.nx + ax) * C4 + c] = t;
     }
 }
 
@@ -809,6 +851,8 @@ extern "C" size_t ape_adaptive_avgpool_multi_workspace_bytes(int B, int C)
 extern "C" int ape_adaptive_avgpool_multi_nhwc_ld(const void* x, int in_fmt, float* const* ys_host, const int* sizes_host, int nsizes, int B, int H,
                                                   int W, int C, int ldx, void* workspace, size_t workspace_bytes, void* stream)
 {
+    const bool atom_rows = in_fmt >= 0 && (in_fmt & APE_POOL_ATOM_ROWS);       // A/B: the former pass 1, one workgroup per atom ROW (same bits)
+    if (in_fmt >= 0) in_fmt &= ~APE_POOL_ATOM_ROWS;
     if ((in_fmt != APE_FMT_F32 && in_fmt != APE_FMT_S32) || (in_fmt == APE_FMT_S32 && (C % 32 || ldx % 32))) return APE_EINVAL;
     if (!x || !ys_host || !sizes_host || !workspace || nsizes < 1 || nsizes > kPoolMaxSizes || B < 0 || H < 1 || W < 1 || C < 4 || C % 4 ||
         ldx < C || ldx % 4)
@@ -829,12 +873,15 @@ extern "C" int ape_adaptive_avgpool_multi_nhwc_ld(const void* x, int in_fmt, flo
     if (pl.ny < 0 || pl.nx < 0) return APE_EINVAL;
     if (workspace_bytes < (size_t)B * pl.ny * pl.nx * C * sizeof(float)) return APE_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    if (in_fmt == APE_FMT_S32)
-        hipLaunchKernelGGL(avgpool_atoms_kernel<true>, dim3(B * pl.ny, ape::ceil_div(C / 4, 64)), dim3(256), 0, st, (const float4*)x,
-                           (float4*)workspace, pl, H, W, C / 4, ldx / 4);
-    else
-        hipLaunchKernelGGL(avgpool_atoms_kernel<false>, dim3(B * pl.ny, ape::ceil_div(C / 4, 64)), dim3(256), 0, st, (const float4*)x,
-                           (float4*)workspace, pl, H, W, C / 4, ldx / 4);
+    if ((long)B * pl.ny * pl.nx >= (1L << 31)) return APE_EINVAL;
+    const dim3 grid(atom_rows ? B * pl.ny : B * pl.ny * pl.nx, ape::ceil_div(C / 4, 64));
+    if (in_fmt == APE_FMT_S32) {
+        if (atom_rows) hipLaunchKernelGGL(avgpool_atoms_kernel<true>, grid, dim3(256), 0, st, (const float4*)x, (float4*)workspace, pl, H, W, C / 4, ldx / 4);
+        else hipLaunchKernelGGL(avgpool_atom_kernel<true>, grid, dim3(256), 0, st, (const float4*)x, (float4*)workspace, pl, H, W, C / 4, ldx / 4);
+    } else {
+        if (atom_rows) hipLaunchKernelGGL(avgpool_atoms_kernel<false>, grid, dim3(256), 0, st, (const float4*)x, (float4*)workspace, pl, H, W, C / 4, ldx / 4);
+        else hipLaunchKernelGGL(avgpool_atom_kernel<false>, grid, dim3(256), 0, st, (const float4*)x, (float4*)workspace, pl, H, W, C / 4, ldx / 4);
+    }
     const long total = (long)B * bins_total * (C / 4);
     hipLaunchKernelGGL(avgpool_bins_kernel, dim3(ape::grid_for(total, kThreads, kGridCap)), dim3(kThreads), 0, st, (const float4*)workspace, pl, B, H, W, C / 4,
                        bins_total);

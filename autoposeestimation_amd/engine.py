@@ -88,6 +88,8 @@ USE_HALO_KERNEL = True    # route eligible 3x3 convs of the bf16 paths to the LD
 USE_GEMM_KERNEL = os.environ.get("APE_USE_GEMM_KERNEL", "1") != "0"    # route Cin % 32 == 0 layers the halo kernel does not take to conv_gemm.hip (else conv_bf16.hip)
 USE_CONV_MULTI = os.environ.get("APE_USE_CONV_MULTI", "1") != "0"     # the PSP stage convolutions in one launch (conv1x1_multi); 0: one launch each (A/B)
 GEMM_VARIANT = int(os.environ.get("APE_GEMM_VARIANT", "0"))          # 0 = chosen from the shape; 1..4 force a block shape (tools/microbench_generic.py)
+USE_GEMM_ROWS = os.environ.get("APE_USE_GEMM_ROWS", "1") != "0"      # pure 1x1 layers of at most GEMM_ROWS_MAX_M rows take conv_rows_kernel (conv_gemm.hip variant 7); 0: the block shapes only (A/B)
+GEMM_ROWS_MAX_M = 128                                                # = ROWS_MAX_M of conv_gemm.hip
 
 
 FMT_F32, FMT_S32 = 0, 1
@@ -282,13 +284,16 @@ class Conv:
             return "conv_bf16_kernel<%d,256,256,4,2,32,true>" % self.nsplit
         return self.variant
 
-    def _gemm_variant(self, m):
-        """name of the conv_gemm.hip instantiation ape_conv_gemm_bf16 dispatches to (mirrors the C++ rule; profiling label only)"""
+    def _gemm_variant(self, m, residual=False, out_fmt=FMT_F32):
+        """name of the conv_gemm.hip instantiation ape_conv_gemm_bf16_fmt dispatches to (mirrors the C++ rule; profiling label only)"""
         pure = "true" if (self.kh == 1 and self.kw == 1 and self.stride == 1 and self.pad == 0) else "false"
         v = GEMM_VARIANT & 15
         if v == 0:
             k = self.kh * self.kw * self.cin
-            if self.cout <= 64:
+            if (m <= GEMM_ROWS_MAX_M and USE_GEMM_ROWS and not (GEMM_VARIANT & 0x100) and pure == "true" and not residual
+                    and out_fmt == FMT_F32):
+                v = 7
+            elif self.cout <= 64:
                 v = 3
             elif (self.cout >= 256 and ((-(-self.cout // 256)) * 256 - self.cout) * 8 <= self.cout and k >= 256
                   and -(-m // 256) * -(-self.cout // 256) >= 192):
@@ -298,6 +303,8 @@ class Conv:
                 v = 4
             else:
                 v = 2
+        if v == 7:
+            return "conv_rows_kernel<%d>" % self.nsplit
         # the same spelling as rocprofv3's kernel name (template arguments NSPLIT, BM, BN, WM, WN, PURE, PP), so that bench.py finds
         # this kernel's HBM traffic in profiles/*_pmc_traffic.json
         return "conv_gemm_kernel<%d,%s,%s,%s>" % (self.nsplit, {1: "256,256,2,4", 2: "128,128,2,2", 3: "256,64,4,1", 4: "256,192,2,4",
@@ -342,7 +349,7 @@ class Conv:
                 # k-tiles dealt to several workgroups per output tile where the library finds it worth it (fewer than 96 tiles and >= 8 k-tiles)
                 sk_bytes = int(L.ape_conv_gemm_splitk_workspace_bytes(pref)) if splitk and out_fmt == FMT_F32 else 0
                 args, entry = (_ARGS_SPLITK, "ape_conv_gemm_bf16_splitk") if sk_bytes else (_ARGS_GEMM, "ape_conv_gemm_bf16_fmt")
-                label = self._gemm_variant(m)
+                label = self._gemm_variant(m, ldr != 0, out_fmt)
             else:
                 args, entry = (_ARGS_BF16, "ape_conv2d_nhwc_bf16") if self.nsplit else (_ARGS_F32, "ape_conv2d_nhwc_f32")
                 label = self._generic_variant(m)
@@ -401,7 +408,7 @@ class Conv:
         splitk = bool(splitk or (self.splitk and _POSE_STAGE.get()))
         # the call signature: geometry and formats, then the module switches that take part in routing
         key = (b, h, w, ldx, xoff, out.shape[3], yoff, self.act if act is None else act, bias_bstride, 0 if residual is None else residual.shape[3], roff,
-               bool(upsample2x), splitk, in_fmt, out_fmt, USE_HALO_KERNEL, USE_GEMM_KERNEL, GEMM_VARIANT, USE_MX6, MX6_CIN)
+               bool(upsample2x), splitk, in_fmt, out_fmt, USE_HALO_KERNEL, USE_GEMM_KERNEL, GEMM_VARIANT, USE_MX6, MX6_CIN, USE_GEMM_ROWS)
         plan = self._plans.get(key) or self._make_plan(key)
         p, pref, args, fn, sk_bytes, label, shape, flop, nbytes = plan
         if p.alpha != self.alpha:
@@ -413,7 +420,7 @@ class Conv:
         e0 = None if PROFILE is None else PROFILE.begin(label)
         xp, bp, rp, yp = _lib.dptr(x, torch.float32), _lib.dptr(bias), _lib.dptr(residual), _lib.dptr(out, torch.float32)
         if args == _ARGS_GEMM:
-            fn(xp, _lib.dptr(self.wp), bp, rp, yp, out_fmt, pref, self.nsplit, GEMM_VARIANT, _st())
+            fn(xp, _lib.dptr(self.wp), bp, rp, yp, out_fmt, pref, self.nsplit, GEMM_VARIANT if USE_GEMM_ROWS else GEMM_VARIANT | 0x100, _st())
         elif args == _ARGS_BF16:
             fn(xp, _lib.dptr(self.wp), bp, rp, yp, pref, self.nsplit, _st())
         elif args == _ARGS_S32:
@@ -674,6 +681,9 @@ def adaptive_avgpool(x, s):
     return y
 
 
+POOL_ATOM_ROWS = False   # adaptive_avgpool_multi's first pass with one workgroup per atom ROW (the former kernel; A/B, same bits)
+
+
 def adaptive_avgpool_multi(x, sizes, channels=None):
     """{s: AdaptiveAvgPool2d((s, s))(x[..., :channels])} for several sizes in one pass over x[B,H,W,C]; per-size launches when the bin edges
     of the sizes cut an axis into more than 12 atoms.  `channels` (default: all) pools the leading channels only and gives [B,s,s,channels]."""
@@ -687,7 +697,7 @@ def adaptive_avgpool_multi(x, sizes, channels=None):
     ptrs = (ctypes.c_void_p * len(sizes))(*[y.data_ptr() for y in ys])
     szs = (ctypes.c_int * len(sizes))(*sizes)
     try:
-        _lib.call.ape_adaptive_avgpool_multi_nhwc_ld(_lib.dptr(xt, torch.float32), fmt, ptrs, szs, len(sizes), b, h, w, c, ld, _lib.dptr(ws),
+        _lib.call.ape_adaptive_avgpool_multi_nhwc_ld(_lib.dptr(xt, torch.float32), fmt | (0x100 if POOL_ATOM_ROWS else 0), ptrs, szs, len(sizes), b, h, w, c, ld, _lib.dptr(ws),
                                                      ws.numel() * ws.element_size(), _st())
     except _lib.ApeError as e:
         if e.code != -1:

@@ -127,6 +127,9 @@ int ape_psp_fold_operands(const void* wf_s32k, const float* z1, const float* z2,
  * in either format (ape_upconv3x3_gather_ex: up_1's result feeds up_2's S32 channel mixing). */
 int ape_conv_gemm_bf16_fmt(const float* x, const void* w_packed, const float* bias, const float* residual, void* y, int out_fmt,
                            const ape_conv_params* params_host, int nsplit, int variant, void* stream);
+/* (variant, of both entry points: 0 = chosen from the shape, 1..6 a block shape of conv_gemm_kernel, 7 = conv_rows_kernel, the small-M form of
+ * the pure 1x1 / stride-1 convolution with fp32 output and no residual -- APE_EINVAL for anything else -- which variant 0 takes up to 128
+ * rows; 0 | 0x100 = variant 0 without that form.  Every variant forms the same sum per output element: same results bit for bit.) */
 /* The PSP module's stage convolutions (pspnet.py:15-18, 22: `stage(feats) for stage in self.stages` -- four bias-free 1x1 convolutions of the
  * 1x1 / 2x2 / 3x3 / 6x6 pooled maps) are independent problems of 1 .. 18 tiles each: n <= 4 such 1x1 / stride-1 convolutions (fp32 in, fp32 out,
  * no residual) in ONE launch.  Problem i multiplies x[i] by w_packed[i] (ape_pack_weights_bf16 layout) under params_host[i]; bias may be NULL
@@ -143,7 +146,9 @@ int ape_conv_gemm_bf16_splitk(const float* x, const void* w_packed, const float*
 /* The multi-size adaptive average pool (documented with ape_adaptive_avgpool_multi_workspace_bytes below) of x in either activation
  * format (APE_FMT_S32: C % 32 == 0 and ldx % 32 == 0), over the first C channels of a map that holds ldx >= C channels per pixel (the PSP
  * module's feature map with the 64 spare channels of ape_psp_fold_operands behind its 512: pspnet.py:15 pools the 512); outputs
- * [B,s,s,C] fp32 */
+ * [B,s,s,C] fp32.  in_fmt | APE_POOL_ATOM_ROWS: pass 1 with one workgroup per atom ROW instead of one per atom (the former kernel, kept
+ * for A/B: same results bit for bit) */
+enum { APE_POOL_ATOM_ROWS = 0x100 };
 int ape_adaptive_avgpool_multi_nhwc_ld(const void* x, int in_fmt, float* const* ys_host, const int* sizes_host, int nsizes, int B, int H, int W,
                                        int C, int ldx, void* workspace, size_t workspace_bytes, void* stream);
 /* ape_upconv3x3_gather_f32 with the OUTPUT in either activation format (APE_FMT_S32: C % 32 == 0) and the interpolation arithmetic
