@@ -410,28 +410,55 @@ class _FeatPlan:
         self.precision = precision
         self.pf_s32 = None
 
-    def __call__(self, x4, emb):
-        """x4[B,N,4], emb[B,N,32] -> pf[B,N,1,384], ap[B,1024]"""
+    def __call__(self, x4, emb, want_pf=True, cache=None):
+        """x4[B,N,4], emb[B,N,32] -> pf[B,N,1,384], ap[B,1024].
+        want_pf=False: the caller does not read the fp32 pf; on the pre-split route it is then neither written nor returned (None).
+        cache: a caller-owned `FeatCache` for calls that share `emb` and these weights (the refiner's iterations): the first call
+        fills it, later calls recompute the x half only."""
         b, n, _ = x4.shape
         x4 = x4.view(b, n, 1, 4)
         emb = emb.view(b, n, 1, 32)
-        pf = torch.empty(b, n, 1, 384, dtype=torch.float32, device=x4.device)
-        self.conv1(x4, out=pf, yoff=0)
-        self.e_conv1(emb, out=pf, yoff=64)
-        self.conv2(pf, out=pf, xoff=0, yoff=128)
-        self.e_conv2(pf, out=pf, xoff=64, yoff=256)
+        dev = x4.device
         # Enough rows to fill 256-row tiles: the 1x1 layers run on PRE-SPLIT activations (conv_gemm_s32.hip, LDS-DMA operands) -- the same
         # MFMA operands as the on-the-fly split of conv_gemm.hip, so every value below is bit for bit what the fp32 route gives
         # (tests/test_gpu_posenet.py); `self.pf_s32` hands the split point features to the estimator's heads
-        self.pf_s32 = None
-        if self.precision == "bf16x3" and E.USE_S32 and b * n >= S32_MIN_ROWS:
-            pfs = self.pf_s32 = E.S32.from_f32(pf)
+        split = self.precision == "bf16x3" and E.USE_S32 and b * n >= S32_MIN_ROWS
+        if self.precision == "bf16x3" and E.USE_POINT_FEAT:
+            # the four layers and the split in one launch (point_feat.hip), the same bits as the five launches below
+            parts = E.PF_X | E.PF_EMB
+            key = (b, n, split, want_pf)
+            if cache is not None and cache.key == key:
+                pf, pfs, parts = cache.pf, cache.pf_s32, E.PF_X                 # the emb half's columns are in the buffers already
+            else:
+                pfs = E.S32(torch.empty(b, n, 1, 384, dtype=torch.float32, device=dev)) if split else None
+                pf = torch.empty(b, n, 1, 384, dtype=torch.float32, device=dev) if want_pf or not split else None
+                if cache is not None:
+                    cache.key, cache.pf, cache.pf_s32 = key, pf, pfs
+            E.point_feat(x4, emb, self.conv1, self.e_conv1, self.conv2, self.e_conv2, pf=pf, pf_s32=pfs, parts=parts)
+            self.pf_s32 = pfs
+        else:
+            pf = torch.empty(b, n, 1, 384, dtype=torch.float32, device=dev)
+            self.conv1(x4, out=pf, yoff=0)
+            self.e_conv1(emb, out=pf, yoff=64)
+            self.conv2(pf, out=pf, xoff=0, yoff=128)
+            self.e_conv2(pf, out=pf, xoff=64, yoff=256)
+            pfs = self.pf_s32 = E.S32.from_f32(pf) if split else None
+        if split:
             x5 = self.conv5(pfs, xoff=0 if self.refine else 128, out_fmt=E.FMT_S32)
             x6 = self.conv6(x5)
         else:
             x5 = self.conv5(pf, xoff=0 if self.refine else 128)
             x6 = self.conv6(x5)
         return pf, E.mean_rows(x6.view(b, n, 1024))
+
+
+class FeatCache:
+    """What `_FeatPlan` keeps between calls that share `emb` and the weights: the point-feature buffers, whose emb-half columns
+    (e_conv1, e_conv2) the first call wrote.  Owned by the caller, who makes one per batch of objects and drops it with the batch."""
+    __slots__ = ("key", "pf", "pf_s32")
+
+    def __init__(self):
+        self.key, self.pf, self.pf_s32 = None, None, None
 
 
 class PoseNet(_HipModule):
@@ -601,13 +628,15 @@ class PoseRefineNet(_HipModule):
                  for h in "rt" for t in (sd[f"conv3_{h}.weight"], sd[f"conv3_{h}.bias"])]
         return pl
 
-    def forward_batch(self, points4, emb, obj):
-        """points4[B,N,4], emb[B,N,32], obj[B] -> out[B,8] (qw,qx,qy,qz,tx,ty,tz,0)"""
+    def forward_batch(self, points4, emb, obj, cache=None):
+        """points4[B,N,4], emb[B,N,32], obj[B] -> out[B,8] (qw,qx,qy,qz,tx,ty,tz,0).
+        cache: a `FeatCache` shared by the forwards of one object batch, which all see the same `emb` (the refinement iterations): the
+        emb half of the point features is computed by the first of them only.  Same output with and without."""
         pl = self.plan()
         for t, name in ((points4, "points"), (emb, "emb"), (obj, "obj")):
             _need_cuda(t, name)
         b = points4.shape[0]
-        _, ap = pl.feat(points4, emb)
+        _, ap = pl.feat(points4, emb, want_pf=False, cache=cache)      # (only the pooled feature is read: the fp32 pf is not asked for)
         h1 = pl.l1(ap.view(b, 1, 1, 1024))                                   # [B,1,1,1024]
         h2 = torch.empty(b, 1, 1, 256, dtype=torch.float32, device=points4.device)
         pl.l2[0](h1, out=h2, xoff=0, yoff=0)

@@ -26,6 +26,7 @@ SIGNATURES = {
     "ape_conv_gemm_bf16": [_P, _P, _P, _P, _P, _P, _I, _I, _P],
     "ape_pack_weights_s32k": [_P, _P, _I, _I, _P],
     "ape_convert_s32": [_P, _P, _c.c_long, _I, _I, _P],
+    "ape_point_feat_bf16": [_P] * 12 + [_c.c_long, _I, _I, _P],
     "ape_conv_gemm_s32_supported": [_P],
     "ape_conv_gemm_s32_debug": [_I],
     "ape_conv3x3_halo_s32_debug": [_I],
@@ -313,7 +314,7 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
 _lib = None
 
 
-ABI_VERSION = 20 # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 21 # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

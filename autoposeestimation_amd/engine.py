@@ -90,6 +90,7 @@ USE_CONV_MULTI = os.environ.get("APE_USE_CONV_MULTI", "1") != "0"     # the PSP 
 GEMM_VARIANT = int(os.environ.get("APE_GEMM_VARIANT", "0"))          # 0 = chosen from the shape; 1..4 force a block shape (tools/microbench_generic.py)
 USE_GEMM_ROWS = os.environ.get("APE_USE_GEMM_ROWS", "1") != "0"      # pure 1x1 layers of at most GEMM_ROWS_MAX_M rows take conv_rows_kernel (conv_gemm.hip variant 7); 0: the block shapes only (A/B)
 GEMM_ROWS_MAX_M = 128                                                # = ROWS_MAX_M of conv_gemm.hip
+USE_POINT_FEAT = os.environ.get("APE_USE_POINT_FEAT", "1") != "0"    # the point-feature front of the pose networks in one launch (point_feat.hip); 0: its five launches (A/B)
 
 
 FMT_F32, FMT_S32 = 0, 1
@@ -130,6 +131,44 @@ class S32:
         c = x.shape[-1]
         _lib.call.ape_convert_s32(_lib.dptr(x, torch.float32), _lib.dptr(y), x.numel() // c, c, 1, _st())
         return S32(y)
+
+
+PF_X, PF_EMB = 1, 2                    # APE_POINT_FEAT_X / _EMB: the halves of the point-feature front
+POINT_FEAT_LABEL = "point_feat_kernel"
+
+
+def point_feat(x4, emb, conv1, e_conv1, conv2, e_conv2, pf=None, pf_s32=None, parts=PF_X | PF_EMB):
+    """The front of PoseNetFeat / PoseRefineNetFeat in one launch (ape_point_feat_bf16): x4[..,4], emb[..,32] -> the rows
+    [conv1 64 | e_conv1 64 | conv2 128 | e_conv2 128] into pf ([..,384] f32) and / or pf_s32 (an `S32` of the same shape), whichever is
+    given; `parts` selects the x half, the emb half or both (the other half's columns are left as they are).  The layers are the `Conv`
+    objects of the five-launch route, in 'bf16x3'; every value is bit for bit what that route gives."""
+    layers = (conv1, e_conv1, conv2, e_conv2)
+    want = ((64, 4), (64, 32), (128, 64), (128, 64))
+    for c, (cout, cin) in zip(layers, want):
+        if (c.nsplit != 3 or (c.cout, c.cin, c.kh, c.kw) != (cout, cin, 1, 1) or c.stride != 1 or c.pad != 0 or c.act != ACT_RELU
+                or c.bias is None):
+            raise ValueError("point_feat needs the bf16x3 1x1 ReLU layers 4->64, 32->64, 64->128, 64->128 with biases")
+    if pf is None and pf_s32 is None:
+        raise ValueError("point_feat needs an output buffer")
+    m = x4.numel() // 4
+    if x4.shape[-1] != 4 or emb.shape[-1] != 32 or emb.numel() != m * 32:
+        raise ValueError("point_feat takes x4[..,4] and emb[..,32] of the same rows")
+    for t in (pf, None if pf_s32 is None else pf_s32.t):
+        if t is not None and (t.shape[-1] != 384 or t.numel() != m * 384):
+            raise ValueError("point_feat output buffer %s does not hold %d rows of 384" % (tuple(t.shape), m))
+    e0 = _prof_begin(POINT_FEAT_LABEL)
+    _lib.call.ape_point_feat_bf16(_lib.dptr(x4, torch.float32), _lib.dptr(emb, torch.float32),
+                                  _lib.dptr(conv1.wp), _lib.dptr(conv1.bias), _lib.dptr(e_conv1.wp), _lib.dptr(e_conv1.bias),
+                                  _lib.dptr(conv2.wp), _lib.dptr(conv2.bias), _lib.dptr(e_conv2.wp), _lib.dptr(e_conv2.bias),
+                                  _lib.dptr(pf, torch.float32), _lib.dptr(None if pf_s32 is None else pf_s32.t, torch.float32),
+                                  m, parts, 3, _st())
+    if e0 is not None:
+        cols = (192 if parts & PF_X else 0) + (192 if parts & PF_EMB else 0)
+        k = (4 * 64 + 64 * 128 if parts & PF_X else 0) + (32 * 64 + 64 * 128 if parts & PF_EMB else 0)
+        nout = (pf is not None) + (pf_s32 is not None)
+        _prof_end(e0, POINT_FEAT_LABEL, "%dx%d parts%d out%d" % (m, cols, parts, nout), 2.0 * m * k,
+                  4.0 * m * ((4 if parts & PF_X else 0) + (32 if parts & PF_EMB else 0) + cols * nout) + 4.0 * k)
+    return pf, pf_s32
 
 
 def pack_conv_weight(w, device):

@@ -121,6 +121,18 @@ int ape_conv_gemm_s32_per_image(const void* x_s32, const void* w_s32k, long w_im
                                 const ape_conv_params* params_host, void* stream);
 int ape_psp_fold_operands(const void* wf_s32k, const float* z1, const float* z2, const float* z3, const float* z6, void* w_out, void* x_s32,
                           int B, int h, int w, int ld, int Cin, int Cout, void* stream);
+/* ---- the point-feature front of the pose networks in one launch ----------------------------------------------------------------
+ * Replaces PoseNetFeat / PoseRefineNetFeat up to the concatenation (DenseFusion/lib/network.py:39-68,136-168): with ReLU after every layer
+ *   pf[m] = [conv1(x4[m]) 64 | e_conv1(emb[m]) 64 | conv2(conv1 out) 128 | e_conv2(e_conv1 out) 128],  x4[M][4], emb[M][32] f32,
+ * the weights as ape_pack_weights_bf16 packs them (conv1 from w[64][4], e_conv1 [64][32], conv2 / e_conv2 [128][64]) and the biases.
+ * Outputs, each optional (NULL = not written, at least one): pf[M][384] f32 and pf_s32, the same rows in the S32 layout.  parts selects
+ * the x half (conv1, conv2: columns 0..63, 128..255) and / or the emb half (e_conv1, e_conv2: 64..127, 256..383); the columns and operands
+ * of an unselected half are neither read nor written.  nsplit must be 3.  Every fp32 value and every S32 byte equals what
+ * ape_conv2d_nhwc_bf16 (conv1), ape_conv_gemm_bf16 (the other three) and ape_convert_s32 give in five launches. */
+enum { APE_POINT_FEAT_X = 1, APE_POINT_FEAT_EMB = 2 };
+int ape_point_feat_bf16(const float* x4, const float* emb, const void* w_conv1, const float* b_conv1, const void* w_e_conv1,
+                        const float* b_e_conv1, const void* w_conv2, const float* b_conv2, const void* w_e_conv2, const float* b_e_conv2,
+                        float* pf, void* pf_s32, long M, int parts, int nsplit, void* stream);
 /* Format-aware forms of three fp32 operations, for the tensors that cross between fp32 and S32 kernels: ape_conv_gemm_bf16 with the
  * OUTPUT in either format (the stride-2 convs that feed the first S32 3x3 layer), the multi-size adaptive average pool with the INPUT
  * in either format (ape_adaptive_avgpool_multi_nhwc_ld: the PSP pools of the S32 layer-4 map), ape_upconv3x3_gather_f32 with the OUTPUT
