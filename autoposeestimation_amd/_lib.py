@@ -129,15 +129,7 @@ SIGNATURES = {
     "ape_transform_points_batch_f64": [_I, _P, _P, _P, _P, _P],
     "ape_concat_points_batch_f64": [_I, _P, _P, _P, _P, _P, _P],
     "ape_icp_run_batch_f64": [_I, _I, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _D, _D, _D, _I, _I, _I, _P, _P, _P, _P, _P, _c.c_size_t, _P],
-    # global registration (csrc/registration.hip)
-    "ape_fpfh_workspace_bytes": [_I, _I],
-    "ape_fpfh_f64": [_P, _P, _P, _P, _I, _D, _P, _P, _D, _I, _P, _P, _c.c_size_t, _P],
-    "ape_feature_nn1_workspace_bytes": [_I, _I],
-    "ape_feature_nn1_f64": [_P, _I, _P, _I, _P, _P, _c.c_size_t, _P],
-    "ape_ransac_workspace_bytes": [_I, _I, _I],
-    "ape_ransac_hypotheses_f64": [_P, _I, _P, _I, _P, _I, _c.c_long, _D, _D, _I, _I, _I, _P, _P, _P, _c.c_size_t, _P],
-    "ape_ransac_validate_f64": [_P, _P, _P, _P, _I, _D, _P, _I, _P, _I, _P, _I, _c.c_long, _P, _I, _D, _P, _P, _P, _c.c_size_t, _P],
-    # their batched forms: per-pair arguments as host arrays of pointers / sizes, the pair's index in a grid dimension
+    # global registration (csrc/registration.hip): per-pair arguments as host arrays of pointers / sizes, the pair's index in a grid dimension
     "ape_fpfh_batch_workspace_bytes": [_I, _P, _I],
     "ape_fpfh_batch_f64": [_I, _P, _P, _P, _P, _P, _D, _P, _P, _D, _I, _P, _P, _c.c_size_t, _P],
     "ape_feature_nn1_batch_workspace_bytes": [_I, _P, _P],
@@ -294,7 +286,6 @@ ACT_NONE, ACT_RELU, ACT_PRELU, ACT_SIGMOID = 0, 1, 2, 3
 _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspace_bytes": _c.c_size_t, "ape_seg_components_workspace_bytes": _c.c_size_t,
              "ape_packed_weights_bf16_elems": _c.c_long, "ape_pc_batch_workspace_bytes": _c.c_size_t,
              "ape_conv2d_wgrad_workspace_bytes": _c.c_size_t, "ape_conv_gemm_splitk_workspace_bytes": _c.c_size_t,
-             "ape_fpfh_workspace_bytes": _c.c_size_t, "ape_feature_nn1_workspace_bytes": _c.c_size_t, "ape_ransac_workspace_bytes": _c.c_size_t,
              "ape_fpfh_batch_workspace_bytes": _c.c_size_t, "ape_feature_nn1_batch_workspace_bytes": _c.c_size_t,
              "ape_ransac_batch_workspace_bytes": _c.c_size_t, "ape_fgr_workspace_bytes": _c.c_size_t,
              "ape_bn_workspace_bytes": _c.c_size_t, "ape_jaccard_workspace_bytes": _c.c_size_t,
@@ -314,7 +305,7 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
 _lib = None
 
 
-ABI_VERSION = 21 # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 22 # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

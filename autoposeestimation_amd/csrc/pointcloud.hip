@@ -1386,7 +1386,7 @@ extern "C" int ape_icp_run_batch_f64(int kind, int nb, BGRID_ARGS, double* const
 
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The two steps of an ICP evaluation as calls of their own, for a loop that solves on the host (registration_icp(host_solve=True), the
+// The two steps of an ICP evaluation as calls of their own, for a loop that solves on the host (tests/icp_host_loop.py, the
 // LAPACK check of icp_step): the batch kernels above with ONE record and no state word -- same per-cloud grid sizes, same bits.
 extern "C" int ape_grid_nn1_f64(GRID_ARGS, const double* q, int nq, double max_dist, int* idx, double* dist2, void* stream)
 {

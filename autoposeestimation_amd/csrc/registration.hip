@@ -17,8 +17,8 @@
 // rounds of a 32-lane shuffle reduction over the candidate list -- is most of pass 1's time, and re-reading 1.2 KB per point is not.
 // Every kernel is written in the batched form of pointcloud.hip ("BATCHED forms"): a by-value table of up to kMaxBatch per-pair argument
 // records, the pair's index in a grid dimension, and a per-pair extent so that a block beyond its pair's extent exits.  A pair's blocks,
-// partial layouts and summation orders depend on that pair's sizes alone, so its result does not depend on its slot or its neighbours;
-// the one-pair entry points are nb = 1 callers of the same launch code.
+// partial layouts and summation orders depend on that pair's sizes alone, so its result does not depend on its slot or its neighbours.
+// There are no one-pair entry points: a single pair is a call with nb = 1.
 #include "common.h"
 #include "pc_grid.h"
 
@@ -814,7 +814,7 @@ int live_pairs(int nb, const int* ns, const int* nt)
     return live;
 }
 
-// ---- the launch code: nb records each, the one-pair entry points call it with nb = 1 ----------------------------------------------------
+// ---- the launch code behind the entry points: nb records each (a single pair or cloud is nb = 1) -----------------------------------------
 // both FPFH passes of nb clouds (g[c].n points each, 0: skipped); workspace: the clouds' fpfh_ws regions one after the other
 int fpfh_launch(int nb, const Grid* g, const double* const* pts, const double* const* nrm, double radius, int max_nn, double* const* feature,
                 void* ws, size_t ws_bytes, hipStream_t st, const char* what)
@@ -934,18 +934,6 @@ size_t fgr_ws(int chunk)
 
 #define APE_BATCH_CHECK(nb) if ((nb) < 1 || (nb) > kMaxBatch) return APE_EINVAL
 
-extern "C" size_t ape_fpfh_workspace_bytes(int n, int max_nn) { return fpfh_ws(n, max_nn); }
-
-extern "C" int ape_fpfh_f64(GRID_ARGS, const double* pts, const double* normals, double radius, int max_nn, double* feature, void* ws,
-                            size_t ws_bytes, void* stream)
-{
-    if (!sorted || !keys || !order || !origin3 || !pts || !normals || !feature || !ws || n < 1 || !(radius > 0) || radius > cell ||
-        max_nn < 1 || max_nn > kFeatMaxNN)
-        return APE_EINVAL;
-    MAKE_GRID;
-    return fpfh_launch(1, &g, &pts, &normals, radius, max_nn, &feature, ws, ws_bytes, (hipStream_t)stream, "ape_fpfh_f64");
-}
-
 extern "C" size_t ape_fpfh_batch_workspace_bytes(int nb, const int* n_host, int max_nn)
 {
     size_t s = 0;
@@ -968,15 +956,6 @@ extern "C" int ape_fpfh_batch_f64(int nb, BGRID_ARGS, const double* const* pts, 
     return fpfh_launch(nb, g, pts, normals, radius, max_nn, feature, ws, ws_bytes, (hipStream_t)stream, "ape_fpfh_batch_f64");
 }
 
-extern "C" size_t ape_feature_nn1_workspace_bytes(int ns, int nt) { return nn_ws(ns, nt, 1); }
-
-extern "C" int ape_feature_nn1_f64(const double* src_feature, int ns, const double* tgt_feature, int nt, int* nn, void* ws, size_t ws_bytes,
-                                   void* stream)
-{
-    if (!src_feature || !tgt_feature || !nn || !ws || ns < 0 || nt < 1) return APE_EINVAL;
-    return nn_launch(1, &src_feature, &ns, &tgt_feature, &nt, &nn, ws, ws_bytes, (hipStream_t)stream, "ape_feature_nn1_f64");
-}
-
 extern "C" size_t ape_feature_nn1_batch_workspace_bytes(int nb, const int* ns_host, const int* nt_host)
 {
     if (!ns_host || !nt_host || nb < 1 || nb > kMaxBatch) return 0;
@@ -996,19 +975,6 @@ extern "C" int ape_feature_nn1_batch_f64(int nb, const double* const* src_featur
         if (ns[c] > 0 && nt[c] > 0 && (!src_feature[c] || !tgt_feature[c] || !nn[c] || !ws)) return APE_EINVAL;
     }
     return nn_launch(nb, src_feature, ns, tgt_feature, nt, nn, ws, ws_bytes, (hipStream_t)stream, "ape_feature_nn1_batch_f64");
-}
-
-extern "C" size_t ape_ransac_workspace_bytes(int ns, int chunk, int max_validation) { return ransac_ws(ns, chunk, max_validation); }
-
-extern "C" int ape_ransac_hypotheses_f64(const double* src, int ns, const double* tgt, int nt, const int* nn, int ransac_n, long seed,
-                                         double edge_sim, double dist_thr, int it_begin, int n_it, int max_validation, int* kept, int* n_kept,
-                                         void* ws, size_t ws_bytes, void* stream)
-{
-    if (!src || !tgt || !nn || !kept || !n_kept || !ws || ns < 1 || nt < 1 || ransac_n < 3 || ransac_n > kMaxRansacN || it_begin < 0 ||
-        n_it < 0 || max_validation < 1)
-        return APE_EINVAL;
-    const Hyp h{src, ns, tgt, nt, nn, ransac_n, (u64)seed, edge_sim, dist_thr};
-    return hyp_launch(1, &h, it_begin, n_it, max_validation, &kept, &n_kept, ws, ws_bytes, (hipStream_t)stream, "ape_ransac_hypotheses_f64");
 }
 
 extern "C" size_t ape_ransac_batch_workspace_bytes(int nb, const int* ns_host, int chunk, int max_validation)
@@ -1037,18 +1003,6 @@ extern "C" int ape_ransac_hypotheses_batch_f64(int nb, const double* const* src,
         np[c] = n_kept + c;
     }
     return hyp_launch(nb, h, it_begin, n_it, max_validation, kp, np, ws, ws_bytes, (hipStream_t)stream, "ape_ransac_hypotheses_batch_f64");
-}
-
-extern "C" int ape_ransac_validate_f64(GRID_ARGS, const double* src, int ns, const double* tgt, int nt, const int* nn, int ransac_n,
-                                       long seed, const int* kept, int n_kept, double max_dist, double* result, double* fit_rmse,
-                                       void* ws, size_t ws_bytes, void* stream)
-{
-    if (!sorted || !keys || !order || !origin3 || !src || !tgt || !nn || !result || !ws || n < 1 || ns < 1 || nt != n || ransac_n < 3 ||
-        ransac_n > kMaxRansacN || n_kept < 0 || n_kept > 65535 || (n_kept > 0 && !kept) || !(max_dist > 0) || max_dist > cell)
-        return APE_EINVAL;
-    MAKE_GRID;
-    const Hyp h{src, ns, tgt, nt, nn, ransac_n, (u64)seed, -1.0, -1.0};
-    return validate_launch(1, &g, &h, &kept, &n_kept, max_dist, result, &fit_rmse, ws, ws_bytes, (hipStream_t)stream, "ape_ransac_validate_f64");
 }
 
 extern "C" int ape_ransac_validate_batch_f64(int nb, BGRID_ARGS, const double* const* src, const int* ns, const double* const* tgt, const int* nt,

@@ -14,8 +14,9 @@ implementation: the methods of `PointCloud` and `pointcloud.registration_icp` ca
 The global registration that `global_regression=True` puts in front of every ICP (reference open3d_utils.py:19-49) advances in lock step
 too: `compute_fpfh_feature`, `feature_nn` and `registration_ransac` below take lists of clouds / pairs and drive the batched entry points
 of csrc/registration.hip (two FPFH launches for all clouds, one hypothesis chunk for every pair that is not yet full, one copy of all
-`n_kept` words per chunk, one validation for all pairs).  `pointcloud.registration_ransac_based_on_feature_matching` stays the one-pair
-reference of it (the same kernels launched with nb = 1); tests/test_gpu_registration_batch.py compares the two bit for bit.
+`n_kept` words per chunk, one validation for all pairs).  They are the only implementation as well: `pointcloud.compute_fpfh_feature`,
+`feature_nn` and `registration_ransac_based_on_feature_matching` call them with one-element lists (tests/test_gpu_registration_batch.py
+compares a pair in a batch with the same pair as a batch of one, bit for bit).
 `registration_fast` is fast global registration on the same features (mutual matches, tuple test, one optimisation launch per batch); its
 one-pair form `pointcloud.registration_fast_based_on_feature_matching` is a batch of one.
 """
@@ -562,8 +563,8 @@ def registration_ransac(sources, targets, source_features, target_features, max_
             _lib.call.ape_ransac_hypotheses_batch_f64(nb, *pair, edge_sim, dist_thr, it, c, max_val, _lib.dptr(kept), _lib.dptr(n_kept),
                                                       _lib.dptr(ws), ws.numel(), _st())
             it += c
-            k = n_kept.cpu().numpy()                     # ONE copy of all pairs' counters per chunk
-            if (k >= max_val).all():
+            k = n_kept.tolist()                          # ONE copy of all pairs' counters per chunk (plain ints: the GPU idles while the host decides)
+            if min(k) >= max_val:
                 break
             chunk = min(chunk * 2, cap)
         res = torch.empty(nb, 24, dtype=_D, device=dev)
@@ -571,7 +572,7 @@ def registration_ransac(sources, targets, source_features, target_features, max_
                                                 max_dist, _lib.dptr(res), None, _lib.dptr(ws), ws.numel(), _st())
         r_all, kept_all = res.cpu().numpy(), kept.cpu().numpy()
         for m, i in enumerate(sel):
-            r, km = r_all[m], int(k[m])
+            r, km = r_all[m], k[m]
             o = PC.RegistrationResult(r[:16].reshape(4, 4).copy(), float(r[16]), float(r[17]), int(round(r[18])))
             o.validated = kept_all[m, :km].astype(np.int64)
             o.iterations = int(o.validated[-1]) + 1 if km >= max_val else it
@@ -672,11 +673,21 @@ def registration_fast(sources, targets, source_features, target_features, option
     return out
 
 
-def execute_fast_global_registration_batch(sources_down, targets_down, voxel_size):
-    """[open3d_utils.execute_fast_global_registration(s, t, None, None, voxel_size)]: FPFH (radius 5 * voxel, max_nn 100) of all clouds,
-    then fast global registration with maximum_correspondence_distance 0.5 * voxel and the other defaults"""
+def _recipe_features(clouds, features, voxel_size):
+    """the FPFH of both global-registration recipes (radius 5 * voxel, max_nn 100) for every cloud whose entry of `features` is None"""
+    feats = list(features)
+    missing = [i for i, f in enumerate(feats) if f is None]
+    for i, f in zip(missing, compute_fpfh_feature([clouds[i] for i in missing], voxel_size * 5, 100)):
+        feats[i] = f
+    return feats
+
+
+def execute_fast_global_registration_batch(sources_down, targets_down, voxel_size, source_features=None, target_features=None):
+    """The open3d tutorial's fast global registration in execute_global_registration_batch's place, and the one definition of that recipe
+    (open3d_utils.execute_fast_global_registration is this with one pair): FPFH of all clouds (a feature that is given is used, a None one
+    computed), then registration_fast with maximum_correspondence_distance 0.5 * voxel and the other defaults"""
     n = len(sources_down)
-    feats = compute_fpfh_feature(list(sources_down) + list(targets_down), voxel_size * 5, 100)
+    feats = _recipe_features(list(sources_down) + list(targets_down), list(source_features or [None] * n) + list(target_features or [None] * n), voxel_size)
     opt = PC.FastGlobalRegistrationOption(maximum_correspondence_distance=voxel_size * 0.5)
     return registration_fast(sources_down, targets_down, feats[:n], feats[n:], [opt] * n)
 
@@ -689,12 +700,13 @@ def _global_registration_batch(method):
     raise ValueError("global_method must be 'ransac' or 'fgr', not %r" % (method,))
 
 
-def execute_global_registration_batch(sources_down, targets_down, voxel_size):
-    """[open3d_utils.execute_global_registration(s, t, None, None, voxel_size)] (reference :28-49): FPFH (radius 5 * voxel, max_nn 100) of
-    all clouds, then RANSAC on the feature matches: distance 1.5 * voxel, ransac_n 4, edge length 0.9, 4 000 000 iterations / 500
+def execute_global_registration_batch(sources_down, targets_down, voxel_size, source_features=None, target_features=None):
+    """Reference open3d_utils.py:28-49 for pairs advancing together, and the one definition of that recipe
+    (open3d_utils.execute_global_registration is this with one pair): FPFH of all clouds (a feature that is given is used, a None one
+    computed), then RANSAC on the feature matches: distance 1.5 * voxel, ransac_n 4, edge length 0.9, 4 000 000 iterations / 500
     validations, seed 0"""
     n = len(sources_down)
-    feats = compute_fpfh_feature(list(sources_down) + list(targets_down), voxel_size * 5, 100)
+    feats = _recipe_features(list(sources_down) + list(targets_down), list(source_features or [None] * n) + list(target_features or [None] * n), voxel_size)
     thr = voxel_size * 1.5
     return registration_ransac(sources_down, targets_down, feats[:n], feats[n:], thr, 4, 0.9, thr, PC.RANSACConvergenceCriteria(4000000, 500), [0] * n)
 

@@ -51,6 +51,7 @@ def get_my_source_center(source):
 
 
 # ---- the open3d-backed half, on the gfx950 point-cloud kernels ----------------------------
+from autoposeestimation_amd.pc_reconstruction import batched as _batched  # noqa: E402
 from autoposeestimation_amd.pc_reconstruction import pointcloud as _pc  # noqa: E402
 
 
@@ -67,31 +68,16 @@ def preprocess_point_cloud(pcd, voxel_size):
 def execute_global_registration(source_down, target_down, source_fpfh, target_fpfh, voxel_size):
     """reference :36-49: RANSAC on FPFH matches, distance threshold 1.5 * voxel, ransac_n 4, edge-length (0.9) and distance checkers,
     4 000 000 iterations / 500 validations.  A None feature is computed here (radius 5 * voxel, max_nn 100, as :28-32), so
-    reference-shaped code that passes preprocess_point_cloud's features works.  Seeded and reproducible (pointcloud.
-    registration_ransac_based_on_feature_matching)."""
-    distance_threshold = voxel_size * 1.5
-    param = _pc.KDTreeSearchParamHybrid(radius=voxel_size * 5, max_nn=100)
-    if source_fpfh is None:
-        source_fpfh = _pc.compute_fpfh_feature(source_down, param)
-    if target_fpfh is None:
-        target_fpfh = _pc.compute_fpfh_feature(target_down, param)
-    return _pc.registration_ransac_based_on_feature_matching(
-        source_down, target_down, source_fpfh, target_fpfh, distance_threshold, _pc.TransformationEstimationPointToPoint(False), 4,
-        [_pc.CorrespondenceCheckerBasedOnEdgeLength(0.9), _pc.CorrespondenceCheckerBasedOnDistance(distance_threshold)],
-        _pc.RANSACConvergenceCriteria(4000000, 500))
+    reference-shaped code that passes preprocess_point_cloud's features works.  Seeded and reproducible.  The recipe itself is stated once,
+    in batched.execute_global_registration_batch: this is that function with one pair."""
+    return _batched.execute_global_registration_batch([source_down], [target_down], voxel_size, [source_fpfh], [target_fpfh])[0]
 
 
 def execute_fast_global_registration(source_down, target_down, source_fpfh, target_fpfh, voxel_size):
     """The open3d tutorial's fast global registration in execute_global_registration's place: FastGlobalRegistrationOption with
     maximum_correspondence_distance = 0.5 * voxel on the same FPFH features (a None feature is computed here, radius 5 * voxel, max_nn
-    100).  Seeded and reproducible (pointcloud.registration_fast_based_on_feature_matching)."""
-    param = _pc.KDTreeSearchParamHybrid(radius=voxel_size * 5, max_nn=100)
-    if source_fpfh is None:
-        source_fpfh = _pc.compute_fpfh_feature(source_down, param)
-    if target_fpfh is None:
-        target_fpfh = _pc.compute_fpfh_feature(target_down, param)
-    return _pc.registration_fast_based_on_feature_matching(
-        source_down, target_down, source_fpfh, target_fpfh, _pc.FastGlobalRegistrationOption(maximum_correspondence_distance=voxel_size * 0.5))
+    100).  Seeded and reproducible.  batched.execute_fast_global_registration_batch with one pair."""
+    return _batched.execute_fast_global_registration_batch([source_down], [target_down], voxel_size, [source_fpfh], [target_fpfh])[0]
 
 
 def _global_registration(method):

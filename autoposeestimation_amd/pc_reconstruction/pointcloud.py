@@ -7,7 +7,6 @@ scipy/numpy restatement (oracle/pointcloud_oracle.py) plus recover-a-known-trans
 Points live on the GPU as a contiguous float64 [n,3] tensor; `np.array(pcd.points)` / `np.asarray(pcd.points)` copies to
 the host like open3d's Vector3dVector does; assigning `pcd.points = array` uploads.  No CPU fallback."""
 import threading
-import math
 import os
 
 import numpy as np
@@ -16,10 +15,6 @@ import torch
 from autoposeestimation_amd import _lib
 
 _D = torch.float64
-
-
-def _st():
-    return _lib.stream_ptr()
 
 
 class _Points:
@@ -196,102 +191,26 @@ class RegistrationResult:
                                                                                            self.correspondence_count)
 
 
-def _umeyama(s):
-    """Eigen::umeyama(src, dst, with_scaling=false) from the one-pass sums s[17]."""
-    n = s[0]
-    mu_s, mu_t = s[2:5] / n, s[5:8] / n
-    cov = s[8:17].reshape(3, 3).T / n - np.outer(mu_t, mu_s)        # (1/n) sum (t - mu_t)(s - mu_s)^T
-    U, d, Vt = np.linalg.svd(cov)
-    S = np.eye(3)
-    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
-        S[2, 2] = -1
-    R = U @ S @ Vt
-    T = np.eye(4)
-    T[:3, :3] = R
-    T[:3, 3] = mu_t - R @ mu_s
-    return T
-
-
-def _vec6_to_mat4(x):
-    """open3d TransformVector6dToMatrix4d: R = Rz(x[2]) Ry(x[1]) Rx(x[0]), t = x[3:6]"""
-    cx, sx, cy, sy, cz, sz = math.cos(x[0]), math.sin(x[0]), math.cos(x[1]), math.sin(x[1]), math.cos(x[2]), math.sin(x[2])
-    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
-    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
-    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
-    T = np.eye(4)
-    T[:3, :3] = Rz @ Ry @ Rx
-    T[:3, 3] = x[3:6]
-    return T
-
-
-def _point_to_plane(s):
-    JTJ = np.zeros((6, 6))
-    k = 2
-    for a in range(6):
-        for b in range(a, 6):
-            JTJ[a, b] = JTJ[b, a] = s[k]
-            k += 1
-    JTr = s[23:29]
-    try:
-        x = np.linalg.solve(JTJ, -JTr)
-    except np.linalg.LinAlgError:
-        return np.eye(4)
-    return _vec6_to_mat4(x)
-
-
 ICP_STATS = None          # bench.py --workload label sets a dict here: registrations, evaluations, point pairs, (start, end) events
 _ICP_STATS_LOCK = threading.Lock()     # registrations of different chains run on different host threads (sharding.run_side_by_side)
 _ICP_CHUNK = 5            # batched.icp_states: iterations enqueued per device round trip (3 launches each); the reference's criteria (1e-2) stop after 2-4
 
 
-def registration_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None, host_solve=False):
+def registration_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None):
     """open3d 0.9 registration::RegistrationICP (call sites open3d_utils.py:56-58,98-117).  The source cloud is NOT
     modified (open3d works on a transformed copy).  The whole iteration -- correspondence search, the 17/29 reduced sums, the
     3x3 SVD / 6x6 solve, T <- update . T and the convergence test -- runs on the device (batched.icp_states with this one pair): a chunk of
     iterations is enqueued at once, launches after convergence are no-ops, and the 40-double state comes back once per chunk (normally once
-    per registration).  `host_solve=True` keeps the round-1 loop (numpy SVD / solve, one D2H per iteration) for the parity tests."""
+    per registration).  (The round-1 loop with the numpy SVD / solve on the host lives on as the parity reference tests/icp_host_loop.py.)"""
     estimation_method = estimation_method or TransformationEstimationPointToPoint()
     criteria = criteria or ICPConvergenceCriteria()
     T = np.eye(4) if init is None else np.array(init, dtype=np.float64)
-    ns, nt = len(source), len(target)
-    if ns == 0 or nt == 0:
+    if len(source) == 0 or len(target) == 0:
         return RegistrationResult(T, 0.0, 0.0, 0)
     if estimation_method.kind == 1 and not target.has_normals():
         raise RuntimeError("TransformationEstimationPointToPlane requires target normals")
-    if not host_solve:
-        out = _B.icp_states([source], [target], max_correspondence_distance, [T], estimation_method.kind, criteria)[0]
-        return RegistrationResult(out[5:21].reshape(4, 4).copy(), float(out[2]), float(out[3]), int(out[4]))
-    dev = source.device
-    pcd = source.clone().transform(T)
-    grid = target._grid(max_correspondence_distance)
-    corr = torch.empty(ns, dtype=torch.int32, device=dev)
-    d2 = torch.empty(ns, dtype=_D, device=dev)
-    sums = torch.empty(29, dtype=_D, device=dev)
-    ws = torch.empty(512 * 29 * 8, dtype=torch.uint8, device=dev)
-
-    def evaluate():
-        _lib.call.ape_grid_nn1_f64(*PointCloud._gargs(grid), _lib.dptr(pcd._p, _D), ns, float(max_correspondence_distance),
-                                   _lib.dptr(corr), _lib.dptr(d2), _st())
-        _lib.call.ape_icp_sums_f64(estimation_method.kind, _lib.dptr(pcd._p, _D), _lib.dptr(target._p, _D), _lib.dptr(target._n),
-                                   _lib.dptr(corr), _lib.dptr(d2), ns, _lib.dptr(sums), _lib.dptr(ws), ws.numel(), _st())
-        s = sums.cpu().numpy()
-        n_corr = int(round(s[0]))
-        fitness = n_corr / ns
-        rmse = math.sqrt(s[1] / n_corr) if n_corr else 0.0
-        return s, n_corr, fitness, rmse
-
-    s, n_corr, fitness, rmse = evaluate()
-    for _ in range(criteria.max_iteration):
-        if n_corr < (3 if estimation_method.kind == 0 else 6):
-            break
-        update = _umeyama(s) if estimation_method.kind == 0 else _point_to_plane(s)
-        T = update @ T
-        pcd.transform(update)
-        prev_f, prev_r = fitness, rmse
-        s, n_corr, fitness, rmse = evaluate()
-        if abs(prev_f - fitness) < criteria.relative_fitness and abs(prev_r - rmse) < criteria.relative_rmse:
-            break
-    return RegistrationResult(T, fitness, rmse, n_corr)
+    out = _B.icp_states([source], [target], max_correspondence_distance, [T], estimation_method.kind, criteria)[0]
+    return RegistrationResult(out[5:21].reshape(4, 4).copy(), float(out[2]), float(out[3]), int(out[4]))
 
 
 # ---- global registration: FPFH + RANSAC on feature matches (reference open3d_utils.py:19-49; csrc/registration.hip) ------------------
@@ -314,20 +233,8 @@ class Feature:
 
 def compute_fpfh_feature(pcd, search_param):
     """open3d 0.9 registration::ComputeFPFHFeature with KDTreeSearchParamHybrid(radius, max_nn <= 128); the cloud needs normals.
-    The neighbour list of a point is every point with d^2 < radius^2, ordered by (d^2, index), first max_nn (ape_fpfh_f64)."""
-    n = len(pcd)
-    if n == 0:
-        return Feature(device=pcd.device)
-    if not pcd.has_normals():
-        raise RuntimeError("compute_fpfh_feature requires normals (estimate_normals first)")
-    radius, max_nn = float(search_param.radius), int(search_param.max_nn)
-    g = pcd._grid(radius)
-    out = torch.empty(n, 33, dtype=_D, device=pcd.device)
-    L = _lib.lib()
-    ws = torch.empty(L.ape_fpfh_workspace_bytes(n, max_nn), dtype=torch.uint8, device=pcd.device)
-    _lib.call.ape_fpfh_f64(*PointCloud._gargs(g), _lib.dptr(pcd._p, _D), _lib.dptr(pcd._n, _D), radius, max_nn, _lib.dptr(out),
-                           _lib.dptr(ws), ws.numel(), _st())
-    return Feature(out)
+    The neighbour list of a point is every point with d^2 < radius^2, ordered by (d^2, index), first max_nn (ape_fpfh_batch_f64)."""
+    return _B.compute_fpfh_feature([pcd], search_param.radius, search_param.max_nn)[0]
 
 
 class RANSACConvergenceCriteria:
@@ -350,16 +257,7 @@ _RANSAC_CHUNK = (1 << 14, 1 << 20)   # iterations of the first hypothesis chunk,
 
 def feature_nn(source_feature, target_feature):
     """index of the nearest target feature of every source feature (squared L2 over the 33 dimensions, ties -> lowest index)"""
-    ns, nt = source_feature.num(), target_feature.num()
-    dev = source_feature.t.device
-    nn = torch.empty(ns, dtype=torch.int32, device=dev)
-    if ns == 0 or nt == 0:
-        return nn.fill_(-1)
-    L = _lib.lib()
-    ws = torch.empty(L.ape_feature_nn1_workspace_bytes(ns, nt), dtype=torch.uint8, device=dev)
-    _lib.call.ape_feature_nn1_f64(_lib.dptr(source_feature.t.contiguous(), _D), ns, _lib.dptr(target_feature.t.contiguous(), _D), nt,
-                                  _lib.dptr(nn), _lib.dptr(ws), ws.numel(), _st())
-    return nn
+    return _B.feature_nn([source_feature], [target_feature])[0]
 
 
 def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature, max_correspondence_distance,
@@ -389,48 +287,8 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
             dist_thr = float(c.distance_threshold) if dist_thr < 0 else min(dist_thr, float(c.distance_threshold))
         else:
             raise NotImplementedError("correspondence checker %s" % type(c).__name__)
-    empty = RegistrationResult(np.eye(4), 0.0, 0.0, 0)
-    empty.validated, empty.iterations = np.zeros(0, np.int64), 0
-    ransac_n, max_dist = int(ransac_n), float(max_correspondence_distance)
-    if ransac_n < 3 or max_dist <= 0.0:
-        return empty
-    if ransac_n > 16:
-        raise ValueError("ransac_n > 16 is not supported")
-    ns, nt = len(source), len(target)
-    if source_feature.num() != ns or target_feature.num() != nt:
-        raise ValueError("features and clouds differ in size")
-    max_it, max_val = int(criteria.max_iteration), int(criteria.max_validation)
-    if max_val > 65535:
-        raise ValueError("max_validation > 65535 is not supported")
-    if ns == 0 or nt == 0 or max_it <= 0 or max_val <= 0:
-        return empty
-    dev = source.device
-    L = _lib.lib()
-    nn = feature_nn(source_feature, target_feature)
-    chunk, cap = min(_RANSAC_CHUNK[0], max_it), min(_RANSAC_CHUNK[1], max_it)
-    ws = torch.empty(L.ape_ransac_workspace_bytes(ns, max(chunk, cap), max_val), dtype=torch.uint8, device=dev)
-    kept = torch.empty(max_val, dtype=torch.int32, device=dev)
-    n_kept = torch.zeros(1, dtype=torch.int32, device=dev)
-    src, tgt = _lib.dptr(source._p, _D), _lib.dptr(target._p, _D)
-    it, k = 0, 0
-    while it < max_it:                                  # bounded by max_iteration; the device list stops growing once full
-        c = min(chunk, max_it - it)
-        _lib.call.ape_ransac_hypotheses_f64(src, ns, tgt, nt, _lib.dptr(nn), ransac_n, int(seed), edge_sim, dist_thr, it, c, max_val,
-                                            _lib.dptr(kept), _lib.dptr(n_kept), _lib.dptr(ws), ws.numel(), _st())
-        it += c
-        k = int(n_kept.item())
-        if k >= max_val:
-            break
-        chunk = min(chunk * 2, cap)
-    grid = target._grid(max_dist)
-    out = torch.empty(24, dtype=_D, device=dev)
-    _lib.call.ape_ransac_validate_f64(*PointCloud._gargs(grid), src, ns, tgt, nt, _lib.dptr(nn), ransac_n, int(seed), _lib.dptr(kept), k,
-                                      max_dist, _lib.dptr(out), None, _lib.dptr(ws), ws.numel(), _st())
-    r = out.cpu().numpy()
-    res = RegistrationResult(r[:16].reshape(4, 4).copy(), float(r[16]), float(r[17]), int(round(r[18])))
-    res.validated = kept[:k].cpu().numpy().astype(np.int64)
-    res.iterations = int(res.validated[-1]) + 1 if k >= max_val else it
-    return res
+    return _B.registration_ransac([source], [target], [source_feature], [target_feature], max_correspondence_distance, ransac_n,
+                                  edge_sim if edge_sim >= 0 else None, dist_thr if dist_thr >= 0 else None, criteria, [seed])[0]
 
 
 # ---- fast global registration on the same features (Zhou, Park, Koltun, ECCV 2016; csrc/registration.hip fgr_*) ----------------------

@@ -482,63 +482,46 @@ int ape_icp_run_batch_f64(int kind, int nb, const double* const* sorted, const u
 
 /* ---- global registration (reference pc_reconstruction/open3d_utils.py:19-49; open3d 0.9 compute_fpfh_feature and
  * registration_ransac_based_on_feature_matching), float64, autoposeestimation_amd/csrc/registration.hip ----------------------------
- * Workspace of ape_fpfh_f64 for a cloud of n points and the given max_nn. */
-size_t ape_fpfh_workspace_bytes(int n, int max_nn);
-/* FPFH feature[n][33] of a cloud with normals (pts / normals [n][3] in the cloud's own order) through its search grid (one cloud's buffers of
- * ape_grid_build_batch_f64 over the same n points, cell >= radius): hybrid neighbour list d^2 < radius^2, ordered by (d^2, index), first max_nn
- * (<= 128); SPFH over the list without its entry 0, then FPFH = per 11-bin block normalised sum_k SPFH_k / d^2_k (d^2 != 0) + SPFH_i.
- * Points with at most one list entry get zeros.  Two launches. */
-int ape_fpfh_f64(const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n, double cell,
-                 const double* pts, const double* normals, double radius, int max_nn, double* feature, void* ws, size_t ws_bytes, void* stream);
-size_t ape_feature_nn1_workspace_bytes(int ns, int nt);
-/* nn[s] = argmin_t sum_j (src_feature[s][j] - tgt_feature[t][j])^2 over the 33 dimensions in j order, fp64, ties -> lowest t. */
-int ape_feature_nn1_f64(const double* src_feature, int ns, const double* tgt_feature, int nt, int* nn, void* ws, size_t ws_bytes, void* stream);
-/* Workspace of the two RANSAC calls below: hypotheses in chunks of up to `chunk` iterations, up to max_validation kept. */
-size_t ape_ransac_workspace_bytes(int ns, int chunk, int max_validation);
-/* RANSAC iterations [it_begin, it_begin + n_it): iteration i draws source s_j = splitmix64(((uint64_t)seed << 32) ^ (i * ransac_n + j)) mod ns,
- * j < ransac_n (3..16), pairs it with nn[s_j], runs the edge-length checker (edge_sim < 0: none), Umeyama without scaling and the
- * distance checker (dist_thr < 0: none).  The passing iteration indices are appended IN ITERATION ORDER to kept[*n_kept ..] until
- * max_validation are kept (kept / n_kept on the device, the caller zeroes *n_kept before the first chunk; a full list makes the call
- * a no-op).  Two launches. */
-int ape_ransac_hypotheses_f64(const double* src, int ns, const double* tgt, int nt, const int* nn, int ransac_n, long seed,
-                              double edge_sim, double dist_thr, int it_begin, int n_it, int max_validation, int* kept, int* n_kept, void* ws,
-                              size_t ws_bytes, void* stream);
-/* Validation of the n_kept (host count, <= 65535) kept iterations: each one's transformation recomputed, every source point moved by it
- * and matched to its nearest target within max_dist (d^2 < max_dist^2; the GRID args are the target's, cell >= max_dist, n = nt);
- * fitness = count / ns, rmse = sqrt(sum d^2 / count) (0 without matches), fixed-order sums.  result[24] on the device: [0..15] the
- * winner's 4x4 (row major), [16] fitness, [17] rmse, [18] correspondences, [19] its position in kept, [20] its iteration (-1 / -1 and
- * the identity with fitness 0 when nothing is better than that); the winner has the highest fitness, then the lowest rmse, then the
- * lowest iteration.  fit_rmse (optional, [n_kept][3] on the device): fitness, rmse, correspondences of every kept iteration. */
-int ape_ransac_validate_f64(const double* sorted, const unsigned long long* keys, const unsigned* order, const double* origin3, int n,
-                            double cell, const double* src, int ns, const double* tgt, int nt, const int* nn, int ransac_n,
-                            long seed, const int* kept, int n_kept, double max_dist, double* result, double* fit_rmse,
-                            void* ws, size_t ws_bytes, void* stream);
-/* The four calls above for nb = 1..16 clouds / pairs per launch (APE_EINVAL otherwise): the kernels take a by-value table of per-pair
- * records and the pair's index in a grid dimension, the one-pair calls above are their nb = 1 callers.  Per-pair arguments are HOST arrays
- * [nb] of device pointers / sizes (as the `*_batch_f64` point-cloud calls); a pair's result is bit-identical to the one-pair call of it
- * and does not depend on its slot or its neighbours.  Workspaces: the pairs' one-pair regions one after the other.
- * FPFH of nb clouds in two launches; a cloud with gn[c] == 0 is skipped. */
+ * Every call takes nb = 1..16 clouds / pairs per launch (APE_EINVAL otherwise); a single cloud or pair is a call with nb = 1, there are no
+ * one-pair entry points.  The kernels take a by-value table of per-pair records and the pair's index in a grid dimension.  Per-pair
+ * arguments are HOST arrays [nb] of device pointers / sizes (as the `*_batch_f64` point-cloud calls); a pair's result depends on that
+ * pair alone, not on its slot or its neighbours.  Workspaces: the pairs' own regions one after the other.
+ * FPFH feature[c][n][33] of nb clouds with normals (pts[c] / normals[c] [n][3] in the cloud's own order) through their search grids (the
+ * buffers of ape_grid_build_batch_f64 over the same points, gn[c] points, cell >= radius): hybrid neighbour list d^2 < radius^2, ordered by
+ * (d^2, index), first max_nn (<= 128); SPFH over the list without its entry 0, then FPFH = per 11-bin block normalised
+ * sum_k SPFH_k / d^2_k (d^2 != 0) + SPFH_i.  Points with at most one list entry get zeros.  Two launches; a cloud with gn[c] == 0 is
+ * skipped.  Workspace: for n_host[nb] points per cloud and the given max_nn. */
 size_t ape_fpfh_batch_workspace_bytes(int nb, const int* n_host, int max_nn);
 int ape_fpfh_batch_f64(int nb, const double* const* sorted, const unsigned long long* const* keys, const unsigned* const* order,
                        const double* const* origin3, const int* gn, double cell, const double* const* pts, const double* const* normals,
                        double radius, int max_nn, double* const* feature, void* ws, size_t ws_bytes, void* stream);
-/* Nearest target feature for nb (source, target) feature pairs in two launches; a pair with ns[c] == 0 or nt[c] == 0 is skipped (its nn
- * is not written).  The target range of a pair is cut into slices so that the whole launch has about 2048 blocks. */
+/* Nearest target feature for nb (source, target) feature pairs in two launches: nn[c][s] = argmin_t sum_j (src_feature[c][s][j] -
+ * tgt_feature[c][t][j])^2 over the 33 dimensions in j order, fp64, ties -> lowest t.  A pair with ns[c] == 0 or nt[c] == 0 is skipped (its
+ * nn is not written).  The target range of a pair is cut into slices so that the whole launch has about 2048 blocks. */
 size_t ape_feature_nn1_batch_workspace_bytes(int nb, const int* ns_host, const int* nt_host);
 int ape_feature_nn1_batch_f64(int nb, const double* const* src_feature, const int* ns, const double* const* tgt_feature, const int* nt,
                               int* const* nn, void* ws, size_t ws_bytes, void* stream);
-/* Workspace of the two batched RANSAC calls below (ns_host[nb] source sizes). */
+/* Workspace of the two RANSAC calls below (ns_host[nb] source sizes): hypotheses in chunks of up to `chunk` iterations, up to
+ * max_validation kept per pair. */
 size_t ape_ransac_batch_workspace_bytes(int nb, const int* ns_host, int chunk, int max_validation);
-/* Iterations [it_begin, it_begin + n_it) for every pair whose list is not yet full: pair c draws with seed_host[c] and appends to
- * kept[c * max_validation ..] / n_kept[c] (device, n_kept zeroed by the caller before the first chunk); a pair whose n_kept[c] has
- * reached max_validation turns its blocks into no-ops by reading that word.  ns[c], nt[c] >= 1.  Two launches. */
+/* RANSAC iterations [it_begin, it_begin + n_it) for every pair whose list is not yet full: iteration i of pair c draws source
+ * s_j = splitmix64(((uint64_t)seed_host[c] << 32) ^ (i * ransac_n + j)) mod ns[c], j < ransac_n (3..16), pairs it with nn[c][s_j], runs the
+ * edge-length checker (edge_sim < 0: none), Umeyama without scaling and the distance checker (dist_thr < 0: none).  The passing
+ * iteration indices are appended IN ITERATION ORDER to kept[c * max_validation ..] / n_kept[c] (device, n_kept zeroed by the caller
+ * before the first chunk) until max_validation are kept; a pair whose n_kept[c] has reached max_validation turns its blocks into no-ops
+ * by reading that word.  ns[c], nt[c] >= 1.  Two launches. */
 int ape_ransac_hypotheses_batch_f64(int nb, const double* const* src, const int* ns, const double* const* tgt, const int* nt,
                                     const int* const* nn, int ransac_n, const long* seed_host, double edge_sim, double dist_thr,
                                     int it_begin, int n_it, int max_validation, int* kept, int* n_kept, void* ws, size_t ws_bytes,
                                     void* stream);
-/* Models, validation and selection of all pairs in three launches: pair c validates kept[c * kept_stride .. + n_kept_host[c]) against
- * its target's grid (gn[c] == nt[c]); result[nb][24] laid out as ape_ransac_validate_f64's; fit_rmse: NULL or [nb] pointers (NULL or
- * [n_kept_host[c]][3]). */
+/* Models, validation and selection of all pairs in three launches: pair c validates the n_kept_host[c] (host count, <= 65535 and
+ * <= kept_stride) iterations kept[c * kept_stride ..] (kept non-NULL, kept_stride >= 1 even when every count is 0): each one's
+ * transformation recomputed, every source point moved by it and matched to its nearest target within max_dist (d^2 < max_dist^2; the
+ * grid arguments are the targets', cell >= max_dist, gn[c] == nt[c]); fitness = count / ns, rmse = sqrt(sum d^2 / count) (0 without
+ * matches), fixed-order sums.  result[nb][24] on the device, per pair: [0..15] the winner's 4x4 (row major), [16] fitness, [17] rmse,
+ * [18] correspondences, [19] its position in kept, [20] its iteration (-1 / -1 and the identity with fitness 0 when nothing is better
+ * than that); the winner has the highest fitness, then the lowest rmse, then the lowest iteration.  fit_rmse: NULL or [nb] pointers
+ * (NULL or [n_kept_host[c]][3] on the device: fitness, rmse, correspondences of every kept iteration). */
 int ape_ransac_validate_batch_f64(int nb, const double* const* sorted, const unsigned long long* const* keys, const unsigned* const* order,
                                   const double* const* origin3, const int* gn, double cell, const double* const* src, const int* ns,
                                   const double* const* tgt, const int* nt, const int* const* nn, int ransac_n, const long* seed_host,

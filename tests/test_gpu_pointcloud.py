@@ -153,6 +153,7 @@ def test_icp_device_loop_equals_host_solve(point_to_plane, crit):
     round-1 loop that brings the sums to the host every iteration and solves with LAPACK: same stopping iteration (fitness and the
     correspondence count equal), transforms to 1e-11 (the kernels before the solve are shared and bitwise reproducible)."""
     from autoposeestimation_amd.pc_reconstruction import pointcloud as PC
+    from icp_host_loop import registration_icp_host
     tgt = PO.voxel_down_sample(_bumpy_sphere(20000, 15), 3.0)
     T_true = _rot(0.05, -0.02, 0.03, (1.5, -2.5, 2.0))
     src = PO.voxel_down_sample(_bumpy_sphere(15000, 16), 3.0)
@@ -162,7 +163,7 @@ def test_icp_device_loop_equals_host_solve(point_to_plane, crit):
     c = PC.ICPConvergenceCriteria(*crit)
     init = _rot(0.01, 0.0, -0.01, (0.5, 0.0, 0.0))
     a = PC.registration_icp(PC.PointCloud(src), target, 10.0, init, est, c)
-    b = PC.registration_icp(PC.PointCloud(src), target, 10.0, init, est, c, host_solve=True)
+    b = registration_icp_host(PC.PointCloud(src), target, 10.0, init, est, c)
     assert a.fitness == b.fitness and a.correspondence_count == b.correspondence_count
     np.testing.assert_allclose(a.transformation, b.transformation, rtol=0, atol=1e-11)
     assert abs(a.inlier_rmse - b.inlier_rmse) < 1e-11
@@ -175,6 +176,7 @@ def test_icp_device_loop_degenerate_inputs():
     """too few correspondences (stops before any update, T = init), a planar pair (rank-2 covariance in Umeyama: the reflection
     guard must still return a proper rotation) and a long chain of chunks (more iterations than one enqueue)."""
     from autoposeestimation_amd.pc_reconstruction import pointcloud as PC
+    from icp_host_loop import registration_icp_host
     rng = np.random.default_rng(3)
     far = PC.PointCloud(rng.random((200, 3)) + 1000.0)
     near = PC.PointCloud(rng.random((300, 3)))
@@ -189,7 +191,7 @@ def test_icp_device_loop_degenerate_inputs():
     src = (plane - T_true[:3, 3]) @ T_true[:3, :3]
     c = PC.ICPConvergenceCriteria(1e-14, 1e-14, 50)
     a = PC.registration_icp(PC.PointCloud(src), PC.PointCloud(plane), 2.0, np.eye(4), None, c)
-    b = PC.registration_icp(PC.PointCloud(src), PC.PointCloud(plane), 2.0, np.eye(4), None, c, host_solve=True)
+    b = registration_icp_host(PC.PointCloud(src), PC.PointCloud(plane), 2.0, np.eye(4), None, c)
     np.testing.assert_allclose(a.transformation, b.transformation, atol=1e-10)
     np.testing.assert_allclose(a.transformation, T_true, atol=1e-8)
     assert abs(np.linalg.det(a.transformation[:3, :3]) - 1) < 1e-12
@@ -200,6 +202,7 @@ def test_icp_device_solve_random_small_systems():
     6x6 elimination against the host LAPACK solve on the same sums; for collinear sources (rotation about the line is free) only a
     proper rotation and the same residual are required."""
     from autoposeestimation_amd.pc_reconstruction import pointcloud as PC
+    from icp_host_loop import registration_icp_host
     rng = np.random.default_rng(77)
     c1 = PC.ICPConvergenceCriteria(0.0, 0.0, 1)
     for case in range(36):
@@ -222,7 +225,7 @@ def test_icp_device_solve_random_small_systems():
             if est.kind == 1 and n < 6:
                 continue
             a = PC.registration_icp(PC.PointCloud(src), target, 50.0, np.eye(4), est, c1)
-            b = PC.registration_icp(PC.PointCloud(src), target, 50.0, np.eye(4), est, c1, host_solve=True)
+            b = registration_icp_host(PC.PointCloud(src), target, 50.0, np.eye(4), est, c1)
             assert a.correspondence_count == b.correspondence_count == n
             R = a.transformation[:3, :3]
             assert abs(np.linalg.det(R) - 1) < 1e-9 and np.allclose(R @ R.T, np.eye(3), atol=1e-9), (case, est.kind)

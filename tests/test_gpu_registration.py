@@ -1,6 +1,7 @@
 """GPU checks of the global registration (csrc/registration.hip through pc_reconstruction.pointcloud / open3d_utils): FPFH, feature
 matching, the RANSAC hypothesis list and the winner against the numpy restatement (tests/registration_reference.py, fed the device's
-own normals), reproducibility, an end-to-end recovery of a large known motion, and the drivers with global_regression=True."""
+own normals), reproducibility, an end-to-end recovery of a large known motion, the drivers with global_regression=True, and the one-pair
+API against the bits recorded from its former own implementation (tests/golden/registration_one_pair.npz)."""
 import math
 import os
 
@@ -8,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import registration_golden as G
 import registration_reference as R
 from test_gpu_pointcloud import INTR, _render, _rot
 
@@ -195,3 +197,15 @@ def test_drivers_with_global_regression(tmp_path):
     tgt, src, _ = _pair()
     merged = U.align_point_clouds([PC.PointCloud(tgt), PC.PointCloud(src)], 10, 10, 5, global_regression=True, voxel_size=VOXEL, threshold=10)
     assert len(merged) > 0
+
+
+@pytest.mark.parametrize("group", list(G.GROUPS))
+def test_one_pair_api_equals_the_recorded_parent(group):
+    """The one-pair functions are one-element calls into batched.py; the fixture holds what their own implementation (ABI 21, the seven
+    one-pair entry points) returned for the same seeded inputs on an MI355X.  float64 kernels with fixed summation orders: exact."""
+    want = G.load()
+    for case, fields, run in G.GROUPS[group]():
+        got = run()
+        for f in fields:
+            a, w = np.asarray(got[f]), want[G.key(group, case, f)]
+            assert a.dtype == w.dtype and a.shape == w.shape and np.array_equal(a, w), (group, case, f)

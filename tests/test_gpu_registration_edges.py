@@ -116,19 +116,19 @@ def test_matching_non_finite_rows_and_ransac_over_them():
 
 # ---- hypothesis lists -----------------------------------------------------------------------------------------------------------------
 def _hypotheses(src, tgt, nn, ransac_n, seed, edge, dist, calls, max_val):
-    """ape_ransac_hypotheses_f64 for every (it_begin, n_it) of `calls` onto one kept list -> the kept iterations (host); the entries
-    behind the count must be untouched"""
-    _lib, _, _ = _mods()
+    """ape_ransac_hypotheses_batch_f64 with nb = 1 for every (it_begin, n_it) of `calls` onto one kept list -> the kept iterations (host);
+    the entries behind the count must be untouched"""
+    _lib, B, _ = _mods()
     L = _lib.lib()
     s, t, n = _dev(src), _dev(tgt), _dev(nn, torch.int32)
     ns, nt = len(src), len(tgt)
     kept = torch.full((max_val,), -7, dtype=torch.int32, device="cuda")
     n_kept = torch.zeros(1, dtype=torch.int32, device="cuda")
     for it0, n_it in calls:
-        ws = torch.empty(L.ape_ransac_workspace_bytes(ns, n_it, max_val), dtype=torch.uint8, device="cuda")
-        _lib.call.ape_ransac_hypotheses_f64(_lib.dptr(s, _D), ns, _lib.dptr(t, _D), nt, _lib.dptr(n), ransac_n, int(seed), float(edge),
-                                            float(dist), it0, n_it, max_val, _lib.dptr(kept), _lib.dptr(n_kept), _lib.dptr(ws), ws.numel(),
-                                            _lib.stream_ptr())
+        ws = torch.empty(L.ape_ransac_batch_workspace_bytes(1, B._ints([ns]), n_it, max_val), dtype=torch.uint8, device="cuda")
+        _lib.call.ape_ransac_hypotheses_batch_f64(1, B._ptrs([s]), B._ints([ns]), B._ptrs([t]), B._ints([nt]), B._ptrs([n]), ransac_n, B._longs([seed]),
+                                                  float(edge), float(dist), it0, n_it, max_val, _lib.dptr(kept), _lib.dptr(n_kept), _lib.dptr(ws),
+                                                  ws.numel(), _lib.stream_ptr())
     k = int(n_kept.item())
     out = kept.cpu().numpy()
     assert 0 <= k <= max_val and np.all(out[k:] == -7)
@@ -204,8 +204,9 @@ def test_tiny_cloud_hypothesis_lists(ns):
 
 # ---- validation and winner -------------------------------------------------------------------------------------------------------------
 def _validate(src, tgt, nn, ransac_n, seed, kept, max_dist):
-    """ape_ransac_validate_f64 on a given kept list -> (out[24], fit_rmse [k, 3]) on the host"""
-    _lib, _, PC = _mods()
+    """ape_ransac_validate_batch_f64 with nb = 1 on a given kept list -> (out[24], fit_rmse [k, 3]) on the host; the entry point wants a
+    kept array and a stride of at least 1 for k = 0 too"""
+    _lib, B, _ = _mods()
     L = _lib.lib()
     s, n = _dev(src), _dev(nn, torch.int32)
     target = _cloud(tgt)
@@ -214,10 +215,10 @@ def _validate(src, tgt, nn, ransac_n, seed, kept, max_dist):
     kt = _dev(np.asarray(kept, np.int32) if k else np.zeros(1, np.int32), torch.int32)
     out = torch.full((24,), -7.0, dtype=_D, device="cuda")
     fr = torch.full((max(k, 1), 3), -7.0, dtype=_D, device="cuda")
-    ws = torch.empty(L.ape_ransac_workspace_bytes(len(src), 1, max(k, 1)), dtype=torch.uint8, device="cuda")
-    _lib.call.ape_ransac_validate_f64(*PC.PointCloud._gargs(grid), _lib.dptr(s, _D), len(src), _lib.dptr(target._p, _D), len(tgt), _lib.dptr(n), ransac_n,
-                                      int(seed), _lib.dptr(kt), k, float(max_dist), _lib.dptr(out), _lib.dptr(fr), _lib.dptr(ws), ws.numel(),
-                                      _lib.stream_ptr())
+    ws = torch.empty(L.ape_ransac_batch_workspace_bytes(1, B._ints([len(src)]), 1, max(k, 1)), dtype=torch.uint8, device="cuda")
+    _lib.call.ape_ransac_validate_batch_f64(1, *B._grid_args([grid]), float(max_dist), B._ptrs([s]), B._ints([len(src)]), B._ptrs([target._p]),
+                                            B._ints([len(tgt)]), B._ptrs([n]), ransac_n, B._longs([seed]), _lib.dptr(kt), max(k, 1), B._ints([k]),
+                                            float(max_dist), _lib.dptr(out), B._ptrs([fr]), _lib.dptr(ws), ws.numel(), _lib.stream_ptr())
     return out.cpu().numpy(), fr.cpu().numpy()[:k]
 
 

@@ -1,4 +1,5 @@
-"""CPU checks of the global registration (FPFH + RANSAC): the library exports its entry points, the seeded sampler and the pair
+"""CPU checks of the global registration (FPFH + RANSAC): the library exports its entry points (and no one-pair ones), the recorded
+one-pair fixture is complete, the seeded sampler and the pair
 feature of the restatement (tests/registration_reference.py) are pinned on hand-made values, the restatement's own invariants hold,
 and unsupported checkers / estimators are refused before any device work."""
 import ctypes
@@ -10,8 +11,11 @@ import pytest
 
 import registration_reference as R
 
-_SYMS = ["ape_fpfh_workspace_bytes", "ape_fpfh_f64", "ape_feature_nn1_workspace_bytes", "ape_feature_nn1_f64",
-         "ape_ransac_workspace_bytes", "ape_ransac_hypotheses_f64", "ape_ransac_validate_f64"]
+_SYMS = ["ape_fpfh_batch_workspace_bytes", "ape_fpfh_batch_f64", "ape_feature_nn1_batch_workspace_bytes", "ape_feature_nn1_batch_f64",
+         "ape_ransac_batch_workspace_bytes", "ape_ransac_hypotheses_batch_f64", "ape_ransac_validate_batch_f64"]
+# the one-pair entry points that existed up to ABI 21: a single pair is a call of the ones above with nb = 1
+_REMOVED = ["ape_fpfh_workspace_bytes", "ape_fpfh_f64", "ape_feature_nn1_workspace_bytes", "ape_feature_nn1_f64",
+            "ape_ransac_workspace_bytes", "ape_ransac_hypotheses_f64", "ape_ransac_validate_f64"]
 
 
 def test_library_exports_registration_and_abi_3():
@@ -20,8 +24,23 @@ def test_library_exports_registration_and_abi_3():
     for s in _SYMS:
         assert hasattr(h, s), s
         assert s in _lib.SIGNATURES, s
+    for s in _REMOVED:
+        assert not hasattr(h, s), s
+        assert s not in _lib.SIGNATURES, s
     h.ape_abi_version.restype = ctypes.c_int
     assert h.ape_abi_version() >= 3
+
+
+def test_recorded_one_pair_fixture_holds_every_group_and_field():
+    """what test_gpu_registration.py::test_one_pair_api_equals_the_recorded_parent reads is all there (tests/registration_golden.py)"""
+    import registration_golden as G
+    z = G.load()
+    want = {G.key(g, case, f) for g, cases in G.GROUPS.items() for case, fields, _ in cases() for f in fields}
+    assert len(want) > 100 and want <= set(z), sorted(want - set(z))
+    assert set(z) - want == {"abi"} and int(z["abi"]) == 21          # recorded at the last ABI with one-pair entry points
+    assert os.path.getsize(G.FIXTURE) < 300 * 1024
+    assert z[G.key("ransac", "crit20000_17000_checkers0", "validated")].dtype == np.int64
+    assert all(z[G.key("fpfh", c, "sha256")].shape == (32,) for c, _, _ in G.fpfh_group())
 
 
 def test_splitmix64_sampler_values():
