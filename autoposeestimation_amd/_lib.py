@@ -143,6 +143,7 @@ SIGNATURES = {
     "ape_fgr_tuples_batch_f64": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _D, _I, _I, _I, _P, _P, _P, _c.c_size_t, _P],
     "ape_fgr_optimize_batch_f64": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _D, _D, _I, _P, _P, _P],
     "ape_icp_polish_batch_f64": [_I, _P, _P, _I, _P, _P, _I, _I, _D, _P, _D, _D, _D, _I, _D, _P, _P, _P],
+    "ape_icp_polish_plane_batch_f64": [_I, _P, _P, _I, _P, _P, _P, _I, _I, _D, _P, _D, _D, _D, _I, _D, _P, _P, _P],
     # segmentor training (csrc/segtrain.hip)
     "ape_bn_workspace_bytes": [_I],
     "ape_bn_train_fwd_f32": [_P] * 10 + [_c.c_long, _I, _F, _F, _I, _P, _c.c_size_t, _P],
@@ -305,7 +306,7 @@ _RESTYPES = {"ape_last_error": _c.c_char_p, "ape_adaptive_avgpool_multi_workspac
 _lib = None
 
 
-ABI_VERSION = 22 # what ape_abi_version() of the library this table mirrors returns
+ABI_VERSION = 23 # what ape_abi_version() of the library this table mirrors returns
 
 
 class ApeError(RuntimeError):

@@ -20,6 +20,15 @@
 //   * the 17 sums of an evaluation are taken by one wave each: lane l adds the points l, l + 64, ... in that order, then a butterfly
 //     over the wave: an order that depends on the object's point count alone, hence the same bits alone and in any batch;
 //   * thread 0 runs the step (3x3 SVD, composition, convergence test) between two barriers; no cross-workgroup synchronisation.
+//
+// The estimator is a compile-time parameter of the loop (kEst): kPointToPoint is the above; kPointToPlane is open3d's
+// TransformationEstimationPointToPlane on the model's normals, the loop ape_icp_run_batch_f64 runs with kind 1 (icp_step, pointcloud.hip):
+// the same search, 29 sums in p2plane_sums_kernel_body's layout -- one wave each, in the order above -- and thread 0 solves the 6x6
+// normal equations (pc_grid.h's solve6) where point-to-point runs the SVD.  The normals stay in global memory ([M][3] float64 in the
+// order of the cloud's points, fetched through the grid's `order`): read once per correspondence and sum, resident in L2, and 24 B more
+// per model point in LDS would push a 2600-point model out of it.
+#include <string>
+
 #include "pc_grid.h"
 #include "pose_quat.h"
 
@@ -31,9 +40,12 @@ constexpr int kNS = 17;               // [0] count, [1] sum d^2, [2..4] sum s, [
 constexpr int kMaxObs = 2048;         // observed points per object (36 B of LDS each: the point, its d^2, its correspondence)
 constexpr int kLdsBudget = 144 * 1024;   // dynamic LDS of the kernel: 160 KB per CU minus the static arrays and some air
 constexpr int kTableCols = 5;         // model_table[c] = (sorted, keys, order, origin as addresses, n)
+constexpr int kPointToPoint = 0, kPointToPlane = 1;
+constexpr int kNSPlane = 29;          // [0] count, [1] sum d^2, [2..22] upper triangle of J^T J (row major), [23..28] J^T r (p2plane_sums_kernel_body)
 
 struct PolishArgs {
     const float4* pts4; const int* n_cand; const int* obj_class; const int64_t* table; const double* pose_in; double* pose_out; double* stats;
+    const int64_t* ntable;            // kPointToPlane: normals_table[c] = address of class c's normals; unused (null) otherwise
     int N, n_classes, max_m, lds_model, max_iteration;
     double cell, r2, rel_fitness, rel_rmse, min_fitness;
 };
@@ -46,12 +58,22 @@ struct PolishArgs {
 #define APE_POLISH_CLK(...)
 #endif
 
-// the loop of one object; g: the model's grid (in LDS or in global memory); src, cj, cd: the object's points, their correspondences
-// (position in the grid's sorted order, -1 none) and squared distances, in LDS
-__device__ __forceinline__ void polish_loop(const Grid& g, double* __restrict__ src, int* __restrict__ cj, double* __restrict__ cd, int ns, const PolishArgs& a, const double* __restrict__ pin,
-                                            double* __restrict__ pout, double* __restrict__ so)
+// component k of a point-to-plane Jacobian row J = [s x n, n], in p2plane_sums_kernel_body's expressions
+__device__ __forceinline__ double plane_j(const double* s, const double* nn, int k)
 {
-    __shared__ double tot[kNS];
+    if (k >= 3) return nn[k - 3];
+    const int u = k == 2 ? 0 : k + 1, w = k == 0 ? 2 : k - 1;
+    return s[u] * nn[w] - s[w] * nn[u];
+}
+
+// the loop of one object; g: the model's grid (in LDS or in global memory); src, cj, cd: the object's points, their correspondences
+// (position in the grid's sorted order, -1 none) and squared distances, in LDS; nrm (kPointToPlane): the model's normals [g.n][3] in the
+// order of the cloud's points, in global memory
+template <int kEst>
+__device__ __forceinline__ void polish_loop(const Grid& g, const double* __restrict__ nrm, double* __restrict__ src, int* __restrict__ cj, double* __restrict__ cd, int ns, const PolishArgs& a,
+                                            const double* __restrict__ pin, double* __restrict__ pout, double* __restrict__ so)
+{
+    __shared__ double tot[kEst == kPointToPoint ? kNS : kNSPlane];
     __shared__ double Up[12];         // the pending update (rows 0..2 of a 4x4): the initial guess first, then every step's U
     __shared__ double Tm[12];         // T, camera frame -> model frame
     __shared__ double st[4];          // fitness, inlier rmse, correspondences, stop reason
@@ -129,7 +151,7 @@ __device__ __forceinline__ void polish_loop(const Grid& g, double* __restrict__ 
         APE_POLISH_CLK(if (tid == 0) { const long long c1 = wall_clock64(); clk[0] += c1 - c0; c0 = c1; })
         // part 2: the 17 sums, one wave per sum (wave 0 also takes the 17th): lane l adds the points l, l + 64, ... in that order, then a
         // butterfly over the wave -- an order that depends on ns alone
-        for (int v = tid >> 6; v < kNS; v += kPT / 64) {
+        if constexpr (kEst == kPointToPoint) for (int v = tid >> 6; v < kNS; v += kPT / 64) {
             const int l = tid & 63, sa = v < 8 ? (v - 2) : (v - 8) / 3, ta = v < 8 ? (v - 5) : (v - 8) % 3;
             double w = 0.0;
             for (int i = l; i < ns; i += 64) {
@@ -146,9 +168,37 @@ __device__ __forceinline__ void polish_loop(const Grid& g, double* __restrict__ 
             for (int m = 32; m >= 1; m >>= 1) w += __shfl_xor(w, m, 64);
             if (l == 0) tot[v] = w;
         }
+        // point-to-plane: the 29 sums in the same order, two rounds of the 16 waves; sum v >= 2 is J_ja J_jb (the triangle row major) or
+        // J_ja r, and every wave works out r and its two components of J per point -- nothing per point is kept between the sums
+        if constexpr (kEst == kPointToPlane) for (int v = tid >> 6; v < kNSPlane; v += kPT / 64) {
+            const int l = tid & 63;
+            int ja = v >= 23 ? v - 23 : 0, jb = 0;
+            if (v >= 2 && v < 23) { int k = v - 2; while (k >= 6 - ja) { k -= 6 - ja; ++ja; } jb = ja + k; }
+            double w = 0.0;
+            for (int i = l; i < ns; i += 64) {
+                const int j = cj[i];
+                if (j < 0) continue;
+                double term;
+                if (v == 0) term = 1.0;
+                else if (v == 1) term = cd[i];
+                else {
+                    const double* s = src + i * 3;
+                    const double* nn = nrm + (size_t)g.order[j] * 3;
+                    if (v < 23) term = plane_j(s, nn, ja) * plane_j(s, nn, jb);
+                    else {
+                        const double* t = g.sorted + (size_t)j * 3;
+                        const double r = ((s[0] - t[0]) * nn[0] + (s[1] - t[1]) * nn[1]) + (s[2] - t[2]) * nn[2];
+                        term = plane_j(s, nn, ja) * r;
+                    }
+                }
+                w += term;
+            }
+            for (int m = 32; m >= 1; m >>= 1) w += __shfl_xor(w, m, 64);
+            if (l == 0) tot[v] = w;
+        }
         __syncthreads();
         APE_POLISH_CLK(if (tid == 0) { const long long c1 = wall_clock64(); clk[1] += c1 - c0; c0 = c1; ++evals; })
-        if (tid == 0) {
+        if constexpr (kEst == kPointToPoint) if (tid == 0) {
             // icp_step of pointcloud.hip, kind 0
             const double n_corr = tot[0];
             const double fitness = n_corr / (double)ns;
@@ -176,6 +226,39 @@ __device__ __forceinline__ void polish_loop(const Grid& g, double* __restrict__ 
             }
             first = false;
         }
+        if constexpr (kEst == kPointToPlane) if (tid == 0) {
+            // icp_step of pointcloud.hip, kind 1
+            const double n_corr = tot[0];
+            const double fitness = n_corr / (double)ns;
+            const double rmse = n_corr > 0 ? sqrt(tot[1] / n_corr) : 0.0;
+            const double pf = st[0], pr = st[1];
+            st[0] = fitness; st[1] = rmse; st[2] = n_corr;
+            if (!first && fabs(pf - fitness) < a.rel_fitness && fabs(pr - rmse) < a.rel_rmse) { ctl[0] = 1; st[3] = 1.0; }
+            else if (ctl[1] >= a.max_iteration) { ctl[0] = 1; st[3] = 3.0; }
+            else if (n_corr < 6.0) { ctl[0] = 1; st[3] = 2.0; }
+            else {
+                double M[6][7];
+                int k = 2;
+                for (int c = 0; c < 6; ++c) for (int d = c; d < 6; ++d) { M[c][d] = M[d][c] = tot[k]; ++k; }
+                for (int c = 0; c < 6; ++c) M[c][6] = -tot[23 + c];
+                double U[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, Tn[12];      // a singular system: the identity, and still an update
+                if (solve6(M)) {
+                    const double x[6] = {M[0][6], M[1][6], M[2][6], M[3][6], M[4][6], M[5][6]};
+                    double R[3][3];
+                    vec6_rotation(x, R);
+                    for (int c = 0; c < 3; ++c) {
+                        for (int d = 0; d < 3; ++d) U[c * 4 + d] = R[c][d];
+                        U[c * 4 + 3] = x[3 + c];
+                    }
+                }
+                for (int c = 0; c < 3; ++c)
+                    for (int d = 0; d < 4; ++d)                      // row 3 of T is (0, 0, 0, 1)
+                        Tn[c * 4 + d] = ((U[c * 4] * Tm[d] + U[c * 4 + 1] * Tm[4 + d]) + U[c * 4 + 2] * Tm[8 + d]) + (d == 3 ? U[c * 4 + 3] : 0.0);
+                for (int k2 = 0; k2 < 12; ++k2) { Tm[k2] = Tn[k2]; Up[k2] = U[k2]; }
+                ctl[1] += 1;
+            }
+            first = false;
+        }
         __syncthreads();
         APE_POLISH_CLK(if (tid == 0) { const long long c1 = wall_clock64(); clk[2] += c1 - c0; c0 = c1; })
         if (ctl[0]) break;
@@ -199,6 +282,7 @@ __device__ __forceinline__ void polish_loop(const Grid& g, double* __restrict__ 
     }
 }
 
+template <int kEst>
 __global__ __launch_bounds__(kPT) void icp_polish_kernel(const PolishArgs a)
 {
     extern __shared__ double dyn[];   // observed points [N][3], d^2 [N], correspondence [N + (N & 1)], then (lds_model) sorted [max_m][3], keys [max_m], order [max_m]
@@ -212,7 +296,9 @@ __global__ __launch_bounds__(kPT) void icp_polish_kernel(const PolishArgs a)
     const int cls = a.obj_class[b];
     const bool known = cls >= 0 && cls < a.n_classes;
     const int64_t* row = a.table + (size_t)(known ? cls : 0) * kTableCols;
-    const int64_t m64 = known ? row[4] : 0;
+    const double* g_normals = nullptr;
+    if constexpr (kEst == kPointToPlane) g_normals = known ? (const double*)(uintptr_t)a.ntable[cls] : nullptr;
+    const int64_t m64 = known && (kEst == kPointToPoint || g_normals) ? row[4] : 0;       // (a class without normals: as one without points)
     if (m64 < 1 || m64 > 0x7fffffff || ns < 1) {        // (uniform over the workgroup) nothing to register: the pose passes through
         if (tid < 7) pout[tid] = pin[tid];
         if (tid < 4) so[tid] = (tid == 3 && known) ? 2.0 : 0.0;
@@ -241,11 +327,39 @@ __global__ __launch_bounds__(kPT) void icp_polish_kernel(const PolishArgs a)
         for (int i = tid; i < m * 3; i += kPT) l_sorted[i] = g_sorted[i];
         for (int i = tid; i < m; i += kPT) { l_keys[i] = g_keys[i]; l_order[i] = g_order[i]; }
         __syncthreads();
-        polish_loop(Grid{l_sorted, l_keys, l_order, org, m, a.cell}, src, cj, cd, ns, a, pin, pout, so);
+        polish_loop<kEst>(Grid{l_sorted, l_keys, l_order, org, m, a.cell}, g_normals, src, cj, cd, ns, a, pin, pout, so);
     } else {
         __syncthreads();
-        polish_loop(Grid{g_sorted, g_keys, g_order, org, m, a.cell}, src, cj, cd, ns, a, pin, pout, so);
+        polish_loop<kEst>(Grid{g_sorted, g_keys, g_order, org, m, a.cell}, g_normals, src, cj, cd, ns, a, pin, pout, so);
     }
+}
+
+// the checks and the launch of both exports; `who`: the export's name for ape_last_error
+template <int kEst>
+int launch_polish(const char* who, int n, const float* points4, const int* n_cand, int N, const int* obj_class, const int64_t* model_table,
+                  const int64_t* normals_table, int n_classes, int max_model_points, double cell, const double* pose_in, double max_dist,
+                  double relative_fitness, double relative_rmse, int max_iteration, double min_fitness, double* pose_out, double* stats, void* stream)
+{
+    const auto refuse = [who](const char* what) { ape::set_last_error((std::string(who) + ": " + what).c_str()); return APE_EINVAL; };
+    if (n < 0) return refuse("n < 0");
+    if (N <= 0 || N > kMaxObs) return refuse("N must be in 1..2048");
+    if (!(max_dist > 0)) return refuse("max_dist <= 0");
+    if (!(cell >= max_dist)) return refuse("cell < max_dist");
+    if (n_classes < 1 || max_model_points < 1 || !model_table) return refuse("empty model table");
+    if (kEst == kPointToPlane && !normals_table) return refuse("no normals table");
+    if (max_iteration < 0) return refuse("max_iteration < 0");
+    if (n == 0) return APE_OK;
+    if (!points4 || !n_cand || !obj_class || !pose_in || !pose_out || !stats) return refuse("null buffer");
+    const size_t obs = (size_t)N * 32 + (size_t)(N + (N & 1)) * 4, grid = (size_t)max_model_points * 36 + 4;     // (+4: an odd count of order words keeps the total a multiple of 8)
+    const int lds_model = obs + grid <= (size_t)kLdsBudget;
+    const size_t lds = obs + (lds_model ? (grid & ~(size_t)7) : 0);
+    static ape::DeviceOnce once;      // (one per instantiation)
+    int rc = ape::device_once(once, reinterpret_cast<const void*>(icp_polish_kernel<kEst>), kLdsBudget, nullptr);
+    if (rc != APE_OK) return rc;
+    const PolishArgs a{(const float4*)points4, n_cand, obj_class, model_table, pose_in, pose_out, stats, normals_table, N, n_classes, max_model_points,
+                       lds_model, max_iteration, cell, max_dist * max_dist, relative_fitness, relative_rmse, min_fitness};
+    hipLaunchKernelGGL(icp_polish_kernel<kEst>, dim3(n), dim3(kPT), lds, (hipStream_t)stream, a);
+    return ape::check_launch(who);
 }
 
 }  // namespace
@@ -256,22 +370,17 @@ extern "C" int ape_icp_polish_batch_f64(int n, const float* points4, const int* 
                                         double relative_fitness, double relative_rmse, int max_iteration, double min_fitness, double* pose_out,
                                         double* stats, void* stream)
 {
-    if (n < 0) { ape::set_last_error("ape_icp_polish_batch_f64: n < 0"); return APE_EINVAL; }
-    if (N <= 0 || N > kMaxObs) { ape::set_last_error("ape_icp_polish_batch_f64: N must be in 1..2048"); return APE_EINVAL; }
-    if (!(max_dist > 0)) { ape::set_last_error("ape_icp_polish_batch_f64: max_dist <= 0"); return APE_EINVAL; }
-    if (!(cell >= max_dist)) { ape::set_last_error("ape_icp_polish_batch_f64: cell < max_dist"); return APE_EINVAL; }
-    if (n_classes < 1 || max_model_points < 1 || !model_table) { ape::set_last_error("ape_icp_polish_batch_f64: empty model table"); return APE_EINVAL; }
-    if (max_iteration < 0) { ape::set_last_error("ape_icp_polish_batch_f64: max_iteration < 0"); return APE_EINVAL; }
-    if (n == 0) return APE_OK;
-    if (!points4 || !n_cand || !obj_class || !pose_in || !pose_out || !stats) { ape::set_last_error("ape_icp_polish_batch_f64: null buffer"); return APE_EINVAL; }
-    const size_t obs = (size_t)N * 32 + (size_t)(N + (N & 1)) * 4, grid = (size_t)max_model_points * 36 + 4;     // (+4: an odd count of order words keeps the total a multiple of 8)
-    const int lds_model = obs + grid <= (size_t)kLdsBudget;
-    const size_t lds = obs + (lds_model ? (grid & ~(size_t)7) : 0);
-    static ape::DeviceOnce once;
-    int rc = ape::device_once(once, reinterpret_cast<const void*>(icp_polish_kernel), kLdsBudget, nullptr);
-    if (rc != APE_OK) return rc;
-    const PolishArgs a{(const float4*)points4, n_cand, obj_class, model_table, pose_in, pose_out, stats, N, n_classes, max_model_points, lds_model,
-                       max_iteration, cell, max_dist * max_dist, relative_fitness, relative_rmse, min_fitness};
-    hipLaunchKernelGGL(icp_polish_kernel, dim3(n), dim3(kPT), lds, (hipStream_t)stream, a);
-    return ape::check_launch("ape_icp_polish_batch_f64");
+    return launch_polish<kPointToPoint>("ape_icp_polish_batch_f64", n, points4, n_cand, N, obj_class, model_table, nullptr, n_classes, max_model_points, cell,
+                                        pose_in, max_dist, relative_fitness, relative_rmse, max_iteration, min_fitness, pose_out, stats, stream);
+}
+
+/* see include/ape_hip.h */
+extern "C" int ape_icp_polish_plane_batch_f64(int n, const float* points4, const int* n_cand, int N, const int* obj_class, const int64_t* model_table,
+                                              const int64_t* normals_table, int n_classes, int max_model_points, double cell, const double* pose_in,
+                                              double max_dist, double relative_fitness, double relative_rmse, int max_iteration, double min_fitness,
+                                              double* pose_out, double* stats, void* stream)
+{
+    return launch_polish<kPointToPlane>("ape_icp_polish_plane_batch_f64", n, points4, n_cand, N, obj_class, model_table, normals_table, n_classes,
+                                        max_model_points, cell, pose_in, max_dist, relative_fitness, relative_rmse, max_iteration, min_fitness, pose_out,
+                                        stats, stream);
 }

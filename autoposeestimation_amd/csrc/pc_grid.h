@@ -1,5 +1,6 @@
 // Device helpers shared by the point-cloud kernels (pointcloud.hip) and the global-registration kernels (registration.hip): the uniform
-// search grid over a cloud sorted by cell key (27-cell walk, kG lanes per query) and the 3x3 rotation of Eigen::umeyama without scaling.
+// search grid over a cloud sorted by cell key (27-cell walk, kG lanes per query), the 3x3 rotation of Eigen::umeyama without scaling, and
+// -- shared with the depth ICP polish (icp_polish.hip) -- the 6x6 solve and the rotation of the point-to-plane update.
 // Everything here lives in the including translation unit's anonymous namespace.
 #pragma once
 #include "common.h"
@@ -120,6 +121,37 @@ __device__ void svd3_rotation(const double C[3][3], double R[3][3])
     const double s33 = det3(U) * det3(W) < 0 ? -1.0 : 1.0;
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) R[i][j] = (U[i][0] * W[j][0] + U[i][1] * W[j][1]) + s33 * U[i][2] * W[j][2];
+}
+
+__device__ bool solve6(double M[6][7])
+{
+    // Gaussian elimination with partial pivoting on the augmented system (numpy.linalg.solve = LAPACK gesv); false when exactly singular
+    for (int c = 0; c < 6; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < 6; ++r) if (fabs(M[r][c]) > fabs(M[piv][c])) piv = r;
+        if (M[piv][c] == 0.0) return false;
+        if (piv != c) for (int k = 0; k < 7; ++k) { const double t = M[c][k]; M[c][k] = M[piv][k]; M[piv][k] = t; }
+        for (int r = c + 1; r < 6; ++r) {
+            const double f = M[r][c] / M[c][c];
+            for (int k = c; k < 7; ++k) M[r][k] -= f * M[c][k];
+        }
+    }
+    for (int r = 5; r >= 0; --r) {
+        double v = M[r][6];
+        for (int k = r + 1; k < 6; ++k) v -= M[r][k] * M[k][6];
+        M[r][6] = v / M[r][r];
+    }
+    return true;
+}
+
+// rotation of open3d's TransformVector6dToMatrix4d: R = Rz(x2) Ry(x1) Rx(x0)
+__device__ __forceinline__ void vec6_rotation(const double x[6], double R[3][3])
+{
+    const double cx = cos(x[0]), sx = sin(x[0]), cy = cos(x[1]), sy = sin(x[1]), cz = cos(x[2]), sz = sin(x[2]);
+    const double Rx[3][3] = {{1, 0, 0}, {0, cx, -sx}, {0, sx, cx}}, Ry[3][3] = {{cy, 0, sy}, {0, 1, 0}, {-sy, 0, cy}}, Rz[3][3] = {{cz, -sz, 0}, {sz, cz, 0}, {0, 0, 1}};
+    double T1[3][3];
+    for (int a = 0; a < 3; ++a) for (int b2 = 0; b2 < 3; ++b2) T1[a][b2] = (Rz[a][0] * Ry[0][b2] + Rz[a][1] * Ry[1][b2]) + Rz[a][2] * Ry[2][b2];
+    for (int a = 0; a < 3; ++a) for (int b2 = 0; b2 < 3; ++b2) R[a][b2] = (T1[a][0] * Rx[0][b2] + T1[a][1] * Rx[1][b2]) + T1[a][2] * Rx[2][b2];
 }
 
 }  // namespace

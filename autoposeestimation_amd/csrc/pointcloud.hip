@@ -503,27 +503,6 @@ extern "C" int ape_knn_mean_dist_f64(const double* pts, int n, int k, double* me
 namespace {
 
 
-__device__ bool solve6(double M[6][7])
-{
-    // Gaussian elimination with partial pivoting on the augmented system (numpy.linalg.solve = LAPACK gesv); false when exactly singular
-    for (int c = 0; c < 6; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < 6; ++r) if (fabs(M[r][c]) > fabs(M[piv][c])) piv = r;
-        if (M[piv][c] == 0.0) return false;
-        if (piv != c) for (int k = 0; k < 7; ++k) { const double t = M[c][k]; M[c][k] = M[piv][k]; M[piv][k] = t; }
-        for (int r = c + 1; r < 6; ++r) {
-            const double f = M[r][c] / M[c][c];
-            for (int k = c; k < 7; ++k) M[r][k] -= f * M[c][k];
-        }
-    }
-    for (int r = 5; r >= 0; --r) {
-        double v = M[r][6];
-        for (int k = r + 1; k < 6; ++k) v -= M[r][k] * M[k][6];
-        M[r][6] = v / M[r][r];
-    }
-    return true;
-}
-
 __device__ void icp_step(int kind, const double* s, double* __restrict__ st, int ns, double rel_fitness, double rel_rmse, int max_iteration)
 {
     if (st[0] != 0.0) return;
@@ -554,13 +533,10 @@ __device__ void icp_step(int kind, const double* s, double* __restrict__ st, int
         for (int a = 0; a < 6; ++a) M[a][6] = -s[23 + a];
         if (solve6(M)) {
             const double x[6] = {M[0][6], M[1][6], M[2][6], M[3][6], M[4][6], M[5][6]};
-            const double cx = cos(x[0]), sx = sin(x[0]), cy = cos(x[1]), sy = sin(x[1]), cz = cos(x[2]), sz = sin(x[2]);
-            // TransformVector6dToMatrix4d: R = Rz(x2) Ry(x1) Rx(x0)
-            const double Rx[3][3] = {{1, 0, 0}, {0, cx, -sx}, {0, sx, cx}}, Ry[3][3] = {{cy, 0, sy}, {0, 1, 0}, {-sy, 0, cy}}, Rz[3][3] = {{cz, -sz, 0}, {sz, cz, 0}, {0, 0, 1}};
-            double T1[3][3];
-            for (int a = 0; a < 3; ++a) for (int b2 = 0; b2 < 3; ++b2) T1[a][b2] = (Rz[a][0] * Ry[0][b2] + Rz[a][1] * Ry[1][b2]) + Rz[a][2] * Ry[2][b2];
+            double R[3][3];
+            vec6_rotation(x, R);
             for (int a = 0; a < 3; ++a) {
-                for (int b2 = 0; b2 < 3; ++b2) U[a][b2] = (T1[a][0] * Rx[0][b2] + T1[a][1] * Rx[1][b2]) + T1[a][2] * Rx[2][b2];
+                for (int b2 = 0; b2 < 3; ++b2) U[a][b2] = R[a][b2];
                 U[a][3] = x[3 + a];
             }
         }

@@ -11,5 +11,5 @@ void set_last_error(const char* what)
 }
 }  // namespace ape
 
-extern "C" int ape_abi_version(void) { return 22; }
+extern "C" int ape_abi_version(void) { return 23; }
 extern "C" const char* ape_last_error(void) { return ape::g_err; }

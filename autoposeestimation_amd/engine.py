@@ -1121,12 +1121,21 @@ def backproject(depth, objects, choose, intr, depth_scale):
     return pts
 
 
-def icp_polish(points4, n_cand, obj_class, models, pose, max_correspondence_distance, criteria, min_fitness=0.0):
+ICP_ESTIMATIONS = ("point_to_point", "point_to_plane")
+
+
+def icp_polish(points4, n_cand, obj_class, models, pose, max_correspondence_distance, criteria, min_fitness=0.0, estimation="point_to_point"):
     """Depth ICP polish of a batch of objects in ONE launch (csrc/icp_polish.hip): points4[n,N,4] f32 as `backproject` leaves
     them, n_cand[n] i32, obj_class[n] (row of `models` per object: an int32 device tensor, or a host sequence that is checked against the
     table and uploaded), models = pipeline.polish.ModelSet, pose[n,7] f64 (w,x,y,z,tx,ty,tz), criteria with relative_fitness /
     relative_rmse / max_iteration -> (pose_out[n,7] f64, stats[n,4] f64 = fitness, inlier rmse, correspondences, stop reason).
+    estimation: "point_to_point", or "point_to_plane" on the normals of `models` (a set without normals is refused).
     Enqueues on the current stream, reads nothing back: safe inside a graph capture."""
+    if estimation not in ICP_ESTIMATIONS:
+        raise ValueError("icp_polish: estimation must be one of %s, not %r" % (", ".join(ICP_ESTIMATIONS), estimation))
+    plane = estimation == "point_to_plane"
+    if plane and getattr(models, "normals_table", None) is None:
+        raise ValueError("icp_polish: point_to_plane needs a ModelSet with normals (normal_radius=... or normals=...)")
     n, npts = int(points4.shape[0]), int(points4.shape[1])
     if not torch.is_tensor(obj_class) or not obj_class.is_cuda:
         host = [int(c) for c in (obj_class.tolist() if torch.is_tensor(obj_class) else obj_class)]
@@ -1141,11 +1150,15 @@ def icp_polish(points4, n_cand, obj_class, models, pose, max_correspondence_dist
         raise ValueError("icp_polish: points4[n,N,4], n_cand[n], obj_class[n] and pose[n,7] must agree")
     pose_out = torch.empty(n, 7, dtype=torch.float64, device=points4.device)
     stats = torch.empty(n, 4, dtype=torch.float64, device=points4.device)
-    _lib.call.ape_icp_polish_batch_f64(n, _lib.dptr(points4, torch.float32), _lib.dptr(n_cand, torch.int32), npts, _lib.dptr(obj_class, torch.int32),
-                                       _lib.dptr(models.table, torch.int64), models.n_classes, models.max_points, models.cell,
-                                       _lib.dptr(pose, torch.float64), float(max_correspondence_distance), float(criteria.relative_fitness),
-                                       float(criteria.relative_rmse), int(criteria.max_iteration), float(min_fitness), _lib.dptr(pose_out),
-                                       _lib.dptr(stats), _st())
+    head = (n, _lib.dptr(points4, torch.float32), _lib.dptr(n_cand, torch.int32), npts, _lib.dptr(obj_class, torch.int32),
+            _lib.dptr(models.table, torch.int64))
+    tail = (models.n_classes, models.max_points, models.cell, _lib.dptr(pose, torch.float64), float(max_correspondence_distance),
+            float(criteria.relative_fitness), float(criteria.relative_rmse), int(criteria.max_iteration), float(min_fitness), _lib.dptr(pose_out),
+            _lib.dptr(stats), _st())
+    if plane:
+        _lib.call.ape_icp_polish_plane_batch_f64(*head, _lib.dptr(models.normals_table, torch.int64), *tail)
+    else:
+        _lib.call.ape_icp_polish_batch_f64(*head, *tail)
     return pose_out, stats
 
 

@@ -40,6 +40,8 @@ class FramePipeline:
         # one-launch depth ICP polish (csrc/icp_polish.hip) of its objects against their classes' model clouds, on the bucket's own
         # back-projection: it rides the pose stream and the bucket graphs.  The result dict gains `fit` [n,4] f64 (fitness, inlier rmse,
         # correspondences, stop reason) and `pose_raw` (what `pose` held without the switch); `pose` holds the polished pose.
+        # IcpPolish(estimation="point_to_plane") runs the point-to-plane launch instead, on model normals that are built
+        # with the grids, before anything is captured.
         if icp_polish is not None:
             from autoposeestimation_amd.pipeline.polish import IcpPolish
             if not isinstance(icp_polish, IcpPolish):
@@ -125,9 +127,8 @@ class FramePipeline:
             ncand_all = torch.zeros(n, dtype=torch.int32, device=dev)
             choose_all = torch.zeros(n, self.num_points, dtype=torch.int64, device=dev)
             more_all = (torch.zeros(n, 4, dtype=torch.float64, device=dev), torch.zeros(n, 7, dtype=torch.float64, device=dev)) if self.icp_polish is not None else ()
-        if self.icp_polish is not None:                 # (upload + grids once per cloud set, before anything is captured)
-            from autoposeestimation_amd.pipeline.polish import ModelSet
-            ModelSet.cached(self.icp_polish.point_clouds, dev, self.icp_polish.max_correspondence_distance)
+        if self.icp_polish is not None:                 # (upload + grids [+ normals] once per cloud set, before anything is captured)
+            self.icp_polish.model_set(dev)
         use_graphs = self.pose_graphs and choose_override is None and E.PROFILE is None and not torch.cuda.is_current_stream_capturing()
         if use_graphs:
             if self._static_objmap is None or self._static_objmap.shape != objmap.shape:
@@ -202,11 +203,10 @@ class FramePipeline:
                 out = self.refiner.forward_batch(E.pose_recentre(pts4, pose), emb, obj_idx, cache=cache)
                 E.pose_compose(pose, out[:, 0:4], out[:, 4:7])
         if self.icp_polish is not None:
-            from autoposeestimation_amd.pipeline.polish import ModelSet, polish_poses
+            from autoposeestimation_amd.pipeline.polish import polish_poses
             ip = self.icp_polish
-            models = ModelSet.cached(ip.point_clouds, dev, ip.max_correspondence_distance)
-            polished, fit = polish_poses(depth, objs, choose, n_cand, pose, meta, models, ip.max_correspondence_distance, ip.criteria, ip.min_fitness,
-                                         points4=pts4)
+            polished, fit = polish_poses(depth, objs, choose, n_cand, pose, meta, ip.model_set(dev), ip.max_correspondence_distance, ip.criteria,
+                                         ip.min_fitness, points4=pts4, estimation=ip.estimation)
             return polished, n_cand, choose, fit, pose
         return pose, n_cand, choose
 
@@ -311,6 +311,17 @@ def _as_u8_frame(image):
     return np.ascontiguousarray(arr[:, :, :3].astype(np.uint8))
 
 
+def polish_switch(point_clouds, icp_params=None):
+    """the IcpPolish of full_prediction(icp_polish=True): `icp_params` (an IcpPolish, or a dict of its keyword arguments) on the call's
+    own clouds -- threshold, criteria, gate, estimator and normal parameters are carried over"""
+    from autoposeestimation_amd.pipeline.polish import IcpPolish
+    if point_clouds is None:
+        raise ValueError("full_prediction(icp_polish=True) needs point_clouds: the model clouds the depth points are registered to")
+    if isinstance(icp_params, IcpPolish):
+        return icp_params.replace(point_clouds)
+    return IcpPolish(point_clouds, **dict(icp_params or {}))
+
+
 def full_prediction(image, depth, meta, segmentor, estimator, refiner, to_tensor, normalize, device, cuda, color_dict,
                     class_names=None, point_clouds=None, plot=False, color_prediction=False, bbox=False, put_text=False,
                     refine_mode="live_compat", choose_override=None, icp_polish=False, icp_params=None):
@@ -323,16 +334,9 @@ def full_prediction(image, depth, meta, segmentor, estimator, refiner, to_tensor
     rasteriser and font cannot be pinned without it).  Objects without a valid depth pixel are dropped like the reference (:530-531,623-635).
     `icp_polish=True` (needs `point_clouds`) ends the pose stage with the depth ICP polish (pipeline/polish.py): 'position' / 'rotation'
     then hold the polished pose and every prediction gains 'fitness' and 'inlier_rmse'; `icp_params`: an IcpPolish, or a dict of its
-    max_correspondence_distance / criteria / min_fitness."""
-    polish = None
-    if icp_polish:
-        from autoposeestimation_amd.pipeline.polish import IcpPolish
-        if point_clouds is None:
-            raise ValueError("full_prediction(icp_polish=True) needs point_clouds: the model clouds the depth points are registered to")
-        if isinstance(icp_params, IcpPolish):
-            polish = IcpPolish(point_clouds, icp_params.max_correspondence_distance, icp_params.criteria, icp_params.min_fitness)
-        else:
-            polish = IcpPolish(point_clouds, **dict(icp_params or {}))
+    max_correspondence_distance / criteria / min_fitness / estimation ("point_to_plane": DESIGN.md 6ze) / normal_radius /
+    normal_max_nn / normals."""
+    polish = polish_switch(point_clouds, icp_params) if icp_polish else None
     if not cuda or not torch.cuda.is_available():
         raise RuntimeError("full_prediction needs the GPU: the MI355X path has no CPU fallback")
     start_time = time.time()

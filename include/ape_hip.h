@@ -573,14 +573,32 @@ int ape_fgr_optimize_batch_f64(int nb, const double* const* src, const int* ns, 
  *                          correspondences, 3 iteration limit: state[37] of ape_icp_run_batch_f64)
  * pose_out[i] is pose_in[i] bit for bit when no update was applied (ns < 3, too few correspondences at the first evaluation,
  * max_iteration 0) and when the final fitness is below min_fitness (stats stay the registration's).  An object with ns == 0 reports
- * (0, 0, 0, 2).  obj_class lives on the device, so a class outside the table cannot be refused on the host: such an object, or one
- * whose table row has M < 1, passes its pose through with stats (0, 0, 0, 0).  The sums are added in an order that depends on ns
- * alone: an object's result has the same bits alone and in any batch.
+ * (0, 0, 0, 2), and so does one whose table row has M < 1.  obj_class lives on the device, so a class outside the table cannot be
+ * refused on the host: such an object passes its pose through with stats (0, 0, 0, 0).  The sums are added in an order that depends
+ * on ns alone: an object's result has the same bits alone and in any batch.
  * APE_EINVAL (with ape_last_error): n < 0, N outside 1..2048, max_dist <= 0, cell < max_dist, an empty table, max_iteration < 0. */
 int ape_icp_polish_batch_f64(int n, const float* points4, const int* n_cand, int N, const int* obj_class, const int64_t* model_table,
                              int n_classes, int max_model_points, double cell, const double* pose_in, double max_dist,
                              double relative_fitness, double relative_rmse, int max_iteration, double min_fitness, double* pose_out,
                              double* stats, void* stream);
+
+/* ape_icp_polish_batch_f64 with TransformationEstimationPointToPlane (the loop of ape_icp_run_batch_f64, kind 1) on the model clouds'
+ * normals; the same launch shape, buffers, pass-through rules and refusals, and:
+ *   normals_table[n_classes] i64 (device, built once per cloud set): the address of the class's normals, [M][3] f64 in the order of
+ *                          the cloud's points (row order[j] belongs to sorted[j]); neither sign nor length matters to the fixed
+ *                          point's existence -- J and r flip together -- but the normals are used as given.  They are read from
+ *                          global memory whether or not the grid is staged into LDS.
+ *   stats[n][4] f64        stop reason 2 is "fewer than 6 correspondences"
+ * An update is the solution x of (J^T J) x = -J^T r over the correspondences, r = (s - t).n_t, J = [s x n_t, n_t], applied as
+ * Rz(x2) Ry(x1) Rx(x0) with translation x[3..5]; an exactly singular system gives the identity update, which counts as an update (so
+ * pose_out is then inverse(T) of an unchanged T, not pose_in bit for bit).  pose_out[i] is pose_in[i] bit for bit when ns < 6 or
+ * fewer than 6 correspondences were found at the first evaluation, with max_iteration 0 and below min_fitness; a class whose
+ * normals_table entry is 0 is treated like one with M < 1.
+ * APE_EINVAL as ape_icp_polish_batch_f64, and for a null normals_table. */
+int ape_icp_polish_plane_batch_f64(int n, const float* points4, const int* n_cand, int N, const int* obj_class, const int64_t* model_table,
+                                   const int64_t* normals_table, int n_classes, int max_model_points, double cell, const double* pose_in,
+                                   double max_dist, double relative_fitness, double relative_rmse, int max_iteration, double min_fitness,
+                                   double* pose_out, double* stats, void* stream);
 
 /* ape_conv3x3_halo_bf16 for a 64-channel layer (the segmentor's up_3, pspnet.py:51) with ape_seg_head_f32 fused into its
  * epilogue: the [B][H][W][64] activation is never written, label[B][H][W] u8 / score[B][H][W] f32 are (bit-identical to the

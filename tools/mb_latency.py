@@ -1,8 +1,12 @@
 """Single-frame latency of the live path (FramePipeline.run on ONE 640x480 frame: what main.py's 'Run Live Prediction' does per frame),
-host wall clock from resident inputs to the pose on the host.  python tools/mb_latency.py [--icp-polish]
+host wall clock from resident inputs to the pose on the host.  python tools/mb_latency.py [--icp-polish [--estimation E] [--out F.json]]
 --icp-polish: every batch size a second time with FramePipeline(icp_polish=...) (pipeline/polish.py), the two pipelines alternating frame
 by frame; the model clouds are the detected objects' own depth points in the model frame of the unpolished pose, turned by 2 degrees and
-shifted by 2 mm, so every point finds a partner and the polish runs a realistic number of iterations."""
+shifted by 2 mm, so every point finds a partner and the polish runs a realistic number of iterations.
+--estimation point_to_point (the default) | point_to_plane | both: the polish's estimator; `both` times a pipeline for
+each, the three alternating frame by frame.  --out: the rows as JSON."""
+import datetime
+import json
 import os
 import sys
 import time
@@ -25,7 +29,7 @@ pipe = FramePipeline(seg, est, ref, bench.CLASSES, num_points=1000, refine_mode=
                      low_latency=os.environ.get("APE_LOW_LATENCY", "1") != "0")       # (what full_prediction uses; APE_LOW_LATENCY=0: the batched default)
 
 
-def polished_pipeline(rgb, depth):
+def polished_pipeline(rgb, depth, estimation="point_to_point"):
     """a second pipeline with the depth ICP polish on; clouds from one unpolished run of the same frames (see the module docstring)"""
     from autoposeestimation_amd import engine as E
     from autoposeestimation_amd.pipeline.polish import IcpPolish
@@ -42,31 +46,41 @@ def polished_pipeline(rgb, depth):
         m = (pts4[i, :min(int(n_cand[i]), 1000), :3].cpu().numpy().astype(np.float64) - pose[i, 4:7]) @ R        # R^T (p - t)
         clouds[o[1] - 1] = (m - m.mean(0)) @ turn.T + m.mean(0) + np.array([0.0015, -0.001, 0.0008])
     return FramePipeline(seg, est, ref, bench.CLASSES, num_points=1000, refine_mode="live_compat", pose_stream=False, low_latency=pipe.low_latency,
-                         icp_polish=IcpPolish(clouds))
+                         icp_polish=IcpPolish(clouds, estimation=estimation))
 
 
+arg = lambda name, default=None: sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default  # noqa: E731
+estimations = {"both": ("point_to_point", "point_to_plane")}.get(arg("--estimation", "point_to_point"), (arg("--estimation", "point_to_point"),))
+rows = []
 for b in (1, 4):
     rgb = torch.from_numpy(np.stack([f[0] for f in frames[:b]])).to(dev)
     depth = torch.from_numpy(np.stack([f[1] for f in frames[:b]])).to(dev)
     pipes = {"": pipe}
     if "--icp-polish" in sys.argv:
-        pipes[" icp_polish"] = polished_pipeline(rgb, depth)
+        for e in estimations:
+            pipes[" icp_polish" + ("" if e == "point_to_point" else " " + e)] = polished_pipeline(rgb, depth, e)
     for _ in range(5):
         for p_ in pipes.values():
             out = p_.run(rgb, depth, S.REALSENSE_META, seed=0)
             out["pose"].cpu()
     torch.cuda.synchronize()
-    ts = {k: [] for k in pipes}
+    ts, last = {k: [] for k in pipes}, {}
     for i in range(30):
         for k, p_ in pipes.items():
             t0 = time.perf_counter()
             out = p_.run(rgb, depth, S.REALSENSE_META, seed=i)
             p = out["pose"].cpu()
             ts[k].append(time.perf_counter() - t0)
+            last[k] = out
     for k, t in ts.items():
         t = np.sort(t) * 1e3
-        extra = "" if not k else "  fitness %s" % np.round(out["fit"][:, 0].cpu().numpy(), 3).tolist()
-        print("batch %d%s: median %.2f ms  min %.2f ms  (%d objects)%s" % (b, k, t[len(t) // 2], t[0], len(out["objects"]), extra))
+        extra = "" if not k else "  fitness %s" % np.round(last[k]["fit"][:, 0].cpu().numpy(), 3).tolist()
+        print("batch %d%s: median %.2f ms  min %.2f ms  (%d objects)%s" % (b, k, t[len(t) // 2], t[0], len(last[k]["objects"]), extra))
+        rows.append({"batch": b, "pipeline": k.strip() or "no polish", "median_ms": round(float(t[len(t) // 2]), 3), "min_ms": round(float(t[0]), 3),
+                     "max_ms": round(float(t[-1]), 3), "objects": len(last[k]["objects"]), "date": datetime.date.today().isoformat()})
+if arg("--out"):
+    os.makedirs(os.path.dirname(os.path.abspath(arg("--out"))), exist_ok=True)
+    json.dump({"what": "tools/mb_latency.py " + " ".join(sys.argv[1:]), "rows": rows}, open(arg("--out"), "w"), indent=1)
 
 if os.environ.get("APE_LAT_PROFILE"):
     import cProfile
